@@ -20,9 +20,13 @@ A leg that stalls is killed at its own time limit and noted; the legs that finis
 the requested configuration that passed its cross-check against one GPU; every leg is in `legs`.
 
 Prints ONE JSON line (rank 0).  `value` = CG iterations/s of the whole job (weak scaling: in units of config-2-sized
-parts advanced per second), the MEDIAN of R timed solves of exactly K iterations each (host clock between device
-synchronisations, max over ranks); `hbm_gbps` = bytes the iteration really moves (58 B per unknown for the REL_2NORM loop) per
-second; the per-kernel roofline comes from HIP events.
+parts advanced per second); `hbm_gbps` = bytes the iteration really moves (58 B per unknown for the REL_2NORM loop) per
+second.  N = 1: ONE timed solve of exactly K = --steps iterations (host clock between device synchronisations; --repeats R:
+the median of R such solves), and nothing else unless asked for:
+  --full                 also the per-kernel roofline pass (HIP events), the spread of up to 11 repeated solves and the CPU baseline
+  --dump-outputs DIR     after the timed solve, what it hands its caller: DIR/x.npy (the solution; a fixed, seeded sample of
+                         4 Mi entries when it is larger) and DIR/results.npy (iterations, r_norm2, initial_r_norm2), float64
+N > 1: the MEDIAN of R timed solves of exactly K iterations each, max over ranks.
 """
 from __future__ import annotations
 
@@ -65,11 +69,32 @@ def median(v):
 
 
 def repeats(args, ms_per_step_guess: float) -> int:
-    """R timed solves of K iterations each: 11 unless that would take more than ~3 s of device time."""
+    """R timed solves of K iterations each: --repeats, else 11 unless that would take more than ~3 s of device time."""
     if args.repeats > 0:
         return args.repeats
-    per = max(1e-6, args.steps * ms_per_step_guess * 1e-3)
+    return spread_repeats(args.steps, ms_per_step_guess)
+
+
+def spread_repeats(steps: int, ms_per_step_guess: float) -> int:
+    per = max(1e-6, steps * ms_per_step_guess * 1e-3)
     return max(1, min(11, int(3.0 / per)))
+
+
+DUMP_SAMPLE = 1 << 22          # --dump-outputs: entries of x written (32 MB of float64); a larger solution is sampled
+DUMP_SEED = 20261016
+
+
+def dump_outputs(d: str, x, res) -> dict:
+    """What the timed solve hands its caller (mi355cg_get_solution + the Results record), as float64 .npy files in d."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    n = x.size
+    if n > DUMP_SAMPLE:            # the same indices for the same grid, run after run
+        x = x[np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_SAMPLE, replace=False))]
+    np.save(os.path.join(d, "x.npy"), np.ascontiguousarray(x, dtype=np.float64))
+    np.save(os.path.join(d, "results.npy"), np.array([res.iterations, res.r_norm2, res.initial_r_norm2], dtype=np.float64))
+    return {"x": f"solution, {'all ' + str(n) if n <= DUMP_SAMPLE else f'{DUMP_SAMPLE} of {n} (sorted indices, numpy default_rng({DUMP_SEED}).choice)'} entries",
+            "results": "[iterations, r_norm2, initial_r_norm2]"}
 
 
 def cpu_baseline(n: int, iters: int):
@@ -611,26 +636,40 @@ def bench_one_gpu(args, emit):
         h.set_profiling(profile)
         return h.solve(p)
 
+    def timed_solves(count: int):
+        """count solves of exactly K iterations each (plus the initialisation pass of a solve), back to back."""
+        times, loops = [], []
+        for _ in range(count):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            res = run(args.steps, False)
+            torch.cuda.synchronize()
+            times.append(time.perf_counter() - t0)
+            loops.append(res.loop_seconds)
+            assert res.iterations == args.steps, (res.iterations, args.steps)
+        return times, loops, res
+
     run(args.warmup, False)                                   # untimed warm-up iterations
-    # R timed solves of exactly K iterations each (plus the initialisation pass of a solve), back to back; the median is the value
-    times, loops = [], []
-    for _ in range(repeats(args, 0.14 * max(1.0, U / 12.6e6) * (0.5 if f32 else 1.0))):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        res = run(args.steps, False)
-        torch.cuda.synchronize()
-        times.append(time.perf_counter() - t0)
-        loops.append(res.loop_seconds)
-        assert res.iterations == args.steps, (res.iterations, args.steps)
+    # the headline: ONE timed solve of exactly K iterations (--repeats R: R of them, the median is the value)
+    times, loops, res = timed_solves(max(1, args.repeats))
     dt = median(times)
     its = args.steps / dt
     loop = median(loops)
     its_loop = args.steps / loop if loop > 0 else None        # HIP events around the K iterations alone
+    outputs = dump_outputs(args.dump_outputs, h.solution(), res) if args.dump_outputs else None
+
+    spread = None
+    if args.full:
+        # the run-to-run spread: up to 11 more solves of K iterations (~3 s of device time at most), median and extremes
+        st, _, _ = timed_solves(spread_repeats(args.steps, 0.14 * max(1.0, U / 12.6e6) * (0.5 if f32 else 1.0)))
+        spread = {"solves": len(st), "median_iters_per_sec": round(args.steps / median(st), 2),
+                  "value_min_max": [round(args.steps / max(st), 2), round(args.steps / min(st), 2)],
+                  "ms_per_step_median": round(1e3 * median(st) / args.steps, 5)}
 
     words = WORDS[args.rule]
     words_iter = sum(words.values())
     roofline = None
-    if not args.no_roofline_pass:
+    if args.full and not args.no_roofline_pass:
         # same loop again with a HIP-event pair around every launch on the solve stream
         k = min(max(args.steps, 200), 500)
         run(k, True)
@@ -659,7 +698,8 @@ def bench_one_gpu(args, emit):
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
         "config": {"workload": f"{n}x{n} L-shaped Dirichlet Poisson {'fp32 inner CG of the mixed-precision path' if f32 else 'fp64'}, matrix-free CG, fixed {args.steps} iterations",
                    "n": n, "unknowns": U, "rule": args.rule, "layout": h.layout()},
-        "timing": f"median of {len(times)} back-to-back solves of K iterations each, host clock between device synchronisations (each includes the solve's "
+        "timing": (f"median of {len(times)} back-to-back solves" if len(times) > 1 else "one solve") +
+                  " of K iterations, host clock between device synchronisations (includes the solve's "
                   "initialisation pass: one pass x = 0, r = b, z = 0, ||r0||, and the last poll ~ 0.2 ms); loop_only_* = HIP events around the K iterations on the solve stream",
         "repeats": len(times),
         "value_min_max": [round(args.steps / max(times), 2), round(args.steps / min(times), 2)],
@@ -673,7 +713,11 @@ def bench_one_gpu(args, emit):
         "algorithmic_equivalent_gbps_88B": round(SURVEY_BYTES_PER_UNKNOWN * (wbytes / 8.0) * U * its / 1e9, 1),
         "roofline": roofline,
     }
-    if args.cpu_iters > 0 and not f32:
+    if outputs:
+        out["outputs"] = outputs
+    if spread:
+        out["repeat_spread"] = spread
+    if args.full and args.cpu_iters > 0 and not f32:
         out["cpu_baseline"] = cpu_baseline(n, args.cpu_iters)
     emit(out)
 
@@ -689,9 +733,14 @@ def main():
                     help="f32 = BASELINE config 3: the fp32-storage inner CG of the mixed-precision path (use --grid 8192)")
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak", help="N > 1: weak (part size fixed) or strong (--grid fixed)")
     ap.add_argument("--decomp", choices=["rows", "2d"], default="rows", help="N > 1: row slabs or (N/2) x 2 blocks")
-    ap.add_argument("--cpu-iters", type=int, default=20, help="oracle iterations for cpu_baseline (0 = skip)")
-    ap.add_argument("--no-roofline-pass", action="store_true")
-    ap.add_argument("--repeats", type=int, default=0, help="timed solves of K iterations each, the median is reported (0 = 11, fewer for long solves)")
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: besides the headline, the roofline pass, the spread of repeated solves and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="N = 1: write what the last timed solve computed to DIR/*.npy (float64, at most 32 MB)")
+    ap.add_argument("--cpu-iters", type=int, default=20, help="--full: oracle iterations for cpu_baseline (0 = skip)")
+    ap.add_argument("--no-roofline-pass", action="store_true", help="--full without the roofline pass")
+    ap.add_argument("--repeats", type=int, default=0,
+                    help="timed solves of K iterations each, the median is reported (0: N = 1 one solve; N > 1 11, fewer for long solves)")
     ap.add_argument("--verify", type=int, default=30, help="N > 1: iterations of the untimed cross-check against one GPU (0 = skip)")
     ap.add_argument("--verify-max-unknowns", type=float, default=2.6e8, help="skip that cross-check above this size (host set-up time)")
     ap.add_argument("--legs", default="all", help="N > 1: all | default (the two headline transports only) | comma-separated leg names")
@@ -701,6 +750,9 @@ def main():
     ap.add_argument("--child-leg", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--child-out", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    multi = int(os.environ.get("WORLD_SIZE", "1")) > 1 or args.gpus > 1 or os.environ.get("MI355CG_BENCH_DIST") == "1"
+    if args.dump_outputs and multi:
+        ap.error("--dump-outputs is for the one-GPU run (--gpus 1)")
 
     if args.child_leg:                                            # a rank process of one leg
         import threading
@@ -737,8 +789,7 @@ def main():
         os.dup2(real_stdout, 1)
         print(json.dumps(obj), flush=True)
 
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    if world > 1 or args.gpus > 1 or os.environ.get("MI355CG_BENCH_DIST") == "1":
+    if multi:
         got = coordinate(args)                                     # before anything could touch a GPU in this process
         if got is None:
             return                                                 # a non-zero rank's coordinator: rank 0 prints

@@ -6,7 +6,7 @@ while [ "$#" -gt 0 ] && [ "$1" != "--" ]; do cfgs+=("$1"); shift; done
 shift
 for rep in 1 2 3; do
   for cfg in "${cfgs[@]}"; do
-    env $cfg python bench.py --cpu-iters 0 "$@" > /tmp/b.json 2>/tmp/b.err || { cat /tmp/b.err; exit 1; }
+    env $cfg python bench.py --full --cpu-iters 0 "$@" > /tmp/b.json 2>/tmp/b.err || { cat /tmp/b.err; exit 1; }
     python - "$cfg" <<'PY'
 import json, sys
 j = json.load(open('/tmp/b.json'))

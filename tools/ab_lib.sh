@@ -2,7 +2,7 @@
 # A/B two builds of libmi355cg.so on one box, interleaved: $1 = alternative library
 for rep in 1 2 3 4; do
   for lib in "" "$1"; do
-    MI355CG_LIB=$lib python bench.py --steps 1500 --warmup 100 --cpu-iters 0 > /tmp/b.json 2>/dev/null
+    MI355CG_LIB=$lib python bench.py --full --steps 1500 --warmup 100 --cpu-iters 0 > /tmp/b.json 2>/dev/null
     python - "${lib:-default}" <<'PY'
 import json, sys
 j = json.load(open('/tmp/b.json'))

@@ -16,7 +16,7 @@ echo "pmc FETCH_SIZE rc=$?"
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "${P}_write" -- python3 $ARGS > "${P}_write.log" 2>&1
 echo "pmc WRITE_SIZE rc=$?"
 cd "$REPO"
-python3 bench.py --grid $GRID --steps $STEPS --warmup 50 --cpu-iters 0 2>/dev/null | tail -1 > "${P}_bench.json"
+python3 bench.py --full --grid $GRID --steps $STEPS --warmup 50 --cpu-iters 0 2>/dev/null | tail -1 > "${P}_bench.json"
 for k in kt fetch write; do python3 tools/prof_summary.py "${P}_$k" --json "${P}_$k.json" > "${P}_${k}_summary.txt" 2>&1; done
 cat "${P}_kt_summary.txt" "${P}_fetch_summary.txt" "${P}_write_summary.txt"
 # keep the merged-back payload small: drop the per-dispatch CSVs, keep stats
