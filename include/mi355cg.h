@@ -20,6 +20,12 @@
  *   mi355cg_iter_cb                Solver::setIterationCallback             solver/solver.hpp:46-50
  *   stop_flag                      MSGSolver::requestStop (atomic flag)     solver/msg_solver.hpp:35,76; msg_solver.cpp:82-87
  *
+ * Extension without a reference counterpart (the reference has no preconditioner):
+ *   mi355cg_set_preconditioner     opt-in geometric multigrid V-cycle M ~ A^-1 for single-GPU fp64 grid handles; while it is
+ *                                  set, mi355cg_solve runs preconditioned CG (same stop rules, callbacks, stop flag, results)
+ *   mi355cg_apply_preconditioner   z = M r on host vectors (packed order)
+ *   mi355cg_mg_levels              the hierarchy a grid gets (pure host arithmetic, no GPU needed)
+ *
  * Plain pointers and sizes only; no C++/torch types.  All host vectors are in the reference's
  * PACKED unknown order (bottom-right block row-major, then the upper block row-major;
  * grid_system.cpp:84-111) and are caller-owned.  Every function returns MI355CG_OK (0) or an
@@ -135,6 +141,23 @@ int  mi355cg_solve(mi355cg_handle h, const mi355cg_params *params,
 int  mi355cg_get_solution(mi355cg_handle h, double *x);         /* packed x of the last solve   */
 int  mi355cg_get_recursive_residual(mi355cg_handle h, double *r);
 int  mi355cg_get_true_residual(mi355cg_handle h, double *ax_minus_b); /* A x - b, one more apply */
+
+/* ---- preconditioner (extension: no reference twin) -------------------------------------------------------------------
+ * MI355CG_PRECOND_MG: geometric multigrid.  Level 0 is the handle's grid; level l + 1 has N_l / 2 intervals (steps doubled)
+ * and exists while N_l % 4 == 0 and N_l > 32; the coarsest level must have N_L <= 32, so 10, 16, 32 (one level: M = A^-1),
+ * 64, 256, 4096 (8 levels) qualify and 258 or 1000 do not.  M = one V-cycle: two damped-Jacobi sweeps (omega 0.8), the
+ * residual restricted by full weighting, the coarse correction (recursively; on the coarsest level a dense inverse of A_L
+ * computed once on the host) prolonged bilinearly, two more sweeps.  M is symmetric and, like A, negative definite.
+ * mi355cg_solve then runs Hestenes-Stiefel PCG from x = 0 (z = M r, p = z + beta p, beta = (r, z) / (r, z)_previous) with the
+ * rule, callbacks, stop flag, fixed_iterations and result fields of the plain path; mi355cg_get_solution / _residual report it.
+ * MG is refused (MI355CG_ERR_INVALID) on CSR handles, slab / part handles, MI355CG_F32_MIXED handles and grids without a
+ * hierarchy.  Memory: level 0 adds five vectors of the handle's size, the coarser levels about one more, the inverse <= 4 MB.
+ * set_preconditioner(MI355CG_PRECOND_NONE) frees it: the handle then runs exactly the plain path again.                      */
+#define MI355CG_PRECOND_NONE  0
+#define MI355CG_PRECOND_MG    1
+int  mi355cg_set_preconditioner(mi355cg_handle h, int kind);                   /* builds or frees the hierarchy            */
+int  mi355cg_apply_preconditioner(mi355cg_handle h, const double *r, double *z); /* host vectors, packed; MI355CG_ERR_STATE if none is set */
+int  mi355cg_mg_levels(int n, int *levels, int *coarsest_n);                   /* MI355CG_ERR_INVALID: no hierarchy          */
 
 /* ---- measurement hooks (bench.py) ------------------------------------------------------------ */
 /* Per-kernel device time of the last mi355cg_solve, measured with HIP events on the solve

@@ -409,6 +409,9 @@ public:
     }
     std::vector<double> operator*(const std::vector<double>& x) const { std::vector<double> y; apply(x, y); return y; }
     int size() const { return (int)rhs.size(); }
+    // Extension (the reference has no preconditioner): MI355CG_PRECOND_MG makes every solve on this system multigrid-preconditioned
+    // CG, MI355CG_PRECOND_NONE returns to plain CG.  std::invalid_argument for grids without a multigrid hierarchy.
+    void setPreconditioner(int kind) { mi355cg_compat::check(mi355cg_set_preconditioner(ctx_->h, kind)); }
     const std::shared_ptr<mi355cg_compat::Context>& context() const { return ctx_; }
     friend std::ostream& operator<<(std::ostream& os, const MatrixFreeSystem& s) {
         return os << "MatrixFreeSystem Information:\n  Dimensions: " << s.ctx_->n << "x" << s.ctx_->m << "\n  System size: " << s.size() << "\n";
@@ -578,6 +581,15 @@ public:
         solver.reset();
         grid = std::make_unique<GridSystem>(m_internal, n_internal, a_bound, b_bound, c_bound, d_bound);
         if (!devices_.empty()) grid->distribute(devices_, decomp_);
+        if (precond_ != MI355CG_PRECOND_NONE) mi355cg_compat::check(mi355cg_set_preconditioner(grid->context()->h, precond_));
+    }
+    // Extension (the reference has no preconditioner): MI355CG_PRECOND_MG = multigrid-preconditioned CG for the solves of this
+    // facade, single-GPU only (not together with setDevices).  Kept across setGridParameters; std::invalid_argument for grids
+    // without a multigrid hierarchy.
+    void setPreconditioner(int kind) {
+        if (kind != MI355CG_PRECOND_NONE && !devices_.empty()) throw std::invalid_argument("the multigrid preconditioner is single-GPU only");
+        if (grid) mi355cg_compat::check(mi355cg_set_preconditioner(grid->context()->h, kind));
+        precond_ = kind;
     }
     void setSolverParameters(double eps_p, double eps_r, double eps_e, int max_iter) {
         eps_precision = eps_p; eps_residual = eps_r; eps_exact_error = eps_e; max_iterations = max_iter;
@@ -594,6 +606,7 @@ public:
     void setPollInterval(int iterations) { poll_interval_ = iterations; }         // see MSGSolver::setPollInterval
     // Extension: solve on several GPUs of this process (see GridSystem::distribute).  Kept across setGridParameters.
     void setDevices(const std::vector<int>& devices, int decomp = MI355CG_DECOMP_ROWS) {
+        if (!devices.empty() && precond_ != MI355CG_PRECOND_NONE) throw std::invalid_argument("the multigrid preconditioner is single-GPU only");
         devices_ = devices; decomp_ = decomp;
         if (grid) grid->distribute(devices_, decomp_);
     }
@@ -659,4 +672,5 @@ private:
     int poll_interval_ = 0;
     std::vector<int> devices_;
     int decomp_ = MI355CG_DECOMP_ROWS;
+    int precond_ = MI355CG_PRECOND_NONE;
 };

@@ -6,6 +6,7 @@
 #include "cg_kernels.h"
 #include "csr_kernels.h"
 #include "grid_setup.h"
+#include "mg_kernels.h"
 
 #include <algorithm>
 #include <chrono>
@@ -60,6 +61,20 @@ struct EventPool {
 
 // One launch shape: the work items of a set of rows x strips and the persistent grid that marches them.
 struct Plan { WorkList wl{}; int grid = 0; int ty = 0; };
+
+// Geometric multigrid preconditioner (mi355cg_set_preconditioner; kernels in mg_kernels.h).  Level 0 is the handle's grid; level
+// l + 1 has N_l / 2 intervals and doubled steps.  Per level: the right-hand side of its cycle (level 0: the caller's vector), a
+// work vector and the cycle's result (level 0: the caller's output); the coarsest level keeps its dense inverse.
+struct MgLevel { Geom g{}; long long len = 0; int grid = 0; double *rhs = nullptr, *a = nullptr, *out = nullptr; };
+struct MgHier {
+    std::vector<MgLevel> lv;
+    int ncoarse = 0;                    // unknowns of the coarsest level
+    double* inv = nullptr;              // A_L^-1, ncoarse x ncoarse, row-major (unknowns in packed order)
+    int* coff = nullptr;                // storage offset of every coarsest unknown
+    double *z = nullptr, *p[2] = {nullptr, nullptr}, *q = nullptr;    // PCG vectors of level 0 (p: ping-pong)
+    double* part = nullptr;             // per-block partials, MG_NFIELDS x kMgMaxGrid
+    double* part_h = nullptr;           // pinned copy
+};
 
 }  // namespace
 
@@ -120,6 +135,7 @@ struct mi355cg_ctx {
     int use_graph = -1;                 // env MI355CG_GRAPH: -1 auto (small grids), 0 off, 1 on
 
     hipEvent_t ev_loop[2] = {nullptr, nullptr};   // brackets the iterations of the last solve (mi355cg_results::loop_seconds)
+    MgHier* mg = nullptr;               // opt-in preconditioner (mi355cg_set_preconditioner): mi355cg_solve runs solve_mg while set
     bool profiling = false;
     EventPool events;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pairs[2];
@@ -785,6 +801,258 @@ int solve_mixed(mi355cg_ctx* c, const mi355cg_params* prm, mi355cg_iter_cb cb, v
 
 }  // namespace
 
+// ---- geometric multigrid preconditioner and the preconditioned CG on it (opt-in) -----------------
+// Algorithm (fixed; tests/test_mg_cpu.py restates it in NumPy):  V(r, l): u = 0, two damped-Jacobi sweeps (omega = 0.8),
+// s = r - A_l u restricted by full weighting, u += P V(R s, l + 1), two more sweeps; the coarsest level solves with the dense
+// inverse.  R = P^T / 4 and equal pre- and post-smoothers make M symmetric; A is negative definite and so is M, (r, z) < 0.
+// PCG (Hestenes-Stiefel, x0 = 0) driven from the host: the scalars of an iteration come back from three short waits (after the
+// cycle, after q = A p, after the update), which lets the stop rules, callbacks and stop flag run exactly as in the plain path.
+namespace {
+
+constexpr double kMgOmega = 0.8;
+
+// N_{l+1} = N_l / 2 while N_l % 4 == 0 and N_l > 32; the coarsest level must have N_L <= 32.  Pure host arithmetic.
+int mg_shape(int n, int* levels, int* coarsest) {
+    if (n < 6 || n % 2 != 0) return fail(MI355CG_ERR_INVALID, "grid %d rejected: the L-shaped index map needs an even n >= 6", n);
+    int N = n, L = 1;
+    while (N % 4 == 0 && N > 32) { N /= 2; ++L; }
+    if (N > 32)
+        return fail(MI355CG_ERR_INVALID, "grid %d has no multigrid hierarchy: halving stops at N = %d, and the coarsest grid must have "
+                    "N <= 32 (a level is halved while N %% 4 == 0 and N > 32)", n, N);
+    if (levels) *levels = L;
+    if (coarsest) *coarsest = N;
+    return MI355CG_OK;
+}
+
+// build_geom's storage layout for a whole grid of N intervals (base0 = 0) with the level's 5-point coefficients
+Geom mg_geom(int N, double hx, double hy, long long* len) {
+    Geom g{};
+    g.N = N; g.half = N / 2;
+    g.Pu = (int)round_up(N + 1, 32); g.cb = g.half & ~31; g.Pb = g.Pu - g.cb;
+    g.xlim = (int)round_up(N + 1, 2);
+    g.y_lo = 1; g.y_hi = N - 1; g.base0 = 0;
+    g.own_begin = phys_start(g, 1); g.own_len = phys_end(g, N - 1) - g.own_begin;
+    g.xk = 1 / (hx * hx); g.yk = 1 / (hy * hy);               // grid_system.cpp:316-318 with the level's steps
+    g.A = -2 * (g.xk + g.yk);
+    *len = phys_end(g, N);
+    return g;
+}
+
+void mg_free(MgHier* H) {
+    if (!H) return;
+    for (auto& L : H->lv) for (double* v : {L.rhs, L.a, L.out}) if (v) hipFree(v);
+    for (double* v : {H->inv, H->z, H->p[0], H->p[1], H->q, H->part}) if (v) hipFree(v);
+    if (H->coff) hipFree(H->coff);
+    if (H->part_h) hipHostFree(H->part_h);
+    delete H;
+}
+
+// A_L^-1 of the coarsest level in its packed unknown order, from the Cholesky factor of -A_L (fp64, host), and the storage
+// offset of every unknown.  -A_L = L L^T, T = L^-1 kept transposed (row j = column j of L^-1), -A_L^-1 = T^T T.
+void mg_coarse_inverse(const Geom& g, std::vector<double>& inv, std::vector<int>& off) {
+    const int N = g.N, W = N + 1;
+    std::vector<int> idx((size_t)W * W, -1);
+    off.clear();
+    for (int y = 1; y <= N - 1; ++y)
+        for (int x = (y <= g.half ? g.half + 1 : 1); x <= N - 1; ++x) { idx[(size_t)y * W + x] = (int)off.size(); off.push_back((int)mg_off(g, x, y)); }
+    const int n = (int)off.size();
+    std::vector<double> S((size_t)n * n, 0.0);
+    for (int y = 1; y <= N - 1; ++y)
+        for (int x = 1; x <= N - 1; ++x) {
+            const int i = idx[(size_t)y * W + x];
+            if (i < 0) continue;
+            S[(size_t)i * n + i] = -g.A;
+            const int nb[4] = {idx[(size_t)y * W + x - 1], idx[(size_t)y * W + x + 1], idx[(size_t)(y - 1) * W + x], idx[(size_t)(y + 1) * W + x]};
+            for (int k = 0; k < 4; ++k) if (nb[k] >= 0) S[(size_t)i * n + nb[k]] = k < 2 ? -g.xk : -g.yk;
+        }
+    for (int j = 0; j < n; ++j) {                              // in place: S's lower triangle becomes L
+        double* Sj = &S[(size_t)j * n];
+        double d = Sj[j];
+        for (int k = 0; k < j; ++k) d -= Sj[k] * Sj[k];
+        Sj[j] = std::sqrt(d);
+        for (int i = j + 1; i < n; ++i) {
+            double* Si = &S[(size_t)i * n];
+            double v = Si[j];
+            for (int k = 0; k < j; ++k) v -= Si[k] * Sj[k];
+            Si[j] = v / Sj[j];
+        }
+    }
+    std::vector<double> T((size_t)n * n, 0.0);               // T[j][i] = (L^-1)[i][j], i >= j
+    for (int j = 0; j < n; ++j) {
+        double* Tj = &T[(size_t)j * n];
+        Tj[j] = 1 / S[(size_t)j * n + j];
+        for (int i = j + 1; i < n; ++i) {
+            const double* Si = &S[(size_t)i * n];
+            double v = 0;
+            for (int k = j; k < i; ++k) v += Si[k] * Tj[k];
+            Tj[i] = -v / Si[i];
+        }
+    }
+    inv.assign((size_t)n * n, 0.0);
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j <= i; ++j) {                         // (-A_L)^-1 [i][j] = sum_{k >= i} T[i][k] T[j][k]; exactly symmetric
+            const double* Ti = &T[(size_t)i * n];
+            const double* Tj = &T[(size_t)j * n];
+            double v = 0;
+            for (int k = i; k < n; ++k) v += Ti[k] * Tj[k];
+            inv[(size_t)i * n + j] = inv[(size_t)j * n + i] = -v;
+        }
+}
+
+int mg_build(mi355cg_ctx* c, MgHier** out) {
+    int nl = 0;
+    if (int rc = mg_shape(c->gp.n, &nl, nullptr)) return rc;
+    MgHier* H = new MgHier();
+    auto bail = [&](int rc) { mg_free(H); return rc; };
+    H->lv.resize(nl);
+    for (int l = 0; l < nl; ++l) {
+        MgLevel& L = H->lv[l];
+        L.g = mg_geom(c->gp.n >> l, std::ldexp(c->gp.x_step, l), std::ldexp(c->gp.y_step, l), &L.len);
+        L.grid = std::min(L.g.N - 1, kMgMaxGrid);
+        if (l > 0) { if (int rc = alloc_vec(&L.rhs, L.len)) return bail(rc); if (int rc = alloc_vec(&L.out, L.len)) return bail(rc); }
+        if (l + 1 < nl) if (int rc = alloc_vec(&L.a, L.len)) return bail(rc);
+    }
+    const Geom& g0 = H->lv[0].g;
+    if (H->lv[0].len != c->storage_len || g0.Pb != c->g.Pb || g0.Pu != c->g.Pu || g0.cb != c->g.cb || c->g.base0 != 0)
+        return bail(fail(MI355CG_ERR_STATE, "multigrid level 0 does not match the handle's storage layout"));
+    for (double** v : {&H->z, &H->p[0], &H->p[1], &H->q}) if (int rc = alloc_vec(v, c->storage_len)) return bail(rc);
+    if (int rc = alloc_vec(&H->part, (long long)MG_NFIELDS * kMgMaxGrid)) return bail(rc);
+    if (hipHostMalloc((void**)&H->part_h, sizeof(double) * MG_NFIELDS * kMgMaxGrid) != hipSuccess)
+        return bail(fail(MI355CG_ERR_HIP, "pinned partials allocation failed"));
+    std::vector<double> inv;
+    std::vector<int> off;
+    mg_coarse_inverse(H->lv.back().g, inv, off);
+    H->ncoarse = (int)off.size();
+    if (H->ncoarse > kMgMaxCoarse) return bail(fail(MI355CG_ERR_STATE, "coarsest grid has %d unknowns (> %d)", H->ncoarse, kMgMaxCoarse));
+    if (hipMalloc((void**)&H->inv, sizeof(double) * inv.size()) != hipSuccess || hipMalloc((void**)&H->coff, sizeof(int) * off.size()) != hipSuccess ||
+        hipMemcpy(H->inv, inv.data(), sizeof(double) * inv.size(), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(H->coff, off.data(), sizeof(int) * off.size(), hipMemcpyHostToDevice) != hipSuccess)
+        return bail(fail(MI355CG_ERR_HIP, "coarse inverse upload failed"));
+    // the zero-fills ran on the NULL stream; the context's stream does not order with them (see create_impl)
+    if (hipDeviceSynchronize() != hipSuccess) return bail(fail(MI355CG_ERR_HIP, "hipDeviceSynchronize failed"));
+    *out = H;
+    return MI355CG_OK;
+}
+
+// out = V(rhs, l) on level l's vectors.  dot != nullptr (level 0): the last launch also leaves the partials of (rhs, out) there.
+void mg_vcycle(mi355cg_ctx* c, int l, const double* rhs, double* out, double* dot) {
+    const MgHier& H = *c->mg;
+    const MgLevel& L = H.lv[l];
+    const hipStream_t st = c->stream;
+    const dim3 grid(L.grid), blk(kBlock);
+    if (l + 1 == (int)H.lv.size()) {
+        hipLaunchKernelGGL(k_mg_coarse, dim3(H.ncoarse), blk, 0, st, H.ncoarse, (const double*)H.inv, (const int*)H.coff, rhs, out);
+        if (dot) hipLaunchKernelGGL(k_mg_dot, grid, blk, 0, st, L.g, rhs, (const double*)out, dot);
+        return;
+    }
+    const MgLevel& C = H.lv[l + 1];
+    hipLaunchKernelGGL((k_mg_smooth<true, false>), grid, blk, 0, st, L.g, kMgOmega, rhs, (const double*)nullptr, L.a, (double*)nullptr);
+    hipLaunchKernelGGL((k_mg_smooth<false, false>), grid, blk, 0, st, L.g, kMgOmega, rhs, (const double*)L.a, out, (double*)nullptr);
+    hipLaunchKernelGGL(k_mg_restrict, dim3(C.grid), blk, 0, st, L.g, C.g, rhs, (const double*)out, C.rhs);
+    mg_vcycle(c, l + 1, C.rhs, C.out, nullptr);
+    hipLaunchKernelGGL(k_mg_prolong, grid, blk, 0, st, L.g, C.g, (const double*)C.out, out);
+    hipLaunchKernelGGL((k_mg_smooth<false, false>), grid, blk, 0, st, L.g, kMgOmega, rhs, (const double*)out, L.a, (double*)nullptr);
+    if (dot) hipLaunchKernelGGL((k_mg_smooth<false, true>), grid, blk, 0, st, L.g, kMgOmega, rhs, (const double*)L.a, out, dot);
+    else hipLaunchKernelGGL((k_mg_smooth<false, false>), grid, blk, 0, st, L.g, kMgOmega, rhs, (const double*)L.a, out, (double*)nullptr);
+}
+
+// PCG with z = M r.  Same stop rules, callback cadence, stop-flag handling and result fields as mi355cg_solve's plain path.
+int solve_mg(mi355cg_ctx* c, const mi355cg_params* prm, mi355cg_iter_cb cb, void* user,
+             const volatile int* stop_flag, mi355cg_results* out) {
+    MgHier& H = *c->mg;
+    const Geom& g = H.lv[0].g;
+    const bool msg = prm->rule == MI355CG_RULE_MSG_MAXNORM;
+    const bool diag = !msg && prm->diagnostics;
+    const bool has_u = (msg && prm->use_true_solution) || diag;
+    if (has_u) if (int rc = ensure_u_on_device(c)) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    const hipStream_t st = c->stream;
+    const int G = H.lv[0].grid;
+    const dim3 grid(G), blk(kBlock);
+    const size_t bytes = sizeof(double) * c->storage_len;
+    // partials of the last launch -> host, summed (maxed) in block order: the fixed reduction order
+    auto fetch = [&](int nfields, double* v) -> int {
+        HIPCK(hipGetLastError());
+        HIPCK(hipMemcpyAsync(H.part_h, H.part, sizeof(double) * nfields * G, hipMemcpyDeviceToHost, st));
+        HIPCK(hipStreamSynchronize(st));
+        for (int f = 0; f < nfields; ++f) {
+            double s = 0;
+            for (int b = 0; b < G; ++b) s = f < MG_RMAX ? s + H.part_h[f * G + b] : std::max(s, H.part_h[f * G + b]);
+            v[f] = s;
+        }
+        return MI355CG_OK;
+    };
+    double nm[MG_NFIELDS];
+    auto update = [&](double alpha, const double* p, const double* q) -> int {
+        hipLaunchKernelGGL(k_mg_update, grid, blk, 0, st, g, alpha, c->x, c->r, p, q, has_u ? (const double*)c->u : (const double*)nullptr, H.part);
+        return fetch(MG_NFIELDS, nm);
+    };
+    // x = 0, r = b (msg_solver.cpp:33-39); a zero step gives the norms of r0 and of x0 - u
+    HIPCK(hipMemsetAsync(c->x, 0, bytes, st));
+    HIPCK(hipMemsetAsync(H.q, 0, bytes, st));
+    HIPCK(hipMemcpyAsync(c->r, c->b, bytes, hipMemcpyDeviceToDevice, st));
+    if (int rc = update(0.0, H.q, H.q)) return rc;
+    const double r0norm = std::sqrt(nm[MG_RR]);
+    double rnorm = r0norm;
+    if (!c->ev_loop[0]) { HIPCK(hipEventCreate(&c->ev_loop[0])); HIPCK(hipEventCreate(&c->ev_loop[1])); }
+    HIPCK(hipEventRecord(c->ev_loop[0], st));
+    if (msg && cb) cb(user, 0, DBL_MAX, nm[MG_RMAX], has_u ? nm[MG_EMAX] : DBL_MAX);          // msg_solver.cpp:75-77
+    const int every = prm->callback_every;
+    int it = 0, reason = MI355CG_STOP_ITERATIONS;
+    bool converged = false, interrupted = false;
+    double rho = 0.0;
+    for (;;) {
+        if (!(it < prm->max_iterations)) break;                                               // msg_solver.cpp:80
+        if (!msg && !prm->fixed_iterations && !(rnorm > prm->eps_rel * r0norm)) break;        // matrix_free_system.cpp:409
+        if (stop_flag && *stop_flag) { interrupted = true; break; }                           // msg_solver.cpp:82-87
+        double rz = 0, pq = 0;
+        mg_vcycle(c, 0, c->r, H.z, H.part);                                                  // z = M r, partials of (r, z)
+        if (int rc = fetch(1, &rz)) return rc;
+        const double beta = it == 0 ? 0.0 : rz / rho;
+        rho = rz;
+        double* p = H.p[it & 1];
+        if (it == 0) hipLaunchKernelGGL((k_mg_dir_apply<true>), grid, blk, 0, st, g, 0.0, (const double*)H.z, (const double*)nullptr, p, H.q, H.part);
+        else hipLaunchKernelGGL((k_mg_dir_apply<false>), grid, blk, 0, st, g, beta, (const double*)H.z, (const double*)H.p[(it + 1) & 1], p, H.q, H.part);
+        if (int rc = fetch(1, &pq)) return rc;
+        if (int rc = update(rho / pq, p, H.q)) return rc;
+        ++it;
+        rnorm = std::sqrt(nm[MG_RR]);
+        if (msg && !prm->fixed_iterations) {                                                  // msg_solver.cpp:144-163, this order, strict <
+            if (prm->eps_precision > 0 && nm[MG_DMAX] < prm->eps_precision) { converged = true; reason = MI355CG_STOP_PRECISION; break; }
+            if (prm->eps_residual > 0 && nm[MG_RMAX] < prm->eps_residual) { converged = true; reason = MI355CG_STOP_RESIDUAL; break; }
+            if (prm->eps_exact_error > 0 && has_u && nm[MG_EMAX] < prm->eps_exact_error) { converged = true; reason = MI355CG_STOP_EXACT_ERROR; break; }
+        }
+        if (diag && cb) {                                                                     // matrix_free_system.cpp:457-468 (0-based index)
+            double tr2 = 0;
+            hipLaunchKernelGGL(k_mg_resid2, grid, blk, 0, st, g, (const double*)c->b, (const double*)c->x, H.part);
+            if (int rc = fetch(1, &tr2)) return rc;
+            cb(user, it - 1, std::sqrt(nm[MG_D2]), std::sqrt(tr2), std::sqrt(nm[MG_E2]));
+        } else if (msg && cb && (it == 1 || (every > 0 && it % every == 0))) {               // msg_solver.cpp:172-183
+            cb(user, it, nm[MG_DMAX], nm[MG_RMAX], has_u ? nm[MG_EMAX] : DBL_MAX);
+        }
+    }
+    HIPCK(hipEventRecord(c->ev_loop[1], st));
+    if (!msg) converged = rnorm <= prm->eps_rel * r0norm;                                     // matrix_free_system.cpp:472
+    c->solved = true;
+    c->kernel_ms[0] = c->kernel_ms[1] = 0.0; c->kernel_launches[0] = c->kernel_launches[1] = 0;   // per-kernel times: plain path only
+    mi355cg_results res{};
+    res.iterations = it;
+    res.converged = interrupted ? 0 : (converged ? 1 : 0);
+    res.stop_reason = interrupted ? MI355CG_STOP_INTERRUPTED : reason;
+    res.final_residual_norm = nm[MG_RMAX];
+    res.final_precision = it > 0 ? nm[MG_DMAX] : DBL_MAX;
+    res.final_error_norm = has_u ? nm[MG_EMAX] : DBL_MAX;
+    res.r_norm2 = rnorm;
+    res.initial_r_norm2 = r0norm;
+    res.solve_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    { float ms = 0; HIPCK(hipEventSynchronize(c->ev_loop[1])); if (hipEventElapsedTime(&ms, c->ev_loop[0], c->ev_loop[1]) == hipSuccess) res.loop_seconds = 1e-3 * ms; }
+    if (msg && cb) cb(user, res.iterations, res.final_precision, res.final_residual_norm, res.final_error_norm);   // msg_solver.cpp:193-195
+    if (out) *out = res;
+    return MI355CG_OK;
+}
+
+}  // namespace
+
 // ====================================================================================================
 extern "C" {
 
@@ -977,6 +1245,7 @@ void mi355cg_destroy(mi355cg_handle c) {
     if (c->partR_h) hipHostFree(c->partR_h);
     if (c->stop_h) hipHostFree(c->stop_h);
     clear_graphs(c);
+    mg_free(c->mg);
     c->events.destroy();
     for (hipEvent_t e : c->ev_loop) if (e) hipEventDestroy(e);
     if (c->stream) hipStreamDestroy(c->stream);
@@ -1086,6 +1355,7 @@ int mi355cg_solve(mi355cg_handle c, const mi355cg_params* prm, mi355cg_iter_cb c
     HIPCK(hipSetDevice(c->device));
     if (c->is_csr) return solve_csr(c, prm, cb, user, stop_flag, out);
     if (c->dtype == MI355CG_F32_MIXED) return solve_mixed(c, prm, cb, user, stop_flag, out);
+    if (c->mg) return solve_mg(c, prm, cb, user, stop_flag, out);                     // opt-in preconditioner (fp64 grid handles only)
     const bool msg = prm->rule == MI355CG_RULE_MSG_MAXNORM;
     const IterCfg cfg = make_cfg(prm);
     const bool diag = cfg.want_diag != 0;
@@ -1327,6 +1597,37 @@ int mi355cg_get_layout(mi355cg_handle c, long long* padded_len, int* pitch_botto
     if (grid_update) *grid_update = c->whole.grid;
     if (rows_per_item) *rows_per_item = c->whole.ty;
     return MI355CG_OK;
+}
+
+// ---- geometric multigrid preconditioner (opt-in) ----------------------------------------------------------------------
+int mi355cg_mg_levels(int n, int* levels, int* coarsest_n) { return mg_shape(n, levels, coarsest_n); }
+
+int mi355cg_set_preconditioner(mi355cg_handle c, int kind) {
+    if (!c) return fail(MI355CG_ERR_INVALID, "null handle");
+    if (kind != MI355CG_PRECOND_NONE && kind != MI355CG_PRECOND_MG)
+        return fail(MI355CG_ERR_INVALID, "unknown preconditioner kind %d (MI355CG_PRECOND_NONE = 0, MI355CG_PRECOND_MG = 1)", kind);
+    HIPCK(hipSetDevice(c->device));
+    if (kind == MI355CG_PRECOND_NONE) {
+        if (c->mg) { HIPCK(hipStreamSynchronize(c->stream)); mg_free(c->mg); c->mg = nullptr; }
+        return MI355CG_OK;
+    }
+    if (c->is_csr) return fail(MI355CG_ERR_INVALID, "the multigrid preconditioner needs the grid operator: a CSR handle has no grid");
+    if (c->is_slab) return fail(MI355CG_ERR_INVALID, "the multigrid preconditioner is single-GPU only: this handle owns one part of a decomposed grid");
+    if (c->dtype != MI355CG_F64) return fail(MI355CG_ERR_INVALID, "the multigrid preconditioner is fp64 only: this handle was created with MI355CG_F32_MIXED");
+    if (c->mg) return MI355CG_OK;
+    return mg_build(c, &c->mg);
+}
+
+// z = M r on host vectors (packed order).  Works on the PCG's q (input) and z (output), which hold nothing between iterations,
+// so an iteration callback may call it in the middle of a solve.
+int mi355cg_apply_preconditioner(mi355cg_handle c, const double* r, double* z) {
+    if (!c || !r || !z) return fail(MI355CG_ERR_INVALID, "null argument");
+    if (!c->mg) return fail(MI355CG_ERR_STATE, "no preconditioner is set on this handle (mi355cg_set_preconditioner)");
+    HIPCK(hipSetDevice(c->device));
+    if (int rc = upload_packed<double>(c, r, c->mg->q)) return rc;
+    mg_vcycle(c, 0, c->mg->q, c->mg->z, nullptr);
+    HIPCK(hipGetLastError());
+    return download_packed<double>(c, c->mg->z, z);
 }
 
 // ---- checksums (tests of large decomposed grids compare these instead of host copies of the vectors) -----------------

@@ -128,6 +128,23 @@ class _Handle:
         _capi.check(rc)
         return res
 
+    def set_preconditioner(self, kind: int):
+        """Extension (no reference twin): _capi.PRECOND_MG builds the multigrid hierarchy, after which solve() runs
+        preconditioned CG; _capi.PRECOND_NONE frees it (include/mi355cg.h, mi355cg_set_preconditioner)."""
+        rc = self._lib.mi355cg_set_preconditioner(self._h, int(kind))
+        if rc == _capi.ERR_INVALID:
+            raise ValueError(self._lib.mi355cg_last_error().decode())
+        _capi.check(rc)
+
+    def apply_preconditioner(self, r):
+        """z = M r for a packed vector r (needs set_preconditioner(PRECOND_MG) first)."""
+        r = np.ascontiguousarray(r, dtype=np.float64)
+        if r.shape != (self.size,):
+            raise ValueError(f"vector has shape {r.shape}, expected ({self.size},)")
+        z = np.empty(self.size)
+        _capi.check(self._lib.mi355cg_apply_preconditioner(self._h, r, z))
+        return z
+
     def setup_on_device(self):
         """Opt-in: regenerate b and u on the GPU (<= 1 ulp from the host values)."""
         _capi.check(self._lib.mi355cg_setup_on_device(self._h))
@@ -154,6 +171,17 @@ def default_params(rule: int) -> _capi.Params:
     return p
 
 
+def mg_levels(n: int):
+    """(levels, coarsest n) of the multigrid hierarchy of an n x n grid (host arithmetic, no GPU); ValueError if it has none."""
+    L, nc = C.c_int(), C.c_int()
+    lib = _capi.load()
+    rc = lib.mi355cg_mg_levels(int(n), C.byref(L), C.byref(nc))
+    if rc == _capi.ERR_INVALID:
+        raise ValueError(lib.mi355cg_last_error().decode())
+    _capi.check(rc)
+    return L.value, nc.value
+
+
 # ---------------------------------------------------------------------------------------------
 class MatrixFreeSystem:
     """solver/matrix_free_system.hpp:12-70.  Constructor order is (m, n, a, b, c, d)."""
@@ -175,6 +203,11 @@ class MatrixFreeSystem:
         return out
 
     def __mul__(self, x): return self.apply(x)             # operator* (matrix_free_system.hpp:59-63)
+
+    def set_preconditioner(self, kind: int):
+        """Extension (no reference twin): _capi.PRECOND_MG / PRECOND_NONE.  Every solver built on this system
+        (MatrixFreeSolver, MSGSolver) runs preconditioned CG while it is set."""
+        self._handle.set_preconditioner(kind)
 
 
 class GridSystem(MatrixFreeSystem):
