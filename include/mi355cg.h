@@ -25,6 +25,7 @@
  *                                  set, mi355cg_solve runs preconditioned CG (same stop rules, callbacks, stop flag, results)
  *   mi355cg_apply_preconditioner   z = M r on host vectors (packed order)
  *   mi355cg_mg_levels              the hierarchy a grid gets (pure host arithmetic, no GPU needed)
+ *   mi355cg_mg_hierarchy           every level's N of either multigrid kind (pure host arithmetic, no GPU needed)
  *
  * Plain pointers and sizes only; no C++/torch types.  All host vectors are in the reference's
  * PACKED unknown order (bottom-right block row-major, then the upper block row-major;
@@ -152,12 +153,27 @@ int  mi355cg_get_true_residual(mi355cg_handle h, double *ax_minus_b); /* A x - b
  * rule, callbacks, stop flag, fixed_iterations and result fields of the plain path; mi355cg_get_solution / _residual report it.
  * MG is refused (MI355CG_ERR_INVALID) on CSR handles, slab / part handles, MI355CG_F32_MIXED handles and grids without a
  * hierarchy.  Memory: level 0 adds five vectors of the handle's size, the coarser levels about one more, the inverse <= 4 MB.
- * set_preconditioner(MI355CG_PRECOND_NONE) frees it: the handle then runs exactly the plain path again.                      */
-#define MI355CG_PRECOND_NONE  0
-#define MI355CG_PRECOND_MG    1
+ * set_preconditioner(MI355CG_PRECOND_NONE) frees it: the handle then runs exactly the plain path again.
+ *
+ * MI355CG_PRECOND_MG_ANY: the same preconditioner for every grid mi355cg_create accepts (even n >= 6).  Its ladder is
+ * N_{l+1} = 2 floor(N_l / 4) while N_l > 32, so the coarsest level has 16 <= N_L <= 32 (or N_L = n when n <= 32): 1000 -> 500 ->
+ * 250 -> 124 -> 62 -> 30, 258 -> 128 -> 64 -> 32.  A level with N_l % 4 == 0 is nested (N_{l+1} = N_l / 2) and is exactly a
+ * PRECOND_MG level; where PRECOND_MG has a hierarchy the two kinds build the same one and give the same bits.  A non-nested
+ * level (N_l % 4 == 2) keeps the domain, hx_{l+1} = hx_l N_l / N_{l+1} (same in y), and transfers by the bilinear weights
+ * w(x, X) = max(0, 1 - |x N_c - X N_f| / N_f) between the two grids: P interpolates, R = (N_c / N_f)^2 P^T, so M is again
+ * symmetric and negative definite.  Refusals as for MG; set_preconditioner(MG) on a grid only MG_ANY covers is refused and
+ * leaves the handle as it was; switching kinds where both have a hierarchy keeps it.  Memory: since N_{l+1} <= N_l / 2, at
+ * most what PRECOND_MG needs for a grid of the same size.
+ * mi355cg_mg_hierarchy: *levels = the number of levels of kind's hierarchy for n, level_n[0 .. min(levels, max_levels) - 1]
+ * = N_0 = n, N_1, ...; MI355CG_ERR_INVALID if the kind has none for n (PRECOND_MG: 258, 1000), n is odd or < 6, or the kind
+ * is unknown.                                                                                                              */
+#define MI355CG_PRECOND_NONE    0
+#define MI355CG_PRECOND_MG      1
+#define MI355CG_PRECOND_MG_ANY  2
 int  mi355cg_set_preconditioner(mi355cg_handle h, int kind);                   /* builds or frees the hierarchy            */
 int  mi355cg_apply_preconditioner(mi355cg_handle h, const double *r, double *z); /* host vectors, packed; MI355CG_ERR_STATE if none is set */
-int  mi355cg_mg_levels(int n, int *levels, int *coarsest_n);                   /* MI355CG_ERR_INVALID: no hierarchy          */
+int  mi355cg_mg_levels(int n, int *levels, int *coarsest_n);                   /* PRECOND_MG; MI355CG_ERR_INVALID: no hierarchy */
+int  mi355cg_mg_hierarchy(int kind, int n, int max_levels, int *levels, int *level_n);   /* no GPU needed               */
 
 /* ---- measurement hooks (bench.py) ------------------------------------------------------------ */
 /* Per-kernel device time of the last mi355cg_solve, measured with HIP events on the solve

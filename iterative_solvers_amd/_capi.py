@@ -29,9 +29,10 @@ EXPORTS = [
     "mi355cg_team_solve", "mi355cg_team_info", "mi355cg_team_part", "mi355cg_team_get_vector", "mi355cg_team_set_vector", "mi355cg_team_checksum",
     "mi355cg_team_set_profiling", "mi355cg_team_phase_times", "mi355cg_team_describe", "mi355cg_setup_on_device", "mi355cg_team_setup_on_device", "mi355cg_debug_plan",
     "mi355cg_team_set_dtype", "mi355cg_set_preconditioner", "mi355cg_apply_preconditioner", "mi355cg_mg_levels",
+    "mi355cg_mg_hierarchy",
 ]
 DECOMP_ROWS, DECOMP_2D = 0, 1
-PRECOND_NONE, PRECOND_MG = 0, 1
+PRECOND_NONE, PRECOND_MG, PRECOND_MG_ANY = 0, 1, 2
 
 
 class Params(C.Structure):
@@ -160,6 +161,7 @@ def load():
     L.mi355cg_set_preconditioner.argtypes = [H, C.c_int]
     L.mi355cg_apply_preconditioner.argtypes = [H, _DP, _DP]
     L.mi355cg_mg_levels.argtypes = [C.c_int, IP, IP]
+    L.mi355cg_mg_hierarchy.argtypes = [C.c_int, C.c_int, C.c_int, IP, IP]
     _lib = L
     return L
 

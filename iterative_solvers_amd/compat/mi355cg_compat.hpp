@@ -409,8 +409,9 @@ public:
     }
     std::vector<double> operator*(const std::vector<double>& x) const { std::vector<double> y; apply(x, y); return y; }
     int size() const { return (int)rhs.size(); }
-    // Extension (the reference has no preconditioner): MI355CG_PRECOND_MG makes every solve on this system multigrid-preconditioned
-    // CG, MI355CG_PRECOND_NONE returns to plain CG.  std::invalid_argument for grids without a multigrid hierarchy.
+    // Extension (the reference has no preconditioner): MI355CG_PRECOND_MG_ANY (every grid) or MI355CG_PRECOND_MG (grids with a
+    // nested hierarchy, mi355cg_mg_levels) makes every solve on this system multigrid-preconditioned CG, MI355CG_PRECOND_NONE
+    // returns to plain CG.  std::invalid_argument for PRECOND_MG on a grid without a nested hierarchy.
     void setPreconditioner(int kind) { mi355cg_compat::check(mi355cg_set_preconditioner(ctx_->h, kind)); }
     const std::shared_ptr<mi355cg_compat::Context>& context() const { return ctx_; }
     friend std::ostream& operator<<(std::ostream& os, const MatrixFreeSystem& s) {
@@ -583,9 +584,9 @@ public:
         if (!devices_.empty()) grid->distribute(devices_, decomp_);
         if (precond_ != MI355CG_PRECOND_NONE) mi355cg_compat::check(mi355cg_set_preconditioner(grid->context()->h, precond_));
     }
-    // Extension (the reference has no preconditioner): MI355CG_PRECOND_MG = multigrid-preconditioned CG for the solves of this
-    // facade, single-GPU only (not together with setDevices).  Kept across setGridParameters; std::invalid_argument for grids
-    // without a multigrid hierarchy.
+    // Extension (the reference has no preconditioner): MI355CG_PRECOND_MG_ANY or MI355CG_PRECOND_MG = multigrid-preconditioned CG
+    // for the solves of this facade, single-GPU only (not together with setDevices).  The kind is kept across setGridParameters;
+    // MG_ANY takes every grid, std::invalid_argument for PRECOND_MG on a grid without a nested hierarchy (mi355cg_mg_levels).
     void setPreconditioner(int kind) {
         if (kind != MI355CG_PRECOND_NONE && !devices_.empty()) throw std::invalid_argument("the multigrid preconditioner is single-GPU only");
         if (grid) mi355cg_compat::check(mi355cg_set_preconditioner(grid->context()->h, kind));

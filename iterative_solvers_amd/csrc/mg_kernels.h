@@ -5,6 +5,9 @@
 //                   + per-block partials of (r, t): the (r, z) of the PCG, fused into the last sweep of level 0]
 //   k_mg_restrict   residual s = r - A u on the fine grid fused with full weighting onto the coarse interior
 //   k_mg_prolong    bilinear prolongation of the coarse correction fused with u += P e, masked to the fine interior
+//   k_mg_residual   s = r - A u at the fine interior nodes (non-nested levels, N_f % 4 == 2; into the level's work vector)
+//   k_mg_restrict_nn   R s = (N_c / N_f)^2 P^T s: a gather over the <= 5 x 5 fine nodes of a coarse node's bilinear support
+//   k_mg_prolong_nn    u += P e with the bilinear weights of non-nested grids, masked to the fine interior
 //   k_mg_coarse     coarsest level: z = A_L^-1 r, one dense mat-vec with the inverse built on the host
 //   k_mg_dir_apply  PCG direction p = z + beta p_old (ping-pong buffers) fused with q = A p and partials of (p, q)
 //   k_mg_update     x += alpha p, r -= alpha q with partials of (r, r), (dx, dx), (x - u, x - u) and the max-norms
@@ -89,6 +92,57 @@ __global__ __launch_bounds__(kBlock) void k_mg_prolong(const Geom gf, const Geom
         else if (x & 1) corr = 0.5 * (e00 + mg_at(gc, e, cx + 1, cy));
         else if (y & 1) corr = 0.5 * (e00 + mg_at(gc, e, cx, cy + 1));
         else corr = e00;
+        const long long o = mg_off(gf, x, y);
+        u[o] = u[o] + corr;
+    }
+}
+
+// ---- non-nested levels (MI355CG_PRECOND_MG_ANY, N_f % 4 == 2, N_c = 2 floor(N_f / 4) = (N_f - 2) / 2) -------------------------
+// 1-D bilinear weight of coarse node X at fine node x: the hat of coarse width around X at x's physical place x / N_f, i.e.
+// max(0, 1 - |x N_c - X N_f| / N_f).  The numerator is an exact integer, so P and R use the same bits.  At N_f = 2 N_c it gives
+// 1 and 1/2: the kernels above.
+__host__ __device__ inline double mg_w(int x, int X, int Nf, int Nc) {
+    long long d = (long long)x * Nc - (long long)X * Nf;
+    if (d < 0) d = -d;
+    return d < Nf ? (double)(Nf - d) / (double)Nf : 0.0;
+}
+
+// s = r - A u at fine interior nodes; nothing else is written, so s keeps the zero boundary of the level's vectors
+__global__ __launch_bounds__(kBlock) void k_mg_residual(const Geom g, const double* __restrict__ r, const double* __restrict__ u,
+                                                        double* __restrict__ s) {
+    MG_FOR_INTERIOR(g, x, y) {
+        const long long o = mg_off(g, x, y);
+        s[o] = r[o] - mg_Av(g, u, x, y);
+    }
+}
+
+// coarse interior node (X, Y) <- scale * sum over fine nodes y ascending, then x ascending, of w(y, Y) w(x, X) s(x, y), scale =
+// (N_c / N_f)^2.  The support |x N_c - X N_f| < N_f is x_lo..x_hi below, <= 5 nodes wide and inside 1..N_f - 1 for 1 <= X <= N_c - 1.
+__global__ __launch_bounds__(kBlock) void k_mg_restrict_nn(const Geom gf, const Geom gc, double scale, const double* __restrict__ s,
+                                                           double* __restrict__ rc) {
+    const int Nf = gf.N, Nc = gc.N;
+    MG_FOR_INTERIOR(gc, X, Y) {
+        const int x_lo = (int)((long long)(X - 1) * Nf / Nc) + 1, x_hi = (int)(((long long)(X + 1) * Nf - 1) / Nc);
+        const int y_lo = (int)((long long)(Y - 1) * Nf / Nc) + 1, y_hi = (int)(((long long)(Y + 1) * Nf - 1) / Nc);
+        double acc = 0.0;
+        for (int y = y_lo; y <= y_hi; ++y) {
+            const double wy = mg_w(y, Y, Nf, Nc);
+            for (int x = x_lo; x <= x_hi; ++x) acc += (wy * mg_w(x, X, Nf, Nc)) * mg_at(gf, s, x, y);
+        }
+        rc[mg_off(gc, X, Y)] = scale * acc;
+    }
+}
+
+// fine interior node (x, y): u += sum of w(x, X) w(y, Y) e(X, Y) over the coarse nodes X0 = floor(x N_c / N_f), X0 + 1 (same in y)
+__global__ __launch_bounds__(kBlock) void k_mg_prolong_nn(const Geom gf, const Geom gc, const double* __restrict__ e,
+                                                          double* __restrict__ u) {
+    const int Nf = gf.N, Nc = gc.N;
+    MG_FOR_INTERIOR(gf, x, y) {
+        const int X0 = (int)((long long)x * Nc / Nf), Y0 = (int)((long long)y * Nc / Nf);
+        const double wx0 = mg_w(x, X0, Nf, Nc), wx1 = mg_w(x, X0 + 1, Nf, Nc);
+        const double wy0 = mg_w(y, Y0, Nf, Nc), wy1 = mg_w(y, Y0 + 1, Nf, Nc);
+        const double corr = wy0 * (wx0 * mg_at(gc, e, X0, Y0) + wx1 * mg_at(gc, e, X0 + 1, Y0)) +
+                            wy1 * (wx0 * mg_at(gc, e, X0, Y0 + 1) + wx1 * mg_at(gc, e, X0 + 1, Y0 + 1));
         const long long o = mg_off(gf, x, y);
         u[o] = u[o] + corr;
     }

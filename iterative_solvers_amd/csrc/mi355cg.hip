@@ -63,10 +63,12 @@ struct EventPool {
 struct Plan { WorkList wl{}; int grid = 0; int ty = 0; };
 
 // Geometric multigrid preconditioner (mi355cg_set_preconditioner; kernels in mg_kernels.h).  Level 0 is the handle's grid; level
-// l + 1 has N_l / 2 intervals and doubled steps.  Per level: the right-hand side of its cycle (level 0: the caller's vector), a
-// work vector and the cycle's result (level 0: the caller's output); the coarsest level keeps its dense inverse.
+// l + 1 has 2 floor(N_l / 4) intervals (mg_shape) and the steps that keep the domain.  Per level: the right-hand side of its cycle
+// (level 0: the caller's vector), a work vector and the cycle's result (level 0: the caller's output); the coarsest level keeps
+// its dense inverse.
 struct MgLevel { Geom g{}; long long len = 0; int grid = 0; double *rhs = nullptr, *a = nullptr, *out = nullptr; };
 struct MgHier {
+    int kind = 0;                       // MI355CG_PRECOND_MG or _MG_ANY: the kind last set (where both have a hierarchy it is this one)
     std::vector<MgLevel> lv;
     int ncoarse = 0;                    // unknowns of the coarsest level
     double* inv = nullptr;              // A_L^-1, ncoarse x ncoarse, row-major (unknowns in packed order)
@@ -802,25 +804,30 @@ int solve_mixed(mi355cg_ctx* c, const mi355cg_params* prm, mi355cg_iter_cb cb, v
 }  // namespace
 
 // ---- geometric multigrid preconditioner and the preconditioned CG on it (opt-in) -----------------
-// Algorithm (fixed; tests/test_mg_cpu.py restates it in NumPy):  V(r, l): u = 0, two damped-Jacobi sweeps (omega = 0.8),
-// s = r - A_l u restricted by full weighting, u += P V(R s, l + 1), two more sweeps; the coarsest level solves with the dense
-// inverse.  R = P^T / 4 and equal pre- and post-smoothers make M symmetric; A is negative definite and so is M, (r, z) < 0.
+// Algorithm (fixed; tests/test_mg_cpu.py restates it in NumPy, tests/test_mg_any_cpu.py its non-nested levels):  V(r, l): u = 0,
+// two damped-Jacobi sweeps (omega = 0.8), s = r - A_l u restricted, u += P V(R s, l + 1), two more sweeps; the coarsest level
+// solves with the dense inverse.  A nested level (N_l = 2 N_{l+1}) uses full weighting and bilinear P, R = P^T / 4; a non-nested
+// one the bilinear P between the two grids and R = (N_{l+1} / N_l)^2 P^T.  R proportional to P^T and equal pre- and
+// post-smoothers make M symmetric; A is negative definite and so is M, (r, z) < 0.
 // PCG (Hestenes-Stiefel, x0 = 0) driven from the host: the scalars of an iteration come back from three short waits (after the
 // cycle, after q = A p, after the update), which lets the stop rules, callbacks and stop flag run exactly as in the plain path.
 namespace {
 
 constexpr double kMgOmega = 0.8;
 
-// N_{l+1} = N_l / 2 while N_l % 4 == 0 and N_l > 32; the coarsest level must have N_L <= 32.  Pure host arithmetic.
-int mg_shape(int n, int* levels, int* coarsest) {
+// The intervals N_0 = n, N_1, ... of a kind's levels.  MI355CG_PRECOND_MG: N_{l+1} = N_l / 2 while N_l % 4 == 0 and N_l > 32, and
+// the coarsest level must have N_L <= 32.  MI355CG_PRECOND_MG_ANY: N_{l+1} = 2 floor(N_l / 4) while N_l > 32, so every even n >= 6
+// has one (16 <= N_L <= 32, or N_L = n <= 32); where MG has a hierarchy the two ladders are the same.  Pure host arithmetic.
+int mg_shape(int kind, int n, std::vector<int>* ns) {
+    if (kind != MI355CG_PRECOND_MG && kind != MI355CG_PRECOND_MG_ANY)
+        return fail(MI355CG_ERR_INVALID, "preconditioner kind %d has no multigrid hierarchy (MI355CG_PRECOND_MG = 1, MI355CG_PRECOND_MG_ANY = 2)", kind);
     if (n < 6 || n % 2 != 0) return fail(MI355CG_ERR_INVALID, "grid %d rejected: the L-shaped index map needs an even n >= 6", n);
-    int N = n, L = 1;
-    while (N % 4 == 0 && N > 32) { N /= 2; ++L; }
+    ns->assign(1, n);
+    int N = n;
+    while (N > 32 && (kind == MI355CG_PRECOND_MG_ANY || N % 4 == 0)) { N = 2 * (N / 4); ns->push_back(N); }
     if (N > 32)
         return fail(MI355CG_ERR_INVALID, "grid %d has no multigrid hierarchy: halving stops at N = %d, and the coarsest grid must have "
                     "N <= 32 (a level is halved while N %% 4 == 0 and N > 32)", n, N);
-    if (levels) *levels = L;
-    if (coarsest) *coarsest = N;
     return MI355CG_OK;
 }
 
@@ -899,15 +906,20 @@ void mg_coarse_inverse(const Geom& g, std::vector<double>& inv, std::vector<int>
         }
 }
 
-int mg_build(mi355cg_ctx* c, MgHier** out) {
-    int nl = 0;
-    if (int rc = mg_shape(c->gp.n, &nl, nullptr)) return rc;
+int mg_build(mi355cg_ctx* c, int kind, MgHier** out) {
+    std::vector<int> ns;
+    if (int rc = mg_shape(kind, c->gp.n, &ns)) return rc;
+    const int nl = (int)ns.size();
     MgHier* H = new MgHier();
     auto bail = [&](int rc) { mg_free(H); return rc; };
+    H->kind = kind;
     H->lv.resize(nl);
+    double hx = c->gp.x_step, hy = c->gp.y_step;
     for (int l = 0; l < nl; ++l) {
         MgLevel& L = H->lv[l];
-        L.g = mg_geom(c->gp.n >> l, std::ldexp(c->gp.x_step, l), std::ldexp(c->gp.y_step, l), &L.len);
+        if (l > 0 && ns[l - 1] == 2 * ns[l]) { hx = std::ldexp(hx, 1); hy = std::ldexp(hy, 1); }   // nested: exactly doubled
+        else if (l > 0) { hx = hx * ns[l - 1] / ns[l]; hy = hy * ns[l - 1] / ns[l]; }              // non-nested: same domain
+        L.g = mg_geom(ns[l], hx, hy, &L.len);
         L.grid = std::min(L.g.N - 1, kMgMaxGrid);
         if (l > 0) { if (int rc = alloc_vec(&L.rhs, L.len)) return bail(rc); if (int rc = alloc_vec(&L.out, L.len)) return bail(rc); }
         if (l + 1 < nl) if (int rc = alloc_vec(&L.a, L.len)) return bail(rc);
@@ -946,11 +958,19 @@ void mg_vcycle(mi355cg_ctx* c, int l, const double* rhs, double* out, double* do
         return;
     }
     const MgLevel& C = H.lv[l + 1];
+    const bool nested = L.g.N == 2 * C.g.N;
     hipLaunchKernelGGL((k_mg_smooth<true, false>), grid, blk, 0, st, L.g, kMgOmega, rhs, (const double*)nullptr, L.a, (double*)nullptr);
     hipLaunchKernelGGL((k_mg_smooth<false, false>), grid, blk, 0, st, L.g, kMgOmega, rhs, (const double*)L.a, out, (double*)nullptr);
-    hipLaunchKernelGGL(k_mg_restrict, dim3(C.grid), blk, 0, st, L.g, C.g, rhs, (const double*)out, C.rhs);
+    if (nested) {
+        hipLaunchKernelGGL(k_mg_restrict, dim3(C.grid), blk, 0, st, L.g, C.g, rhs, (const double*)out, C.rhs);
+    } else {                            // L.a is free until the first post-sweep: it holds s = rhs - A out for the gather
+        const double scale = (double)((long long)C.g.N * C.g.N) / (double)((long long)L.g.N * L.g.N);
+        hipLaunchKernelGGL(k_mg_residual, grid, blk, 0, st, L.g, rhs, (const double*)out, L.a);
+        hipLaunchKernelGGL(k_mg_restrict_nn, dim3(C.grid), blk, 0, st, L.g, C.g, scale, (const double*)L.a, C.rhs);
+    }
     mg_vcycle(c, l + 1, C.rhs, C.out, nullptr);
-    hipLaunchKernelGGL(k_mg_prolong, grid, blk, 0, st, L.g, C.g, (const double*)C.out, out);
+    if (nested) hipLaunchKernelGGL(k_mg_prolong, grid, blk, 0, st, L.g, C.g, (const double*)C.out, out);
+    else hipLaunchKernelGGL(k_mg_prolong_nn, grid, blk, 0, st, L.g, C.g, (const double*)C.out, out);
     hipLaunchKernelGGL((k_mg_smooth<false, false>), grid, blk, 0, st, L.g, kMgOmega, rhs, (const double*)out, L.a, (double*)nullptr);
     if (dot) hipLaunchKernelGGL((k_mg_smooth<false, true>), grid, blk, 0, st, L.g, kMgOmega, rhs, (const double*)L.a, out, dot);
     else hipLaunchKernelGGL((k_mg_smooth<false, false>), grid, blk, 0, st, L.g, kMgOmega, rhs, (const double*)L.a, out, (double*)nullptr);
@@ -1600,12 +1620,28 @@ int mi355cg_get_layout(mi355cg_handle c, long long* padded_len, int* pitch_botto
 }
 
 // ---- geometric multigrid preconditioner (opt-in) ----------------------------------------------------------------------
-int mi355cg_mg_levels(int n, int* levels, int* coarsest_n) { return mg_shape(n, levels, coarsest_n); }
+int mi355cg_mg_levels(int n, int* levels, int* coarsest_n) {
+    std::vector<int> ns;
+    if (int rc = mg_shape(MI355CG_PRECOND_MG, n, &ns)) return rc;
+    if (levels) *levels = (int)ns.size();
+    if (coarsest_n) *coarsest_n = ns.back();
+    return MI355CG_OK;
+}
+
+int mi355cg_mg_hierarchy(int kind, int n, int max_levels, int* levels, int* level_n) {
+    if (max_levels < 0 || (max_levels > 0 && !level_n)) return fail(MI355CG_ERR_INVALID, "level_n must hold max_levels >= 0 entries");
+    std::vector<int> ns;
+    if (int rc = mg_shape(kind, n, &ns)) return rc;
+    if (levels) *levels = (int)ns.size();
+    for (int l = 0; l < (int)ns.size() && l < max_levels; ++l) level_n[l] = ns[l];
+    return MI355CG_OK;
+}
 
 int mi355cg_set_preconditioner(mi355cg_handle c, int kind) {
     if (!c) return fail(MI355CG_ERR_INVALID, "null handle");
-    if (kind != MI355CG_PRECOND_NONE && kind != MI355CG_PRECOND_MG)
-        return fail(MI355CG_ERR_INVALID, "unknown preconditioner kind %d (MI355CG_PRECOND_NONE = 0, MI355CG_PRECOND_MG = 1)", kind);
+    if (kind != MI355CG_PRECOND_NONE && kind != MI355CG_PRECOND_MG && kind != MI355CG_PRECOND_MG_ANY)
+        return fail(MI355CG_ERR_INVALID, "unknown preconditioner kind %d (MI355CG_PRECOND_NONE = 0, MI355CG_PRECOND_MG = 1, "
+                    "MI355CG_PRECOND_MG_ANY = 2)", kind);
     HIPCK(hipSetDevice(c->device));
     if (kind == MI355CG_PRECOND_NONE) {
         if (c->mg) { HIPCK(hipStreamSynchronize(c->stream)); mg_free(c->mg); c->mg = nullptr; }
@@ -1614,8 +1650,10 @@ int mi355cg_set_preconditioner(mi355cg_handle c, int kind) {
     if (c->is_csr) return fail(MI355CG_ERR_INVALID, "the multigrid preconditioner needs the grid operator: a CSR handle has no grid");
     if (c->is_slab) return fail(MI355CG_ERR_INVALID, "the multigrid preconditioner is single-GPU only: this handle owns one part of a decomposed grid");
     if (c->dtype != MI355CG_F64) return fail(MI355CG_ERR_INVALID, "the multigrid preconditioner is fp64 only: this handle was created with MI355CG_F32_MIXED");
-    if (c->mg) return MI355CG_OK;
-    return mg_build(c, &c->mg);
+    std::vector<int> ns;
+    if (int rc = mg_shape(kind, c->gp.n, &ns)) return rc;          // refused: the handle keeps what it had
+    if (c->mg) { c->mg->kind = kind; return MI355CG_OK; }            // both kinds have a hierarchy here: it is the same one
+    return mg_build(c, kind, &c->mg);
 }
 
 // z = M r on host vectors (packed order).  Works on the PCG's q (input) and z (output), which hold nothing between iterations,

@@ -129,15 +129,17 @@ class _Handle:
         return res
 
     def set_preconditioner(self, kind: int):
-        """Extension (no reference twin): _capi.PRECOND_MG builds the multigrid hierarchy, after which solve() runs
-        preconditioned CG; _capi.PRECOND_NONE frees it (include/mi355cg.h, mi355cg_set_preconditioner)."""
+        """Extension (no reference twin): _capi.PRECOND_MG (grids with a nested hierarchy, see mg_levels) or _capi.PRECOND_MG_ANY
+        (every grid, see mg_hierarchy) builds the multigrid hierarchy, after which solve() runs preconditioned CG;
+        _capi.PRECOND_NONE frees it (include/mi355cg.h, mi355cg_set_preconditioner).  ValueError if refused; the handle then
+        keeps what it had."""
         rc = self._lib.mi355cg_set_preconditioner(self._h, int(kind))
         if rc == _capi.ERR_INVALID:
             raise ValueError(self._lib.mi355cg_last_error().decode())
         _capi.check(rc)
 
     def apply_preconditioner(self, r):
-        """z = M r for a packed vector r (needs set_preconditioner(PRECOND_MG) first)."""
+        """z = M r for a packed vector r (needs set_preconditioner(PRECOND_MG or PRECOND_MG_ANY) first)."""
         r = np.ascontiguousarray(r, dtype=np.float64)
         if r.shape != (self.size,):
             raise ValueError(f"vector has shape {r.shape}, expected ({self.size},)")
@@ -182,6 +184,19 @@ def mg_levels(n: int):
     return L.value, nc.value
 
 
+def mg_hierarchy(n: int, kind: int = _capi.PRECOND_MG_ANY):
+    """The intervals (N_0 = n, N_1, ..., N_L) of the multigrid levels kind builds for an n x n grid (host arithmetic, no GPU);
+    ValueError if kind has none for n, n is odd or < 6, or kind is not a multigrid kind."""
+    L = C.c_int()
+    buf = (C.c_int * 64)()
+    lib = _capi.load()
+    rc = lib.mi355cg_mg_hierarchy(int(kind), int(n), len(buf), C.byref(L), buf)
+    if rc == _capi.ERR_INVALID:
+        raise ValueError(lib.mi355cg_last_error().decode())
+    _capi.check(rc)
+    return tuple(buf[:L.value])
+
+
 # ---------------------------------------------------------------------------------------------
 class MatrixFreeSystem:
     """solver/matrix_free_system.hpp:12-70.  Constructor order is (m, n, a, b, c, d)."""
@@ -205,7 +220,7 @@ class MatrixFreeSystem:
     def __mul__(self, x): return self.apply(x)             # operator* (matrix_free_system.hpp:59-63)
 
     def set_preconditioner(self, kind: int):
-        """Extension (no reference twin): _capi.PRECOND_MG / PRECOND_NONE.  Every solver built on this system
+        """Extension (no reference twin): _capi.PRECOND_MG / PRECOND_MG_ANY / PRECOND_NONE.  Every solver built on this system
         (MatrixFreeSolver, MSGSolver) runs preconditioned CG while it is set."""
         self._handle.set_preconditioner(kind)
 

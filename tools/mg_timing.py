@@ -5,7 +5,11 @@ For every N and rule: one handle, the plain solve, then set_preconditioner(MG) (
 preconditioned solve; each solve twice, the faster wall time reported.  Rules: REL_2NORM eps 1e-8 (no iteration cap in effect)
 and the MSG rule with mi355cg_default_params (eps 1e-6, at most 10 000 iterations, the true solution in the error norm).
 The true relative residual ||b - A x|| / ||b|| comes from mi355cg_get_true_residual.
-Usage: python tools/mg_timing.py [N ...]      (default 256 1024 4096 8192; writes profiles/mg_time_to_solution.txt)"""
+--kind any: the plain solve, MG where the grid has a nested hierarchy, and MG_ANY (MI355CG_PRECOND_MG_ANY), each preconditioner
+built afresh on the handle.
+Usage: python tools/mg_timing.py [N ...]      (default 256 1024 4096 8192; writes profiles/mg_time_to_solution.txt)
+       python tools/mg_timing.py --kind any [N ...]   (default 100 258 1000 1002 4096 4098 10000;
+                                                      writes profiles/mg_any_time_to_solution.txt)"""
 import os
 import sys
 import time
@@ -17,7 +21,9 @@ sys.path.insert(0, ROOT)
 import iterative_solvers_amd as isa  # noqa: E402
 from iterative_solvers_amd import _capi  # noqa: E402
 
-OUT = os.path.join(ROOT, "profiles", "mg_time_to_solution.txt")
+OUT = {"mg": os.path.join(ROOT, "profiles", "mg_time_to_solution.txt"),
+       "any": os.path.join(ROOT, "profiles", "mg_any_time_to_solution.txt")}
+SIZES = {"mg": [256, 1024, 4096, 8192], "any": [100, 258, 1000, 1002, 4096, 4098, 10000]}
 RULES = {"REL_2NORM 1e-8": _capi.RULE_REL_2NORM, "MSG defaults": _capi.RULE_MSG_MAXNORM}
 
 
@@ -41,32 +47,53 @@ def run(h, rule, b_norm):
     return wall, res, rel
 
 
-def main(ns):
-    lines = ["# time to solution on one MI355X: plain CG against MG-preconditioned CG (tools/mg_timing.py)",
+def main(ns, kind="mg"):
+    pw = 5 if kind == "mg" else 6
+    what = "MG-preconditioned CG" if kind == "mg" else "MG- and MG_ANY-preconditioned CG"
+    lines = [f"# time to solution on one MI355X: plain CG against {what} (tools/mg_timing.py{' --kind any' if kind == 'any' else ''})",
              "# wall = host wall time of mi355cg_solve (best of 2); solve_s = mi355cg_results.solve_seconds; true_rel = ||b - A x|| / ||b||",
-             f"# {'N':>5} {'rule':<15} {'path':<5} {'iters':>7} {'stop':>5} {'conv':>4} {'wall_s':>10} {'solve_s':>10} {'true_rel':>9}  speed-up"]
+             f"# {'N':>5} {'rule':<15} {'path':<{pw}} {'iters':>7} {'stop':>5} {'conv':>4} {'wall_s':>10} {'solve_s':>10} {'true_rel':>9}  speed-up"]
     print("\n".join(lines), flush=True)
     for n in ns:
         s = isa.MatrixFreeSystem(n, n, 1.0, 2.0, 1.0, 2.0)
         h = s._handle
         b_norm = np.linalg.norm(s.get_rhs())
+        kinds = [("MG", isa.PRECOND_MG)]
+        if kind == "any":
+            try:
+                isa.mg_levels(n)
+            except ValueError:
+                kinds = []
+            kinds.append(("MG_ANY", isa.PRECOND_MG_ANY))
         for name, rule in RULES.items():
             h.set_preconditioner(isa.PRECOND_NONE)
             wp, rp, tp = run(h, rule, b_norm)
-            t0 = time.perf_counter()
-            h.set_preconditioner(isa.PRECOND_MG)
-            setup = time.perf_counter() - t0
-            wm, rm, tm = run(h, rule, b_norm)
-            for path, w, r, t, extra in (("plain", wp, rp, tp, ""), ("MG", wm, rm, tm, f"  {wp / wm:8.1f}x  (MG set-up {setup:.3f} s)")):
-                line = (f"  {n:>5} {name:<15} {path:<5} {r.iterations:>7} {r.stop_reason:>5} {r.converged:>4} {w:>10.4f} "
+            rows = [("plain", wp, rp, tp, "")]
+            for path, pk in kinds:
+                h.set_preconditioner(isa.PRECOND_NONE)                      # every kind builds its own hierarchy
+                t0 = time.perf_counter()
+                h.set_preconditioner(pk)
+                setup = time.perf_counter() - t0
+                wm, rm, tm = run(h, rule, b_norm)
+                rows.append((path, wm, rm, tm, f"  {wp / wm:8.1f}x  ({path} set-up {setup:.3f} s)"))
+            for path, w, r, t, extra in rows:
+                line = (f"  {n:>5} {name:<15} {path:<{pw}} {r.iterations:>7} {r.stop_reason:>5} {r.converged:>4} {w:>10.4f} "
                         f"{r.solve_seconds:>10.4f} {t:>9.2e}{extra}")
                 lines.append(line)
                 print(line, flush=True)
         h.close()
-    with open(OUT, "w") as f:
+    with open(OUT[kind], "w") as f:
         f.write("\n".join(lines) + "\n")
-    print("wrote", OUT)
+    print("wrote", OUT[kind])
 
 
 if __name__ == "__main__":
-    main([int(a) for a in sys.argv[1:]] or [256, 1024, 4096, 8192])
+    args = sys.argv[1:]
+    kind = "mg"
+    if "--kind" in args:
+        i = args.index("--kind")
+        kind = args[i + 1]
+        del args[i:i + 2]
+        if kind not in OUT:
+            sys.exit(f"--kind must be one of {sorted(OUT)}")
+    main([int(a) for a in args] or SIZES[kind], kind)
