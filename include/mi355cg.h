@@ -23,6 +23,8 @@
  * Extension without a reference counterpart (the reference has no preconditioner):
  *   mi355cg_set_preconditioner     opt-in geometric multigrid V-cycle M ~ A^-1 for single-GPU fp64 grid handles; while it is
  *                                  set, mi355cg_solve runs preconditioned CG (same stop rules, callbacks, stop flag, results)
+ *   mi355cg_set_preconditioner_ex  the same with the precision of the V-cycle: MI355CG_CYCLE_F64 or MI355CG_CYCLE_F32
+ *   mi355cg_preconditioner_info    kind, cycle precision and number of levels of what is set
  *   mi355cg_apply_preconditioner   z = M r on host vectors (packed order)
  *   mi355cg_mg_levels              the hierarchy a grid gets (pure host arithmetic, no GPU needed)
  *   mi355cg_mg_hierarchy           every level's N of either multigrid kind (pure host arithmetic, no GPU needed)
@@ -174,6 +176,23 @@ int  mi355cg_set_preconditioner(mi355cg_handle h, int kind);                   /
 int  mi355cg_apply_preconditioner(mi355cg_handle h, const double *r, double *z); /* host vectors, packed; MI355CG_ERR_STATE if none is set */
 int  mi355cg_mg_levels(int n, int *levels, int *coarsest_n);                   /* PRECOND_MG; MI355CG_ERR_INVALID: no hierarchy */
 int  mi355cg_mg_hierarchy(int kind, int n, int max_levels, int *levels, int *level_n);   /* no GPU needed               */
+
+/* Precision of the V-cycle of either kind.  MI355CG_CYCLE_F32: z = M32 r runs the same cycle (hierarchy, V(2,2), omega, transfer
+ * operators, expression order) with every vector, constant and operation in fp32, on r32 = fl32(r / s), s = 2^e the power of two
+ * with 0.5 <= max|r| / s < 1, and returns z = s * (double) z32; max|r| = 0 gives z = 0.  The level constants, the non-nested
+ * weights and the coarse inverse are the fp64 values rounded to fp32.  The PCG around it stays fp64: vectors, (r, z), (p, A p),
+ * the norms and the stop tests, so the accuracy of the answer is that of the fp64 cycle and the iteration counts are the same
+ * (DESIGN section 10.2); the scale makes M32(2^k r) = 2^k M32(r) bit for bit.  One-level grids (n <= 32), where the fp64 cycle
+ * is the exact inverse and a solve takes one iteration, take a second one.  Memory: about that of the fp64 hierarchy.
+ * mi355cg_set_preconditioner(h, kind) is mi355cg_set_preconditioner_ex(h, kind, MI355CG_CYCLE_F64).  _ex refuses what
+ * set_preconditioner refuses, and an unknown cycle (MI355CG_ERR_INVALID); a refused call leaves the handle as it was.  Changing
+ * only the precision rebuilds the levels' vectors; MI355CG_PRECOND_NONE frees everything whatever cycle says.
+ * mi355cg_preconditioner_info: what is set (kind MI355CG_PRECOND_NONE, cycle MI355CG_CYCLE_F64, levels 0 without a
+ * preconditioner); null out-pointers are skipped.                                                                          */
+#define MI355CG_CYCLE_F64 0   /* the V-cycle in fp64: what mi355cg_set_preconditioner builds */
+#define MI355CG_CYCLE_F32 1   /* the V-cycle in fp32 inside the fp64 PCG */
+int  mi355cg_set_preconditioner_ex(mi355cg_handle h, int kind, int cycle);
+int  mi355cg_preconditioner_info(mi355cg_handle h, int *kind, int *cycle, int *levels);
 
 /* ---- measurement hooks (bench.py) ------------------------------------------------------------ */
 /* Per-kernel device time of the last mi355cg_solve, measured with HIP events on the solve

@@ -29,10 +29,11 @@ EXPORTS = [
     "mi355cg_team_solve", "mi355cg_team_info", "mi355cg_team_part", "mi355cg_team_get_vector", "mi355cg_team_set_vector", "mi355cg_team_checksum",
     "mi355cg_team_set_profiling", "mi355cg_team_phase_times", "mi355cg_team_describe", "mi355cg_setup_on_device", "mi355cg_team_setup_on_device", "mi355cg_debug_plan",
     "mi355cg_team_set_dtype", "mi355cg_set_preconditioner", "mi355cg_apply_preconditioner", "mi355cg_mg_levels",
-    "mi355cg_mg_hierarchy",
+    "mi355cg_mg_hierarchy", "mi355cg_set_preconditioner_ex", "mi355cg_preconditioner_info",
 ]
 DECOMP_ROWS, DECOMP_2D = 0, 1
 PRECOND_NONE, PRECOND_MG, PRECOND_MG_ANY = 0, 1, 2
+CYCLE_F64, CYCLE_F32 = 0, 1
 
 
 class Params(C.Structure):
@@ -159,6 +160,8 @@ def load():
     L.mi355cg_team_phase_times.argtypes = [H, DBP, DBP, DBP]
     L.mi355cg_team_describe.argtypes = [H, C.c_char_p, C.c_int]
     L.mi355cg_set_preconditioner.argtypes = [H, C.c_int]
+    L.mi355cg_set_preconditioner_ex.argtypes = [H, C.c_int, C.c_int]
+    L.mi355cg_preconditioner_info.argtypes = [H, IP, IP, IP]
     L.mi355cg_apply_preconditioner.argtypes = [H, _DP, _DP]
     L.mi355cg_mg_levels.argtypes = [C.c_int, IP, IP]
     L.mi355cg_mg_hierarchy.argtypes = [C.c_int, C.c_int, C.c_int, IP, IP]

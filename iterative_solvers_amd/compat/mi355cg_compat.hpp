@@ -412,7 +412,8 @@ public:
     // Extension (the reference has no preconditioner): MI355CG_PRECOND_MG_ANY (every grid) or MI355CG_PRECOND_MG (grids with a
     // nested hierarchy, mi355cg_mg_levels) makes every solve on this system multigrid-preconditioned CG, MI355CG_PRECOND_NONE
     // returns to plain CG.  std::invalid_argument for PRECOND_MG on a grid without a nested hierarchy.
-    void setPreconditioner(int kind) { mi355cg_compat::check(mi355cg_set_preconditioner(ctx_->h, kind)); }
+    // cycle: MI355CG_CYCLE_F32 runs the V-cycle in fp32 inside the fp64 PCG (mi355cg_set_preconditioner_ex).
+    void setPreconditioner(int kind, int cycle = MI355CG_CYCLE_F64) { mi355cg_compat::check(mi355cg_set_preconditioner_ex(ctx_->h, kind, cycle)); }
     const std::shared_ptr<mi355cg_compat::Context>& context() const { return ctx_; }
     friend std::ostream& operator<<(std::ostream& os, const MatrixFreeSystem& s) {
         return os << "MatrixFreeSystem Information:\n  Dimensions: " << s.ctx_->n << "x" << s.ctx_->m << "\n  System size: " << s.size() << "\n";
@@ -582,15 +583,19 @@ public:
         solver.reset();
         grid = std::make_unique<GridSystem>(m_internal, n_internal, a_bound, b_bound, c_bound, d_bound);
         if (!devices_.empty()) grid->distribute(devices_, decomp_);
-        if (precond_ != MI355CG_PRECOND_NONE) mi355cg_compat::check(mi355cg_set_preconditioner(grid->context()->h, precond_));
+        if (precond_ != MI355CG_PRECOND_NONE) mi355cg_compat::check(mi355cg_set_preconditioner_ex(grid->context()->h, precond_, cycle_));
     }
     // Extension (the reference has no preconditioner): MI355CG_PRECOND_MG_ANY or MI355CG_PRECOND_MG = multigrid-preconditioned CG
     // for the solves of this facade, single-GPU only (not together with setDevices).  The kind is kept across setGridParameters;
     // MG_ANY takes every grid, std::invalid_argument for PRECOND_MG on a grid without a nested hierarchy (mi355cg_mg_levels).
-    void setPreconditioner(int kind) {
+    // cycle (MI355CG_CYCLE_F64 or MI355CG_CYCLE_F32, the V-cycle in fp32) is kept with the kind.
+    void setPreconditioner(int kind, int cycle = MI355CG_CYCLE_F64) {
         if (kind != MI355CG_PRECOND_NONE && !devices_.empty()) throw std::invalid_argument("the multigrid preconditioner is single-GPU only");
-        if (grid) mi355cg_compat::check(mi355cg_set_preconditioner(grid->context()->h, kind));
+        if (grid) mi355cg_compat::check(mi355cg_set_preconditioner_ex(grid->context()->h, kind, cycle));
+        else if (kind != MI355CG_PRECOND_NONE && cycle != MI355CG_CYCLE_F64 && cycle != MI355CG_CYCLE_F32)
+            throw std::invalid_argument("unknown V-cycle precision (MI355CG_CYCLE_F64 = 0, MI355CG_CYCLE_F32 = 1)");
         precond_ = kind;
+        cycle_ = cycle;
     }
     void setSolverParameters(double eps_p, double eps_r, double eps_e, int max_iter) {
         eps_precision = eps_p; eps_residual = eps_r; eps_exact_error = eps_e; max_iterations = max_iter;
@@ -674,4 +679,5 @@ private:
     std::vector<int> devices_;
     int decomp_ = MI355CG_DECOMP_ROWS;
     int precond_ = MI355CG_PRECOND_NONE;
+    int cycle_ = MI355CG_CYCLE_F64;
 };

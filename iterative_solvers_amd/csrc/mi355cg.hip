@@ -7,6 +7,7 @@
 #include "csr_kernels.h"
 #include "grid_setup.h"
 #include "mg_kernels.h"
+#include "mg_kernels_f32.h"
 
 #include <algorithm>
 #include <chrono>
@@ -67,9 +68,15 @@ struct Plan { WorkList wl{}; int grid = 0; int ty = 0; };
 // (level 0: the caller's vector), a work vector and the cycle's result (level 0: the caller's output); the coarsest level keeps
 // its dense inverse.
 struct MgLevel { Geom g{}; long long len = 0; int grid = 0; double *rhs = nullptr, *a = nullptr, *out = nullptr; };
+// The same three vectors of a level in fp32 (MI355CG_CYCLE_F32; level 0 too: r32, the work vector, the iterate) with the level's
+// constants rounded to fp32; vec: columns per lane of its kernels (mg_kernels_f32.h)
+struct MgLevel32 { float *rhs = nullptr, *a = nullptr, *out = nullptr; MgCoef32 c{}; float scale = 0.f; int vec = 1; };
 struct MgHier {
     int kind = 0;                       // MI355CG_PRECOND_MG or _MG_ANY: the kind last set (where both have a hierarchy it is this one)
+    int cycle = MI355CG_CYCLE_F64;      // precision of the V-cycle; F32 keeps lv32 / inv32 instead of the levels' fp64 vectors and inv
     std::vector<MgLevel> lv;
+    std::vector<MgLevel32> lv32;
+    float* inv32 = nullptr;             // A_L^-1 rounded to fp32
     int ncoarse = 0;                    // unknowns of the coarsest level
     double* inv = nullptr;              // A_L^-1, ncoarse x ncoarse, row-major (unknowns in packed order)
     int* coff = nullptr;                // storage offset of every coarsest unknown
@@ -849,6 +856,8 @@ void mg_free(MgHier* H) {
     if (!H) return;
     for (auto& L : H->lv) for (double* v : {L.rhs, L.a, L.out}) if (v) hipFree(v);
     for (double* v : {H->inv, H->z, H->p[0], H->p[1], H->q, H->part}) if (v) hipFree(v);
+    for (auto& L : H->lv32) for (float* v : {L.rhs, L.a, L.out}) if (v) hipFree(v);
+    if (H->inv32) hipFree(H->inv32);
     if (H->coff) hipFree(H->coff);
     if (H->part_h) hipHostFree(H->part_h);
     delete H;
@@ -906,13 +915,17 @@ void mg_coarse_inverse(const Geom& g, std::vector<double>& inv, std::vector<int>
         }
 }
 
-int mg_build(mi355cg_ctx* c, int kind, MgHier** out) {
+int mg_build32(MgHier* H, const std::vector<double>& inv);
+
+int mg_build(mi355cg_ctx* c, int kind, MgHier** out, int cycle = MI355CG_CYCLE_F64) {
     std::vector<int> ns;
     if (int rc = mg_shape(kind, c->gp.n, &ns)) return rc;
     const int nl = (int)ns.size();
     MgHier* H = new MgHier();
     auto bail = [&](int rc) { mg_free(H); return rc; };
     H->kind = kind;
+    H->cycle = cycle;
+    const bool f64 = cycle == MI355CG_CYCLE_F64;
     H->lv.resize(nl);
     double hx = c->gp.x_step, hy = c->gp.y_step;
     for (int l = 0; l < nl; ++l) {
@@ -921,6 +934,7 @@ int mg_build(mi355cg_ctx* c, int kind, MgHier** out) {
         else if (l > 0) { hx = hx * ns[l - 1] / ns[l]; hy = hy * ns[l - 1] / ns[l]; }              // non-nested: same domain
         L.g = mg_geom(ns[l], hx, hy, &L.len);
         L.grid = std::min(L.g.N - 1, kMgMaxGrid);
+        if (!f64) continue;                                     // the fp32 cycle has its own vectors (mg_build32)
         if (l > 0) { if (int rc = alloc_vec(&L.rhs, L.len)) return bail(rc); if (int rc = alloc_vec(&L.out, L.len)) return bail(rc); }
         if (l + 1 < nl) if (int rc = alloc_vec(&L.a, L.len)) return bail(rc);
     }
@@ -936,8 +950,11 @@ int mg_build(mi355cg_ctx* c, int kind, MgHier** out) {
     mg_coarse_inverse(H->lv.back().g, inv, off);
     H->ncoarse = (int)off.size();
     if (H->ncoarse > kMgMaxCoarse) return bail(fail(MI355CG_ERR_STATE, "coarsest grid has %d unknowns (> %d)", H->ncoarse, kMgMaxCoarse));
-    if (hipMalloc((void**)&H->inv, sizeof(double) * inv.size()) != hipSuccess || hipMalloc((void**)&H->coff, sizeof(int) * off.size()) != hipSuccess ||
-        hipMemcpy(H->inv, inv.data(), sizeof(double) * inv.size(), hipMemcpyHostToDevice) != hipSuccess ||
+    if (!f64) { if (int rc = mg_build32(H, inv)) return bail(rc); }
+    else if (hipMalloc((void**)&H->inv, sizeof(double) * inv.size()) != hipSuccess ||
+        hipMemcpy(H->inv, inv.data(), sizeof(double) * inv.size(), hipMemcpyHostToDevice) != hipSuccess)
+        return bail(fail(MI355CG_ERR_HIP, "coarse inverse upload failed"));
+    if (hipMalloc((void**)&H->coff, sizeof(int) * off.size()) != hipSuccess ||
         hipMemcpy(H->coff, off.data(), sizeof(int) * off.size(), hipMemcpyHostToDevice) != hipSuccess)
         return bail(fail(MI355CG_ERR_HIP, "coarse inverse upload failed"));
     // the zero-fills ran on the NULL stream; the context's stream does not order with them (see create_impl)
@@ -974,6 +991,115 @@ void mg_vcycle(mi355cg_ctx* c, int l, const double* rhs, double* out, double* do
     hipLaunchKernelGGL((k_mg_smooth<false, false>), grid, blk, 0, st, L.g, kMgOmega, rhs, (const double*)out, L.a, (double*)nullptr);
     if (dot) hipLaunchKernelGGL((k_mg_smooth<false, true>), grid, blk, 0, st, L.g, kMgOmega, rhs, (const double*)L.a, out, dot);
     else hipLaunchKernelGGL((k_mg_smooth<false, false>), grid, blk, 0, st, L.g, kMgOmega, rhs, (const double*)L.a, out, (double*)nullptr);
+}
+
+// ---- the fp32 V-cycle (MI355CG_CYCLE_F32; kernels in mg_kernels_f32.h) -----------------------------------
+constexpr int kMg32VecMinN = 256;       // levels with at least this many intervals take 4 columns per lane (a row fills a wave)
+
+// fp32 vectors and constants of every level and the coarse inverse rounded to fp32
+int mg_build32(MgHier* H, const std::vector<double>& inv) {
+    const int nl = (int)H->lv.size();
+    H->lv32.resize(nl);
+    auto alloc32 = [](float** p, long long n) -> int {
+        HIPCK(hipMalloc((void**)p, sizeof(float) * n));
+        HIPCK(hipMemset(*p, 0, sizeof(float) * n));
+        return MI355CG_OK;
+    };
+    for (int l = 0; l < nl; ++l) {
+        const MgLevel& L = H->lv[l];
+        MgLevel32& F = H->lv32[l];
+        F.c = MgCoef32{(float)L.g.A, (float)L.g.xk, (float)L.g.yk, (float)kMgOmega};
+        F.vec = L.g.N >= kMg32VecMinN ? 4 : 1;
+        if (l + 1 < nl) {
+            const Geom& C = H->lv[l + 1].g;
+            F.scale = (float)((double)((long long)C.N * C.N) / (double)((long long)L.g.N * L.g.N));
+        }
+        for (float** v : {&F.rhs, &F.out}) if (int rc = alloc32(v, L.len)) return rc;
+        if (l + 1 < nl) if (int rc = alloc32(&F.a, L.len)) return rc;
+    }
+    std::vector<float> inv32(inv.begin(), inv.end());
+    HIPCK(hipMalloc((void**)&H->inv32, sizeof(float) * inv32.size()));
+    HIPCK(hipMemcpy(H->inv32, inv32.data(), sizeof(float) * inv32.size(), hipMemcpyHostToDevice));
+    return MI355CG_OK;
+}
+
+// levels l >= 1: out = V(rhs, l) on the level's fp32 vectors
+void mg_vcycle32_level(mi355cg_ctx* c, int l);
+
+// the part of a level between its two pre-sweeps and its two post-sweeps: residual, restriction, the coarser cycle, prolongation
+template <int V>
+void mg_vcycle32_coarse_part(mi355cg_ctx* c, int l) {
+    const MgHier& H = *c->mg;
+    const MgLevel &L = H.lv[l], &C = H.lv[l + 1];
+    const MgLevel32 &F = H.lv32[l], &G = H.lv32[l + 1];
+    const hipStream_t st = c->stream;
+    const dim3 grid(L.grid), blk(kBlock);
+    const bool nested = L.g.N == 2 * C.g.N;
+    if (nested) {
+        if (G.vec == 4) hipLaunchKernelGGL((k_mg32_restrict<4>), dim3(C.grid), blk, 0, st, L.g, C.g, F.c, (const float*)F.rhs, (const float*)F.out, G.rhs);
+        else hipLaunchKernelGGL((k_mg32_restrict<1>), dim3(C.grid), blk, 0, st, L.g, C.g, F.c, (const float*)F.rhs, (const float*)F.out, G.rhs);
+    } else {                            // F.a is free until the first post-sweep: it holds s = rhs - A out for the gather
+        hipLaunchKernelGGL((k_mg32_residual<V>), grid, blk, 0, st, L.g, F.c, (const float*)F.rhs, (const float*)F.out, F.a);
+        hipLaunchKernelGGL(k_mg32_restrict_nn, dim3(C.grid), blk, 0, st, L.g, C.g, F.scale, (const float*)F.a, G.rhs);
+    }
+    mg_vcycle32_level(c, l + 1);
+    if (nested) hipLaunchKernelGGL((k_mg32_prolong<V>), grid, blk, 0, st, L.g, C.g, (const float*)G.out, F.out);
+    else hipLaunchKernelGGL(k_mg32_prolong_nn, grid, blk, 0, st, L.g, C.g, (const float*)G.out, F.out);
+}
+
+template <int V>
+void mg_vcycle32_sweeps(mi355cg_ctx* c, int l, int e, const double* r64, double* z64) {
+    const MgHier& H = *c->mg;
+    const MgLevel& L = H.lv[l];
+    const MgLevel32& F = H.lv32[l];
+    const hipStream_t st = c->stream;
+    const dim3 grid(L.grid), blk(kBlock);
+    const float* nf = nullptr;
+    float* nfw = nullptr;
+    double* nd = nullptr;
+    if (l == 0) hipLaunchKernelGGL((k_mg32_smooth<V, 1>), grid, blk, 0, st, L.g, F.c, e, r64, nf, F.rhs, nf, F.a, nd, nd);
+    else hipLaunchKernelGGL((k_mg32_smooth<V, 0>), grid, blk, 0, st, L.g, F.c, 0, (const double*)nd, (const float*)F.rhs, nfw, nf, F.a, nd, nd);
+    hipLaunchKernelGGL((k_mg32_smooth<V, 2>), grid, blk, 0, st, L.g, F.c, 0, (const double*)nd, (const float*)F.rhs, nfw, (const float*)F.a, F.out, nd, nd);
+    mg_vcycle32_coarse_part<V>(c, l);
+    hipLaunchKernelGGL((k_mg32_smooth<V, 2>), grid, blk, 0, st, L.g, F.c, 0, (const double*)nd, (const float*)F.rhs, nfw, (const float*)F.out, F.a, nd, nd);
+    if (l == 0) hipLaunchKernelGGL((k_mg32_smooth<V, 3>), grid, blk, 0, st, L.g, F.c, e, r64, nf, nfw, (const float*)F.a, nfw, z64, H.part);
+    else hipLaunchKernelGGL((k_mg32_smooth<V, 2>), grid, blk, 0, st, L.g, F.c, 0, (const double*)nd, (const float*)F.rhs, nfw, (const float*)F.a, F.out, nd, nd);
+}
+
+void mg_vcycle32_level(mi355cg_ctx* c, int l) {
+    const MgHier& H = *c->mg;
+    if (l + 1 == (int)H.lv.size()) {
+        hipLaunchKernelGGL(k_mg32_coarse, dim3(H.ncoarse), dim3(kBlock), 0, c->stream, H.ncoarse, (const float*)H.inv32, (const int*)H.coff,
+                           (const float*)H.lv32[l].rhs, H.lv32[l].out);
+        return;
+    }
+    if (H.lv32[l].vec == 4) mg_vcycle32_sweeps<4>(c, l, 0, nullptr, nullptr);
+    else mg_vcycle32_sweeps<1>(c, l, 0, nullptr, nullptr);
+}
+
+// z = M32 r on level 0 and the partials of (r, z) in H.part; rmax = max|r| (the scale 2^e is its binary exponent)
+int mg_apply32(mi355cg_ctx* c, const double* r, double* z, double rmax) {
+    const MgHier& H = *c->mg;
+    const MgLevel& L = H.lv[0];
+    const hipStream_t st = c->stream;
+    const dim3 grid(L.grid), blk(kBlock);
+    if (!(rmax > 0)) {                                            // r = 0: z = 0 and (r, z) = 0
+        HIPCK(hipMemsetAsync(z, 0, sizeof(double) * L.len, st));
+        HIPCK(hipMemsetAsync(H.part, 0, sizeof(double) * L.grid, st));
+        return MI355CG_OK;
+    }
+    int e = 0;
+    if (std::isfinite(rmax)) std::frexp(rmax, &e);
+    if (H.lv.size() == 1) {
+        hipLaunchKernelGGL(k_mg32_cast, grid, blk, 0, st, L.g, e, r, H.lv32[0].rhs);
+        mg_vcycle32_level(c, 0);
+        hipLaunchKernelGGL(k_mg32_uncast_dot, grid, blk, 0, st, L.g, e, r, (const float*)H.lv32[0].out, z, H.part);
+    } else if (H.lv32[0].vec == 4) {
+        mg_vcycle32_sweeps<4>(c, 0, e, r, z);
+    } else {
+        mg_vcycle32_sweeps<1>(c, 0, e, r, z);
+    }
+    return MI355CG_OK;
 }
 
 // PCG with z = M r.  Same stop rules, callback cadence, stop-flag handling and result fields as mi355cg_solve's plain path.
@@ -1026,6 +1152,8 @@ int solve_mg(mi355cg_ctx* c, const mi355cg_params* prm, mi355cg_iter_cb cb, void
         if (!msg && !prm->fixed_iterations && !(rnorm > prm->eps_rel * r0norm)) break;        // matrix_free_system.cpp:409
         if (stop_flag && *stop_flag) { interrupted = true; break; }                           // msg_solver.cpp:82-87
         double rz = 0, pq = 0;
+        if (H.cycle == MI355CG_CYCLE_F32) { if (int rc = mg_apply32(c, c->r, H.z, nm[MG_RMAX])) return rc; }   // nm: of the last update
+        else
         mg_vcycle(c, 0, c->r, H.z, H.part);                                                  // z = M r, partials of (r, z)
         if (int rc = fetch(1, &rz)) return rc;
         const double beta = it == 0 ? 0.0 : rz / rho;
@@ -1637,7 +1765,9 @@ int mi355cg_mg_hierarchy(int kind, int n, int max_levels, int* levels, int* leve
     return MI355CG_OK;
 }
 
-int mi355cg_set_preconditioner(mi355cg_handle c, int kind) {
+int mi355cg_set_preconditioner(mi355cg_handle c, int kind) { return mi355cg_set_preconditioner_ex(c, kind, MI355CG_CYCLE_F64); }
+
+int mi355cg_set_preconditioner_ex(mi355cg_handle c, int kind, int cycle) {
     if (!c) return fail(MI355CG_ERR_INVALID, "null handle");
     if (kind != MI355CG_PRECOND_NONE && kind != MI355CG_PRECOND_MG && kind != MI355CG_PRECOND_MG_ANY)
         return fail(MI355CG_ERR_INVALID, "unknown preconditioner kind %d (MI355CG_PRECOND_NONE = 0, MI355CG_PRECOND_MG = 1, "
@@ -1652,8 +1782,25 @@ int mi355cg_set_preconditioner(mi355cg_handle c, int kind) {
     if (c->dtype != MI355CG_F64) return fail(MI355CG_ERR_INVALID, "the multigrid preconditioner is fp64 only: this handle was created with MI355CG_F32_MIXED");
     std::vector<int> ns;
     if (int rc = mg_shape(kind, c->gp.n, &ns)) return rc;          // refused: the handle keeps what it had
-    if (c->mg) { c->mg->kind = kind; return MI355CG_OK; }            // both kinds have a hierarchy here: it is the same one
-    return mg_build(c, kind, &c->mg);
+    if (cycle != MI355CG_CYCLE_F64 && cycle != MI355CG_CYCLE_F32)
+        return fail(MI355CG_ERR_INVALID, "unknown V-cycle precision %d (MI355CG_CYCLE_F64 = 0, MI355CG_CYCLE_F32 = 1)", cycle);
+    if (c->mg && c->mg->cycle == cycle) { c->mg->kind = kind; return MI355CG_OK; }   // both kinds have a hierarchy here: it is the same one
+    if (!c->mg) return mg_build(c, kind, &c->mg, cycle);
+    // another precision: the levels' vectors and the coarse inverse change type.  Built first, so a failure keeps the old one.
+    HIPCK(hipStreamSynchronize(c->stream));
+    MgHier* H = nullptr;
+    if (int rc = mg_build(c, kind, &H, cycle)) return rc;
+    mg_free(c->mg);
+    c->mg = H;
+    return MI355CG_OK;
+}
+
+int mi355cg_preconditioner_info(mi355cg_handle c, int* kind, int* cycle, int* levels) {
+    if (!c) return fail(MI355CG_ERR_INVALID, "null handle");
+    if (kind) *kind = c->mg ? c->mg->kind : MI355CG_PRECOND_NONE;
+    if (cycle) *cycle = c->mg ? c->mg->cycle : MI355CG_CYCLE_F64;
+    if (levels) *levels = c->mg ? (int)c->mg->lv.size() : 0;
+    return MI355CG_OK;
 }
 
 // z = M r on host vectors (packed order).  Works on the PCG's q (input) and z (output), which hold nothing between iterations,
@@ -1663,6 +1810,11 @@ int mi355cg_apply_preconditioner(mi355cg_handle c, const double* r, double* z) {
     if (!c->mg) return fail(MI355CG_ERR_STATE, "no preconditioner is set on this handle (mi355cg_set_preconditioner)");
     HIPCK(hipSetDevice(c->device));
     if (int rc = upload_packed<double>(c, r, c->mg->q)) return rc;
+    if (c->mg->cycle == MI355CG_CYCLE_F32) {
+        double rmax = 0;
+        for (long long i = 0; i < c->pk_len; ++i) rmax = std::max(rmax, std::fabs(r[i]));
+        if (int rc = mg_apply32(c, c->mg->q, c->mg->z, rmax)) return rc;
+    } else
     mg_vcycle(c, 0, c->mg->q, c->mg->z, nullptr);
     HIPCK(hipGetLastError());
     return download_packed<double>(c, c->mg->z, z);

@@ -128,15 +128,22 @@ class _Handle:
         _capi.check(rc)
         return res
 
-    def set_preconditioner(self, kind: int):
+    def set_preconditioner(self, kind: int, cycle: int = _capi.CYCLE_F64):
         """Extension (no reference twin): _capi.PRECOND_MG (grids with a nested hierarchy, see mg_levels) or _capi.PRECOND_MG_ANY
         (every grid, see mg_hierarchy) builds the multigrid hierarchy, after which solve() runs preconditioned CG;
-        _capi.PRECOND_NONE frees it (include/mi355cg.h, mi355cg_set_preconditioner).  ValueError if refused; the handle then
+        _capi.PRECOND_NONE frees it (include/mi355cg.h, mi355cg_set_preconditioner).  cycle: _capi.CYCLE_F64, or _capi.CYCLE_F32
+        for the V-cycle in fp32 inside the fp64 PCG (mi355cg_set_preconditioner_ex).  ValueError if refused; the handle then
         keeps what it had."""
-        rc = self._lib.mi355cg_set_preconditioner(self._h, int(kind))
+        rc = self._lib.mi355cg_set_preconditioner_ex(self._h, int(kind), int(cycle))
         if rc == _capi.ERR_INVALID:
             raise ValueError(self._lib.mi355cg_last_error().decode())
         _capi.check(rc)
+
+    def preconditioner_info(self):
+        """(kind, cycle, levels) of the preconditioner that is set; (PRECOND_NONE, CYCLE_F64, 0) without one."""
+        k, cy, lv = C.c_int(), C.c_int(), C.c_int()
+        _capi.check(self._lib.mi355cg_preconditioner_info(self._h, C.byref(k), C.byref(cy), C.byref(lv)))
+        return k.value, cy.value, lv.value
 
     def apply_preconditioner(self, r):
         """z = M r for a packed vector r (needs set_preconditioner(PRECOND_MG or PRECOND_MG_ANY) first)."""
@@ -219,10 +226,15 @@ class MatrixFreeSystem:
 
     def __mul__(self, x): return self.apply(x)             # operator* (matrix_free_system.hpp:59-63)
 
-    def set_preconditioner(self, kind: int):
+    def set_preconditioner(self, kind: int, cycle: int = _capi.CYCLE_F64):
         """Extension (no reference twin): _capi.PRECOND_MG / PRECOND_MG_ANY / PRECOND_NONE.  Every solver built on this system
-        (MatrixFreeSolver, MSGSolver) runs preconditioned CG while it is set."""
-        self._handle.set_preconditioner(kind)
+        (MatrixFreeSolver, MSGSolver) runs preconditioned CG while it is set.  cycle = _capi.CYCLE_F32 runs the V-cycle in fp32;
+        the CG vectors, inner products and stop tests stay fp64."""
+        self._handle.set_preconditioner(kind, cycle)
+
+    def preconditioner_info(self):
+        """(kind, cycle, levels) of the preconditioner that is set; (PRECOND_NONE, CYCLE_F64, 0) without one."""
+        return self._handle.preconditioner_info()
 
 
 class GridSystem(MatrixFreeSystem):

@@ -7,9 +7,18 @@ and the MSG rule with mi355cg_default_params (eps 1e-6, at most 10 000 iteration
 The true relative residual ||b - A x|| / ||b|| comes from mi355cg_get_true_residual.
 --kind any: the plain solve, MG where the grid has a nested hierarchy, and MG_ANY (MI355CG_PRECOND_MG_ANY), each preconditioner
 built afresh on the handle.
+--cycle f32 (with --kind any): MG_ANY with the fp64 V-cycle against MG_ANY with the fp32 V-cycle (MI355CG_CYCLE_F32), one handle per
+N, one warm-up solve per setting, then three timed solves of each setting alternating, the best of each.  --baseline-tree DIR adds the
+same fp64-cycle solves by another checkout of the project (built, e.g. the commit before the option), whose package a child process
+of the same job imports instead of this one, on the same GPU: the yardstick for what the option gains over the code before it.
 Usage: python tools/mg_timing.py [N ...]      (default 256 1024 4096 8192; writes profiles/mg_time_to_solution.txt)
        python tools/mg_timing.py --kind any [N ...]   (default 100 258 1000 1002 4096 4098 10000;
-                                                      writes profiles/mg_any_time_to_solution.txt)"""
+                                                      writes profiles/mg_any_time_to_solution.txt)
+       python tools/mg_timing.py --kind any --cycle f32 [--baseline-tree DIR] [N ...]
+                                                     (default 100 1000 4096 4098 8192 10000;
+                                                      writes profiles/mg_f32_time_to_solution.txt)"""
+import json
+import subprocess
 import os
 import sys
 import time
@@ -17,7 +26,7 @@ import time
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.environ.get("MG_TIMING_TREE") or ROOT)     # --baseline-tree: the child imports that checkout's package
 import iterative_solvers_amd as isa  # noqa: E402
 from iterative_solvers_amd import _capi  # noqa: E402
 
@@ -25,6 +34,8 @@ OUT = {"mg": os.path.join(ROOT, "profiles", "mg_time_to_solution.txt"),
        "any": os.path.join(ROOT, "profiles", "mg_any_time_to_solution.txt")}
 SIZES = {"mg": [256, 1024, 4096, 8192], "any": [100, 258, 1000, 1002, 4096, 4098, 10000]}
 RULES = {"REL_2NORM 1e-8": _capi.RULE_REL_2NORM, "MSG defaults": _capi.RULE_MSG_MAXNORM}
+OUT_F32 = os.path.join(ROOT, "profiles", "mg_f32_time_to_solution.txt")
+SIZES_F32 = [100, 1000, 4096, 4098, 8192, 10000]
 
 
 def params(rule):
@@ -87,13 +98,104 @@ def main(ns, kind="mg"):
     print("wrote", OUT[kind])
 
 
+def best_of_three(h, settings, rule, b_norm):
+    """settings: {name: callable that sets the preconditioner}.  One warm-up solve per setting, then three timed solves of each
+    alternating; per setting the best wall time, its results and the true relative residual of the last solve."""
+    best = {}
+    for name, setp in settings.items():
+        setp()
+        h.solve(params(rule))
+    for _ in range(3):
+        for name, setp in settings.items():
+            setp()
+            t0 = time.perf_counter()
+            res = h.solve(params(rule))
+            wall = time.perf_counter() - t0
+            rel = float(np.linalg.norm(h.true_residual()) / b_norm)
+            if name not in best or wall < best[name][0]:
+                best[name] = (wall, res.iterations, res.stop_reason, res.converged, res.solve_seconds, rel)
+    return best
+
+
+def baseline_worker(ns):
+    """Child process of --baseline-tree: the package is the other checkout's, which may only have mi355cg_set_preconditioner.  Prints one
+    JSON line: {N: {rule: [wall, iterations, stop, converged, solve_seconds, true_rel]}}."""
+    lib = _capi.load()
+    out = {}
+    for n in ns:
+        s = isa.MatrixFreeSystem(n, n, 1.0, 2.0, 1.0, 2.0)
+        h = s._handle
+        b_norm = np.linalg.norm(s.get_rhs())
+        setp = lambda: _capi.check(lib.mi355cg_set_preconditioner(h._h, isa.PRECOND_MG_ANY))  # noqa: E731
+        out[n] = {name: best_of_three(h, {"base": setp}, rule, b_norm)["base"] for name, rule in RULES.items()}
+        h.close()
+    print("BASELINE " + json.dumps(out), flush=True)
+
+
+def main_f32(ns, baseline_tree):
+    base = None
+    if baseline_tree:
+        env = dict(os.environ, MG_TIMING_TREE=os.path.abspath(baseline_tree))
+        txt = subprocess.run([sys.executable, os.path.abspath(__file__), "--baseline-worker"] + [str(n) for n in ns], env=env, check=True,
+                             capture_output=True, text=True, timeout=900).stdout
+        base = json.loads([l for l in txt.splitlines() if l.startswith("BASELINE ")][-1][len("BASELINE "):])
+    lines = ["# time to solution on one MI355X: MG_ANY-preconditioned CG with the fp64 V-cycle against the fp32 V-cycle "
+             "(MI355CG_CYCLE_F32; tools/mg_timing.py --kind any --cycle f32)",
+             "# one warm-up solve per setting, then three timed solves of each alternating on one handle; wall = best host wall time of "
+             "mi355cg_solve; true_rel = ||b - A x|| / ||b||",
+             "# f64 = the fp64 cycle of this build, f32 = the fp32 cycle"
+             + (", base = the fp64 cycle of the --baseline-tree checkout (the commit before the option) in a child process of the same job"
+                if base else ""),
+             "# ratio = wall / wall of " + ("base" if base else "f64"),
+             f"# {'N':>5} {'rule':<15} {'cycle':<5} {'iters':>5} {'stop':>4} {'conv':>4} {'wall_s':>9} {'solve_s':>9} {'true_rel':>9} {'ratio':>6}"]
+    print("\n".join(lines), flush=True)
+    for n in ns:
+        s = isa.MatrixFreeSystem(n, n, 1.0, 2.0, 1.0, 2.0)
+        h = s._handle
+        b_norm = np.linalg.norm(s.get_rhs())
+        settings = {"f64": lambda: h.set_preconditioner(isa.PRECOND_MG_ANY, isa.CYCLE_F64),
+                    "f32": lambda: h.set_preconditioner(isa.PRECOND_MG_ANY, isa.CYCLE_F32)}
+        for name, rule in RULES.items():
+            rows = dict(best_of_three(h, settings, rule, b_norm))
+            if base:
+                rows = {"base": tuple(base[str(n)][name]), **rows}
+            ref_wall = rows["base" if base else "f64"][0]
+            for cyc, (w, it, stop, conv, ss, rel) in rows.items():
+                line = f"  {n:>5} {name:<15} {cyc:<5} {it:>5} {stop:>4} {conv:>4} {w:>9.5f} {ss:>9.5f} {rel:>9.2e} {w / ref_wall:>6.3f}"
+                lines.append(line)
+                print(line, flush=True)
+        h.close()
+    with open(OUT_F32, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    print("wrote", OUT_F32)
+
+
 if __name__ == "__main__":
     args = sys.argv[1:]
+    if args and args[0] == "--baseline-worker":
+        baseline_worker([int(a) for a in args[1:]])
+        sys.exit(0)
     kind = "mg"
+    cycle, baseline_tree = "f64", None
+    if "--cycle" in args:
+        i = args.index("--cycle")
+        cycle = args[i + 1]
+        del args[i:i + 2]
+        if cycle not in ("f64", "f32"):
+            sys.exit("--cycle must be f64 or f32")
+    if "--baseline-tree" in args:
+        i = args.index("--baseline-tree")
+        baseline_tree = args[i + 1]
+        del args[i:i + 2]
     if "--kind" in args:
         i = args.index("--kind")
         kind = args[i + 1]
         del args[i:i + 2]
         if kind not in OUT:
             sys.exit(f"--kind must be one of {sorted(OUT)}")
-    main([int(a) for a in args] or SIZES[kind], kind)
+    if cycle == "f32":
+        if kind != "any":
+            sys.exit("--cycle f32 goes with --kind any")
+        main_f32([int(a) for a in args] or SIZES_F32, baseline_tree)
+    else:
+        main([int(a) for a in args] or SIZES[kind], kind)
