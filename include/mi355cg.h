@@ -28,6 +28,9 @@
  *   mi355cg_apply_preconditioner   z = M r on host vectors (packed order)
  *   mi355cg_mg_levels              the hierarchy a grid gets (pure host arithmetic, no GPU needed)
  *   mi355cg_mg_hierarchy           every level's N of either multigrid kind (pure host arithmetic, no GPU needed)
+ *   mi355cg_solve_batch            many right-hand sides on one grid by one preconditioned CG loop (host vectors)
+ *   mi355cg_solve_batch_device     the same with the vectors in device memory
+ *   mi355cg_batch_release          free the workspace the batched solves keep on the handle
  *
  * Plain pointers and sizes only; no C++/torch types.  All host vectors are in the reference's
  * PACKED unknown order (bottom-right block row-major, then the upper block row-major;
@@ -193,6 +196,36 @@ int  mi355cg_mg_hierarchy(int kind, int n, int max_levels, int *levels, int *lev
 #define MI355CG_CYCLE_F32 1   /* the V-cycle in fp32 inside the fp64 PCG */
 int  mi355cg_set_preconditioner_ex(mi355cg_handle h, int kind, int cycle);
 int  mi355cg_preconditioner_info(mi355cg_handle h, int *kind, int *cycle, int *levels);
+
+/* Batched solves: nrhs right-hand sides on one handle that has a multigrid preconditioner set (fp64 cycle), solved together by
+ * one preconditioned CG loop whose every launch carries all systems that are still iterating, so the launches and the three
+ * host waits per iteration of one solve are paid once per batch.
+ * b, x: nrhs vectors of mi355cg_size(h) doubles each, packed order, one after the other; out: nrhs entries.
+ * System s gets exactly the bits that mi355cg_set_rhs(h, b_s); mi355cg_solve(h, params, NULL, NULL, stop_flag, &res);
+ * mi355cg_get_solution(h, x_s) gives on the same handle: all of x_s and iterations, converged, stop_reason,
+ * final_residual_norm, final_precision, r_norm2, initial_r_norm2.  Every system follows the stop rule on its own numbers; one
+ * that stops is frozen and later launches cover only the others.  stop_flag is read once per iteration: when it is set, every
+ * system still iterating ends MI355CG_STOP_INTERRUPTED and the finished ones keep their results.  Both rules and
+ * fixed_iterations work.  final_error_norm is DBL_MAX; solve_seconds and loop_seconds are the whole batch's, the same in every
+ * entry.  The handle's own state is untouched: its b, its last x and r, what mi355cg_get_solution returns.
+ * MI355CG_ERR_INVALID, before anything is allocated or written: a null pointer, nrhs < 1 or > MI355CG_BATCH_MAX, x overlapping
+ * b, use_true_solution != 0 or diagnostics != 0 (a batch has no per-system exact solution and no callbacks; note that
+ * mi355cg_default_params sets use_true_solution = 1), a preconditioner set with MI355CG_CYCLE_F32.  MI355CG_ERR_STATE: no
+ * preconditioner is set (CSR, part and F32_MIXED handles cannot have one).
+ * _device: b_dev and x_dev are in device memory of the handle's GPU.  The work runs on the handle's own stream: the caller
+ * makes b_dev complete before the call, and the call returns after that stream is idle, x_dev written.
+ * Workspace: per system the PCG vectors of level 0 (x, r, z, two directions, A p, the cycle's work vector: seven vectors of the
+ * handle's storage size) and the three vectors of every coarser level (about one more), i.e. about 8 level-0 vectors a system
+ * -- about 1 GB a system at n = 4096, 50 MB at n = 1000 (computed from the layout) -- plus nrhs packed vectors of staging for
+ * the host entry point.  Allocated on first use, kept on the handle, grown when a larger nrhs comes; freed by
+ * mi355cg_batch_release (MI355CG_OK if there is none), every mi355cg_set_preconditioner* call that is not refused and
+ * mi355cg_destroy.  If it cannot be allocated: MI355CG_ERR_HIP, nothing leaked, the handle usable as before.                                                */
+#define MI355CG_BATCH_MAX 64  /* the per-system scalars and the list of active systems travel as kernel arguments */
+int  mi355cg_solve_batch(mi355cg_handle h, const mi355cg_params *params, int nrhs, const double *b, double *x,
+                         const volatile int *stop_flag, mi355cg_results *out);
+int  mi355cg_solve_batch_device(mi355cg_handle h, const mi355cg_params *params, int nrhs, const double *b_dev, double *x_dev,
+                                const volatile int *stop_flag, mi355cg_results *out);
+int  mi355cg_batch_release(mi355cg_handle h);
 
 /* ---- measurement hooks (bench.py) ------------------------------------------------------------ */
 /* Per-kernel device time of the last mi355cg_solve, measured with HIP events on the solve

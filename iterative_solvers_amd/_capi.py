@@ -30,10 +30,12 @@ EXPORTS = [
     "mi355cg_team_set_profiling", "mi355cg_team_phase_times", "mi355cg_team_describe", "mi355cg_setup_on_device", "mi355cg_team_setup_on_device", "mi355cg_debug_plan",
     "mi355cg_team_set_dtype", "mi355cg_set_preconditioner", "mi355cg_apply_preconditioner", "mi355cg_mg_levels",
     "mi355cg_mg_hierarchy", "mi355cg_set_preconditioner_ex", "mi355cg_preconditioner_info",
+    "mi355cg_solve_batch", "mi355cg_solve_batch_device", "mi355cg_batch_release",
 ]
 DECOMP_ROWS, DECOMP_2D = 0, 1
 PRECOND_NONE, PRECOND_MG, PRECOND_MG_ANY = 0, 1, 2
 CYCLE_F64, CYCLE_F32 = 0, 1
+BATCH_MAX = 64          # MI355CG_BATCH_MAX
 
 
 class Params(C.Structure):
@@ -165,6 +167,10 @@ def load():
     L.mi355cg_apply_preconditioner.argtypes = [H, _DP, _DP]
     L.mi355cg_mg_levels.argtypes = [C.c_int, IP, IP]
     L.mi355cg_mg_hierarchy.argtypes = [C.c_int, C.c_int, C.c_int, IP, IP]
+    # vectors as plain addresses: host arrays for _solve_batch, device memory for _solve_batch_device
+    L.mi355cg_solve_batch.argtypes = [H, C.POINTER(Params), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Results)]
+    L.mi355cg_solve_batch_device.argtypes = [H, C.POINTER(Params), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Results)]
+    L.mi355cg_batch_release.argtypes = [H]
     _lib = L
     return L
 

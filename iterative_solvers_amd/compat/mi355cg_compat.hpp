@@ -13,6 +13,7 @@
 // everything else -> std::runtime_error, as the reference throws (grid_system.cpp:86-93,277-279).
 #pragma once
 
+#include <algorithm>
 #include <atomic>
 #include <cfloat>
 #include <cmath>
@@ -414,6 +415,28 @@ public:
     // returns to plain CG.  std::invalid_argument for PRECOND_MG on a grid without a nested hierarchy.
     // cycle: MI355CG_CYCLE_F32 runs the V-cycle in fp32 inside the fp64 PCG (mi355cg_set_preconditioner_ex).
     void setPreconditioner(int kind, int cycle = MI355CG_CYCLE_F64) { mi355cg_compat::check(mi355cg_set_preconditioner_ex(ctx_->h, kind, cycle)); }
+    // Extension: every b[s] solved by one multigrid-preconditioned CG loop (mi355cg_solve_batch; needs setPreconditioner first).
+    // x[s] and results[s] have the bits a single solve of b[s] on this system gives.  params.use_true_solution and
+    // params.diagnostics must be 0 (mi355cg_default_params sets the former to 1).  std::invalid_argument for an empty batch, more
+    // than MI355CG_BATCH_MAX vectors, a vector of the wrong size and what the library refuses as invalid; std::runtime_error
+    // without a preconditioner.
+    std::vector<std::vector<double>> solveBatch(const std::vector<std::vector<double>>& b, const mi355cg_params& params,
+                                                std::vector<mi355cg_results>* results = nullptr) {
+        if (b.empty() || b.size() > (size_t)MI355CG_BATCH_MAX) throw std::invalid_argument("solveBatch: a batch has 1 .. MI355CG_BATCH_MAX right-hand sides");
+        const size_t n = rhs.size(), k = b.size();
+        std::vector<double> bp(n * k), xp(n * k);
+        for (size_t s = 0; s < k; ++s) {
+            if (b[s].size() != n) throw std::invalid_argument("solveBatch: vector size does not match the system");
+            std::copy(b[s].begin(), b[s].end(), bp.begin() + (std::ptrdiff_t)(s * n));
+        }
+        std::vector<mi355cg_results> res(k);
+        mi355cg_compat::check(mi355cg_solve_batch(ctx_->h, &params, (int)k, bp.data(), xp.data(), nullptr, res.data()));
+        std::vector<std::vector<double>> x(k);
+        for (size_t s = 0; s < k; ++s) x[s].assign(xp.begin() + (std::ptrdiff_t)(s * n), xp.begin() + (std::ptrdiff_t)((s + 1) * n));
+        if (results) *results = std::move(res);
+        return x;
+    }
+    void batchRelease() { mi355cg_compat::check(mi355cg_batch_release(ctx_->h)); }
     const std::shared_ptr<mi355cg_compat::Context>& context() const { return ctx_; }
     friend std::ostream& operator<<(std::ostream& os, const MatrixFreeSystem& s) {
         return os << "MatrixFreeSystem Information:\n  Dimensions: " << s.ctx_->n << "x" << s.ctx_->m << "\n  System size: " << s.size() << "\n";

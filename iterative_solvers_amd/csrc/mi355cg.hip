@@ -7,11 +7,14 @@
 #include "csr_kernels.h"
 #include "grid_setup.h"
 #include "mg_kernels.h"
+#include "mg_batch_kernels.h"
 #include "mg_kernels_f32.h"
 
 #include <algorithm>
+#include <cfloat>
 #include <chrono>
 #include <cstdarg>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -85,6 +88,23 @@ struct MgHier {
     double* part_h = nullptr;           // pinned copy
 };
 
+// Workspace of the batched solves (mi355cg_solve_batch*; kernels in mg_batch_kernels.h): one allocation, system-major.  System s
+// keeps its level-0 PCG vectors (x, r, z, p[2], q, the cycle's work vector) and the three vectors of every coarser level at
+// base + s * stride + the offsets below.  Built for a hierarchy on first use, kept on the handle, grown for a larger batch.
+struct MgBatchLevel { long long rhs = -1, a = -1, out = -1; };
+struct MgBatchWs {
+    int cap = 0;                        // systems the vectors hold
+    long long stride = 0;               // doubles per system, a multiple of 32 (256 B)
+    double* base = nullptr;
+    long long x = 0, r = 0, z = 0, p[2] = {0, 0}, q = 0;
+    std::vector<MgBatchLevel> lv;
+    double* part = nullptr;             // [system][field][block], cap x MGB_NFIELDS x level 0's grid
+    double* red = nullptr;              // [position][field] sums of the last launch
+    double* red_h = nullptr;            // pinned copy
+    double* stage = nullptr;            // packed vectors of the host entry point, stage_cap x pk_len
+    int stage_cap = 0;
+};
+
 }  // namespace
 
 struct mi355cg_ctx {
@@ -145,6 +165,7 @@ struct mi355cg_ctx {
 
     hipEvent_t ev_loop[2] = {nullptr, nullptr};   // brackets the iterations of the last solve (mi355cg_results::loop_seconds)
     MgHier* mg = nullptr;               // opt-in preconditioner (mi355cg_set_preconditioner): mi355cg_solve runs solve_mg while set
+    MgBatchWs* batch = nullptr;         // workspace of mi355cg_solve_batch*, nullptr until the first batch
     bool profiling = false;
     EventPool events;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pairs[2];
@@ -1199,6 +1220,230 @@ int solve_mg(mi355cg_ctx* c, const mi355cg_params* prm, mi355cg_iter_cb cb, void
     return MI355CG_OK;
 }
 
+// ---- batched PCG (mi355cg_solve_batch*; kernels in mg_batch_kernels.h) ------------------------------------
+void mg_batch_free(mi355cg_ctx* c) {
+    MgBatchWs* W = c->batch;
+    if (!W) return;
+    if (c->stream) hipStreamSynchronize(c->stream);
+    for (double* v : {W->base, W->part, W->red, W->stage}) if (v) hipFree(v);
+    if (W->red_h) hipHostFree(W->red_h);
+    delete W;
+    c->batch = nullptr;
+}
+
+// Vectors for nsys systems of the handle's hierarchy (and, stage_sys > 0, the host entry point's packed staging).  A workspace
+// that is large enough is kept; a larger one replaces it only once it is complete, so a failure leaves the handle as it was.
+int mg_batch_ensure(mi355cg_ctx* c, int nsys, int stage_sys) {
+    const MgHier& H = *c->mg;
+    if (!c->batch || c->batch->cap < nsys) {
+        MgBatchWs* W = new MgBatchWs();
+        auto bail = [&](const char* what) {
+            for (double* v : {W->base, W->part, W->red}) if (v) hipFree(v);
+            if (W->red_h) hipHostFree(W->red_h);
+            delete W;
+            (void)hipGetLastError();
+            return fail(MI355CG_ERR_HIP, "batch workspace for %d systems: %s allocation failed", nsys, what);
+        };
+        long long off = 0;
+        auto take = [&](long long len) { const long long o = off; off += round_up(len, 32); return o; };
+        const long long len0 = H.lv[0].len;
+        W->x = take(len0); W->r = take(len0); W->z = take(len0); W->p[0] = take(len0); W->p[1] = take(len0); W->q = take(len0);
+        const int nl = (int)H.lv.size();
+        W->lv.resize(nl);
+        for (int l = 0; l < nl; ++l) {                             // the vectors mg_build gives a level
+            if (l > 0) { W->lv[l].rhs = take(H.lv[l].len); W->lv[l].out = take(H.lv[l].len); }
+            if (l + 1 < nl) W->lv[l].a = take(H.lv[l].len);
+        }
+        W->stride = off;
+        W->cap = nsys;
+        const int G = H.lv[0].grid;
+        if (hipMalloc((void**)&W->base, sizeof(double) * W->stride * nsys) != hipSuccess) return bail("vector");
+        if (hipMalloc((void**)&W->part, sizeof(double) * MGB_NFIELDS * G * nsys) != hipSuccess) return bail("partials");
+        if (hipMalloc((void**)&W->red, sizeof(double) * MGB_NFIELDS * kMgBatchMax) != hipSuccess) return bail("sums");
+        if (hipHostMalloc((void**)&W->red_h, sizeof(double) * MGB_NFIELDS * kMgBatchMax) != hipSuccess) return bail("pinned sums");
+        // boundary nodes and pads hold 0 for good: the kernels write interior nodes only
+        if (hipMemsetAsync(W->base, 0, sizeof(double) * W->stride * nsys, c->stream) != hipSuccess ||
+            hipStreamSynchronize(c->stream) != hipSuccess) return bail("zero-filled vector");
+        if (c->batch) { W->stage = c->batch->stage; W->stage_cap = c->batch->stage_cap; c->batch->stage = nullptr; }
+        mg_batch_free(c);
+        c->batch = W;
+    }
+    MgBatchWs* W = c->batch;
+    if (stage_sys > W->stage_cap) {
+        double* st = nullptr;
+        HIPCK(hipStreamSynchronize(c->stream));                    // nothing in flight reads the buffer that is replaced
+        if (hipMalloc((void**)&st, sizeof(double) * c->pk_len * stage_sys) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(MI355CG_ERR_HIP, "batch staging for %d packed vectors: allocation failed", stage_sys);
+        }
+        if (W->stage) hipFree(W->stage);
+        W->stage = st; W->stage_cap = stage_sys;
+    }
+    return MI355CG_OK;
+}
+
+// mg_vcycle for the active systems: the same launches in the same order, each with a row of blocks per active system
+void mg_vcycle_batch(mi355cg_ctx* c, const MgbAct& act, int l, long long rhs, long long out, double* dot) {
+    const MgHier& H = *c->mg;
+    const MgBatchWs& W = *c->batch;
+    const MgLevel& L = H.lv[l];
+    const hipStream_t st = c->stream;
+    const dim3 grid(L.grid, act.n), blk(kBlock);
+    double* const B = W.base;
+    if (l + 1 == (int)H.lv.size()) {
+        hipLaunchKernelGGL(k_mgb_coarse, dim3(H.ncoarse), blk, 0, st, act, H.ncoarse, (const double*)H.inv, (const int*)H.coff, (const double*)(B + rhs), B + out);
+        if (dot) hipLaunchKernelGGL(k_mgb_dot, grid, blk, 0, st, act, L.g, (const double*)(B + rhs), (const double*)(B + out), dot);
+        return;
+    }
+    const MgLevel& C = H.lv[l + 1];
+    const dim3 cgrid(C.grid, act.n);
+    const long long La = W.lv[l].a, Crhs = W.lv[l + 1].rhs, Cout = W.lv[l + 1].out;
+    const bool nested = L.g.N == 2 * C.g.N;
+    hipLaunchKernelGGL((k_mgb_smooth<true, false>), grid, blk, 0, st, act, L.g, kMgOmega, (const double*)(B + rhs), (const double*)nullptr, B + La, (double*)nullptr);
+    hipLaunchKernelGGL((k_mgb_smooth<false, false>), grid, blk, 0, st, act, L.g, kMgOmega, (const double*)(B + rhs), (const double*)(B + La), B + out, (double*)nullptr);
+    if (nested) {
+        hipLaunchKernelGGL(k_mgb_restrict, cgrid, blk, 0, st, act, L.g, C.g, (const double*)(B + rhs), (const double*)(B + out), B + Crhs);
+    } else {
+        const double scale = (double)((long long)C.g.N * C.g.N) / (double)((long long)L.g.N * L.g.N);
+        hipLaunchKernelGGL(k_mgb_residual, grid, blk, 0, st, act, L.g, (const double*)(B + rhs), (const double*)(B + out), B + La);
+        hipLaunchKernelGGL(k_mgb_restrict_nn, cgrid, blk, 0, st, act, L.g, C.g, scale, (const double*)(B + La), B + Crhs);
+    }
+    mg_vcycle_batch(c, act, l + 1, Crhs, Cout, nullptr);
+    if (nested) hipLaunchKernelGGL(k_mgb_prolong, grid, blk, 0, st, act, L.g, C.g, (const double*)(B + Cout), B + out);
+    else hipLaunchKernelGGL(k_mgb_prolong_nn, grid, blk, 0, st, act, L.g, C.g, (const double*)(B + Cout), B + out);
+    hipLaunchKernelGGL((k_mgb_smooth<false, false>), grid, blk, 0, st, act, L.g, kMgOmega, (const double*)(B + rhs), (const double*)(B + out), B + La, (double*)nullptr);
+    if (dot) hipLaunchKernelGGL((k_mgb_smooth<false, true>), grid, blk, 0, st, act, L.g, kMgOmega, (const double*)(B + rhs), (const double*)(B + La), B + out, dot);
+    else hipLaunchKernelGGL((k_mgb_smooth<false, false>), grid, blk, 0, st, act, L.g, kMgOmega, (const double*)(B + rhs), (const double*)(B + La), B + out, (double*)nullptr);
+}
+
+// solve_mg for nrhs systems at once.  b_dev, x_dev: packed vectors in device memory (they may be the same buffer: b is consumed
+// before x is written).  Every system runs solve_mg's tests on its own numbers in solve_mg's order; one that stops leaves the
+// active list and no later launch touches its vectors.  Three host waits per iteration, as there.
+int solve_mg_batch(mi355cg_ctx* c, const mi355cg_params* prm, int nrhs, const double* b_dev, double* x_dev,
+                   const volatile int* stop_flag, mi355cg_results* out) {
+    const MgHier& H = *c->mg;
+    const MgBatchWs& W = *c->batch;
+    const Geom& g = H.lv[0].g;
+    const bool msg = prm->rule == MI355CG_RULE_MSG_MAXNORM;
+    const auto t0 = std::chrono::steady_clock::now();
+    const hipStream_t st = c->stream;
+    const int G = H.lv[0].grid;
+    const dim3 blk(kBlock);
+    double* const B = W.base;
+    MgbAct act{};
+    act.stride = W.stride;
+    // the last launch's partials summed on the device in block order, act.n * nfields sums -> host
+    auto fetch = [&](int nfields, int first_max) -> int {
+        hipLaunchKernelGGL(k_mgb_reduce, dim3(nfields, act.n), dim3(kWave), 0, st, act, nfields, first_max, G, (const double*)W.part, W.red);
+        HIPCK(hipGetLastError());
+        HIPCK(hipMemcpyAsync(W.red_h, W.red, sizeof(double) * nfields * act.n, hipMemcpyDeviceToHost, st));
+        HIPCK(hipStreamSynchronize(st));
+        return MI355CG_OK;
+    };
+    struct Sys { double rr, rmax, dmax, rho, rnorm, r0norm; int it, reason; bool converged, interrupted; };
+    std::vector<Sys> S(nrhs);
+    auto take_norms = [&]() {
+        for (int k = 0; k < act.n; ++k) {
+            Sys& s = S[act.sys[k]];
+            s.rr = W.red_h[k * MGB_NFIELDS + MGB_RR]; s.rmax = W.red_h[k * MGB_NFIELDS + MGB_RMAX]; s.dmax = W.red_h[k * MGB_NFIELDS + MGB_DMAX];
+        }
+    };
+    act.n = nrhs;
+    for (int s = 0; s < nrhs; ++s) act.sys[s] = s;
+    // r = b, x = 0 and the norms of r0 (msg_solver.cpp:33-39)
+    hipLaunchKernelGGL(k_mgb_unpack, dim3(flat_grid(c->pk_len), nrhs), blk, 0, st, c->pg, W.stride, b_dev, B + W.r);
+    hipLaunchKernelGGL(k_mgb_init, dim3(G, nrhs), blk, 0, st, act, g, B + W.x, (const double*)(B + W.r), W.part);
+    if (int rc = fetch(MGB_NFIELDS, MGB_RMAX)) return rc;
+    take_norms();
+    for (Sys& s : S) {
+        s.r0norm = s.rnorm = std::sqrt(s.rr);
+        s.rho = 0.0; s.it = 0; s.reason = MI355CG_STOP_ITERATIONS; s.converged = false; s.interrupted = false;
+    }
+    if (!c->ev_loop[0]) { HIPCK(hipEventCreate(&c->ev_loop[0])); HIPCK(hipEventCreate(&c->ev_loop[1])); }
+    HIPCK(hipEventRecord(c->ev_loop[0], st));
+    MgbScal sc{};
+    for (int it = 0;; ++it) {
+        int n = 0;
+        for (int k = 0; k < act.n; ++k) {                          // the tests before an iteration, per system (solve_mg's order)
+            const Sys& s = S[act.sys[k]];
+            if (!(it < prm->max_iterations)) continue;
+            if (!msg && !prm->fixed_iterations && !(s.rnorm > prm->eps_rel * s.r0norm)) continue;
+            act.sys[n++] = act.sys[k];
+        }
+        act.n = n;
+        if (n == 0) break;
+        if (stop_flag && *stop_flag) { for (int k = 0; k < n; ++k) S[act.sys[k]].interrupted = true; break; }
+        const dim3 grid(G, n);
+        mg_vcycle_batch(c, act, 0, W.r, W.z, W.part);             // z = M r, partials of (r, z)
+        if (int rc = fetch(1, 1)) return rc;
+        for (int k = 0; k < n; ++k) {
+            Sys& s = S[act.sys[k]];
+            const double rz = W.red_h[k];
+            sc.v[k] = it == 0 ? 0.0 : rz / s.rho;
+            s.rho = rz;
+        }
+        const long long p = W.p[it & 1], po = W.p[(it + 1) & 1];
+        if (it == 0) hipLaunchKernelGGL((k_mgb_dir_apply<true>), grid, blk, 0, st, act, sc, g, (const double*)(B + W.z), (const double*)nullptr, B + p, B + W.q, W.part);
+        else hipLaunchKernelGGL((k_mgb_dir_apply<false>), grid, blk, 0, st, act, sc, g, (const double*)(B + W.z), (const double*)(B + po), B + p, B + W.q, W.part);
+        if (int rc = fetch(1, 1)) return rc;
+        for (int k = 0; k < n; ++k) sc.v[k] = S[act.sys[k]].rho / W.red_h[k];
+        hipLaunchKernelGGL(k_mgb_update, grid, blk, 0, st, act, sc, g, B + W.x, B + W.r, (const double*)(B + p), (const double*)(B + W.q), W.part);
+        if (int rc = fetch(MGB_NFIELDS, MGB_RMAX)) return rc;
+        take_norms();
+        int m = 0;
+        for (int k = 0; k < n; ++k) {                              // the tests after an iteration (msg_solver.cpp:144-163)
+            Sys& s = S[act.sys[k]];
+            s.it = it + 1;
+            s.rnorm = std::sqrt(s.rr);
+            if (msg && !prm->fixed_iterations) {
+                if (prm->eps_precision > 0 && s.dmax < prm->eps_precision) { s.converged = true; s.reason = MI355CG_STOP_PRECISION; continue; }
+                if (prm->eps_residual > 0 && s.rmax < prm->eps_residual) { s.converged = true; s.reason = MI355CG_STOP_RESIDUAL; continue; }
+            }
+            act.sys[m++] = act.sys[k];
+        }
+        act.n = m;
+    }
+    HIPCK(hipEventRecord(c->ev_loop[1], st));
+    hipLaunchKernelGGL(k_mgb_pack, dim3(flat_grid(c->pk_len), nrhs), blk, 0, st, c->pg, W.stride, (const double*)(B + W.x), x_dev);
+    HIPCK(hipGetLastError());
+    HIPCK(hipStreamSynchronize(st));
+    float ms = 0;
+    const double loop_s = hipEventElapsedTime(&ms, c->ev_loop[0], c->ev_loop[1]) == hipSuccess ? 1e-3 * ms : 0.0;
+    const double solve_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    for (int i = 0; i < nrhs; ++i) {
+        const Sys& s = S[i];
+        const bool conv = msg ? s.converged : s.rnorm <= prm->eps_rel * s.r0norm;         // matrix_free_system.cpp:472
+        mi355cg_results res{};
+        res.iterations = s.it;
+        res.converged = s.interrupted ? 0 : (conv ? 1 : 0);
+        res.stop_reason = s.interrupted ? MI355CG_STOP_INTERRUPTED : s.reason;
+        res.final_residual_norm = s.rmax;
+        res.final_precision = s.it > 0 ? s.dmax : DBL_MAX;
+        res.final_error_norm = DBL_MAX;
+        res.r_norm2 = s.rnorm;
+        res.initial_r_norm2 = s.r0norm;
+        res.solve_seconds = solve_s;
+        res.loop_seconds = loop_s;
+        out[i] = res;
+    }
+    return MI355CG_OK;
+}
+
+// what both entry points refuse before anything is allocated or written
+int batch_check(mi355cg_ctx* c, const mi355cg_params* prm, int nrhs, const void* b, const void* x, const mi355cg_results* out) {
+    if (!c || !prm || !b || !x || !out) return fail(MI355CG_ERR_INVALID, "null argument");
+    if (nrhs < 1 || nrhs > MI355CG_BATCH_MAX) return fail(MI355CG_ERR_INVALID, "a batch has 1 .. %d right-hand sides, not %d", MI355CG_BATCH_MAX, nrhs);
+    if (prm->rule != MI355CG_RULE_MSG_MAXNORM && prm->rule != MI355CG_RULE_REL_2NORM) return fail(MI355CG_ERR_INVALID, "unknown rule %d", prm->rule);
+    if (prm->use_true_solution) return fail(MI355CG_ERR_INVALID, "a batch has no per-system exact solution: use_true_solution must be 0");
+    if (prm->diagnostics) return fail(MI355CG_ERR_INVALID, "a batch has no callbacks: diagnostics must be 0");
+    const size_t bytes = sizeof(double) * (size_t)c->gp.size * (size_t)nrhs;
+    const uintptr_t bb = (uintptr_t)b, xb = (uintptr_t)x;
+    if (bb < xb + bytes && xb < bb + bytes) return fail(MI355CG_ERR_INVALID, "x overlaps b");
+    if (!c->mg) return fail(MI355CG_ERR_STATE, "no preconditioner is set on this handle (mi355cg_set_preconditioner): a batch is multigrid-preconditioned CG");
+    if (c->mg->cycle != MI355CG_CYCLE_F64) return fail(MI355CG_ERR_INVALID, "a batch runs the fp64 V-cycle: this handle's preconditioner was set with MI355CG_CYCLE_F32");
+    return MI355CG_OK;
+}
+
 }  // namespace
 
 // ====================================================================================================
@@ -1393,6 +1638,7 @@ void mi355cg_destroy(mi355cg_handle c) {
     if (c->partR_h) hipHostFree(c->partR_h);
     if (c->stop_h) hipHostFree(c->stop_h);
     clear_graphs(c);
+    mg_batch_free(c);
     mg_free(c->mg);
     c->events.destroy();
     for (hipEvent_t e : c->ev_loop) if (e) hipEventDestroy(e);
@@ -1774,6 +2020,7 @@ int mi355cg_set_preconditioner_ex(mi355cg_handle c, int kind, int cycle) {
                     "MI355CG_PRECOND_MG_ANY = 2)", kind);
     HIPCK(hipSetDevice(c->device));
     if (kind == MI355CG_PRECOND_NONE) {
+        mg_batch_free(c);                                          // the batch workspace belongs to the hierarchy it was built for
         if (c->mg) { HIPCK(hipStreamSynchronize(c->stream)); mg_free(c->mg); c->mg = nullptr; }
         return MI355CG_OK;
     }
@@ -1784,6 +2031,7 @@ int mi355cg_set_preconditioner_ex(mi355cg_handle c, int kind, int cycle) {
     if (int rc = mg_shape(kind, c->gp.n, &ns)) return rc;          // refused: the handle keeps what it had
     if (cycle != MI355CG_CYCLE_F64 && cycle != MI355CG_CYCLE_F32)
         return fail(MI355CG_ERR_INVALID, "unknown V-cycle precision %d (MI355CG_CYCLE_F64 = 0, MI355CG_CYCLE_F32 = 1)", cycle);
+    mg_batch_free(c);                                              // accepted: the batch workspace goes, a refused call above keeps it
     if (c->mg && c->mg->cycle == cycle) { c->mg->kind = kind; return MI355CG_OK; }   // both kinds have a hierarchy here: it is the same one
     if (!c->mg) return mg_build(c, kind, &c->mg, cycle);
     // another precision: the levels' vectors and the coarse inverse change type.  Built first, so a failure keeps the old one.
@@ -1818,6 +2066,37 @@ int mi355cg_apply_preconditioner(mi355cg_handle c, const double* r, double* z) {
     mg_vcycle(c, 0, c->mg->q, c->mg->z, nullptr);
     HIPCK(hipGetLastError());
     return download_packed<double>(c, c->mg->z, z);
+}
+
+// ---- batched solves: nrhs right-hand sides by one multigrid-PCG loop ----------------------------------------
+int mi355cg_solve_batch_device(mi355cg_handle c, const mi355cg_params* prm, int nrhs, const double* b_dev, double* x_dev,
+                               const volatile int* stop_flag, mi355cg_results* out) {
+    if (int rc = batch_check(c, prm, nrhs, b_dev, x_dev, out)) return rc;
+    HIPCK(hipSetDevice(c->device));
+    if (int rc = mg_batch_ensure(c, nrhs, 0)) return rc;
+    return solve_mg_batch(c, prm, nrhs, b_dev, x_dev, stop_flag, out);
+}
+
+int mi355cg_solve_batch(mi355cg_handle c, const mi355cg_params* prm, int nrhs, const double* b, double* x,
+                        const volatile int* stop_flag, mi355cg_results* out) {
+    if (int rc = batch_check(c, prm, nrhs, b, x, out)) return rc;
+    HIPCK(hipSetDevice(c->device));
+    if (int rc = mg_batch_ensure(c, nrhs, nrhs)) return rc;
+    double* stage = c->batch->stage;                               // b goes up and x comes down through the same buffer
+    const size_t bytes = sizeof(double) * (size_t)c->pk_len * (size_t)nrhs;
+    HIPCK(hipMemcpyAsync(stage, b, bytes, hipMemcpyHostToDevice, c->stream));
+    if (int rc = solve_mg_batch(c, prm, nrhs, stage, stage, stop_flag, out)) return rc;
+    HIPCK(hipMemcpyAsync(x, stage, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(hipStreamSynchronize(c->stream));
+    return MI355CG_OK;
+}
+
+int mi355cg_batch_release(mi355cg_handle c) {
+    if (!c) return fail(MI355CG_ERR_INVALID, "null handle");
+    if (!c->batch) return MI355CG_OK;
+    HIPCK(hipSetDevice(c->device));
+    mg_batch_free(c);
+    return MI355CG_OK;
 }
 
 // ---- checksums (tests of large decomposed grids compare these instead of host copies of the vectors) -----------------

@@ -22,6 +22,7 @@ import numpy as np
 from . import _capi
 
 DBL_MAX = sys.float_info.max
+BATCH_MAX = _capi.BATCH_MAX
 
 
 class StopCriterion(enum.IntEnum):          # solver/msg_solver.hpp:9-15
@@ -53,6 +54,7 @@ class _Handle:
             raise ValueError(self._lib.mi355cg_last_error().decode())   # std::invalid_argument
         _capi.check(rc)
         self.size = int(self._lib.mi355cg_size(self._h))
+        self._device = int(device)
 
     @classmethod
     def from_csr(cls, row_map, entries, values, device=0):
@@ -68,6 +70,7 @@ class _Handle:
             raise ValueError(self._lib.mi355cg_last_error().decode())
         _capi.check(rc)
         self.size = int(self._lib.mi355cg_size(self._h))
+        self._device = int(device)
         return self
 
     def set_true_solution(self, u):
@@ -154,6 +157,60 @@ class _Handle:
         _capi.check(self._lib.mi355cg_apply_preconditioner(self._h, r, z))
         return z
 
+    @staticmethod
+    def _check_batch(b, size):
+        """(nrhs, on_device) of a batch of right-hand sides: a NumPy array or a CUDA torch tensor, [nrhs, size] float64.
+        ValueError for anything else; the library has not been called when it is raised."""
+        on_device = not isinstance(b, np.ndarray)
+        if on_device:
+            if not (type(b).__module__.split(".")[0] == "torch" and hasattr(b, "data_ptr")):
+                raise ValueError(f"a batch of right-hand sides is a NumPy array or a CUDA torch tensor, not {type(b).__name__}")
+            import torch
+            if not b.is_cuda:
+                raise ValueError("a torch batch must be in device memory (a CPU tensor: pass tensor.numpy())")
+            if b.dtype != torch.float64:
+                raise ValueError(f"batch has dtype {b.dtype}, expected torch.float64")
+            if not b.is_contiguous():
+                raise ValueError("batch tensor must be contiguous")
+        elif b.dtype != np.float64:
+            raise ValueError(f"batch has dtype {b.dtype}, expected float64")
+        shape = tuple(b.shape)
+        if len(shape) != 2 or shape[1] != size:
+            raise ValueError(f"batch has shape {shape}, expected (nrhs, {size})")
+        if not 1 <= shape[0] <= _capi.BATCH_MAX:
+            raise ValueError(f"a batch has 1 .. {_capi.BATCH_MAX} right-hand sides, not {shape[0]}")
+        return shape[0], on_device
+
+    def solve_batch(self, params: _capi.Params, b, stop_flag: Optional[C.c_int] = None):
+        """Extension (no reference twin): solve b[s] for every row s of b by one multigrid-preconditioned CG loop
+        (mi355cg_solve_batch; needs set_preconditioner first).  Returns (x, [Results per system]); system s gets the bits
+        set_rhs(b[s]); solve(params); solution() gives.  b: NumPy [nrhs, size] float64 -> NumPy x; or a contiguous CUDA
+        torch.Tensor [nrhs, size] float64 on the handle's device -> a new tensor there (mi355cg_solve_batch_device; torch's
+        current stream is synchronised first, since the library works on its own stream).  params.use_true_solution and
+        params.diagnostics must be 0."""
+        nrhs, on_device = self._check_batch(b, self.size)
+        res = (_capi.Results * nrhs)()
+        sp = C.cast(C.pointer(stop_flag), C.c_void_p) if stop_flag is not None else None
+        if on_device:
+            import torch
+            if b.device.index != self._device:
+                raise ValueError(f"batch is on {b.device}, the handle on device {self._device}")
+            x = torch.empty_like(b)
+            torch.cuda.current_stream(b.device).synchronize()
+            rc = self._lib.mi355cg_solve_batch_device(self._h, C.byref(params), nrhs, b.data_ptr(), x.data_ptr(), sp, res)
+        else:
+            b = np.ascontiguousarray(b)
+            x = np.empty_like(b)
+            rc = self._lib.mi355cg_solve_batch(self._h, C.byref(params), nrhs, b.ctypes.data, x.ctypes.data, sp, res)
+        if rc == _capi.ERR_INVALID:
+            raise ValueError(self._lib.mi355cg_last_error().decode())
+        _capi.check(rc)
+        return x, list(res)
+
+    def batch_release(self):
+        """Free the workspace solve_batch keeps on the handle (nothing to free is fine)."""
+        _capi.check(self._lib.mi355cg_batch_release(self._h))
+
     def setup_on_device(self):
         """Opt-in: regenerate b and u on the GPU (<= 1 ulp from the host values)."""
         _capi.check(self._lib.mi355cg_setup_on_device(self._h))
@@ -235,6 +292,23 @@ class MatrixFreeSystem:
     def preconditioner_info(self):
         """(kind, cycle, levels) of the preconditioner that is set; (PRECOND_NONE, CYCLE_F64, 0) without one."""
         return self._handle.preconditioner_info()
+
+    def solve_batch(self, b, eps: float = 1e-6, max_iterations: int = 10000, rule: int = _capi.RULE_REL_2NORM, params=None):
+        """Extension (no reference twin): many right-hand sides on this grid by one multigrid-preconditioned CG loop (needs
+        set_preconditioner).  b: [nrhs, size()] float64, NumPy or a CUDA torch tensor; returns (x of the same kind, one
+        _capi.Results per system), every system with the bits a MatrixFreeSolver / MSGSolver solve of it on this system
+        gives.  eps: eps_rel (RULE_REL_2NORM) or the precision and residual thresholds (RULE_MSG_MAXNORM); params, if
+        given, is used as it is."""
+        if params is None:
+            params = default_params(rule)
+            params.max_iterations = max_iterations
+            params.eps_rel = params.eps_precision = params.eps_residual = eps
+            params.use_true_solution = 0
+        return self._handle.solve_batch(params, b)
+
+    def batch_release(self):
+        """Free the device workspace solve_batch keeps on this system."""
+        self._handle.batch_release()
 
 
 class GridSystem(MatrixFreeSystem):

@@ -6,7 +6,9 @@
   summary:  a table per trace directory: launches, total and per-PCG-iteration device time of every k_mg_* kernel (the kernels
             of the solve; the set-up's fills are left out), and the solve's sum.
             --cycle f32 runs the V-cycle in fp32 (MI355CG_CYCLE_F32; its kernels are the k_mg32_* ones).
-Usage: python tools/mg_profile.py solve --kind {mg,any} [--cycle {f64,f32}] N [--record FILE]
+            --batch NRHS solves NRHS seeded standard-normal right-hand sides by one batched solve instead (mi355cg_solve_batch; its
+            kernels are the k_mgb_* ones); "iterations" is then the largest count of the batch.
+Usage: python tools/mg_profile.py solve --kind {mg,any} [--cycle {f64,f32}] [--batch NRHS] N [--record FILE]
        python tools/mg_profile.py summary OUT.txt DIR [DIR ...]      (each DIR holds a trace and the FILE of its solve)"""
 import csv
 import glob
@@ -36,13 +38,26 @@ def solve(args):
         i = args.index("--cycle")
         cycle = args[i + 1]
         del args[i:i + 2]
+    nrhs = 0
+    if "--batch" in args:
+        i = args.index("--batch")
+        nrhs = int(args[i + 1])
+        del args[i:i + 2]
     n = int(args[0])
     s = isa.MatrixFreeSystem(n, n, 1.0, 2.0, 1.0, 2.0)
     s.set_preconditioner(kind, {"f64": isa.CYCLE_F64, "f32": isa.CYCLE_F32}[cycle])
     p = isa.default_params(_capi.RULE_REL_2NORM)
     p.eps_rel, p.max_iterations = 1e-8, 1000
-    res = s._handle.solve(p)
-    out = {"n": n, "kind": ("MG_ANY" if kind == isa.PRECOND_MG_ANY else "MG") + (", fp32 V-cycle" if cycle == "f32" else ""),
+    if nrhs:
+        import numpy as np
+        p.use_true_solution = 0
+        _, all_res = s._handle.solve_batch(p, np.random.default_rng(n).standard_normal((nrhs, s.size())))
+        res = max(all_res, key=lambda r: r.iterations)
+        res.converged = int(all(r.converged for r in all_res))
+    else:
+        res = s._handle.solve(p)
+    out = {"n": n, "kind": ("MG_ANY" if kind == isa.PRECOND_MG_ANY else "MG") + (", fp32 V-cycle" if cycle == "f32" else "")
+           + (f", one batch of {nrhs} right-hand sides" if nrhs else ""),
            "levels": list(isa.mg_hierarchy(n, kind)),
            "iterations": res.iterations, "converged": res.converged, "solve_seconds": res.solve_seconds}
     print(json.dumps(out))
@@ -58,7 +73,7 @@ def kernel_times(d):
     for f in glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True):
         with open(f, newline="") as fh:
             for row in csv.DictReader(fh):
-                m = re.search(r"k_mg(32)?_\w+(<[^>]*>)?", row["Kernel_Name"])
+                m = re.search(r"k_mg(32|b)?_\w+(<[^>]*>)?", row["Kernel_Name"])
                 if m:
                     dur[m.group(0)].append((int(row["End_Timestamp"]) - int(row["Start_Timestamp"])) / 1e3)
     return dur

@@ -16,7 +16,15 @@ Usage: python tools/mg_timing.py [N ...]      (default 256 1024 4096 8192; write
                                                       writes profiles/mg_any_time_to_solution.txt)
        python tools/mg_timing.py --kind any --cycle f32 [--baseline-tree DIR] [N ...]
                                                      (default 100 1000 4096 4098 8192 10000;
-                                                      writes profiles/mg_f32_time_to_solution.txt)"""
+                                                      writes profiles/mg_f32_time_to_solution.txt)
+--batch: batched solves (mi355cg_solve_batch_device) against one solve per right-hand side, MG_ANY, fp64 cycle, REL_2NORM 1e-8, seeded
+standard-normal right-hand sides.  Per N and nrhs: one warm-up of each path, then three repetitions alternating {nrhs single solves, one
+batch}; reported are the best sum of the single solves' wall times (set_rhs / get_solution not timed) and the best wall time of the batch
+call on vectors that are already in device memory.  --baseline-tree DIR adds the single solves of another built checkout (the commit
+before the feature) in a child process of the same job: the yardstick.
+       python tools/mg_timing.py --batch [--baseline-tree DIR] [N ...]
+                                                     (default 100 258 1000 2002 4096, nrhs 4 16 64, at N >= 4096 only 4;
+                                                      writes profiles/mg_batch_time_to_solution.txt)"""
 import json
 import subprocess
 import os
@@ -36,6 +44,8 @@ SIZES = {"mg": [256, 1024, 4096, 8192], "any": [100, 258, 1000, 1002, 4096, 4098
 RULES = {"REL_2NORM 1e-8": _capi.RULE_REL_2NORM, "MSG defaults": _capi.RULE_MSG_MAXNORM}
 OUT_F32 = os.path.join(ROOT, "profiles", "mg_f32_time_to_solution.txt")
 SIZES_F32 = [100, 1000, 4096, 4098, 8192, 10000]
+OUT_BATCH = os.path.join(ROOT, "profiles", "mg_batch_time_to_solution.txt")
+SIZES_BATCH = [100, 258, 1000, 2002, 4096]
 
 
 def params(rule):
@@ -170,13 +180,111 @@ def main_f32(ns, baseline_tree):
     print("wrote", OUT_F32)
 
 
+def batch_counts(n):
+    return [4] if n >= 4096 else [4, 16, 64]
+
+
+def batch_rhs(n, size, nrhs):
+    return np.random.default_rng(1000 * n + nrhs).standard_normal((nrhs, size))
+
+
+def batch_params():
+    p = params(_capi.RULE_REL_2NORM)
+    p.use_true_solution = 0
+    return p
+
+
+def sequential_solves(h, rhs, p):
+    """sum of the wall times of mi355cg_solve over the right-hand sides, and the iteration counts"""
+    total, its = 0.0, []
+    for v in rhs:
+        h.set_rhs(v)
+        t0 = time.perf_counter()
+        res = h.solve(p)
+        total += time.perf_counter() - t0
+        its.append(res.iterations)
+    return total, its
+
+
+def batch_baseline_worker(ns):
+    """Child process of --batch --baseline-tree: the other checkout's package, which has no batched solve.  Prints one JSON line:
+    {N: {nrhs: best sum of wall times}}."""
+    out = {}
+    for n in ns:
+        s = isa.MatrixFreeSystem(n, n, 1.0, 2.0, 1.0, 2.0)
+        s.set_preconditioner(isa.PRECOND_MG_ANY)
+        out[n] = {}
+        for nrhs in batch_counts(n):
+            rhs = batch_rhs(n, s.size(), nrhs)
+            sequential_solves(s._handle, rhs, batch_params())
+            out[n][nrhs] = min(sequential_solves(s._handle, rhs, batch_params())[0] for _ in range(3))
+        s._handle.close()
+    print("BASELINE " + json.dumps(out), flush=True)
+
+
+def main_batch(ns, baseline_tree):
+    import torch
+    base = None
+    if baseline_tree:
+        env = dict(os.environ, MG_TIMING_TREE=os.path.abspath(baseline_tree))
+        txt = subprocess.run([sys.executable, os.path.abspath(__file__), "--batch-baseline-worker"] + [str(n) for n in ns], env=env,
+                             check=True, capture_output=True, text=True, timeout=900).stdout
+        base = json.loads([l for l in txt.splitlines() if l.startswith("BASELINE ")][-1][len("BASELINE "):])
+    lines = ["# time to solution of nrhs right-hand sides on one MI355X: one batched solve (mi355cg_solve_batch_device) against nrhs single "
+             "solves (tools/mg_timing.py --batch)",
+             "# MG_ANY, fp64 cycle, REL_2NORM 1e-8, seeded standard-normal right-hand sides; one warm-up of each path, then three "
+             "repetitions alternating, the best of each",
+             "# seq = sum of the wall times of mi355cg_solve (set_rhs / get_solution not timed); batch = wall time of the batch call, "
+             "vectors already in device memory",
+             "# base_seq = seq of the --baseline-tree checkout (the commit before the feature) in a child process of the same job"
+             if base else "# no --baseline-tree: base_seq not measured",
+             f"# {'N':>5} {'nrhs':>4} {'iters':>7} {'base_seq_ms':>11} {'seq_ms':>9} {'batch_ms':>9} {'batch/base':>10} {'batch/seq':>9} {'seq/base':>8}"]
+    print("\n".join(lines), flush=True)
+    for n in ns:
+        s = isa.MatrixFreeSystem(n, n, 1.0, 2.0, 1.0, 2.0)
+        s.set_preconditioner(isa.PRECOND_MG_ANY)
+        h = s._handle
+        for nrhs in batch_counts(n):
+            rhs = batch_rhs(n, s.size(), nrhs)
+            dev = torch.from_numpy(rhs).cuda()
+            p = batch_params()
+            sequential_solves(h, rhs, p)
+            h.solve_batch(p, dev)
+            seq, bat, its = [], [], None
+            for _ in range(3):
+                t, its = sequential_solves(h, rhs, p)
+                seq.append(t)
+                t0 = time.perf_counter()
+                _, res = h.solve_batch(p, dev)
+                bat.append(time.perf_counter() - t0)
+                assert [r.iterations for r in res] == its
+            b = base[str(n)][str(nrhs)] if base else None
+            line = (f"  {n:>5} {nrhs:>4} {f'{min(its)}..{max(its)}':>7} " + (f"{b * 1e3:>11.3f}" if base else f"{'-':>11}") +
+                    f" {min(seq) * 1e3:>9.3f} {min(bat) * 1e3:>9.3f} " + (f"{min(bat) / b:>10.3f}" if base else f"{'-':>10}") +
+                    f" {min(bat) / min(seq):>9.3f} " + (f"{min(seq) / b:>8.3f}" if base else f"{'-':>8}"))
+            lines.append(line)
+            print(line, flush=True)
+            del dev
+            h.batch_release()
+        h.close()
+    with open(OUT_BATCH, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    print("wrote", OUT_BATCH)
+
+
 if __name__ == "__main__":
     args = sys.argv[1:]
     if args and args[0] == "--baseline-worker":
         baseline_worker([int(a) for a in args[1:]])
         sys.exit(0)
+    if args and args[0] == "--batch-baseline-worker":
+        batch_baseline_worker([int(a) for a in args[1:]])
+        sys.exit(0)
     kind = "mg"
     cycle, baseline_tree = "f64", None
+    batch = "--batch" in args
+    if batch:
+        args.remove("--batch")
     if "--cycle" in args:
         i = args.index("--cycle")
         cycle = args[i + 1]
@@ -193,7 +301,9 @@ if __name__ == "__main__":
         del args[i:i + 2]
         if kind not in OUT:
             sys.exit(f"--kind must be one of {sorted(OUT)}")
-    if cycle == "f32":
+    if batch:
+        main_batch([int(a) for a in args] or SIZES_BATCH, baseline_tree)
+    elif cycle == "f32":
         if kind != "any":
             sys.exit("--cycle f32 goes with --kind any")
         main_f32([int(a) for a in args] or SIZES_F32, baseline_tree)
