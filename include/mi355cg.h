@@ -235,6 +235,13 @@ int  mi355cg_get_kernel_time(mi355cg_handle h, int kernel, double *avg_ms, long 
 /* launch geometry: bytes of storage per vector, padded length, grid sizes (for DESIGN/bench)   */
 int  mi355cg_get_layout(mi355cg_handle h, long long *padded_len, int *pitch_bottom, int *pitch_upper,
                         int *grid_stencil, int *grid_update, int *rows_per_item);
+/* Deferred x fold of single-context fp64 solves (REL_2NORM without diagnostics): instead of touching x in every fourth update
+ * launch, a ring of `depth` = 16 or 32 direction buffers is kept and one flat launch applies the last `depth` steps at once --
+ * the same roundings in the same order, so the same bits.  Chosen at mi355cg_create: MI355CG_XFOLD=0 off, =16|32 forced, unset =
+ * on for handles of 4 Mi owned elements or more whose ring fits in a quarter of the device's memory (32, else 16, else off);
+ * an explicit MI355CG_XSTEPS turns it off.  depth: the depth in use, 0 = fused update.  extra_buffers: vectors the ring holds
+ * beyond the handle's own, 0 until the first solve that folds (a failed allocation there sets depth to 0 for good).            */
+int  mi355cg_get_xfold(mi355cg_handle h, int *depth, int *extra_buffers);
 
 /* ---- multi-GPU: one context per rank, one contiguous slab of grid rows per context --------------
  * The reference is single-process (no collectives exist in it); this is the scaling

@@ -30,7 +30,7 @@ EXPORTS = [
     "mi355cg_team_set_profiling", "mi355cg_team_phase_times", "mi355cg_team_describe", "mi355cg_setup_on_device", "mi355cg_team_setup_on_device", "mi355cg_debug_plan",
     "mi355cg_team_set_dtype", "mi355cg_set_preconditioner", "mi355cg_apply_preconditioner", "mi355cg_mg_levels",
     "mi355cg_mg_hierarchy", "mi355cg_set_preconditioner_ex", "mi355cg_preconditioner_info",
-    "mi355cg_solve_batch", "mi355cg_solve_batch_device", "mi355cg_batch_release",
+    "mi355cg_solve_batch", "mi355cg_solve_batch_device", "mi355cg_batch_release", "mi355cg_get_xfold",
 ]
 DECOMP_ROWS, DECOMP_2D = 0, 1
 PRECOND_NONE, PRECOND_MG, PRECOND_MG_ANY = 0, 1, 2
@@ -171,6 +171,8 @@ def load():
     L.mi355cg_solve_batch.argtypes = [H, C.POINTER(Params), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Results)]
     L.mi355cg_solve_batch_device.argtypes = [H, C.POINTER(Params), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Results)]
     L.mi355cg_batch_release.argtypes = [H]
+    if hasattr(L, "mi355cg_get_xfold"):          # absent from an older build loaded through MI355CG_LIB
+        L.mi355cg_get_xfold.argtypes = [H, IP, IP]
     _lib = L
     return L
 

@@ -8,6 +8,8 @@
 //   k_update_st (phase B)   A p rebuilt from three rows of the stored direction, r -= alpha Ap, x update (every fourth
 //                           iteration, four steps at once; every iteration for the MSG rule), partial sums / maxes of
 //                           r.r, |r|, |dx|, |x-u|.  Replaces matrix_free_system.cpp:422-455 / msg_solver.cpp:105-139.
+//   k_fold_x                deferred x fold (single-context fp64, REL_2NORM without diagnostics, larger grids): with a ring of 16 or 32
+//                           directions no update launch touches x; this flat launch applies the last R steps every R-th iteration.
 //   k_update                flat variant: state initialisation, resume step of the mixed-precision path, CSR handles.
 //   k_check, k_flush_x, k_make_record, k_scatter_ghosts, k_pack/k_unpack, k_sub, k_resid2, ...: small helpers.
 //
@@ -1140,6 +1142,8 @@ struct UpdateStArgs {
                          // part's record (every part ORs its own sample with the other parts' records, so all decide alike); may be null
     FlagSpec fl;         // team: every block also stores its partials flagged, for the reducer launch that runs beside this one
     QueueSpec dq;        // dynamic item queues (see QueueSpec)
+    double* fold_alpha;  // deferred x fold (k_fold_x): the step length of iteration k also goes to fold_alpha[k & fold_mask]; null otherwise
+    int fold_mask;
 };
 
 template <typename T, int VEC, int XM, bool HAS_U, int DEPTH, bool DESC>
@@ -1370,6 +1374,7 @@ __global__ __launch_bounds__(kBlock) void k_update_st(const UpdateStArgs<T> a) {
             CgState* o = a.s_out;
             o->it = s.it + 1; o->first = 0; o->alpha = alpha_d; o->rz = rz; o->alpha_hist[(s.it + 1) & (kRing - 1)] = alpha_d;
             o->stop = stop_word != 0;              // the reference tests its flag once per iteration (msg_solver.cpp:82-87)
+            if (a.fold_alpha) a.fold_alpha[(s.it + 1) & a.fold_mask] = alpha_d;
         }
     }
 }
@@ -1421,6 +1426,66 @@ __global__ __launch_bounds__(kBlock) void k_flush_x(const Geom g, const WorkList
             }
             *reinterpret_cast<vec_t*>(x + off) = xn;
         }
+    }
+}
+
+// ---- deferred x fold (single-context fp64 solves, REL_2NORM without diagnostics) --------------------------------------
+// With a ring of R = 16 or 32 direction buffers (p_k in slot k % R) no update launch touches x: every R-th iteration this
+// kernel applies the last R steps at once, x = (((x + a_{k-R+1} p_{k-R+1}) + ...) + a_k p_k), oldest first, one unfused
+// multiply and one add per step -- the roundings of R single updates in their order, hence their bits -- for (R + 2) / R
+// words per iteration instead of the 1.25 of the fused M = 4 launch.  Flat over the owned range like k_init_fresh: pads and
+// boundary cells of every slot hold 0.  The slots and the step lengths come from a table in device memory and the
+// iteration count from the state, never from kernel arguments, so a captured chunk can be replayed:
+//   flush_it < 0  (after the update launch of an iteration the host counts as k = 0 mod R): all R steps, unless the stop
+//                 decision has been taken (then this is a no-op like every launch after it and it % R steps stay pending);
+//   flush_it >= 0 (end of a solve that ran flush_it iterations, as the host read it from the summary): the flush_it % R
+//                 steps still pending.
+// Steps are taken in blocks of up to eight streams whose loads are all issued before the first one is used.
+constexpr int kFoldMax = 32;
+struct FoldTable { const double* p[kFoldMax]; double alpha[kFoldMax]; };    // slot / step length of iteration k at [k % R]; alpha is written by k_update_st
+struct FoldArgs {
+    long long begin, nvec;      // owned flat range in units of two elements
+    double* x;
+    const FoldTable* tab;
+    const CgState* s;           // in-loop: the state the update launch has just written
+    int mask;                   // R - 1
+    int flush_it;
+};
+template <int NS, bool NT>
+__device__ inline void fold_block(VecOf<double, 2>::type& xv, const FoldTable* tab, int k0, int mask, long long i) {
+    typedef VecOf<double, 2>::type vec_t;
+    const vec_t* P[NS]; double al[NS]; vec_t v[NS];
+#pragma unroll
+    for (int j = 0; j < NS; ++j) {
+        const int slot = (k0 + j) & mask;
+        P[j] = reinterpret_cast<const vec_t*>(scalar_load(&tab->p[slot]));
+        al[j] = scalar_load(&tab->alpha[slot]);
+    }
+#pragma unroll
+    for (int j = 0; j < NS; ++j) v[j] = NT ? __builtin_nontemporal_load(P[j] + i) : P[j][i];
+#pragma unroll
+    for (int j = 0; j < NS; ++j) { xv[0] = xv[0] + al[j] * v[j][0]; xv[1] = xv[1] + al[j] * v[j][1]; }      // x = x + alpha*z
+}
+template <bool NT>
+__global__ __launch_bounds__(kBlock) void k_fold_x(const FoldArgs a) {
+    typedef VecOf<double, 2>::type vec_t;
+    const int it = a.flush_it >= 0 ? a.flush_it : scalar_load(&a.s->it);
+    int n = it & a.mask;                                       // flush: the steps after the last multiple of R
+    if (a.flush_it < 0) {
+        if (scalar_load(&a.s->done) || n != 0 || it == 0) return;
+        n = a.mask + 1;
+    }
+    if (n == 0) return;
+    vec_t* __restrict__ X = reinterpret_cast<vec_t*>(a.x);
+    const long long stride = (long long)gridDim.x * kBlock, end = a.begin + a.nvec;
+    for (long long i = a.begin + (long long)blockIdx.x * kBlock + threadIdx.x; i < end; i += stride) {
+        vec_t xv = X[i];
+        int k = it - n + 1;                                    // oldest pending step
+        for (; k + 8 <= it + 1; k += 8) fold_block<8, NT>(xv, a.tab, k, a.mask, i);
+        if (k + 4 <= it + 1) { fold_block<4, NT>(xv, a.tab, k, a.mask, i); k += 4; }
+        if (k + 2 <= it + 1) { fold_block<2, NT>(xv, a.tab, k, a.mask, i); k += 2; }
+        if (k <= it) fold_block<1, NT>(xv, a.tab, k, a.mask, i);
+        X[i] = xv;
     }
 }
 

@@ -14,6 +14,7 @@
 #include <cfloat>
 #include <chrono>
 #include <cstdarg>
+#include <cstddef>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -155,6 +156,15 @@ struct mi355cg_ctx {
     int grid_csr = 0, grid_update = 0;
     int cur = 0;                        // p[cur] holds the current direction after the last stencil: cur = (iterations done) % xsteps
     int nA_dist = 0;                    // slab mode: stencil partial slots written by the last stencil phase
+    // Deferred x fold (k_fold_x; single-context fp64 solves that would otherwise fold x every M-th iteration): a ring of R direction
+    // buffers.  Slots 0 .. xsteps-1 are p[], the others are allocated by the first solve that folds (ensure_fold_ring).
+    int xfold = 0;                      // R (16 | 32), 0 = the fused update (env MI355CG_XFOLD; unset: by size, see create_impl)
+    double* fold_p[kFoldMax] = {};      // the ring's slots: p_k lives in fold_p[k % R]
+    int fold_extra = 0;                 // buffers allocated beyond p[]: 0 until the first solve that folds, then R - xsteps
+    FoldTable* fold_tab = nullptr;      // device: the slots, and the step lengths of the last R iterations (written by the update launches)
+    int fcur = 0;                       // fold mode: (iterations done) % R
+    int fold_grid = 0;                  // workgroups of k_fold_x; 0 = one element pair per thread (env MI355CG_XFOLD_GRID)
+    bool fold_nt = true;                // nontemporal loads of the once-read directions in k_fold_x (env MI355CG_XFOLD_NT, A/B runs)
 
     // hipGraph cache for launch-bound (small) grids: one instantiated graph per distinct chunk shape of a solve
     struct ChunkGraph { int m, cur; std::vector<char> flags; hipGraphExec_t exec; };
@@ -388,7 +398,7 @@ void launch_apply(const mi355cg_ctx* c, const T* v, T* out, const Where& w) {
     hipLaunchKernelGGL((k_stencil<T, VEC, false, false, 2, false, false>), dim3(w.plan->grid), dim3(kBlock), 0, w.stream, a);
 }
 
-struct IterCfg { RuleParams rp; int want_diag; bool has_u; bool x2 = false; };
+struct IterCfg { RuleParams rp; int want_diag; bool has_u; bool x2 = false; bool fold = false; };     // fold: x2 with the x steps deferred to k_fold_x
 
 // Phase A'.  Does NOT flip c->cur (a part's interior and edge launches share one direction pair).
 template <typename T, int VEC>
@@ -429,13 +439,14 @@ void launch_iteration_update(mi355cg_ctx* c, const IterCfg& cfg, T* x, T* r, T* 
     a.s_in = c->sA; a.s_out = c->sB; a.rule = cfg.rp.rule; a.reverse = 1;
     if (fl) a.fl = *fl;
     if (VEC == 2 && c->dyn_rows > 0 && w.plan == &c->whole) a.dq = QueueSpec{c->qctr + kXcds * kQueueSubs * kQueuePitch, c->qctr};
+    if (cfg.fold) { a.fold_alpha = reinterpret_cast<double*>(reinterpret_cast<char*>(c->fold_tab) + offsetof(FoldTable, alpha)); a.fold_mask = c->xfold - 1; }
     a.stop_req = w.slot == 0 ? c->stop_dev : nullptr;   // block 0 samples the pinned stop word once per iteration (of a phase in two launches: the one that runs last and owns slot 0)
     const dim3 grid(w.plan->grid), block(kBlock);
     const bool d3 = c->depth == 3 && !(cfg.x2 && c->cur == 0 && c->xsteps == 8);
 #define MI355CG_UST(XM, HASU) do { if (d3) hipLaunchKernelGGL((k_update_st<T, VEC, XM, HASU, 3, true>), grid, block, 0, w.stream, a); \
                                    else hipLaunchKernelGGL((k_update_st<T, VEC, XM, HASU, 2, true>), grid, block, 0, w.stream, a); } while (0)
     if (cfg.x2) {                    // iterations k = 0 mod M carry all M x steps (c->cur = k % M)
-        if (c->cur != 0) MI355CG_UST(0, false); else if (c->xsteps == 8) MI355CG_UST(8, false); else if (c->xsteps == 4) MI355CG_UST(4, false); else MI355CG_UST(2, false);
+        if (c->cur != 0 || cfg.fold) MI355CG_UST(0, false); else if (c->xsteps == 8) MI355CG_UST(8, false); else if (c->xsteps == 4) MI355CG_UST(4, false); else MI355CG_UST(2, false);
     }
     else if constexpr (VEC == 2) { if (cfg.has_u) MI355CG_UST(1, true); else MI355CG_UST(1, false); }
 #undef MI355CG_UST
@@ -468,6 +479,49 @@ void launch_flush_x(const mi355cg_ctx* c, const Plan& plan, T* x, T* const p[kRi
                        kernel_geom<T, VEC>(c), plan.wl, x, f);
 }
 
+// Deferred x fold.  flush_it < 0: after the update launch of an iteration k = 0 mod R, the R steps up to k (unless that launch's
+// state says the solve is over); flush_it >= 0: after a loop of flush_it iterations, the flush_it % R steps still pending.
+void launch_fold_x(const mi355cg_ctx* c, int flush_it, hipStream_t stream) {
+    FoldArgs a{};
+    a.begin = c->g.own_begin / 2; a.nvec = c->g.own_len / 2;
+    a.x = c->x; a.tab = c->fold_tab; a.s = c->sB; a.mask = c->xfold - 1; a.flush_it = flush_it;
+    const long long one_shot = (a.nvec + kBlock - 1) / kBlock;
+    const int grid = (int)std::max<long long>(1, c->fold_grid > 0 ? std::min<long long>(c->fold_grid, one_shot) : one_shot);
+    if (c->fold_nt) hipLaunchKernelGGL((k_fold_x<true>), dim3(grid), dim3(kBlock), 0, stream, a);
+    else hipLaunchKernelGGL((k_fold_x<false>), dim3(grid), dim3(kBlock), 0, stream, a);
+}
+void free_fold_ring(mi355cg_ctx* c) {
+    for (int k = c->xsteps; k < kFoldMax; ++k) if (c->fold_p[k]) { hipFree(c->fold_p[k]); c->fold_p[k] = nullptr; }
+    if (c->fold_tab) { hipFree(c->fold_tab); c->fold_tab = nullptr; }
+    c->fold_extra = 0;
+}
+// The ring of a handle that folds, allocated and zeroed once (pads, boundary and ghost cells of every slot must hold 0, as in p[]).
+// If the memory is not there the handle goes back to the fused update for good and stays usable.
+bool ensure_fold_ring(mi355cg_ctx* c) {
+    if (c->xfold == 0) return false;
+    if (c->fold_tab) return true;
+    const size_t bytes = sizeof(double) * (size_t)c->storage_len;
+    bool ok = true;
+    for (int k = 0; k < c->xfold && ok; ++k) {
+        if (k < c->xsteps) { c->fold_p[k] = c->p[k]; continue; }
+        ok = hipMalloc((void**)&c->fold_p[k], bytes) == hipSuccess && hipMemsetAsync(c->fold_p[k], 0, bytes, c->stream) == hipSuccess;
+        if (!ok) c->fold_p[k] = nullptr;
+    }
+    FoldTable t{};
+    for (int k = 0; k < c->xfold; ++k) t.p[k] = c->fold_p[k];
+    ok = ok && hipMalloc((void**)&c->fold_tab, sizeof(FoldTable)) == hipSuccess &&
+         hipMemcpyAsync(c->fold_tab, &t, sizeof t, hipMemcpyHostToDevice, c->stream) == hipSuccess && hipStreamSynchronize(c->stream) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();                 // the failed allocation is not an error of the solve
+        hipStreamSynchronize(c->stream);
+        free_fold_ring(c);
+        c->xfold = 0;
+        return false;
+    }
+    c->fold_extra = c->xfold - c->xsteps;
+    return true;
+}
+
 void launch_check(mi355cg_ctx* c, const IterCfg& cfg, hipStream_t stream, const PartSrc& pb) {
     CheckArgs a{};
     a.partB = pb.ptr; a.nB = pb.n; a.strideB = pb.fstride; a.esB = pb.estride; a.src = pb.rec;
@@ -475,7 +529,8 @@ void launch_check(mi355cg_ctx* c, const IterCfg& cfg, hipStream_t stream, const 
     hipLaunchKernelGGL(k_check, dim3(1), dim3(kBlock), 0, stream, a);
 }
 
-// The launch shapes of an iteration: REL_2NORM without diagnostics = x folded every M-th iteration (M = 4: 7.25 words per unknown);
+// The launch shapes of an iteration: REL_2NORM without diagnostics = x folded every M-th iteration (M = 4: 7.25 words per unknown; on a
+// handle with a deferred fold, mi355cg_solve sets cfg.fold: no update launch touches x, k_fold_x does every R-th iteration: 7.0625);
 // MSG, and REL_2NORM with the reference's per-iteration diagnostics = x and its norms every iteration (8 words, + u when read).
 IterCfg make_cfg(const mi355cg_params* prm) {
     IterCfg cfg{};
@@ -1488,6 +1543,21 @@ static int create_impl(int n, int m, double a, double b, double c_, double d, in
     // x is folded every M-th iteration: 4 by default.  8 saves another 0.125 words per iteration and measured +0.2-0.7 % for
     // four more vectors (fp64 only: the fp32 8-step launch needs 262 VGPRs and would halve the resident waves)
     { const int m = env_int("MI355CG_XSTEPS", 4); c->xsteps = m == 2 ? 2 : ((m == 8 && dtype == MI355CG_F64) ? 8 : 4); }
+    // Deferred x fold (fp64, one context, no explicit MI355CG_XSTEPS): MI355CG_XFOLD = 16 | 32 forces that depth, 0 (or anything else) is
+    // the fused update; unset = by size: on from 4 Mi owned elements (the grids that are not graph-replayed), the deepest ring
+    // of 32, then 16 buffers that fits in a quarter of the device's memory (N = 16384: 32; N = 32768: fused).
+    if (!part && dtype == MI355CG_F64 && !getenv("MI355CG_XSTEPS")) {
+        const char* xf = getenv("MI355CG_XFOLD");
+        const int want = (xf && *xf) ? atoi(xf) : -1;
+        if (want == 16 || want == 32) c->xfold = want;
+        else if (want < 0 && c->g.own_len >= (4LL << 20)) {
+            size_t mem_free = 0, mem_total = 0;
+            if (hipMemGetInfo(&mem_free, &mem_total) == hipSuccess)
+                for (int R : {32, 16}) if (c->xfold == 0 && sizeof(double) * (size_t)L * (size_t)R <= mem_total / 4) c->xfold = R;
+        }
+        c->fold_grid = std::max(0, env_int("MI355CG_XFOLD_GRID", 0));
+        c->fold_nt = env_int("MI355CG_XFOLD_NT", 1) != 0;
+    }
     double** vecs[] = {&c->x, &c->r, &c->p[0], &c->p[1], &c->ap, &c->b, &c->u, &c->p[2], &c->p[3], &c->p[4], &c->p[5], &c->p[6], &c->p[7]};
     for (int k = 0; k < 7 + (c->xsteps - 2); ++k) if ((rc = alloc_vec(vecs[k], L))) return cleanup();
     if (dtype == MI355CG_F32_MIXED) {
@@ -1630,6 +1700,7 @@ void mi355cg_destroy(mi355cg_handle c) {
                    c->pf[0], c->pf[1], c->pf[2], c->pf[3], c->pf[4], c->pf[5], c->pf[6], c->pf[7], c->apf,
                    c->packed, c->partA, c->partB, c->partR, c->sumsA, c->sumsB, c->sA, c->sB, c->summary, c->hist, c->qctr};
     for (void* p : dev) if (p) hipFree(p);
+    free_fold_ring(c);
     if (c->csr_row_map) hipFree(c->csr_row_map);
     if (c->csr_entries) hipFree(c->csr_entries);
     if (c->csr_values) hipFree(c->csr_values);
@@ -1751,8 +1822,10 @@ int mi355cg_solve(mi355cg_handle c, const mi355cg_params* prm, mi355cg_iter_cb c
     if (c->dtype == MI355CG_F32_MIXED) return solve_mixed(c, prm, cb, user, stop_flag, out);
     if (c->mg) return solve_mg(c, prm, cb, user, stop_flag, out);                     // opt-in preconditioner (fp64 grid handles only)
     const bool msg = prm->rule == MI355CG_RULE_MSG_MAXNORM;
-    const IterCfg cfg = make_cfg(prm);
-    const bool diag = cfg.want_diag != 0;
+    IterCfg cfg0 = make_cfg(prm);
+    cfg0.fold = cfg0.x2 && ensure_fold_ring(c);
+    const IterCfg cfg = cfg0;
+    const bool diag = cfg.want_diag != 0, fold = cfg.fold;
     c->nB_own = c->whole.grid;
     if (cfg.has_u) if (int rc = ensure_u_on_device(c)) return rc;
     if (diag) if (int rc = ensure_scratch(c)) return rc;
@@ -1764,7 +1837,7 @@ int mi355cg_solve(mi355cg_handle c, const mi355cg_params* prm, mi355cg_iter_cb c
     // One pass over the owned range.  Everything outside it (pitch padding, the rows around the grid) was zeroed when the
     // vectors were allocated and no launch writes anything but zeros there; the other directions of the ring are written
     // (iterations 1 .. M-1) before the folded x update first reads them (iteration M).
-    c->cur = 0;
+    c->cur = 0; c->fcur = 0;
     if (c->qctr && c->dyn_rows > 0) HIPCK(hipMemsetAsync(c->qctr, 0, sizeof(int) * 2 * kXcds * kQueueSubs * kQueuePitch, c->stream));
     {
         FreshArgs<double> f{};
@@ -1837,14 +1910,21 @@ int mi355cg_solve(mi355cg_handle c, const mi355cg_params* prm, mi355cg_iter_cb c
         auto enqueue_chunk = [&]() -> int {
             for (int k = 0; k < m; ++k) {
                 hipEvent_t e0 = nullptr;
+                // Fold mode: the direction pair of this iteration sits in ring slots fcur and fcur + 1.  The launchers address p[] by
+                // c->cur, so they are handed a table with those two slots at cur and cur + 1 (the update launch is XM = 0: no pprev).
+                double* pp[kRing] = {};
+                if (fold) { pp[c->cur] = c->fold_p[c->fcur]; pp[(c->cur + 1) % c->xsteps] = c->fold_p[(c->fcur + 1) % c->xfold]; }
+                double* const* ring = fold ? pp : c->p;
                 prof_begin(c, &e0);
-                launch_iteration_stencil<double, 2>(c, cfg, c->r, c->p, whole_part(c), own_partB(c));
+                launch_iteration_stencil<double, 2>(c, cfg, c->r, ring, whole_part(c), own_partB(c));
                 c->cur = (c->cur + 1) % c->xsteps;
+                if (fold) c->fcur = (c->fcur + 1) % c->xfold;
                 prof_end(c, 0, e0);
                 prof_begin(c, &e0);
                 IterCfg ucfg = cfg;
                 ucfg.has_u = cfg.has_u && need_u(it_done + k + 1);      // skip the u stream when nothing reads the error norm
-                launch_iteration_update<double, 2>(c, ucfg, c->x, c->r, c->p, c->u, whole_part(c), own_partA(c));
+                launch_iteration_update<double, 2>(c, ucfg, c->x, c->r, ring, c->u, whole_part(c), own_partA(c));
+                if (fold && c->fcur == 0) launch_fold_x(c, -1, c->stream);      // iteration k = 0 mod R: the last R x steps (update-phase time)
                 prof_end(c, 1, e0);
                 if (diag) {
                     // MatrixFreeSolver's per-iteration report needs the TRUE residual (matrix_free_system.cpp:457-463): a
@@ -1862,23 +1942,25 @@ int mi355cg_solve(mi355cg_handle c, const mi355cg_params* prm, mi355cg_iter_cb c
             std::vector<char> flags(m);
             for (int k = 0; k < m; ++k) flags[k] = cfg.has_u && need_u(it_done + k + 1);
             mi355cg_ctx::ChunkGraph* hit = nullptr;
-            for (auto& g : c->graphs) if (g.m == m && g.cur == c->cur && g.flags == flags) hit = &g;
+            const int key = fold ? c->fcur : c->cur;             // the ring position the chunk starts at (fcur % xsteps == cur)
+            for (auto& g : c->graphs) if (g.m == m && g.cur == key && g.flags == flags) hit = &g;
             if (!hit) {
                 hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr;
-                const int cur0 = c->cur;
+                const int cur0 = c->cur, fcur0 = c->fcur;
                 HIPCK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
                 const int rc = enqueue_chunk();
                 const hipError_t e1 = hipStreamEndCapture(c->stream, &graph);
-                c->cur = cur0;                                   // the capture only recorded; nothing ran
+                c->cur = cur0; c->fcur = fcur0;                  // the capture only recorded; nothing ran
                 if (rc) return rc;
                 HIPCK(e1);
                 HIPCK(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
                 HIPCK(hipGraphDestroy(graph));
-                c->graphs.push_back({m, cur0, flags, exec});
+                c->graphs.push_back({m, key, flags, exec});
                 hit = &c->graphs.back();
             }
             HIPCK(hipGraphLaunch(hit->exec, c->stream));
             c->cur = (c->cur + m) % c->xsteps;                    // what enqueue_chunk would have left behind
+            if (fold) c->fcur = (c->fcur + m) % c->xfold;
         } else {
             if (int rc = enqueue_chunk()) return rc;
         }
@@ -1906,8 +1988,9 @@ int mi355cg_solve(mi355cg_handle c, const mi355cg_params* prm, mi355cg_iter_cb c
     // Launches enqueued after the stop decision return in their prologue but still flipped c->cur on the
     // host: the direction of the last REAL iteration is p[it % M] (the solve starts with cur = 0).
     c->cur = fin.it % c->xsteps;
-    if (cfg.x2) {                                   // folded x update: the steps after the last multiple of M are still pending
-        launch_flush_x<double, 2>(c, c->whole, c->x, c->p, fin, c->stream);
+    if (cfg.x2) {                                   // folded x update: the steps after the last multiple of M (of R) are still pending
+        if (fold) { c->fcur = fin.it % c->xfold; if (c->fcur != 0) launch_fold_x(c, fin.it, c->stream); }
+        else launch_flush_x<double, 2>(c, c->whole, c->x, c->p, fin, c->stream);
         HIPCK(hipGetLastError());
         HIPCK(hipStreamSynchronize(c->stream));
     }
@@ -1990,6 +2073,13 @@ int mi355cg_get_layout(mi355cg_handle c, long long* padded_len, int* pitch_botto
     if (grid_stencil) *grid_stencil = c->whole.grid;
     if (grid_update) *grid_update = c->whole.grid;
     if (rows_per_item) *rows_per_item = c->whole.ty;
+    return MI355CG_OK;
+}
+
+int mi355cg_get_xfold(mi355cg_handle c, int* depth, int* extra_buffers) {
+    if (!c) return fail(MI355CG_ERR_INVALID, "null handle");
+    if (depth) *depth = c->xfold;
+    if (extra_buffers) *extra_buffers = c->fold_extra;
     return MI355CG_OK;
 }
 

@@ -227,8 +227,13 @@ class _Handle:
         L = C.c_longlong()
         v = [C.c_int() for _ in range(5)]
         _capi.check(self._lib.mi355cg_get_layout(self._h, C.byref(L), *[C.byref(i) for i in v]))
+        fold, extra = C.c_int(), C.c_int()
+        if hasattr(self._lib, "mi355cg_get_xfold"):      # an older build of the ABI (MI355CG_LIB) has no deferred x fold
+            _capi.check(self._lib.mi355cg_get_xfold(self._h, C.byref(fold), C.byref(extra)))
+        # x_fold: depth of the deferred x fold in use (0 = fused update); x_fold_buffers: vectors its ring has allocated so far
         return {"padded_len": L.value, "pitch_bottom": v[0].value, "pitch_upper": v[1].value,
-                "grid_stencil": v[2].value, "grid_update": v[3].value, "rows_per_item": v[4].value}
+                "grid_stencil": v[2].value, "grid_update": v[3].value, "rows_per_item": v[4].value,
+                "x_fold": fold.value, "x_fold_buffers": extra.value}
 
 
 def default_params(rule: int) -> _capi.Params:
