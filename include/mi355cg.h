@@ -227,6 +227,37 @@ int  mi355cg_solve_batch_device(mi355cg_handle h, const mi355cg_params *params, 
                                 const volatile int *stop_flag, mi355cg_results *out);
 int  mi355cg_batch_release(mi355cg_handle h);
 
+/* ---- warm starts (extension: the reference's loops start from x = 0) ---------------------------------------------------
+ * A guess x0 (packed order, mi355cg_size(h) doubles) makes the next mi355cg_solve on the handle start from x = x0 and
+ * r0 = b - A x0, where A x0 is bit for bit what mi355cg_apply returns and the subtraction is one rounding
+ * (matrix_free_system.cpp:389-392); the first direction is built from r0 as the cold start builds it from b, and the loop, the
+ * stop flag and the callbacks are those of a cold solve, on the plain and on the preconditioned path.  A guess of zeros is the
+ * cold solve bit for bit.  REL_2NORM with a guess stops on ||r||_2 <= eps_rel ||b||_2 (the same thing for x0 = 0), so a warm
+ * start or a continuation reaches the cold solve's target with less work; initial_r_norm2 stays ||r0||_2; a start that already
+ * meets the rule returns 0 iterations, converged, x = x0.  MSG_MAXNORM with a guess applies the residual test and (where enabled
+ * and u is present) the exact-error test to the start state before iteration 1 (r0 may be 0); a cold solve enters iteration 1
+ * untested, as the reference does.  The it = 0 callback reports the norms of r0 and x0 - u.
+ * The guess is one-shot: the next mi355cg_solve consumes it whatever it returns, later solves are cold.  It is written straight
+ * into the handle's x (no extra vector), so from the call to that solve mi355cg_get_solution, _get_recursive_residual and
+ * _get_true_residual return MI355CG_ERR_STATE; x0 = NULL withdraws a pending guess and leaves them so until the next solve.
+ * mi355cg_set_rhs between the guess and the solve is the normal use (same guess, new b); changing or removing the
+ * preconditioner keeps the guess.  _device: x0_dev is in device memory of the handle's GPU, complete before the call.
+ * mi355cg_use_solution_as_initial_guess: the x of the last solve is the guess, without a copy -- after a solve that ended
+ * MI355CG_STOP_INTERRUPTED or MI355CG_STOP_ITERATIONS this continues it; MI355CG_ERR_STATE if no solve has run.
+ * MI355CG_ERR_INVALID, the handle left as it was: a null handle, CSR handles, slab / part handles, MI355CG_F32_MIXED handles.
+ * Teams have no warm start.                                                                                                   */
+int  mi355cg_set_initial_guess(mi355cg_handle h, const double *x0);            /* host, packed; NULL withdraws a pending guess */
+int  mi355cg_set_initial_guess_device(mi355cg_handle h, const double *x0_dev); /* packed, device memory of the handle's GPU   */
+int  mi355cg_use_solution_as_initial_guess(mi355cg_handle h);                  /* the x of the last solve, no copy            */
+/* mi355cg_solve_batch* with a guess per system: x is in/out, nrhs guesses on entry, the solutions on return.  System s gets
+ * exactly the bits of mi355cg_set_rhs(h, b_s); mi355cg_set_initial_guess(h, x0_s); mi355cg_solve; mi355cg_get_solution on the
+ * same handle, the 0-iteration case included (such a system never enters a launch of the loop).  Refusals and workspace as for
+ * mi355cg_solve_batch*; the host entry point stages 2 nrhs packed vectors.                                                    */
+int  mi355cg_solve_batch_from(mi355cg_handle h, const mi355cg_params *params, int nrhs, const double *b, double *x,
+                              const volatile int *stop_flag, mi355cg_results *out);
+int  mi355cg_solve_batch_device_from(mi355cg_handle h, const mi355cg_params *params, int nrhs, const double *b_dev, double *x_dev,
+                                     const volatile int *stop_flag, mi355cg_results *out);
+
 /* ---- measurement hooks (bench.py) ------------------------------------------------------------ */
 /* Per-kernel device time of the last mi355cg_solve, measured with HIP events on the solve
  * stream when profiling was enabled.  kernel: 0 = fused stencil (A'), 1 = fused update (B).   */

@@ -31,6 +31,8 @@ EXPORTS = [
     "mi355cg_team_set_dtype", "mi355cg_set_preconditioner", "mi355cg_apply_preconditioner", "mi355cg_mg_levels",
     "mi355cg_mg_hierarchy", "mi355cg_set_preconditioner_ex", "mi355cg_preconditioner_info",
     "mi355cg_solve_batch", "mi355cg_solve_batch_device", "mi355cg_batch_release", "mi355cg_get_xfold",
+    "mi355cg_set_initial_guess", "mi355cg_set_initial_guess_device", "mi355cg_use_solution_as_initial_guess",
+    "mi355cg_solve_batch_from", "mi355cg_solve_batch_device_from",
 ]
 DECOMP_ROWS, DECOMP_2D = 0, 1
 PRECOND_NONE, PRECOND_MG, PRECOND_MG_ANY = 0, 1, 2
@@ -171,6 +173,12 @@ def load():
     L.mi355cg_solve_batch.argtypes = [H, C.POINTER(Params), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Results)]
     L.mi355cg_solve_batch_device.argtypes = [H, C.POINTER(Params), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Results)]
     L.mi355cg_batch_release.argtypes = [H]
+    # warm starts: the guess as a plain address (a host array, NULL to withdraw it; device memory for _device)
+    L.mi355cg_set_initial_guess.argtypes = [H, C.c_void_p]
+    L.mi355cg_set_initial_guess_device.argtypes = [H, C.c_void_p]
+    L.mi355cg_use_solution_as_initial_guess.argtypes = [H]
+    L.mi355cg_solve_batch_from.argtypes = [H, C.POINTER(Params), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Results)]
+    L.mi355cg_solve_batch_device_from.argtypes = [H, C.POINTER(Params), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Results)]
     if hasattr(L, "mi355cg_get_xfold"):          # absent from an older build loaded through MI355CG_LIB
         L.mi355cg_get_xfold.argtypes = [H, IP, IP]
     _lib = L

@@ -270,6 +270,8 @@ class MSGSolver : public Solver {
     std::atomic<int> stop_requested{0};
     bool verbose = true;
     int poll_interval = 0;
+    std::vector<double> guess_;              // setInitialGuess: consumed by the next solve
+    bool has_guess_ = false, continue_ = false;
 public:
     MSGSolver(const KokkosCrsMatrix& a_, const KokkosVector& b_, double eps_ = 1e-6, int maxIterations_ = 10000)
         : Solver(a_, b_, eps_, maxIterations_, "Метод серединных градиентов"),
@@ -301,6 +303,15 @@ public:
     double getFinalErrorNorm() const { return final_error_norm; }
     double getFinalPrecision() const { return final_precision; }
     void setIterationCallback(std::function<void(int, double, double, double)> cb) { iteration_callback = std::move(cb); }
+    // Extension (the reference always starts from x = 0): the next solve starts from x0 and r0 = b - A x0, and applies the residual
+    // and exact-error tests to that start before iteration 1 (mi355cg_set_initial_guess).  One-shot; single-GPU systems only.
+    void setInitialGuess(const KokkosVector& x0) {
+        if (x0.extent(0) != b.extent(0)) throw std::invalid_argument("setInitialGuess: vector size does not match the system");
+        guess_.assign(x0.data(), x0.data() + x0.extent(0)); has_guess_ = true; continue_ = false;
+    }
+    // The next solve starts from the x the last solve on this system left -- the continuation of one that was interrupted or
+    // ran into maxIterations (mi355cg_use_solution_as_initial_guess; no copy).
+    void continueFromSolution() { continue_ = true; has_guess_ = false; }
 
     KokkosVector solve(const KokkosVector& true_solution) override {
         converged = false;
@@ -309,6 +320,12 @@ public:
         if (!a.context()) throw std::runtime_error("MSGSolver: the matrix is not a GridSystem operator");
         mi355cg_handle h = a.context()->h;
         mi355cg_compat::check(mi355cg_set_rhs(h, b.data()));
+        if (has_guess_ || continue_) {
+            const bool cont = continue_;
+            has_guess_ = continue_ = false;                                     // one-shot, whatever happens next
+            if (a.context()->team) throw std::invalid_argument("an initial guess is single-GPU only: this system is distributed");
+            mi355cg_compat::check(cont ? mi355cg_use_solution_as_initial_guess(h) : mi355cg_set_initial_guess(h, guess_.data()));
+        }
         if (true_solution.extent(0) > 0)       // the error norms use the vector that was passed in (msg_solver.cpp:64-72,132-139)
             mi355cg_compat::check(mi355cg_set_true_solution(h, true_solution.data()));
         mi355cg_params p;
@@ -452,6 +469,8 @@ class MatrixFreeSolver {
     std::string name;
     std::function<void(int, double, double, double)> iteration_callback;
     std::function<void(bool, const std::string&)> completion_callback;
+    std::vector<double> guess_;              // setInitialGuess: consumed by the next solve
+    bool has_guess_ = false, continue_ = false;
 public:
     MatrixFreeSolver(const MatrixFreeSystem& system_, const std::vector<double>& b_, double eps_ = 1e-6,
                      int maxIterations_ = 10000, const std::string& name_ = "Matrix-free solver")
@@ -461,10 +480,25 @@ public:
     void setCompletionCallback(std::function<void(bool, const std::string&)> cb) { completion_callback = std::move(cb); }
     int getIterations() const { return iterations; }
     std::string getName() const { return name; }
+    // Extension (the reference always starts from x = 0): the next solve starts from x0 and r0 = b - A x0 and stops on
+    // ||r|| <= eps ||b|| (mi355cg_set_initial_guess).  One-shot.
+    void setInitialGuess(const std::vector<double>& x0) {
+        if (x0.size() != b.size()) throw std::invalid_argument("setInitialGuess: vector size does not match the system");
+        guess_ = x0; has_guess_ = true; continue_ = false;
+    }
+    void setInitialGuess(const KokkosVector& x0) { setInitialGuess(std::vector<double>(x0.data(), x0.data() + x0.extent(0))); }
+    // The next solve starts from the x the last solve on this system left -- the continuation of one that ran into maxIterations
+    // (mi355cg_use_solution_as_initial_guess; no copy).
+    void continueFromSolution() { continue_ = true; has_guess_ = false; }
 
     std::vector<double> solve(const std::vector<double>& true_solution) {        // matrix_free_system.cpp:383-482
         mi355cg_handle h = system.context()->h;
         mi355cg_compat::check(mi355cg_set_rhs(h, b.data()));
+        if (has_guess_ || continue_) {
+            const bool cont = continue_;
+            has_guess_ = continue_ = false;                                      // one-shot, whatever happens next
+            mi355cg_compat::check(cont ? mi355cg_use_solution_as_initial_guess(h) : mi355cg_set_initial_guess(h, guess_.data()));
+        }
         if (true_solution.size() == b.size() && !true_solution.empty())           // :451-455 measures the error against the caller's vector
             mi355cg_compat::check(mi355cg_set_true_solution(h, true_solution.data()));
         mi355cg_params p;
@@ -633,6 +667,14 @@ public:
     void setCompletionCallback(std::function<void(const SolverResults&)> cb) { completion_callback = std::move(cb); }
     void setVerbose(bool v) { verbose_ = v; }
     void setPollInterval(int iterations) { poll_interval_ = iterations; }         // see MSGSolver::setPollInterval
+    // Extension: the starting vector of the next solve() (MSGSolver::setInitialGuess / continueFromSolution).  One-shot.
+    void setInitialGuess(const KokkosVector& x0) {
+        if (!grid || x0.extent(0) != grid->get_rhs().extent(0)) throw std::invalid_argument("setInitialGuess: vector size does not match the grid");
+        guess_ = KokkosVector("x0", x0.extent(0));
+        Kokkos::deep_copy(guess_, x0);
+        has_guess_ = true; continue_ = false;
+    }
+    void continueFromSolution() { continue_ = true; has_guess_ = false; }
     // Extension: solve on several GPUs of this process (see GridSystem::distribute).  Kept across setGridParameters.
     void setDevices(const std::vector<int>& devices, int decomp = MI355CG_DECOMP_ROWS) {
         if (!devices.empty() && precond_ != MI355CG_PRECOND_NONE) throw std::invalid_argument("the multigrid preconditioner is single-GPU only");
@@ -650,6 +692,10 @@ public:
         solver->setResidualEps(use_residual_stopping ? eps_residual : -1.0);
         solver->setExactErrorEps(use_error_stopping ? eps_exact_error : -1.0);
         if (iteration_callback) solver->setIterationCallback(iteration_callback);
+        const bool guess = has_guess_, cont = continue_;
+        has_guess_ = continue_ = false;                                           // one-shot, whatever happens next
+        if (guess) solver->setInitialGuess(guess_);
+        if (cont) solver->continueFromSolution();
         true_solution = grid->get_true_solution_vector();
         solution = solver->solve(true_solution);
         SolverResults r;
@@ -703,4 +749,6 @@ private:
     int decomp_ = MI355CG_DECOMP_ROWS;
     int precond_ = MI355CG_PRECOND_NONE;
     int cycle_ = MI355CG_CYCLE_F64;
+    KokkosVector guess_;
+    bool has_guess_ = false, continue_ = false;
 };

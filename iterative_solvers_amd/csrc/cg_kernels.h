@@ -11,6 +11,7 @@
 //   k_fold_x                deferred x fold (single-context fp64, REL_2NORM without diagnostics, larger grids): with a ring of 16 or 32
 //                           directions no update launch touches x; this flat launch applies the last R steps every R-th iteration.
 //   k_update                flat variant: state initialisation, resume step of the mixed-precision path, CSR handles.
+//   k_init_guess, k_guess_state   the start of a warm solve (x = x0, r = b - A x0, the reference norm ||b||): twin of k_init_fresh.
 //   k_check, k_flush_x, k_make_record, k_scatter_ghosts, k_pack/k_unpack, k_sub, k_resid2, ...: small helpers.
 //
 // Bandwidth-bound: no MFMA.  All arithmetic that the reference does element-wise is done in the reference's
@@ -104,7 +105,7 @@ struct CgState {
     double r0norm;      // ||r0||_2
     double rnorm2;      // ||r||_2
     double rmax, dmax, emax, d2, e2;
-    int it, done, reason, converged, first;
+    int it, done, reason, converged, first;      // first: no iteration has run yet (no beta); 1 = cold start, 2 = warm start (r0norm is set: ||b||_2)
     int stop;           // a stop request was pending when the last update launch ended (single context: read from the pinned word; msg_solver.cpp:82-87)
     double alpha_hist[kRing];   // step length of iteration k at [k % kRing]: the folded x update (XM >= 2) applies up to kRing - 1 earlier steps at once
 };
@@ -278,7 +279,7 @@ __device__ inline Decision decide_after_update(const StateLite& s, const RulePar
                                                double dmax, double emax, double d2, double e2, bool stop = false) {
     Decision d;
     d.rr = rr; d.rnorm2 = sqrt(rr); d.rmax = rmax; d.dmax = dmax; d.emax = emax; d.d2 = d2; d.e2 = e2;
-    d.r0norm = s.first ? d.rnorm2 : s.r0norm;
+    d.r0norm = s.first == 1 ? d.rnorm2 : s.r0norm;      // first == 2 (warm start, k_guess_state): the state already holds the reference norm ||b||
     d.done = 0; d.reason = 0 /*ITERATIONS*/; d.converged = 0; d.beta = 0.0;
     if (rp.rule == 1 /*REL_2NORM*/) {
         // for (...; iterations < maxIterations && r_norm > eps * initial_r_norm; ...)  :409
@@ -1111,6 +1112,84 @@ __global__ __launch_bounds__(kBlock) void k_init_fresh(const FreshArgs<T> a) {
         a.partB[FB_RMAX * st + b] = t_rmax; a.partB[FB_DMAX * st + b] = 0.0; a.partB[FB_EMAX * st + b] = t_emax;
         if (blockIdx.x == 0) { *a.s_out = CgState{}; a.s_out->first = 1; }
     }
+}
+
+// ---- warm start (mi355cg_set_initial_guess): the twin of k_init_fresh for x = x0.  ax holds A x0 (launch_apply into a scratch
+// vector); one flat pass over the same range with the same element-to-thread map forms r = b - A x0 (one rounding,
+// matrix_free_system.cpp:389-392) and z = 0, leaves x alone and reduces the norms of r0 (and of x0 - u) into the partB layout of
+// k_init_fresh.  The (b, b) partial pairs go to partG (hi at [block], lo at [strideG + block]): they are accumulated over the
+// same elements in the same order as k_init_fresh accumulates (r, r) of r = b, so k_guess_state below gets the ||b||_2 a cold
+// solve uses as its reference norm, bit for bit.  b and A x in, r and z out: 4 words per unknown (6 with HAS_U: x and u in) after the
+// 2 of the apply, against the 4 of k_init_fresh (b in; x, r, z out).
+template <typename T>
+struct GuessArgs {
+    long long begin, nvec;     // owned flat range in units of VEC elements
+    const T* b; const T* ax; const T* x; T* r; T* p0; const T* u;
+    double* partB; int strideB;
+    double* partG; int strideG;
+    CgState* s_out;
+};
+template <typename T, int VEC, bool HAS_U>
+__global__ __launch_bounds__(kBlock) void k_init_guess(const GuessArgs<T> a) {
+    typedef typename VecOf<T, VEC>::type vec_t;
+    __shared__ double lds[2 * kWaves];
+    dd s_rr = dd_zero(), s_bb = dd_zero(), s_e2 = dd_zero();
+    double s_rmax = 0, s_emax = 0;
+    const long long stride = (long long)gridDim.x * kBlock;
+    const vec_t* __restrict__ B = reinterpret_cast<const vec_t*>(a.b);
+    const vec_t* __restrict__ AX = reinterpret_cast<const vec_t*>(a.ax);
+    const vec_t* __restrict__ X = reinterpret_cast<const vec_t*>(a.x);
+    const vec_t* __restrict__ Uu = reinterpret_cast<const vec_t*>(a.u);
+    vec_t* __restrict__ R = reinterpret_cast<vec_t*>(a.r);
+    vec_t* __restrict__ P = reinterpret_cast<vec_t*>(a.p0);
+    vec_t zero;
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) zero[j] = (T)0;
+    const long long end = a.begin + a.nvec;
+    for (long long i = a.begin + (long long)blockIdx.x * kBlock + threadIdx.x; i < end; i += stride) {
+        const vec_t bv = B[i], av = AX[i];
+        vec_t xv, uv; if (HAS_U) { xv = X[i]; uv = Uu[i]; }
+        vec_t rv;
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) {
+            rv[j] = bv[j] - av[j];                            // r = b - A*x       matrix_free_system.cpp:389-392
+            const double rd = (double)rv[j], bd = (double)bv[j];
+            dd_acc_prod(s_rr, rd, rd);
+            dd_acc_prod(s_bb, bd, bd);
+            s_rmax = fmax(s_rmax, fabs(rd));
+            if (HAS_U) {
+                const double ee = (double)(xv[j] - uv[j]);    // error = x - u
+                s_emax = fmax(s_emax, fabs(ee));
+                dd_acc_prod(s_e2, ee, ee);
+            }
+        }
+        R[i] = rv; P[i] = zero;
+    }
+    const dd t_rr = block_reduce_dd(s_rr, lds);
+    const double t_rmax = block_reduce<true>(s_rmax, lds);
+    double t_emax = 0; dd t_e2 = dd_zero();
+    if (HAS_U) { t_emax = block_reduce<true>(s_emax, lds); t_e2 = block_reduce_dd(s_e2, lds); }
+    const dd t_bb = block_reduce_dd(s_bb, lds);
+    if (threadIdx.x == 0) {
+        const int b = blockIdx.x, st = a.strideB;
+        a.partB[FB_RR * st + b] = t_rr.hi; a.partB[(FB_RR + FB_LO) * st + b] = t_rr.lo;
+        a.partB[FB_D2 * st + b] = 0.0; a.partB[(FB_D2 + FB_LO) * st + b] = 0.0;
+        a.partB[FB_E2 * st + b] = t_e2.hi; a.partB[(FB_E2 + FB_LO) * st + b] = t_e2.lo;
+        a.partB[FB_RMAX * st + b] = t_rmax; a.partB[FB_DMAX * st + b] = 0.0; a.partB[FB_EMAX * st + b] = t_emax;
+        a.partG[b] = t_bb.hi; a.partG[a.strideG + b] = t_bb.lo;
+        if (blockIdx.x == 0) { *a.s_out = CgState{}; a.s_out->first = 1; }
+    }
+}
+// One block, behind k_init_guess: the reference norm of a warm solve is ||b||_2, not ||r0||_2.  Reduces the (b, b) pairs in the
+// consumers' order (reduce_parts_dd) and arms the state with first = 2: decide_after_update then tests against this norm from
+// the first decision on and still takes beta = 0.  norms[0] = ||r0||_2 (what the first decision computes from the same partials),
+// norms[1] = ||b||_2, for the host's result fields.
+__global__ __launch_bounds__(kBlock) void k_guess_state(const double* partB, int strideB, const double* partG, int strideG, int n,
+                                                        CgState* s, double* norms) {
+    __shared__ double lds[2 * kWaves];
+    const double rr = dd_value(reduce_parts_dd(partB + FB_RR * strideB, partB + (FB_RR + FB_LO) * strideB, n, 1, lds));
+    const double bb = dd_value(reduce_parts_dd(partG, partG + strideG, n, 1, lds));
+    if (threadIdx.x == 0) { s->r0norm = sqrt(bb); s->first = 2; norms[0] = sqrt(rr); norms[1] = sqrt(bb); }
 }
 
 // ---- phase B: r -= alpha * (A_h p) with A_h p rebuilt from the stored direction, x update, norms ----------------

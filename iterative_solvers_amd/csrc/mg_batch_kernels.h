@@ -247,6 +247,39 @@ __global__ __launch_bounds__(kBlock) void k_mgb_init(const MgbAct act, const Geo
     t = block_reduce<true>(rmax, lds); if (threadIdx.x == 0) { part[base + MGB_RMAX * n] = t; part[base + MGB_DMAX * n] = 0.0; }
 }
 
+// The warm start of a batch (mi355cg_solve_batch*_from): x holds the guess and r holds b (k_mgb_unpack wrote both).  Per system
+// r = b - A x with A x in the operation order of the plain operator (k_stencil: ((((A c + xk l) + xk r) + yk up) + yk down); mg_Av
+// groups the neighbours first and differs in the last bit), which is what the single warm solve forms with launch_apply and
+// k_sub.  Only r of the node itself is written, so no neighbour's operand changes under a reader.  Partials of this kernel alone,
+// part[(system * MGBG_NFIELDS + field) * gridDim.x + block]: (r, r) and (b, b) in k_mgb_init's order, max |r|, and max |dx| = 0.
+enum { MGBG_RR = 0, MGBG_BB = 1, MGBG_RMAX = 2, MGBG_DMAX = 3, MGBG_NFIELDS = 4 };   // fields >= MGBG_RMAX are max-norms
+__global__ __launch_bounds__(kBlock) void k_mgb_init_guess(const MgbAct act, const Geom g, const double* __restrict__ x_, double* __restrict__ r_,
+                                                           double* __restrict__ part) {
+    __shared__ double lds[2 * kWaves];
+    const long long so = MGB_SYS(act);
+    const double* __restrict__ x = x_ + so;
+    double* __restrict__ r = r_ + so;
+    double rr = 0, bb = 0, rmax = 0;
+    MGB_FOR_INTERIOR(g, xx, y) {
+        const long long o = mg_off(g, xx, y);
+        double v = g.A * x[o];
+        v = v + g.xk * x[o - 1];
+        v = v + g.xk * x[o + 1];
+        v = v + g.yk * mg_at(g, x, xx, y + 1);
+        v = v + g.yk * mg_at(g, x, xx, y - 1);
+        const double bv = r[o];
+        const double rn = bv - v;
+        r[o] = rn;
+        rr += rn * rn; bb += bv * bv;
+        rmax = fmax(rmax, fabs(rn));
+    }
+    const long long n = gridDim.x, base = (long long)act.sys[blockIdx.y] * MGBG_NFIELDS * n + blockIdx.x;
+    double t;
+    t = block_reduce<false>(rr, lds); if (threadIdx.x == 0) part[base + MGBG_RR * n] = t;
+    t = block_reduce<false>(bb, lds); if (threadIdx.x == 0) part[base + MGBG_BB * n] = t;
+    t = block_reduce<true>(rmax, lds); if (threadIdx.x == 0) { part[base + MGBG_RMAX * n] = t; part[base + MGBG_DMAX * n] = 0.0; }
+}
+
 // k_mg_dot per active system (the (r, z) of a one-level hierarchy)
 __global__ __launch_bounds__(kBlock) void k_mgb_dot(const MgbAct act, const Geom g, const double* __restrict__ a_, const double* __restrict__ b_,
                                                     double* __restrict__ part) {

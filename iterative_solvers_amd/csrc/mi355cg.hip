@@ -99,7 +99,7 @@ struct MgBatchWs {
     double* base = nullptr;
     long long x = 0, r = 0, z = 0, p[2] = {0, 0}, q = 0;
     std::vector<MgBatchLevel> lv;
-    double* part = nullptr;             // [system][field][block], cap x MGB_NFIELDS x level 0's grid
+    double* part = nullptr;             // [system][field][block], cap x MGBG_NFIELDS (the widest launch) x level 0's grid
     double* red = nullptr;              // [position][field] sums of the last launch
     double* red_h = nullptr;            // pinned copy
     double* stage = nullptr;            // packed vectors of the host entry point, stage_cap x pk_len
@@ -149,6 +149,11 @@ struct mi355cg_ctx {
     std::vector<double> rhs_h, u_h;     // host copies (owned cells, the part's packed order)
     bool host_rhs_valid = true, host_u_valid = true;     // false after mi355cg_setup_on_device until somebody asks for the host copy
     bool have_u_dev = false, solved = false;
+    // Warm start (mi355cg_set_initial_guess*, mi355cg_use_solution_as_initial_guess): the guess lives in x itself.
+    bool guess_pending = false;         // the next mi355cg_solve starts from x as it stands (one-shot)
+    bool x_is_guess = false;            // x was overwritten by a guess since the last solve: x and r are not a solution and its residual
+    double* guess_part = nullptr;       // (b, b) partial pairs of k_init_guess (hi, then lo, strideB each), then ||r0||_2 and ||b||_2 (k_guess_state)
+    double* guess_norms_h = nullptr;    // pinned copy of those two norms
     // generic CSR handle (mi355cg_create_csr): vectors are plain length-n arrays, the operator is this matrix
     bool is_csr = false;
     long long csr_n = 0, csr_nnz = 0;
@@ -617,6 +622,14 @@ int ensure_u_on_device(mi355cg_ctx* c) {
 int ensure_scratch(mi355cg_ctx* c) {
     for (auto& s : c->scratch) if (!s) { if (int rc = alloc_vec(&s, c->storage_len)) return rc; }
     HIPCK(hipDeviceSynchronize());      // the zero-fill ran on the NULL stream
+    return MI355CG_OK;
+}
+
+// Work space of a warm start on the plain path, allocated by the first one: k_init_guess's (b, b) partials and the two norms
+// k_guess_state leaves for the host.
+int ensure_guess_ws(mi355cg_ctx* c) {
+    if (!c->guess_part) HIPCK(hipMalloc((void**)&c->guess_part, sizeof(double) * (2 * (size_t)c->strideB + 2)));
+    if (!c->guess_norms_h) HIPCK(hipHostMalloc((void**)&c->guess_norms_h, sizeof(double) * 2));
     return MI355CG_OK;
 }
 
@@ -1179,14 +1192,16 @@ int mg_apply32(mi355cg_ctx* c, const double* r, double* z, double rmax) {
 }
 
 // PCG with z = M r.  Same stop rules, callback cadence, stop-flag handling and result fields as mi355cg_solve's plain path.
+// warm: x holds an initial guess (mi355cg_set_initial_guess*): r0 = b - A x0 with the plain operator's bits, REL_2NORM tests against ||b||_2.
 int solve_mg(mi355cg_ctx* c, const mi355cg_params* prm, mi355cg_iter_cb cb, void* user,
-             const volatile int* stop_flag, mi355cg_results* out) {
+             const volatile int* stop_flag, mi355cg_results* out, bool warm) {
     MgHier& H = *c->mg;
     const Geom& g = H.lv[0].g;
     const bool msg = prm->rule == MI355CG_RULE_MSG_MAXNORM;
     const bool diag = !msg && prm->diagnostics;
     const bool has_u = (msg && prm->use_true_solution) || diag;
     if (has_u) if (int rc = ensure_u_on_device(c)) return rc;
+    if (warm && !(c->scratch[0] && c->scratch[1])) if (int rc = ensure_scratch(c)) return rc;
     const auto t0 = std::chrono::steady_clock::now();
     const hipStream_t st = c->stream;
     const int G = H.lv[0].grid;
@@ -1209,12 +1224,23 @@ int solve_mg(mi355cg_ctx* c, const mi355cg_params* prm, mi355cg_iter_cb cb, void
         hipLaunchKernelGGL(k_mg_update, grid, blk, 0, st, g, alpha, c->x, c->r, p, q, has_u ? (const double*)c->u : (const double*)nullptr, H.part);
         return fetch(MG_NFIELDS, nm);
     };
-    // x = 0, r = b (msg_solver.cpp:33-39); a zero step gives the norms of r0 and of x0 - u
-    HIPCK(hipMemsetAsync(c->x, 0, bytes, st));
+    // x = 0, r = b (msg_solver.cpp:33-39); a zero step gives the norms of r0 and of x0 - u.  Warm: x stays, r = b - A x with the plain
+    // operator (mg_Av groups the neighbours first and is not bit-identical to it), and (b, b) by k_mg_dot, whose sums run in the
+    // order of the zero step's (r, r): with x0 = 0 both norms are the cold start's.
+    double bb = 0.0;
     HIPCK(hipMemsetAsync(H.q, 0, bytes, st));
-    HIPCK(hipMemcpyAsync(c->r, c->b, bytes, hipMemcpyDeviceToDevice, st));
+    if (warm) {
+        launch_apply<double, 2>(c, c->x, c->scratch[0], whole_part(c));
+        hipLaunchKernelGGL((k_sub<double>), dim3(flat_grid(c->g.own_len)), blk, 0, st, c->g.own_begin, c->g.own_len, (const double*)c->b, (const double*)c->scratch[0], c->r);
+        hipLaunchKernelGGL(k_mg_dot, grid, blk, 0, st, g, (const double*)c->b, (const double*)c->b, H.part);
+        if (int rc = fetch(1, &bb)) return rc;
+    } else {
+        HIPCK(hipMemsetAsync(c->x, 0, bytes, st));
+        HIPCK(hipMemcpyAsync(c->r, c->b, bytes, hipMemcpyDeviceToDevice, st));
+    }
     if (int rc = update(0.0, H.q, H.q)) return rc;
     const double r0norm = std::sqrt(nm[MG_RR]);
+    const double refnorm = warm ? std::sqrt(bb) : r0norm;      // what REL_2NORM is relative to: ||b||_2
     double rnorm = r0norm;
     if (!c->ev_loop[0]) { HIPCK(hipEventCreate(&c->ev_loop[0])); HIPCK(hipEventCreate(&c->ev_loop[1])); }
     HIPCK(hipEventRecord(c->ev_loop[0], st));
@@ -1223,9 +1249,14 @@ int solve_mg(mi355cg_ctx* c, const mi355cg_params* prm, mi355cg_iter_cb cb, void
     int it = 0, reason = MI355CG_STOP_ITERATIONS;
     bool converged = false, interrupted = false;
     double rho = 0.0;
+    if (warm && msg && !prm->fixed_iterations) {        // r0 of a guess may be 0 (alpha = 0 / 0): the tests of msg_solver.cpp:144-163 that have their numbers, on the start state
+        if (prm->eps_residual > 0 && nm[MG_RMAX] < prm->eps_residual) { converged = true; reason = MI355CG_STOP_RESIDUAL; }
+        else if (prm->eps_exact_error > 0 && has_u && nm[MG_EMAX] < prm->eps_exact_error) { converged = true; reason = MI355CG_STOP_EXACT_ERROR; }
+    }
     for (;;) {
+        if (converged) break;                                                                 // a warm start that already meets the rule
         if (!(it < prm->max_iterations)) break;                                               // msg_solver.cpp:80
-        if (!msg && !prm->fixed_iterations && !(rnorm > prm->eps_rel * r0norm)) break;        // matrix_free_system.cpp:409
+        if (!msg && !prm->fixed_iterations && !(rnorm > prm->eps_rel * refnorm)) break;       // matrix_free_system.cpp:409
         if (stop_flag && *stop_flag) { interrupted = true; break; }                           // msg_solver.cpp:82-87
         double rz = 0, pq = 0;
         if (H.cycle == MI355CG_CYCLE_F32) { if (int rc = mg_apply32(c, c->r, H.z, nm[MG_RMAX])) return rc; }   // nm: of the last update
@@ -1256,8 +1287,8 @@ int solve_mg(mi355cg_ctx* c, const mi355cg_params* prm, mi355cg_iter_cb cb, void
         }
     }
     HIPCK(hipEventRecord(c->ev_loop[1], st));
-    if (!msg) converged = rnorm <= prm->eps_rel * r0norm;                                     // matrix_free_system.cpp:472
-    c->solved = true;
+    if (!msg) converged = rnorm <= prm->eps_rel * refnorm;                                    // matrix_free_system.cpp:472
+    c->solved = true; c->x_is_guess = false;
     c->kernel_ms[0] = c->kernel_ms[1] = 0.0; c->kernel_launches[0] = c->kernel_launches[1] = 0;   // per-kernel times: plain path only
     mi355cg_results res{};
     res.iterations = it;
@@ -1313,9 +1344,10 @@ int mg_batch_ensure(mi355cg_ctx* c, int nsys, int stage_sys) {
         W->cap = nsys;
         const int G = H.lv[0].grid;
         if (hipMalloc((void**)&W->base, sizeof(double) * W->stride * nsys) != hipSuccess) return bail("vector");
-        if (hipMalloc((void**)&W->part, sizeof(double) * MGB_NFIELDS * G * nsys) != hipSuccess) return bail("partials");
-        if (hipMalloc((void**)&W->red, sizeof(double) * MGB_NFIELDS * kMgBatchMax) != hipSuccess) return bail("sums");
-        if (hipHostMalloc((void**)&W->red_h, sizeof(double) * MGB_NFIELDS * kMgBatchMax) != hipSuccess) return bail("pinned sums");
+        constexpr int kFields = MGBG_NFIELDS > MGB_NFIELDS ? MGBG_NFIELDS : MGB_NFIELDS;      // the warm start's launch has one field more
+        if (hipMalloc((void**)&W->part, sizeof(double) * kFields * G * nsys) != hipSuccess) return bail("partials");
+        if (hipMalloc((void**)&W->red, sizeof(double) * kFields * kMgBatchMax) != hipSuccess) return bail("sums");
+        if (hipHostMalloc((void**)&W->red_h, sizeof(double) * kFields * kMgBatchMax) != hipSuccess) return bail("pinned sums");
         // boundary nodes and pads hold 0 for good: the kernels write interior nodes only
         if (hipMemsetAsync(W->base, 0, sizeof(double) * W->stride * nsys, c->stream) != hipSuccess ||
             hipStreamSynchronize(c->stream) != hipSuccess) return bail("zero-filled vector");
@@ -1374,8 +1406,9 @@ void mg_vcycle_batch(mi355cg_ctx* c, const MgbAct& act, int l, long long rhs, lo
 // solve_mg for nrhs systems at once.  b_dev, x_dev: packed vectors in device memory (they may be the same buffer: b is consumed
 // before x is written).  Every system runs solve_mg's tests on its own numbers in solve_mg's order; one that stops leaves the
 // active list and no later launch touches its vectors.  Three host waits per iteration, as there.
+// warm (mi355cg_solve_batch*_from): x_dev holds nrhs guesses on entry; system s starts as the single warm solve starts.
 int solve_mg_batch(mi355cg_ctx* c, const mi355cg_params* prm, int nrhs, const double* b_dev, double* x_dev,
-                   const volatile int* stop_flag, mi355cg_results* out) {
+                   const volatile int* stop_flag, mi355cg_results* out, bool warm = false) {
     const MgHier& H = *c->mg;
     const MgBatchWs& W = *c->batch;
     const Geom& g = H.lv[0].g;
@@ -1395,7 +1428,7 @@ int solve_mg_batch(mi355cg_ctx* c, const mi355cg_params* prm, int nrhs, const do
         HIPCK(hipStreamSynchronize(st));
         return MI355CG_OK;
     };
-    struct Sys { double rr, rmax, dmax, rho, rnorm, r0norm; int it, reason; bool converged, interrupted; };
+    struct Sys { double rr, rmax, dmax, rho, rnorm, r0norm, refnorm; int it, reason; bool converged, interrupted; };      // refnorm: ||b||_2
     std::vector<Sys> S(nrhs);
     auto take_norms = [&]() {
         for (int k = 0; k < act.n; ++k) {
@@ -1407,11 +1440,23 @@ int solve_mg_batch(mi355cg_ctx* c, const mi355cg_params* prm, int nrhs, const do
     for (int s = 0; s < nrhs; ++s) act.sys[s] = s;
     // r = b, x = 0 and the norms of r0 (msg_solver.cpp:33-39)
     hipLaunchKernelGGL(k_mgb_unpack, dim3(flat_grid(c->pk_len), nrhs), blk, 0, st, c->pg, W.stride, b_dev, B + W.r);
-    hipLaunchKernelGGL(k_mgb_init, dim3(G, nrhs), blk, 0, st, act, g, B + W.x, (const double*)(B + W.r), W.part);
-    if (int rc = fetch(MGB_NFIELDS, MGB_RMAX)) return rc;
-    take_norms();
+    if (warm) {                                                    // x = x0, r = b - A x0, and (b, b) beside the norms of r0
+        hipLaunchKernelGGL(k_mgb_unpack, dim3(flat_grid(c->pk_len), nrhs), blk, 0, st, c->pg, W.stride, (const double*)x_dev, B + W.x);
+        hipLaunchKernelGGL(k_mgb_init_guess, dim3(G, nrhs), blk, 0, st, act, g, (const double*)(B + W.x), B + W.r, W.part);
+        if (int rc = fetch(MGBG_NFIELDS, MGBG_RMAX)) return rc;
+        for (int k = 0; k < nrhs; ++k) {
+            Sys& s = S[k];
+            const double* v = W.red_h + k * MGBG_NFIELDS;
+            s.rr = v[MGBG_RR]; s.rmax = v[MGBG_RMAX]; s.dmax = v[MGBG_DMAX]; s.refnorm = std::sqrt(v[MGBG_BB]);
+        }
+    } else {
+        hipLaunchKernelGGL(k_mgb_init, dim3(G, nrhs), blk, 0, st, act, g, B + W.x, (const double*)(B + W.r), W.part);
+        if (int rc = fetch(MGB_NFIELDS, MGB_RMAX)) return rc;
+        take_norms();
+    }
     for (Sys& s : S) {
         s.r0norm = s.rnorm = std::sqrt(s.rr);
+        if (!warm) s.refnorm = s.r0norm;
         s.rho = 0.0; s.it = 0; s.reason = MI355CG_STOP_ITERATIONS; s.converged = false; s.interrupted = false;
     }
     if (!c->ev_loop[0]) { HIPCK(hipEventCreate(&c->ev_loop[0])); HIPCK(hipEventCreate(&c->ev_loop[1])); }
@@ -1420,9 +1465,12 @@ int solve_mg_batch(mi355cg_ctx* c, const mi355cg_params* prm, int nrhs, const do
     for (int it = 0;; ++it) {
         int n = 0;
         for (int k = 0; k < act.n; ++k) {                          // the tests before an iteration, per system (solve_mg's order)
-            const Sys& s = S[act.sys[k]];
+            Sys& s = S[act.sys[k]];
+            if (warm && it == 0 && msg && !prm->fixed_iterations && prm->eps_residual > 0 && s.rmax < prm->eps_residual) {
+                s.converged = true; s.reason = MI355CG_STOP_RESIDUAL; continue;       // solve_mg's test of a warm start state
+            }
             if (!(it < prm->max_iterations)) continue;
-            if (!msg && !prm->fixed_iterations && !(s.rnorm > prm->eps_rel * s.r0norm)) continue;
+            if (!msg && !prm->fixed_iterations && !(s.rnorm > prm->eps_rel * s.refnorm)) continue;
             act.sys[n++] = act.sys[k];
         }
         act.n = n;
@@ -1467,7 +1515,7 @@ int solve_mg_batch(mi355cg_ctx* c, const mi355cg_params* prm, int nrhs, const do
     const double solve_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     for (int i = 0; i < nrhs; ++i) {
         const Sys& s = S[i];
-        const bool conv = msg ? s.converged : s.rnorm <= prm->eps_rel * s.r0norm;         // matrix_free_system.cpp:472
+        const bool conv = msg ? s.converged : s.rnorm <= prm->eps_rel * s.refnorm;        // matrix_free_system.cpp:472
         mi355cg_results res{};
         res.iterations = s.it;
         res.converged = s.interrupted ? 0 : (conv ? 1 : 0);
@@ -1708,6 +1756,8 @@ void mi355cg_destroy(mi355cg_handle c) {
     if (c->hist_h) hipHostFree(c->hist_h);
     if (c->partR_h) hipHostFree(c->partR_h);
     if (c->stop_h) hipHostFree(c->stop_h);
+    if (c->guess_part) hipFree(c->guess_part);
+    if (c->guess_norms_h) hipHostFree(c->guess_norms_h);
     clear_graphs(c);
     mg_batch_free(c);
     mg_free(c->mg);
@@ -1818,9 +1868,11 @@ int mi355cg_solve(mi355cg_handle c, const mi355cg_params* prm, mi355cg_iter_cb c
     if (prm->rule != MI355CG_RULE_MSG_MAXNORM && prm->rule != MI355CG_RULE_REL_2NORM) return fail(MI355CG_ERR_INVALID, "unknown rule %d", prm->rule);
     if (c->is_slab) return fail(MI355CG_ERR_STATE, "this handle owns one part of a decomposed grid: use the mi355cg_team_* / mi355cg_dist_* entry points");
     HIPCK(hipSetDevice(c->device));
+    const bool warm = c->guess_pending;          // one-shot: this solve consumes the guess, whatever it returns
+    c->guess_pending = false;                    // x_is_guess stays until a solve has completed: a solve that fails before it leaves no solution behind
     if (c->is_csr) return solve_csr(c, prm, cb, user, stop_flag, out);
     if (c->dtype == MI355CG_F32_MIXED) return solve_mixed(c, prm, cb, user, stop_flag, out);
-    if (c->mg) return solve_mg(c, prm, cb, user, stop_flag, out);                     // opt-in preconditioner (fp64 grid handles only)
+    if (c->mg) return solve_mg(c, prm, cb, user, stop_flag, out, warm);               // opt-in preconditioner (fp64 grid handles only)
     const bool msg = prm->rule == MI355CG_RULE_MSG_MAXNORM;
     IterCfg cfg0 = make_cfg(prm);
     cfg0.fold = cfg0.x2 && ensure_fold_ring(c);
@@ -1828,7 +1880,8 @@ int mi355cg_solve(mi355cg_handle c, const mi355cg_params* prm, mi355cg_iter_cb c
     const bool diag = cfg.want_diag != 0, fold = cfg.fold;
     c->nB_own = c->whole.grid;
     if (cfg.has_u) if (int rc = ensure_u_on_device(c)) return rc;
-    if (diag) if (int rc = ensure_scratch(c)) return rc;
+    if (diag || (warm && !(c->scratch[0] && c->scratch[1]))) if (int rc = ensure_scratch(c)) return rc;      // (a device-wide wait: once per handle for warm starts)
+    if (warm) if (int rc = ensure_guess_ws(c)) return rc;
 
     const auto t0 = std::chrono::steady_clock::now();
     c->events.reset(); c->ev_pairs[0].clear(); c->ev_pairs[1].clear();
@@ -1839,7 +1892,21 @@ int mi355cg_solve(mi355cg_handle c, const mi355cg_params* prm, mi355cg_iter_cb c
     // (iterations 1 .. M-1) before the folded x update first reads them (iteration M).
     c->cur = 0; c->fcur = 0;
     if (c->qctr && c->dyn_rows > 0) HIPCK(hipMemsetAsync(c->qctr, 0, sizeof(int) * 2 * kXcds * kQueueSubs * kQueuePitch, c->stream));
-    {
+    if (warm) {
+        // x = x0 (already in x), r = b - A x0 with A x0 from the plain operator (mi355cg_apply's bits), z = 0.  k_guess_state arms the
+        // state with ||b||_2 as the reference norm of REL_2NORM; everything after this block is the cold solve's loop.
+        launch_apply<double, 2>(c, c->x, c->scratch[0], whole_part(c));
+        GuessArgs<double> f{};
+        f.begin = c->g.own_begin / 2; f.nvec = c->g.own_len / 2;
+        f.b = c->b; f.ax = c->scratch[0]; f.x = c->x; f.r = c->r; f.p0 = c->p[0]; f.u = c->u;
+        f.partB = c->partB; f.strideB = c->strideB; f.partG = c->guess_part; f.strideG = c->strideB; f.s_out = c->sB;
+        if (cfg.has_u) hipLaunchKernelGGL((k_init_guess<double, 2, true>), dim3(c->whole.grid), dim3(kBlock), 0, c->stream, f);
+        else hipLaunchKernelGGL((k_init_guess<double, 2, false>), dim3(c->whole.grid), dim3(kBlock), 0, c->stream, f);
+        double* norms = c->guess_part + 2 * (size_t)c->strideB;
+        hipLaunchKernelGGL(k_guess_state, dim3(1), dim3(kBlock), 0, c->stream, (const double*)c->partB, c->strideB, (const double*)c->guess_part, c->strideB,
+                           c->whole.grid, c->sB, norms);
+        HIPCK(hipMemcpyAsync(c->guess_norms_h, norms, sizeof(double) * 2, hipMemcpyDeviceToHost, c->stream));     // complete with the first poll
+    } else {
         FreshArgs<double> f{};
         f.begin = c->g.own_begin / 2; f.nvec = c->g.own_len / 2;
         f.b = c->b; f.x = c->x; f.r = c->r; f.p0 = c->p[0]; f.u = c->u;
@@ -1867,18 +1934,28 @@ int mi355cg_solve(mi355cg_handle c, const mi355cg_params* prm, mi355cg_iter_cb c
         }
         return MI355CG_OK;
     };
+    bool polled = false;
     auto poll = [&]() -> int {
         launch_check(c, cfg, c->stream, own_partB(c));
         HIPCK(hipMemcpyAsync(c->summary_h, c->summary, sizeof(CgState), hipMemcpyDeviceToHost, c->stream));
         HIPCK(hipMemcpyAsync(c->hist_h, c->hist, sizeof(HistEntry) * kHist, hipMemcpyDeviceToHost, c->stream));
+        polled = true;
         return wait_stream();
     };
     // The state of iteration 0 is only fetched when somebody looks at it (the it = 0 callback, msg_solver.cpp:75-77);
     // ||r0|| travels in the state and is read with the last poll.
     *c->summary_h = CgState{};
-    if (msg && cb) {
+    if (msg && (cb || warm)) {
         if (int rc = poll()) return rc;
-        cb(user, 0, DBL_MAX, c->summary_h->rmax, cfg.has_u ? c->summary_h->emax : DBL_MAX);
+        if (cb) cb(user, 0, DBL_MAX, c->summary_h->rmax, cfg.has_u ? c->summary_h->emax : DBL_MAX);
+    }
+    // A cold MSG solve enters iteration 1 untested, as the reference does.  The r0 of a guess may be 0 (alpha = 0 / 0), so a warm one
+    // first applies the tests of msg_solver.cpp:144-163 that have their numbers to the start state (one poll, taken above).
+    if (warm && msg && !prm->fixed_iterations) {
+        int reason = 0;
+        if (prm->eps_residual > 0 && c->summary_h->rmax < prm->eps_residual) reason = MI355CG_STOP_RESIDUAL;
+        else if (prm->eps_exact_error > 0 && cfg.has_u && c->summary_h->emax < prm->eps_exact_error) reason = MI355CG_STOP_EXACT_ERROR;
+        if (reason) { c->summary_h->done = 1; c->summary_h->converged = 1; c->summary_h->reason = reason; }
     }
     if (!c->ev_loop[0]) { HIPCK(hipEventCreate(&c->ev_loop[0])); HIPCK(hipEventCreate(&c->ev_loop[1])); }
     HIPCK(hipEventRecord(c->ev_loop[0], c->stream));
@@ -2002,7 +2079,7 @@ int mi355cg_solve(mi355cg_handle c, const mi355cg_params* prm, mi355cg_iter_cb c
         double m = 0; for (int i = 0; i < 1024; ++i) m = std::max(m, c->partR_h[i]);
         fin.emax = m;
     }
-    c->solved = true;
+    c->solved = true; c->x_is_guess = false;
     prof_collect(c);
 #ifdef MI355CG_WAVE_TIMING
     if (const char* path = getenv("MI355CG_WAVE_TIMING_OUT")) {     // diagnostic build: per-wave timestamps of the last launch of each kernel
@@ -2019,7 +2096,9 @@ int mi355cg_solve(mi355cg_handle c, const mi355cg_params* prm, mi355cg_iter_cb c
     res.final_precision = fin.it > 0 ? fin.dmax : DBL_MAX;
     res.final_error_norm = cfg.has_u ? fin.emax : DBL_MAX;
     res.r_norm2 = fin.rnorm2;
-    res.initial_r_norm2 = fin.r0norm;
+    // `polled` is set by the poll that fills summary_h, so every path that has a non-zero state has the two pinned norms as well; a solve
+    // that never polled (a stop request set before the call) reports the zeros of the empty state, exactly as a cold solve does
+    res.initial_r_norm2 = warm && polled ? c->guess_norms_h[0] : fin.r0norm;       // warm: the state's reference norm is ||b||_2, this field stays ||r0||_2 (read with the first poll)
     res.solve_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     { float ms = 0; HIPCK(hipEventSynchronize(c->ev_loop[1])); if (hipEventElapsedTime(&ms, c->ev_loop[0], c->ev_loop[1]) == hipSuccess) res.loop_seconds = 1e-3 * ms; }
     if (msg && cb) cb(user, res.iterations, res.final_precision, res.final_residual_norm, res.final_error_norm);   // msg_solver.cpp:193-195
@@ -2029,12 +2108,14 @@ int mi355cg_solve(mi355cg_handle c, const mi355cg_params* prm, mi355cg_iter_cb c
 
 int mi355cg_get_solution(mi355cg_handle c, double* x) {
     if (!c || !x) return fail(MI355CG_ERR_INVALID, "null argument");
+    if (c->x_is_guess) return fail(MI355CG_ERR_STATE, "an initial guess was set after the last solve: x holds the guess, not a solution");
     if (!c->solved) return fail(MI355CG_ERR_STATE, "no solve has run on this handle");
     HIPCK(hipSetDevice(c->device));
     return download_packed<double>(c, c->x, x);
 }
 int mi355cg_get_recursive_residual(mi355cg_handle c, double* r) {
     if (!c || !r) return fail(MI355CG_ERR_INVALID, "null argument");
+    if (c->x_is_guess) return fail(MI355CG_ERR_STATE, "an initial guess was set after the last solve: r is not the residual of x");
     if (!c->solved) return fail(MI355CG_ERR_STATE, "no solve has run on this handle");
     HIPCK(hipSetDevice(c->device));
     return download_packed<double>(c, c->r, r);
@@ -2042,6 +2123,7 @@ int mi355cg_get_recursive_residual(mi355cg_handle c, double* r) {
 int mi355cg_get_true_residual(mi355cg_handle c, double* out) {
     if (!c || !out) return fail(MI355CG_ERR_INVALID, "null argument");
     if (c->is_slab) return fail(MI355CG_ERR_STATE, "this handle owns one part of a decomposed grid: use the mi355cg_team_* / mi355cg_dist_* entry points");
+    if (c->x_is_guess) return fail(MI355CG_ERR_STATE, "an initial guess was set after the last solve: x holds the guess, not a solution");
     if (!c->solved) return fail(MI355CG_ERR_STATE, "no solve has run on this handle");
     HIPCK(hipSetDevice(c->device));
     if (int rc = ensure_scratch(c)) return rc;
@@ -2051,6 +2133,47 @@ int mi355cg_get_true_residual(mi355cg_handle c, double* out) {
     hipLaunchKernelGGL((k_sub<double>), dim3(flat_grid(c->g.own_len)), dim3(kBlock), 0, c->stream, c->g.own_begin, c->g.own_len, c->scratch[0], c->b, c->scratch[1]);
     HIPCK(hipGetLastError());
     return download_packed<double>(c, c->scratch[1], out);
+}
+
+// ---- warm starts ----------------------------------------------------------------------------------------
+// The guess is written straight into the handle's x (no extra vector) and consumed by the next mi355cg_solve.  From here to that
+// solve x is not a solution and r does not belong to it: the three getters above refuse.
+static int guess_check(mi355cg_ctx* c) {
+    if (!c) return fail(MI355CG_ERR_INVALID, "null handle");
+    if (c->is_csr) return fail(MI355CG_ERR_INVALID, "an initial guess needs the grid operator's start (r0 = b - A x0): a CSR handle has none");
+    if (c->is_slab) return fail(MI355CG_ERR_INVALID, "an initial guess is single-GPU only: this handle owns one part of a decomposed grid");
+    if (c->dtype != MI355CG_F64) return fail(MI355CG_ERR_INVALID, "an initial guess is fp64 only: this handle was created with MI355CG_F32_MIXED");
+    return MI355CG_OK;
+}
+
+int mi355cg_set_initial_guess(mi355cg_handle c, const double* x0) {
+    if (int rc = guess_check(c)) return rc;
+    if (!x0) { c->guess_pending = false; return MI355CG_OK; }      // withdrawn; if one was set, x stays unusable until the next solve
+    HIPCK(hipSetDevice(c->device));
+    c->x_is_guess = true;                                          // from the first byte written
+    if (int rc = upload_packed<double>(c, x0, c->x)) return rc;
+    c->guess_pending = true;
+    return MI355CG_OK;
+}
+
+int mi355cg_set_initial_guess_device(mi355cg_handle c, const double* x0_dev) {
+    if (int rc = guess_check(c)) return rc;
+    if (!x0_dev) return fail(MI355CG_ERR_INVALID, "null argument");
+    HIPCK(hipSetDevice(c->device));
+    c->x_is_guess = true;
+    hipLaunchKernelGGL((k_unpack<double>), dim3(flat_grid(c->pk_len)), dim3(kBlock), 0, c->stream, c->pg, x0_dev, c->x);
+    HIPCK(hipGetLastError());
+    HIPCK(hipStreamSynchronize(c->stream));
+    c->guess_pending = true;
+    return MI355CG_OK;
+}
+
+int mi355cg_use_solution_as_initial_guess(mi355cg_handle c) {
+    if (int rc = guess_check(c)) return rc;
+    if (!c->solved || c->x_is_guess) return fail(MI355CG_ERR_STATE, "no solve has run on this handle: there is no solution to start from");
+    c->x_is_guess = true;                                          // x is complete when a solve returns (k_fold_x / k_flush_x ran): nothing to flush
+    c->guess_pending = true;
+    return MI355CG_OK;
 }
 
 int mi355cg_set_profiling(mi355cg_handle c, int enable) {
@@ -2177,6 +2300,30 @@ int mi355cg_solve_batch(mi355cg_handle c, const mi355cg_params* prm, int nrhs, c
     HIPCK(hipMemcpyAsync(stage, b, bytes, hipMemcpyHostToDevice, c->stream));
     if (int rc = solve_mg_batch(c, prm, nrhs, stage, stage, stop_flag, out)) return rc;
     HIPCK(hipMemcpyAsync(x, stage, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(hipStreamSynchronize(c->stream));
+    return MI355CG_OK;
+}
+
+// The same with a guess per system: x is in/out.  System s gets the bits of set_rhs(b_s); set_initial_guess(x0_s); solve; get_solution.
+int mi355cg_solve_batch_device_from(mi355cg_handle c, const mi355cg_params* prm, int nrhs, const double* b_dev, double* x_dev,
+                                    const volatile int* stop_flag, mi355cg_results* out) {
+    if (int rc = batch_check(c, prm, nrhs, b_dev, x_dev, out)) return rc;
+    HIPCK(hipSetDevice(c->device));
+    if (int rc = mg_batch_ensure(c, nrhs, 0)) return rc;
+    return solve_mg_batch(c, prm, nrhs, b_dev, x_dev, stop_flag, out, true);
+}
+
+int mi355cg_solve_batch_from(mi355cg_handle c, const mi355cg_params* prm, int nrhs, const double* b, double* x,
+                             const volatile int* stop_flag, mi355cg_results* out) {
+    if (int rc = batch_check(c, prm, nrhs, b, x, out)) return rc;
+    HIPCK(hipSetDevice(c->device));
+    if (int rc = mg_batch_ensure(c, nrhs, 2 * nrhs)) return rc;
+    double* stage = c->batch->stage;                               // b in the first half, the guesses (then the solutions) in the second
+    const size_t count = (size_t)c->pk_len * (size_t)nrhs, bytes = sizeof(double) * count;
+    HIPCK(hipMemcpyAsync(stage, b, bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCK(hipMemcpyAsync(stage + count, x, bytes, hipMemcpyHostToDevice, c->stream));
+    if (int rc = solve_mg_batch(c, prm, nrhs, stage, stage + count, stop_flag, out, true)) return rc;
+    HIPCK(hipMemcpyAsync(x, stage + count, bytes, hipMemcpyDeviceToHost, c->stream));
     HIPCK(hipStreamSynchronize(c->stream));
     return MI355CG_OK;
 }

@@ -121,6 +121,53 @@ class _Handle:
         _capi.check(self._lib.mi355cg_apply(self._h, x, y))
         return y
 
+    @staticmethod
+    def _check_guess(x0, size):
+        """True if the guess x0 is in device memory: a NumPy array or a CUDA torch tensor, [size] float64, contiguous.
+        ValueError for anything else; the library has not been called when it is raised."""
+        on_device = not isinstance(x0, np.ndarray)
+        if on_device:
+            if not (type(x0).__module__.split(".")[0] == "torch" and hasattr(x0, "data_ptr")):
+                raise ValueError(f"an initial guess is a NumPy array or a CUDA torch tensor, not {type(x0).__name__}")
+            import torch
+            if not x0.is_cuda:
+                raise ValueError("a torch guess must be in device memory (a CPU tensor: pass tensor.numpy())")
+            if x0.dtype != torch.float64:
+                raise ValueError(f"initial guess has dtype {x0.dtype}, expected torch.float64")
+            if not x0.is_contiguous():
+                raise ValueError("initial guess tensor must be contiguous")
+        elif x0.dtype != np.float64:
+            raise ValueError(f"initial guess has dtype {x0.dtype}, expected float64")
+        if tuple(x0.shape) != (size,):
+            raise ValueError(f"initial guess has shape {tuple(x0.shape)}, expected ({size},)")
+        return on_device
+
+    def _guess_rc(self, rc):
+        if rc == _capi.ERR_INVALID:
+            raise ValueError(self._lib.mi355cg_last_error().decode())
+        _capi.check(rc)
+
+    def set_initial_guess(self, x0):
+        """Extension (no reference twin): the next solve() starts from x0 and r0 = b - A x0 instead of from zero, and REL_2NORM
+        stops relative to ||b|| (mi355cg_set_initial_guess).  One-shot.  x0: NumPy [size] float64, or a contiguous CUDA
+        torch.Tensor on the handle's device, which is read in place (mi355cg_set_initial_guess_device); None withdraws a
+        pending guess.  Until the next solve solution() and the residuals raise.  ValueError on CSR and F32_MIXED handles."""
+        if x0 is None:
+            return self._guess_rc(self._lib.mi355cg_set_initial_guess(self._h, None))
+        if self._check_guess(x0, self.size):
+            import torch
+            if x0.device.index != self._device:
+                raise ValueError(f"initial guess is on {x0.device}, the handle on device {self._device}")
+            torch.cuda.current_stream(x0.device).synchronize()       # the library works on its own stream
+            return self._guess_rc(self._lib.mi355cg_set_initial_guess_device(self._h, x0.data_ptr()))
+        x0 = np.ascontiguousarray(x0)
+        self._guess_rc(self._lib.mi355cg_set_initial_guess(self._h, x0.ctypes.data))
+
+    def use_solution_as_initial_guess(self):
+        """The x of the last solve is the next solve's starting point, without a copy: after a solve that was interrupted or hit
+        its iteration cap this continues it (mi355cg_use_solution_as_initial_guess)."""
+        self._guess_rc(self._lib.mi355cg_use_solution_as_initial_guess(self._h))
+
     def solve(self, params: _capi.Params, callback=None, stop_flag: Optional[C.c_int] = None) -> _capi.Results:
         res = _capi.Results()
         cb = _capi.ITER_CB(lambda user, it, p, r, e: callback(it, p, r, e)) if callback else _capi.ITER_CB()
@@ -181,27 +228,36 @@ class _Handle:
             raise ValueError(f"a batch has 1 .. {_capi.BATCH_MAX} right-hand sides, not {shape[0]}")
         return shape[0], on_device
 
-    def solve_batch(self, params: _capi.Params, b, stop_flag: Optional[C.c_int] = None):
+    def solve_batch(self, params: _capi.Params, b, stop_flag: Optional[C.c_int] = None, x0=None):
         """Extension (no reference twin): solve b[s] for every row s of b by one multigrid-preconditioned CG loop
         (mi355cg_solve_batch; needs set_preconditioner first).  Returns (x, [Results per system]); system s gets the bits
         set_rhs(b[s]); solve(params); solution() gives.  b: NumPy [nrhs, size] float64 -> NumPy x; or a contiguous CUDA
         torch.Tensor [nrhs, size] float64 on the handle's device -> a new tensor there (mi355cg_solve_batch_device; torch's
         current stream is synchronised first, since the library works on its own stream).  params.use_true_solution and
-        params.diagnostics must be 0."""
+        params.diagnostics must be 0.  x0: a guess per system, of b's kind and shape (mi355cg_solve_batch_from): system s then
+        gets the bits of set_rhs(b[s]); set_initial_guess(x0[s]); solve(params); solution().  x0 is not modified."""
         nrhs, on_device = self._check_batch(b, self.size)
+        if x0 is not None:
+            if self._check_batch(x0, self.size) != (nrhs, on_device):
+                raise ValueError(f"x0 has shape {tuple(x0.shape)}: the guesses are of the kind (NumPy / CUDA tensor) and shape of b, "
+                                 f"{tuple(b.shape)}")
         res = (_capi.Results * nrhs)()
         sp = C.cast(C.pointer(stop_flag), C.c_void_p) if stop_flag is not None else None
         if on_device:
             import torch
             if b.device.index != self._device:
                 raise ValueError(f"batch is on {b.device}, the handle on device {self._device}")
-            x = torch.empty_like(b)
+            if x0 is not None and x0.device != b.device:
+                raise ValueError(f"x0 is on {x0.device}, b on {b.device}")
+            x = torch.empty_like(b) if x0 is None else x0.clone()
             torch.cuda.current_stream(b.device).synchronize()
-            rc = self._lib.mi355cg_solve_batch_device(self._h, C.byref(params), nrhs, b.data_ptr(), x.data_ptr(), sp, res)
+            fn = self._lib.mi355cg_solve_batch_device if x0 is None else self._lib.mi355cg_solve_batch_device_from
+            rc = fn(self._h, C.byref(params), nrhs, b.data_ptr(), x.data_ptr(), sp, res)
         else:
             b = np.ascontiguousarray(b)
-            x = np.empty_like(b)
-            rc = self._lib.mi355cg_solve_batch(self._h, C.byref(params), nrhs, b.ctypes.data, x.ctypes.data, sp, res)
+            x = np.empty_like(b) if x0 is None else np.array(x0, dtype=np.float64, order="C", copy=True)
+            fn = self._lib.mi355cg_solve_batch if x0 is None else self._lib.mi355cg_solve_batch_from
+            rc = fn(self._h, C.byref(params), nrhs, b.ctypes.data, x.ctypes.data, sp, res)
         if rc == _capi.ERR_INVALID:
             raise ValueError(self._lib.mi355cg_last_error().decode())
         _capi.check(rc)
@@ -298,18 +354,19 @@ class MatrixFreeSystem:
         """(kind, cycle, levels) of the preconditioner that is set; (PRECOND_NONE, CYCLE_F64, 0) without one."""
         return self._handle.preconditioner_info()
 
-    def solve_batch(self, b, eps: float = 1e-6, max_iterations: int = 10000, rule: int = _capi.RULE_REL_2NORM, params=None):
+    def solve_batch(self, b, eps: float = 1e-6, max_iterations: int = 10000, rule: int = _capi.RULE_REL_2NORM, params=None, x0=None):
         """Extension (no reference twin): many right-hand sides on this grid by one multigrid-preconditioned CG loop (needs
         set_preconditioner).  b: [nrhs, size()] float64, NumPy or a CUDA torch tensor; returns (x of the same kind, one
         _capi.Results per system), every system with the bits a MatrixFreeSolver / MSGSolver solve of it on this system
         gives.  eps: eps_rel (RULE_REL_2NORM) or the precision and residual thresholds (RULE_MSG_MAXNORM); params, if
-        given, is used as it is."""
+        given, is used as it is.  x0: a starting vector per system, of b's kind and shape (for instance the solutions of
+        the previous step); with it REL_2NORM stops relative to ||b[s]||."""
         if params is None:
             params = default_params(rule)
             params.max_iterations = max_iterations
             params.eps_rel = params.eps_precision = params.eps_residual = eps
             params.use_true_solution = 0
-        return self._handle.solve_batch(params, b)
+        return self._handle.solve_batch(params, b, x0=x0)
 
     def batch_release(self):
         """Free the device workspace solve_batch keeps on this system."""
@@ -363,10 +420,13 @@ class MatrixFreeSolver:
     def getName(self): return self.name
 
     def solve(self, true_solution=None, fixed_iterations: bool = False, sync_every: int = 0,
-              inner_eps: float = 0.0) -> np.ndarray:
-        """inner_eps only matters for a MatrixFreeSystem created with dtype=F32_MIXED (config 3)."""
+              inner_eps: float = 0.0, x0=None) -> np.ndarray:
+        """inner_eps only matters for a MatrixFreeSystem created with dtype=F32_MIXED (config 3).  x0 (extension): the starting
+        vector of this solve instead of zero (_Handle.set_initial_guess); the rule is then relative to ||b||."""
         h = self.system._handle
         h.set_rhs(self.b)
+        if x0 is not None:
+            h.set_initial_guess(x0)
         if true_solution is not None and len(true_solution) > 0:
             h.set_true_solution(true_solution)                   # matrix_free_system.cpp:451-455 uses the caller's vector
         p = default_params(_capi.RULE_REL_2NORM)
@@ -418,12 +478,15 @@ class MSGSolver:
     def getIterations(self): return self.iterations
     def getName(self): return self.name
 
-    def solve(self, true_solution=None, callback_every: int = 100) -> np.ndarray:
-        """true_solution: None / empty = extent 0 (error criterion and norm off)."""
+    def solve(self, true_solution=None, callback_every: int = 100, x0=None) -> np.ndarray:
+        """true_solution: None / empty = extent 0 (error criterion and norm off).  x0 (extension): the starting vector of this
+        solve instead of zero (_Handle.set_initial_guess); the residual and exact-error tests then also run on the start."""
         self.converged = False
         self._stop.value = 0                                     # msg_solver.cpp:12-13
         h = self.a._handle
         h.set_rhs(self.b)
+        if x0 is not None:
+            h.set_initial_guess(x0)
         if true_solution is not None and len(true_solution) > 0:
             h.set_true_solution(true_solution)                   # the error norms use the vector that was passed in (msg_solver.cpp:64-72,132-139)
         p = default_params(_capi.RULE_MSG_MAXNORM)
