@@ -75,9 +75,15 @@ def test_rel_2norm_converges_in_few_iterations(N):
 
 
 def test_stretched_domain_converges():
-    s = any_system(258, (0.0, 1.0, 0.0, 2.0))
-    _, res = rel_solve(s)
-    assert 1 <= res.iterations <= 20 and res.converged
+    from oracle.oracle import OracleGrid
+    for dom in ((0.0, 1.0, 0.0, 2.0), (0.0, 3.0, 0.0, 1.0)):          # xk = 4 yk, and yk = 9 xk: no exchange passes by symmetry
+        s = any_system(258, dom)
+        x, res = rel_solve(s)
+        assert 1 <= res.iterations <= 20 and res.converged
+        b = s.get_rhs()
+        tr = OracleGrid(258, 258, *dom).apply(x) - b
+        print(f"N=258 dom={dom}: {res.iterations} iterations, true residual {np.linalg.norm(tr) / np.linalg.norm(b):.3e}")
+        assert np.linalg.norm(tr) <= 2e-8 * np.linalg.norm(b)
 
 
 def test_msg_rule_stop_reason_and_callbacks():
