@@ -21,15 +21,14 @@
 #include <hip/hip_runtime.h>
 #include <cfloat>
 #include <cmath>
+#include "solve_loop.h"               // CgState, HistEntry, kHist, kRing: what the host loop reads back
 
 namespace mi355cg {
 
 constexpr int kBlock = 256;           // threads per workgroup = 4 wave64
 constexpr int kWave = 64;
 constexpr int kWaves = kBlock / kWave;
-constexpr int kHist = 512;            // per-iteration norm history ring (>= sync_every)
 constexpr int kMaxPanels = 8;
-constexpr int kRing = 8;              // direction buffers of a context (ring; M = xsteps <= kRing of them are in use); also the alpha history depth
 
 // ---- per-wave timing probe (diagnostic build only: -DMI355CG_WAVE_TIMING, tools/wave_timing.py) -------------------
 // Every wave of the two iteration kernels records wall_clock64() (100 MHz) at entry, after the prologue and at exit.
@@ -95,21 +94,6 @@ __device__ inline ItemSeq item_seq(const WorkList& wl, int wave) {
     }
     return ItemSeq{(int)blockIdx.x * kWaves + wave, (int)gridDim.x * kWaves, 0, wl.nitems};
 }
-
-// ---- CG state carried on the device ----------------------------------------------------------------
-struct CgState {
-    double alpha, beta;
-    double rr;          // (r, r) of the current residual
-    double rr_prev;     // (r, r) one decision earlier (lets a stopped solve resume with the right beta denominator)
-    double rz;          // MSG: (r, z) of the current iteration (denominator of the next beta)
-    double r0norm;      // ||r0||_2
-    double rnorm2;      // ||r||_2
-    double rmax, dmax, emax, d2, e2;
-    int it, done, reason, converged, first;      // first: no iteration has run yet (no beta); 1 = cold start, 2 = warm start (r0norm is set: ||b||_2)
-    int stop;           // a stop request was pending when the last update launch ended (single context: read from the pinned word; msg_solver.cpp:82-87)
-    double alpha_hist[kRing];   // step length of iteration k at [k % kRing]: the folded x update (XM >= 2) applies up to kRing - 1 earlier steps at once
-};
-struct HistEntry { double dmax, rmax, emax, rnorm2, d2, e2, tr2; };   // tr2: ||b - A x||_2^2 (REL_2NORM diagnostics mode, written by k_resid2_hist)
 
 // What every wave needs from the state, fetched with SCALAR loads (s_load through the constant address space, one
 // request per scalar cache instead of one per wave).  Copying the whole struct made hipcc fetch half of it with

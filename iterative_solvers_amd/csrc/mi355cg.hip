@@ -664,6 +664,25 @@ void prof_collect(mi355cg_ctx* c) {
     c->events.reset();
 }
 
+// The HIP side of solve_loop.h's protocol.  Summary and history ring -> pinned host memory: there once `st` has reached this point.
+int fetch_state(mi355cg_ctx* c, hipStream_t st) {
+    HIPCK(hipMemcpyAsync(c->summary_h, c->summary, sizeof(CgState), hipMemcpyDeviceToHost, st));
+    HIPCK(hipMemcpyAsync(c->hist_h, c->hist, sizeof(HistEntry) * kHist, hipMemcpyDeviceToHost, st));
+    return MI355CG_OK;
+}
+// mi355cg_results::loop_seconds: two events around the iterations.  The caller waits (for the second event or for its stream)
+// before it reads the seconds.
+int loop_timer_begin(mi355cg_ctx* c, hipStream_t st) {
+    if (!c->ev_loop[0]) { HIPCK(hipEventCreate(&c->ev_loop[0])); HIPCK(hipEventCreate(&c->ev_loop[1])); }
+    HIPCK(hipEventRecord(c->ev_loop[0], st));
+    return MI355CG_OK;
+}
+int loop_timer_end(mi355cg_ctx* c, hipStream_t st) { HIPCK(hipEventRecord(c->ev_loop[1], st)); return MI355CG_OK; }
+double loop_timer_seconds(const mi355cg_ctx* c) {
+    float ms = 0;
+    return hipEventElapsedTime(&ms, c->ev_loop[0], c->ev_loop[1]) == hipSuccess ? 1e-3 * ms : 0.0;
+}
+
 }  // namespace
 
 // ---- generic CSR handles ----------------------------------------------------------------------------------
@@ -707,25 +726,21 @@ int solve_csr(mi355cg_ctx* c, const mi355cg_params* prm, mi355cg_iter_cb cb, voi
     HIPCK(hipGetLastError());
     auto poll = [&]() -> int {
         launch_check(c, cfg, c->stream, own_partB(c));
-        HIPCK(hipMemcpyAsync(c->summary_h, c->summary, sizeof(CgState), hipMemcpyDeviceToHost, c->stream));
-        HIPCK(hipMemcpyAsync(c->hist_h, c->hist, sizeof(HistEntry) * kHist, hipMemcpyDeviceToHost, c->stream));
+        if (int rc = fetch_state(c, c->stream)) return rc;
         HIPCK(hipStreamSynchronize(c->stream));
         return MI355CG_OK;
     };
     if (int rc = poll()) return rc;
     const double initial_rnorm2 = c->summary_h->rnorm2;
     if (msg && cb) cb(user, 0, DBL_MAX, c->summary_h->rmax, cfg.has_u ? c->summary_h->emax : DBL_MAX);
-    const int every = prm->callback_every;
-    const int sync_every = std::min(prm->sync_every > 0 ? prm->sync_every : (msg ? 100 : 200), kHist);
+    const int sync_every = default_sync_every(prm, msg);
     int it_done = 0;
     bool first_chunk = (cb != nullptr || stop_flag != nullptr);
     bool interrupted = false;
     while (!c->summary_h->done) {
         if (stop_flag && *stop_flag) { interrupted = true; break; }
-        int m = std::min(sync_every, prm->max_iterations - it_done);
-        if (msg && every > 0) m = std::min(m, every - it_done % every);
-        if (first_chunk) { m = 1; first_chunk = false; }     // deliver the it == 1 callback / honour a stop request before queueing more
-        if (m <= 0) m = 1;
+        const int m = chunk_len(prm, msg, sync_every, it_done, first_chunk);
+        first_chunk = false;
         for (int k = 0; k < m; ++k) {
             XpayArgs xa{};
             xa.n = c->csr_n; xa.r = c->r; xa.p = c->p[0];
@@ -738,26 +753,11 @@ int solve_csr(mi355cg_ctx* c, const mi355cg_params* prm, mi355cg_iter_cb cb, voi
         HIPCK(hipGetLastError());
         if (int rc = poll()) return rc;
         const int it_now = c->summary_h->it;
-        if (msg && cb)
-            for (int it = it_done + 1; it <= it_now; ++it) {
-                const bool stopped_here = c->summary_h->done && c->summary_h->reason != MI355CG_STOP_ITERATIONS && it == it_now;
-                if ((it == 1 || (every > 0 && it % every == 0)) && !stopped_here) {
-                    const HistEntry& h = c->hist_h[it % kHist];
-                    cb(user, it, h.dmax, h.rmax, cfg.has_u ? h.emax : DBL_MAX);
-                }
-            }
+        replay_callbacks(cb, user, prm, *c->summary_h, c->hist_h, it_done, it_now, cfg.has_u, false);
         it_done = it_now;
     }
-    const CgState fin = *c->summary_h;
     c->solved = true;
-    mi355cg_results res{};
-    res.iterations = fin.it;
-    res.converged = interrupted ? 0 : fin.converged;
-    res.stop_reason = interrupted ? MI355CG_STOP_INTERRUPTED : fin.reason;
-    res.final_residual_norm = fin.rmax;
-    res.final_precision = fin.it > 0 ? fin.dmax : DBL_MAX;
-    res.final_error_norm = cfg.has_u ? fin.emax : DBL_MAX;
-    res.r_norm2 = fin.rnorm2; res.initial_r_norm2 = initial_rnorm2;
+    mi355cg_results res = make_results(*c->summary_h, interrupted, cfg.has_u, initial_rnorm2);
     res.solve_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (msg && cb) cb(user, res.iterations, res.final_precision, res.final_residual_norm, res.final_error_norm);
     if (out) *out = res;
@@ -838,7 +838,7 @@ int solve_mixed(mi355cg_ctx* c, const mi355cg_params* prm, mi355cg_iter_cb cb, v
     // (profiles/r01_tune_notes.md), so it stays experimental and every stage is capped.
     const bool restart = env_int("MI355CG_MIXED_RESTART", 1) != 0;
     int stage_cap = 0;                       // replacement mode: iterations a later stage may spend (3x the first stage)
-    const int sync_every = std::min(prm->sync_every > 0 ? prm->sync_every : 200, kHist);
+    const int sync_every = default_sync_every(prm, false);
     const int rgrid = 1024;
     auto residual_pass = [&](double* norm) -> int {      // rf = (float)(b - ap64), *norm = ||b - ap64||_2
         hipLaunchKernelGGL(k_residual_to_f32, dim3(rgrid), dim3(kBlock), 0, c->stream, c->storage_len, c->g.own_begin, c->g.own_len,
@@ -886,12 +886,7 @@ int solve_mixed(mi355cg_ctx* c, const mi355cg_params* prm, mi355cg_iter_cb cb, v
     HIPCK(hipStreamSynchronize(c->stream));
     c->solved = true; c->cur = 0; c->nB_own = c->whole.grid;
     prof_collect(c);
-    mi355cg_results res{};
-    res.iterations = total; res.converged = converged ? 1 : 0;
-    res.stop_reason = interrupted ? MI355CG_STOP_INTERRUPTED : (converged ? MI355CG_STOP_RESIDUAL : MI355CG_STOP_ITERATIONS);
-    res.final_residual_norm = res.final_precision = res.final_error_norm = DBL_MAX;
-    res.r_norm2 = rnorm; res.initial_r_norm2 = bnorm;
-    res.refine_outer = outer; res.refine_true_rel = bnorm > 0 ? rnorm / bnorm : 0.0;
+    mi355cg_results res = make_mixed_results(total, interrupted, converged, rnorm, bnorm, outer);
     res.solve_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (out) *out = res;
     return MI355CG_OK;
@@ -1242,17 +1237,14 @@ int solve_mg(mi355cg_ctx* c, const mi355cg_params* prm, mi355cg_iter_cb cb, void
     const double r0norm = std::sqrt(nm[MG_RR]);
     const double refnorm = warm ? std::sqrt(bb) : r0norm;      // what REL_2NORM is relative to: ||b||_2
     double rnorm = r0norm;
-    if (!c->ev_loop[0]) { HIPCK(hipEventCreate(&c->ev_loop[0])); HIPCK(hipEventCreate(&c->ev_loop[1])); }
-    HIPCK(hipEventRecord(c->ev_loop[0], st));
+    if (int rc = loop_timer_begin(c, st)) return rc;
     if (msg && cb) cb(user, 0, DBL_MAX, nm[MG_RMAX], has_u ? nm[MG_EMAX] : DBL_MAX);          // msg_solver.cpp:75-77
     const int every = prm->callback_every;
-    int it = 0, reason = MI355CG_STOP_ITERATIONS;
-    bool converged = false, interrupted = false;
+    int it = 0;
+    // r0 of a guess may be 0 (alpha = 0 / 0): a warm solve applies the stop tests that have their numbers to the start state
+    int reason = warm ? msg_stop_reason(prm, false, 0.0, nm[MG_RMAX], has_u, nm[MG_EMAX]) : 0;
+    bool converged = reason != 0, interrupted = false;
     double rho = 0.0;
-    if (warm && msg && !prm->fixed_iterations) {        // r0 of a guess may be 0 (alpha = 0 / 0): the tests of msg_solver.cpp:144-163 that have their numbers, on the start state
-        if (prm->eps_residual > 0 && nm[MG_RMAX] < prm->eps_residual) { converged = true; reason = MI355CG_STOP_RESIDUAL; }
-        else if (prm->eps_exact_error > 0 && has_u && nm[MG_EMAX] < prm->eps_exact_error) { converged = true; reason = MI355CG_STOP_EXACT_ERROR; }
-    }
     for (;;) {
         if (converged) break;                                                                 // a warm start that already meets the rule
         if (!(it < prm->max_iterations)) break;                                               // msg_solver.cpp:80
@@ -1272,11 +1264,8 @@ int solve_mg(mi355cg_ctx* c, const mi355cg_params* prm, mi355cg_iter_cb cb, void
         if (int rc = update(rho / pq, p, H.q)) return rc;
         ++it;
         rnorm = std::sqrt(nm[MG_RR]);
-        if (msg && !prm->fixed_iterations) {                                                  // msg_solver.cpp:144-163, this order, strict <
-            if (prm->eps_precision > 0 && nm[MG_DMAX] < prm->eps_precision) { converged = true; reason = MI355CG_STOP_PRECISION; break; }
-            if (prm->eps_residual > 0 && nm[MG_RMAX] < prm->eps_residual) { converged = true; reason = MI355CG_STOP_RESIDUAL; break; }
-            if (prm->eps_exact_error > 0 && has_u && nm[MG_EMAX] < prm->eps_exact_error) { converged = true; reason = MI355CG_STOP_EXACT_ERROR; break; }
-        }
+        reason = msg_stop_reason(prm, true, nm[MG_DMAX], nm[MG_RMAX], has_u, nm[MG_EMAX]);
+        if (reason) { converged = true; break; }
         if (diag && cb) {                                                                     // matrix_free_system.cpp:457-468 (0-based index)
             double tr2 = 0;
             hipLaunchKernelGGL(k_mg_resid2, grid, blk, 0, st, g, (const double*)c->b, (const double*)c->x, H.part);
@@ -1286,21 +1275,14 @@ int solve_mg(mi355cg_ctx* c, const mi355cg_params* prm, mi355cg_iter_cb cb, void
             cb(user, it, nm[MG_DMAX], nm[MG_RMAX], has_u ? nm[MG_EMAX] : DBL_MAX);
         }
     }
-    HIPCK(hipEventRecord(c->ev_loop[1], st));
+    if (int rc = loop_timer_end(c, st)) return rc;
     if (!msg) converged = rnorm <= prm->eps_rel * refnorm;                                    // matrix_free_system.cpp:472
     c->solved = true; c->x_is_guess = false;
     c->kernel_ms[0] = c->kernel_ms[1] = 0.0; c->kernel_launches[0] = c->kernel_launches[1] = 0;   // per-kernel times: plain path only
-    mi355cg_results res{};
-    res.iterations = it;
-    res.converged = interrupted ? 0 : (converged ? 1 : 0);
-    res.stop_reason = interrupted ? MI355CG_STOP_INTERRUPTED : reason;
-    res.final_residual_norm = nm[MG_RMAX];
-    res.final_precision = it > 0 ? nm[MG_DMAX] : DBL_MAX;
-    res.final_error_norm = has_u ? nm[MG_EMAX] : DBL_MAX;
-    res.r_norm2 = rnorm;
-    res.initial_r_norm2 = r0norm;
+    mi355cg_results res = make_results(it, interrupted, converged ? 1 : 0, reason, nm[MG_DMAX], nm[MG_RMAX], has_u, nm[MG_EMAX], rnorm, r0norm);
     res.solve_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    { float ms = 0; HIPCK(hipEventSynchronize(c->ev_loop[1])); if (hipEventElapsedTime(&ms, c->ev_loop[0], c->ev_loop[1]) == hipSuccess) res.loop_seconds = 1e-3 * ms; }
+    HIPCK(hipEventSynchronize(c->ev_loop[1]));
+    res.loop_seconds = loop_timer_seconds(c);
     if (msg && cb) cb(user, res.iterations, res.final_precision, res.final_residual_norm, res.final_error_norm);   // msg_solver.cpp:193-195
     if (out) *out = res;
     return MI355CG_OK;
@@ -1459,15 +1441,15 @@ int solve_mg_batch(mi355cg_ctx* c, const mi355cg_params* prm, int nrhs, const do
         if (!warm) s.refnorm = s.r0norm;
         s.rho = 0.0; s.it = 0; s.reason = MI355CG_STOP_ITERATIONS; s.converged = false; s.interrupted = false;
     }
-    if (!c->ev_loop[0]) { HIPCK(hipEventCreate(&c->ev_loop[0])); HIPCK(hipEventCreate(&c->ev_loop[1])); }
-    HIPCK(hipEventRecord(c->ev_loop[0], st));
+    if (int rc = loop_timer_begin(c, st)) return rc;
     MgbScal sc{};
     for (int it = 0;; ++it) {
         int n = 0;
         for (int k = 0; k < act.n; ++k) {                          // the tests before an iteration, per system (solve_mg's order)
             Sys& s = S[act.sys[k]];
-            if (warm && it == 0 && msg && !prm->fixed_iterations && prm->eps_residual > 0 && s.rmax < prm->eps_residual) {
-                s.converged = true; s.reason = MI355CG_STOP_RESIDUAL; continue;       // solve_mg's test of a warm start state
+            if (warm && it == 0) {                                 // solve_mg's test of a warm start state
+                s.reason = msg_stop_reason(prm, false, 0.0, s.rmax, false, 0.0);
+                if (s.reason) { s.converged = true; continue; }
             }
             if (!(it < prm->max_iterations)) continue;
             if (!msg && !prm->fixed_iterations && !(s.rnorm > prm->eps_rel * s.refnorm)) continue;
@@ -1494,37 +1476,26 @@ int solve_mg_batch(mi355cg_ctx* c, const mi355cg_params* prm, int nrhs, const do
         if (int rc = fetch(MGB_NFIELDS, MGB_RMAX)) return rc;
         take_norms();
         int m = 0;
-        for (int k = 0; k < n; ++k) {                              // the tests after an iteration (msg_solver.cpp:144-163)
+        for (int k = 0; k < n; ++k) {                              // the tests after an iteration
             Sys& s = S[act.sys[k]];
             s.it = it + 1;
             s.rnorm = std::sqrt(s.rr);
-            if (msg && !prm->fixed_iterations) {
-                if (prm->eps_precision > 0 && s.dmax < prm->eps_precision) { s.converged = true; s.reason = MI355CG_STOP_PRECISION; continue; }
-                if (prm->eps_residual > 0 && s.rmax < prm->eps_residual) { s.converged = true; s.reason = MI355CG_STOP_RESIDUAL; continue; }
-            }
+            s.reason = msg_stop_reason(prm, true, s.dmax, s.rmax, false, 0.0);
+            if (s.reason) { s.converged = true; continue; }
             act.sys[m++] = act.sys[k];
         }
         act.n = m;
     }
-    HIPCK(hipEventRecord(c->ev_loop[1], st));
+    if (int rc = loop_timer_end(c, st)) return rc;
     hipLaunchKernelGGL(k_mgb_pack, dim3(flat_grid(c->pk_len), nrhs), blk, 0, st, c->pg, W.stride, (const double*)(B + W.x), x_dev);
     HIPCK(hipGetLastError());
     HIPCK(hipStreamSynchronize(st));
-    float ms = 0;
-    const double loop_s = hipEventElapsedTime(&ms, c->ev_loop[0], c->ev_loop[1]) == hipSuccess ? 1e-3 * ms : 0.0;
+    const double loop_s = loop_timer_seconds(c);
     const double solve_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     for (int i = 0; i < nrhs; ++i) {
         const Sys& s = S[i];
         const bool conv = msg ? s.converged : s.rnorm <= prm->eps_rel * s.refnorm;        // matrix_free_system.cpp:472
-        mi355cg_results res{};
-        res.iterations = s.it;
-        res.converged = s.interrupted ? 0 : (conv ? 1 : 0);
-        res.stop_reason = s.interrupted ? MI355CG_STOP_INTERRUPTED : s.reason;
-        res.final_residual_norm = s.rmax;
-        res.final_precision = s.it > 0 ? s.dmax : DBL_MAX;
-        res.final_error_norm = DBL_MAX;
-        res.r_norm2 = s.rnorm;
-        res.initial_r_norm2 = s.r0norm;
+        mi355cg_results res = make_results(s.it, s.interrupted, conv ? 1 : 0, s.reason, s.dmax, s.rmax, false, 0.0, s.rnorm, s.r0norm);
         res.solve_seconds = solve_s;
         res.loop_seconds = loop_s;
         out[i] = res;
@@ -1862,6 +1833,36 @@ void mi355cg_default_params(mi355cg_params* p, int rule) {
     p->inner_eps = 0.0;
 }
 
+// The two ways a solve's state starts, each one pass over the owned range on the part's stream.  (They sit here, at mi355cg_solve,
+// because the compiler emits kernels in the order of their first use and the code object keeps the order it was measured in.)
+// x = x0 (already in x), r = b - A x0 with A x0 from the plain operator (mi355cg_apply's bits), z = 0.  k_guess_state arms the
+// state with ||b||_2 as the reference norm of REL_2NORM.
+static int launch_init_guess(mi355cg_ctx* c, bool has_u) {
+    launch_apply<double, 2>(c, c->x, c->scratch[0], whole_part(c));
+    GuessArgs<double> f{};
+    f.begin = c->g.own_begin / 2; f.nvec = c->g.own_len / 2;
+    f.b = c->b; f.ax = c->scratch[0]; f.x = c->x; f.r = c->r; f.p0 = c->p[0]; f.u = c->u;
+    f.partB = c->partB; f.strideB = c->strideB; f.partG = c->guess_part; f.strideG = c->strideB; f.s_out = c->sB;
+    if (has_u) hipLaunchKernelGGL((k_init_guess<double, 2, true>), dim3(c->whole.grid), dim3(kBlock), 0, c->stream, f);
+    else hipLaunchKernelGGL((k_init_guess<double, 2, false>), dim3(c->whole.grid), dim3(kBlock), 0, c->stream, f);
+    double* norms = c->guess_part + 2 * (size_t)c->strideB;
+    hipLaunchKernelGGL(k_guess_state, dim3(1), dim3(kBlock), 0, c->stream, (const double*)c->partB, c->strideB, (const double*)c->guess_part, c->strideB,
+                       c->whole.grid, c->sB, norms);
+    HIPCK(hipMemcpyAsync(c->guess_norms_h, norms, sizeof(double) * 2, hipMemcpyDeviceToHost, c->stream));     // complete with the first poll
+    return MI355CG_OK;
+}
+// x = 0, r = b, z = 0 (the first stencil makes z = r + 0*z = r; msg_solver.cpp:33-39) and the partial norms of r0.  Everything outside
+// the owned range (pitch padding, the rows around the grid) was zeroed when the vectors were allocated and no launch writes anything but
+// zeros there; the other directions of the ring are written (iterations 1 .. M-1) before the folded x update first reads them (iteration M).
+static void launch_init_fresh(mi355cg_ctx* c, bool has_u) {
+    FreshArgs<double> f{};
+    f.begin = c->g.own_begin / 2; f.nvec = c->g.own_len / 2;
+    f.b = c->b; f.x = c->x; f.r = c->r; f.p0 = c->p[0]; f.u = c->u;
+    f.partB = c->partB; f.strideB = c->strideB; f.s_out = c->sB;
+    if (has_u) hipLaunchKernelGGL((k_init_fresh<double, 2, true>), dim3(c->whole.grid), dim3(kBlock), 0, c->stream, f);
+    else hipLaunchKernelGGL((k_init_fresh<double, 2, false>), dim3(c->whole.grid), dim3(kBlock), 0, c->stream, f);
+}
+
 int mi355cg_solve(mi355cg_handle c, const mi355cg_params* prm, mi355cg_iter_cb cb, void* user,
                   const volatile int* stop_flag, mi355cg_results* out) {
     if (!c || !prm) return fail(MI355CG_ERR_INVALID, "null argument");
@@ -1886,34 +1887,10 @@ int mi355cg_solve(mi355cg_handle c, const mi355cg_params* prm, mi355cg_iter_cb c
     const auto t0 = std::chrono::steady_clock::now();
     c->events.reset(); c->ev_pairs[0].clear(); c->ev_pairs[1].clear();
 
-    // x = 0, r = b, z = 0 (the first stencil makes z = r + 0*z = r)    msg_solver.cpp:33-39
-    // One pass over the owned range.  Everything outside it (pitch padding, the rows around the grid) was zeroed when the
-    // vectors were allocated and no launch writes anything but zeros there; the other directions of the ring are written
-    // (iterations 1 .. M-1) before the folded x update first reads them (iteration M).
     c->cur = 0; c->fcur = 0;
     if (c->qctr && c->dyn_rows > 0) HIPCK(hipMemsetAsync(c->qctr, 0, sizeof(int) * 2 * kXcds * kQueueSubs * kQueuePitch, c->stream));
-    if (warm) {
-        // x = x0 (already in x), r = b - A x0 with A x0 from the plain operator (mi355cg_apply's bits), z = 0.  k_guess_state arms the
-        // state with ||b||_2 as the reference norm of REL_2NORM; everything after this block is the cold solve's loop.
-        launch_apply<double, 2>(c, c->x, c->scratch[0], whole_part(c));
-        GuessArgs<double> f{};
-        f.begin = c->g.own_begin / 2; f.nvec = c->g.own_len / 2;
-        f.b = c->b; f.ax = c->scratch[0]; f.x = c->x; f.r = c->r; f.p0 = c->p[0]; f.u = c->u;
-        f.partB = c->partB; f.strideB = c->strideB; f.partG = c->guess_part; f.strideG = c->strideB; f.s_out = c->sB;
-        if (cfg.has_u) hipLaunchKernelGGL((k_init_guess<double, 2, true>), dim3(c->whole.grid), dim3(kBlock), 0, c->stream, f);
-        else hipLaunchKernelGGL((k_init_guess<double, 2, false>), dim3(c->whole.grid), dim3(kBlock), 0, c->stream, f);
-        double* norms = c->guess_part + 2 * (size_t)c->strideB;
-        hipLaunchKernelGGL(k_guess_state, dim3(1), dim3(kBlock), 0, c->stream, (const double*)c->partB, c->strideB, (const double*)c->guess_part, c->strideB,
-                           c->whole.grid, c->sB, norms);
-        HIPCK(hipMemcpyAsync(c->guess_norms_h, norms, sizeof(double) * 2, hipMemcpyDeviceToHost, c->stream));     // complete with the first poll
-    } else {
-        FreshArgs<double> f{};
-        f.begin = c->g.own_begin / 2; f.nvec = c->g.own_len / 2;
-        f.b = c->b; f.x = c->x; f.r = c->r; f.p0 = c->p[0]; f.u = c->u;
-        f.partB = c->partB; f.strideB = c->strideB; f.s_out = c->sB;
-        if (cfg.has_u) hipLaunchKernelGGL((k_init_fresh<double, 2, true>), dim3(c->whole.grid), dim3(kBlock), 0, c->stream, f);
-        else hipLaunchKernelGGL((k_init_fresh<double, 2, false>), dim3(c->whole.grid), dim3(kBlock), 0, c->stream, f);
-    }
+    if (warm) { if (int rc = launch_init_guess(c, cfg.has_u)) return rc; }      // everything after it is the cold solve's loop
+    else launch_init_fresh(c, cfg.has_u);
     HIPCK(hipGetLastError());
 
     // The stop request: the reference tests its flag at the top of EVERY iteration (msg_solver.cpp:82-87).  Here block 0 of every
@@ -1937,8 +1914,7 @@ int mi355cg_solve(mi355cg_handle c, const mi355cg_params* prm, mi355cg_iter_cb c
     bool polled = false;
     auto poll = [&]() -> int {
         launch_check(c, cfg, c->stream, own_partB(c));
-        HIPCK(hipMemcpyAsync(c->summary_h, c->summary, sizeof(CgState), hipMemcpyDeviceToHost, c->stream));
-        HIPCK(hipMemcpyAsync(c->hist_h, c->hist, sizeof(HistEntry) * kHist, hipMemcpyDeviceToHost, c->stream));
+        if (int rc = fetch_state(c, c->stream)) return rc;
         polled = true;
         return wait_stream();
     };
@@ -1950,29 +1926,22 @@ int mi355cg_solve(mi355cg_handle c, const mi355cg_params* prm, mi355cg_iter_cb c
         if (cb) cb(user, 0, DBL_MAX, c->summary_h->rmax, cfg.has_u ? c->summary_h->emax : DBL_MAX);
     }
     // A cold MSG solve enters iteration 1 untested, as the reference does.  The r0 of a guess may be 0 (alpha = 0 / 0), so a warm one
-    // first applies the tests of msg_solver.cpp:144-163 that have their numbers to the start state (one poll, taken above).
-    if (warm && msg && !prm->fixed_iterations) {
-        int reason = 0;
-        if (prm->eps_residual > 0 && c->summary_h->rmax < prm->eps_residual) reason = MI355CG_STOP_RESIDUAL;
-        else if (prm->eps_exact_error > 0 && cfg.has_u && c->summary_h->emax < prm->eps_exact_error) reason = MI355CG_STOP_EXACT_ERROR;
-        if (reason) { c->summary_h->done = 1; c->summary_h->converged = 1; c->summary_h->reason = reason; }
-    }
-    if (!c->ev_loop[0]) { HIPCK(hipEventCreate(&c->ev_loop[0])); HIPCK(hipEventCreate(&c->ev_loop[1])); }
-    HIPCK(hipEventRecord(c->ev_loop[0], c->stream));
+    // first applies the stop tests that have their numbers to the start state (one poll, taken above).
+    if (warm)
+        if (const int reason = msg_stop_reason(prm, false, 0.0, c->summary_h->rmax, cfg.has_u, c->summary_h->emax)) {
+            c->summary_h->done = 1; c->summary_h->converged = 1; c->summary_h->reason = reason;
+        }
+    if (int rc = loop_timer_begin(c, c->stream)) return rc;
 
     // The reference recomputes ||x - u|| every iteration (msg_solver.cpp:132-139), but the value is only
     // observable through the exact-error criterion, the periodic callbacks and the final report: read u
     // on exactly those iterations (same values), and once more after the loop if the last one skipped it.
     const int every = prm->callback_every;
     auto need_u = [&](int it) { return diag || cfg.rp.eps_exact_error > 0 || it == 1 || (every > 0 && it % every == 0); };
-    // iterations enqueued between two host polls (the reference polls its stop flag every iteration, msg_solver.cpp:82)
-    int sync_every = prm->sync_every > 0 ? prm->sync_every : (msg ? 100 : 200);
-    sync_every = std::min(sync_every, kHist);
+    const int sync_every = default_sync_every(prm, msg);
     int it_done = 0;
     bool interrupted = false;
-    // A caller that watches the solve (callback or stop flag) gets the first iteration on its own: the it == 1 callback
-    // is delivered, and a stop requested from it is honoured, before any further work is queued.
-    bool first_chunk = cb != nullptr || stop_flag != nullptr;
+    bool first_chunk = cb != nullptr || stop_flag != nullptr;        // a caller that watches the solve
     if (std::memcmp(&c->graph_prm, prm, sizeof *prm) != 0 || c->graph_stop != (stop_flag != nullptr)) {         // kernel arguments embed the solve's parameters
         clear_graphs(c); c->graph_prm = *prm; c->graph_stop = stop_flag != nullptr;                                // (and whether the stop word is sampled): graphs live as long as those do
     }
@@ -1980,10 +1949,8 @@ int mi355cg_solve(mi355cg_handle c, const mi355cg_params* prm, mi355cg_iter_cb c
                           (c->use_graph == 1 || (c->use_graph < 0 && c->g.own_len < (4LL << 20) && prm->max_iterations >= 4 * sync_every));
     while (!c->summary_h->done) {
         if (stop_flag && *stop_flag) { interrupted = true; break; }            // msg_solver.cpp:82-87
-        int m = std::min(sync_every, prm->max_iterations - it_done);
-        if (msg && every > 0) m = std::min(m, every - it_done % every);        // land on the callback iterations
-        if (first_chunk) { m = 1; first_chunk = false; }
-        if (m <= 0) m = 1;                                                    // lets the kernels record ITERATIONS
+        const int m = chunk_len(prm, msg, sync_every, it_done, first_chunk);
+        first_chunk = false;
         auto enqueue_chunk = [&]() -> int {
             for (int k = 0; k < m; ++k) {
                 hipEvent_t e0 = nullptr;
@@ -2044,21 +2011,10 @@ int mi355cg_solve(mi355cg_handle c, const mi355cg_params* prm, mi355cg_iter_cb c
         HIPCK(hipGetLastError());
         if (int rc = poll()) return rc;
         const int it_now = c->summary_h->it;
-        if (cb) for (int it = it_done + 1; it <= it_now; ++it) {
-            const HistEntry& h = c->hist_h[it % kHist];
-            if (diag) {
-                cb(user, it - 1, std::sqrt(h.d2), std::sqrt(h.tr2), std::sqrt(h.e2));     // matrix_free_system.cpp:466-468 (0-based index)
-            } else if (msg) {
-                // callbacks only on iterations that did NOT stop (msg_solver.cpp:172-183 sits after the breaks)
-                // (an interruption is noticed at the top of the NEXT iteration, :82-87, i.e. after this iteration's callback)
-                const bool stopped_here = c->summary_h->done && c->summary_h->reason != MI355CG_STOP_ITERATIONS &&
-                                          c->summary_h->reason != MI355CG_STOP_INTERRUPTED && it == it_now;
-                if ((it == 1 || (every > 0 && it % every == 0)) && !stopped_here) cb(user, it, h.dmax, h.rmax, cfg.has_u ? h.emax : DBL_MAX);
-            }
-        }
+        replay_callbacks(cb, user, prm, *c->summary_h, c->hist_h, it_done, it_now, cfg.has_u, diag);
         it_done = it_now;
     }
-    HIPCK(hipEventRecord(c->ev_loop[1], c->stream));
+    if (int rc = loop_timer_end(c, c->stream)) return rc;
     CgState fin = *c->summary_h;
     c->stop_dev = nullptr;
     if (fin.done && fin.reason == MI355CG_STOP_INTERRUPTED) interrupted = true;      // the device saw the request in the middle of a chunk
@@ -2088,19 +2044,13 @@ int mi355cg_solve(mi355cg_handle c, const mi355cg_params* prm, mi355cg_iter_cb c
         if (FILE* f = fopen(path, "wb")) { fwrite(buf.data(), sizeof(unsigned long long), buf.size(), f); fclose(f); }
     }
 #endif
-    mi355cg_results res{};
-    res.iterations = fin.it;
-    res.converged = interrupted ? 0 : fin.converged;
-    res.stop_reason = interrupted ? MI355CG_STOP_INTERRUPTED : fin.reason;
-    res.final_residual_norm = fin.rmax;
-    res.final_precision = fin.it > 0 ? fin.dmax : DBL_MAX;
-    res.final_error_norm = cfg.has_u ? fin.emax : DBL_MAX;
-    res.r_norm2 = fin.rnorm2;
     // `polled` is set by the poll that fills summary_h, so every path that has a non-zero state has the two pinned norms as well; a solve
     // that never polled (a stop request set before the call) reports the zeros of the empty state, exactly as a cold solve does
-    res.initial_r_norm2 = warm && polled ? c->guess_norms_h[0] : fin.r0norm;       // warm: the state's reference norm is ||b||_2, this field stays ||r0||_2 (read with the first poll)
+    // warm: the state's reference norm is ||b||_2, this field stays ||r0||_2 (read with the first poll)
+    mi355cg_results res = make_results(fin, interrupted, cfg.has_u, warm && polled ? c->guess_norms_h[0] : fin.r0norm);
     res.solve_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    { float ms = 0; HIPCK(hipEventSynchronize(c->ev_loop[1])); if (hipEventElapsedTime(&ms, c->ev_loop[0], c->ev_loop[1]) == hipSuccess) res.loop_seconds = 1e-3 * ms; }
+    HIPCK(hipEventSynchronize(c->ev_loop[1]));
+    res.loop_seconds = loop_timer_seconds(c);
     if (msg && cb) cb(user, res.iterations, res.final_precision, res.final_residual_norm, res.final_error_norm);   // msg_solver.cpp:193-195
     if (out) *out = res;
     return MI355CG_OK;
@@ -2537,9 +2487,7 @@ int mi355cg_dist_check(mi355cg_handle c, const double* gathered_B, int nranks, i
     const IterCfg cfg = make_cfg(&c->dist_prm);
     hipStream_t st = pick_stream(c, stream);
     launch_check(c, cfg, st, PartSrc{gathered_B, nranks, 1, estride});
-    HIPCK(hipMemcpyAsync(c->summary_h, c->summary, sizeof(CgState), hipMemcpyDeviceToHost, st));
-    HIPCK(hipMemcpyAsync(c->hist_h, c->hist, sizeof(HistEntry) * kHist, hipMemcpyDeviceToHost, st));
-    return MI355CG_OK;
+    return fetch_state(c, st);
 }
 // Call once after the loop (after the last mi355cg_dist_check has been synchronised): applies the x update
 // that is still pending after an odd iteration count (REL_2NORM).  No-op otherwise.
@@ -2557,14 +2505,7 @@ int mi355cg_dist_finish(mi355cg_handle c, void* stream) {
 int mi355cg_dist_summary(mi355cg_handle c, mi355cg_results* out, int* done) {
     if (!c || !out) return fail(MI355CG_ERR_INVALID, "null argument");
     const CgState fin = *c->summary_h;
-    const IterCfg cfg = make_cfg(&c->dist_prm);
-    mi355cg_results res{};
-    res.iterations = fin.it; res.converged = fin.converged; res.stop_reason = fin.reason;
-    res.final_residual_norm = fin.rmax;
-    res.final_precision = fin.it > 0 ? fin.dmax : DBL_MAX;
-    res.final_error_norm = cfg.has_u ? fin.emax : DBL_MAX;
-    res.r_norm2 = fin.rnorm2; res.initial_r_norm2 = fin.r0norm;
-    *out = res;
+    *out = make_results(fin, false, make_cfg(&c->dist_prm).has_u, fin.r0norm);      // the caller's loop decides about interruptions
     if (done) *done = fin.done;
     return MI355CG_OK;
 }

@@ -1052,14 +1052,7 @@ int team_solve(mi355cg_team_s* t, const mi355cg_params* prm, mi355cg_iter_cb cb,
         }
         if (c->qctr && c->dyn_rows > 0) HIPCK(hipMemsetAsync(c->qctr, 0, sizeof(int) * 2 * kXcds * kQueueSubs * kQueuePitch, c->stream));
         c->cur = 0;
-        {
-            FreshArgs<double> f{};
-            f.begin = c->g.own_begin / 2; f.nvec = c->g.own_len / 2;
-            f.b = c->b; f.x = c->x; f.r = c->r; f.p0 = c->p[0]; f.u = c->u;
-            f.partB = c->partB; f.strideB = c->strideB; f.s_out = c->sB;
-            if (cfg.has_u) hipLaunchKernelGGL((k_init_fresh<double, 2, true>), dim3(c->whole.grid), dim3(kBlock), 0, c->stream, f);
-            else hipLaunchKernelGGL((k_init_fresh<double, 2, false>), dim3(c->whole.grid), dim3(kBlock), 0, c->stream, f);
-        }
+        launch_init_fresh(c, cfg.has_u);
         }
         if (p.pack.ns && !t->f32) { ColArgs a = p.pack; a.v = c->r; hipLaunchKernelGGL(k_cols, dim3(16), dim3(kBlock), 0, c->stream, a); }
         if (ev) HIPCK(hipEventRecord(p.ev_redge, c->stream));
@@ -1075,8 +1068,7 @@ int team_solve(mi355cg_team_s* t, const mi355cg_params* prm, mi355cg_iter_cb cb,
     u64 seqB = seq_init;                                           // sequence number of the newest update records
     auto poll_fetch = [&]() -> int {
         HIPCK(hipSetDevice(lead.c->device));
-        HIPCK(hipMemcpyAsync(lead.c->summary_h, lead.c->summary, sizeof(CgState), hipMemcpyDeviceToHost, lead.c->stream));
-        HIPCK(hipMemcpyAsync(lead.c->hist_h, lead.c->hist, sizeof(HistEntry) * kHist, hipMemcpyDeviceToHost, lead.c->stream));
+        if (int rc = fetch_state(lead.c, lead.c->stream)) return rc;
         HIPCK(hipGetLastError());
         const int rc = bounded_sync(t, lead.c->stream, stop_flag, t->timeout_s + 2e-8 * (double)t->budget_ticks);
         if (rc < 0) return team_abandon(t, "the lead part's stream did not drain");
@@ -1120,18 +1112,16 @@ int team_solve(mi355cg_team_s* t, const mi355cg_params* prm, mi355cg_iter_cb cb,
         cb(user, 0, DBL_MAX, lead.c->summary_h->rmax, cfg.has_u ? lead.c->summary_h->emax : DBL_MAX);
     }
 
-    const int every = prm->callback_every;
-    int sync_every = std::min(prm->sync_every > 0 ? prm->sync_every : (msg ? 100 : 200), kHist);
+    const int sync_every = default_sync_every(prm, msg);
     int it_done = 0;
     // The chunk schedule is a function of the PARAMETERS only, so it is the same on every rank whatever callbacks or stop flags the
     // ranks were given: all ranks enqueue the same launches and collectives, poll after the same iterations and leave the loop at the
     // same poll.  (MSG rule with a callback cadence: the first iteration is a chunk of its own, so the it = 1 callback is delivered
     // -- and a stop requested from it seen -- before more work is queued.)
-    bool interrupted = false, first_chunk = msg && every > 0;
+    bool interrupted = false, first_chunk = msg && prm->callback_every > 0;
     const bool act_at_once = !t->rccl || t->world == 1;            // one process holds every part: nobody else to keep in step
-    if (!lead.c->ev_loop[0]) { HIPCK(hipEventCreate(&lead.c->ev_loop[0])); HIPCK(hipEventCreate(&lead.c->ev_loop[1])); }
     HIPCK(hipSetDevice(lead.c->device));
-    HIPCK(hipEventRecord(lead.c->ev_loop[0], lead.c->stream));
+    if (int rc = loop_timer_begin(lead.c, lead.c->stream)) return rc;
     while (!lead.c->summary_h->done) {
         // A stop request (msg_solver.cpp:82-87).  One process: act on it at once between chunks.  Always: raise the pinned word; it
         // travels with the next update record of this rank, every rank finds max(stop words) > 0 in the records of that iteration and
@@ -1139,10 +1129,8 @@ int team_solve(mi355cg_team_s* t, const mi355cg_params* prm, mi355cg_iter_cb cb,
         const bool want_stop = stop_flag && *stop_flag;
         if (want_stop && act_at_once) { interrupted = true; break; }
         if (want_stop) *t->stop_h = 1;
-        int m = std::min(sync_every, prm->max_iterations - it_done);
-        if (msg && every > 0) m = std::min(m, every - it_done % every);
-        if (first_chunk) { m = 1; first_chunk = false; }
-        if (m <= 0) m = 1;
+        const int m = chunk_len(prm, msg, sync_every, it_done, first_chunk);
+        first_chunk = false;
         if (crew) {
             if (int rc = crew->chunk(m, true, seqB)) return rc;
             seqB += m; t->seq = seqB;
@@ -1164,16 +1152,11 @@ int team_solve(mi355cg_team_s* t, const mi355cg_params* prm, mi355cg_iter_cb cb,
             return fail(MI355CG_ERR_STATE, "a part's record did not arrive within %.0f s (MI355CG_TEAM_TIMEOUT_MS): a peer stopped delivering.  The team cannot be used again", t->timeout_s);
         }
         const int it_now = lead.c->summary_h->it;
-        if (msg && cb) for (int it = it_done + 1; it <= it_now; ++it) {
-            const int reason = lead.c->summary_h->reason;
-            const bool stopped_here = lead.c->summary_h->done && reason != MI355CG_STOP_ITERATIONS && reason != MI355CG_STOP_INTERRUPTED && it == it_now;
-            const HistEntry& h = lead.c->hist_h[it % kHist];
-            if ((it == 1 || (every > 0 && it % every == 0)) && !stopped_here) cb(user, it, h.dmax, h.rmax, cfg.has_u ? h.emax : DBL_MAX);
-        }
+        replay_callbacks(cb, user, prm, *lead.c->summary_h, lead.c->hist_h, it_done, it_now, cfg.has_u, false);
         it_done = it_now;
     }
     HIPCK(hipSetDevice(lead.c->device));
-    HIPCK(hipEventRecord(lead.c->ev_loop[1], lead.c->stream));
+    if (int rc = loop_timer_end(lead.c, lead.c->stream)) return rc;
     const CgState fin = *lead.c->summary_h;
     if (fin.done && fin.reason == MI355CG_STOP_INTERRUPTED) interrupted = true;
     for (auto& p : t->parts) {
@@ -1207,16 +1190,9 @@ int team_solve(mi355cg_team_s* t, const mi355cg_params* prm, mi355cg_iter_cb cb,
         t->prof_wall_ms = 1e3 * wall / its;
         for (auto& p : t->parts) { p.c->profiling = false; p.c->events.reset(); p.c->ev_pairs[0].clear(); p.c->ev_pairs[1].clear(); }
     }
-    mi355cg_results res{};
-    res.iterations = fin.it;
-    res.converged = interrupted ? 0 : fin.converged;
-    res.stop_reason = interrupted ? MI355CG_STOP_INTERRUPTED : fin.reason;
-    res.final_residual_norm = fin.rmax;
-    res.final_precision = fin.it > 0 ? fin.dmax : DBL_MAX;
-    res.final_error_norm = cfg.has_u ? fin.emax : DBL_MAX;
-    res.r_norm2 = fin.rnorm2; res.initial_r_norm2 = fin.r0norm;
+    mi355cg_results res = make_results(fin, interrupted, cfg.has_u, fin.r0norm);
     res.solve_seconds = wall;
-    { float ms = 0; if (hipEventElapsedTime(&ms, lead.c->ev_loop[0], lead.c->ev_loop[1]) == hipSuccess) res.loop_seconds = 1e-3 * ms; }
+    res.loop_seconds = loop_timer_seconds(lead.c);
     if (msg && cb) cb(user, res.iterations, res.final_precision, res.final_residual_norm, res.final_error_norm);
     if (out) *out = res;
     return MI355CG_OK;
@@ -1365,12 +1341,7 @@ int team_solve_mixed(mi355cg_team_s* t, const mi355cg_params* prm, mi355cg_iter_
     }
     // nobody's next solve may write ghost cells a slower rank's last pass still reads
     if (int rc = team_meet(t, "the end of the mixed solve")) return rc;
-    mi355cg_results res{};
-    res.iterations = total; res.converged = converged ? 1 : 0;
-    res.stop_reason = interrupted ? MI355CG_STOP_INTERRUPTED : (converged ? MI355CG_STOP_RESIDUAL : MI355CG_STOP_ITERATIONS);
-    res.final_residual_norm = res.final_precision = res.final_error_norm = DBL_MAX;
-    res.r_norm2 = rnorm; res.initial_r_norm2 = bnorm;
-    res.refine_outer = outer; res.refine_true_rel = bnorm > 0 ? rnorm / bnorm : 0.0;
+    mi355cg_results res = make_mixed_results(total, interrupted, converged, rnorm, bnorm, outer);
     res.solve_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     res.loop_seconds = loop_s;
     if (out) *out = res;
