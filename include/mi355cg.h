@@ -31,6 +31,9 @@
  *   mi355cg_solve_batch            many right-hand sides on one grid by one preconditioned CG loop (host vectors)
  *   mi355cg_solve_batch_device     the same with the vectors in device memory
  *   mi355cg_batch_release          free the workspace the batched solves keep on the handle
+ *   mi355cg_set_shift / _get_shift the operator becomes A - sigma I (implicit time steps, screened Poisson, shift-and-invert)
+ *   mi355cg_time_steps             theta-scheme steps of u_t = A u - g with the state kept on the device
+ *   mi355cg_get_solution_device    the x of the last solve into device memory
  *
  * Plain pointers and sizes only; no C++/torch types.  All host vectors are in the reference's
  * PACKED unknown order (bottom-right block row-major, then the upper block row-major;
@@ -257,6 +260,46 @@ int  mi355cg_solve_batch_from(mi355cg_handle h, const mi355cg_params *params, in
                               const volatile int *stop_flag, mi355cg_results *out);
 int  mi355cg_solve_batch_device_from(mi355cg_handle h, const mi355cg_params *params, int nrhs, const double *b_dev, double *x_dev,
                                      const volatile int *stop_flag, mi355cg_results *out);
+
+/* ---- diagonal shift and implicit time steps (extension: the reference inverts the Laplacian only) ------------------------
+ * mi355cg_set_shift: while sigma is set the handle's operator is A - sigma I.  The stored diagonal is A_diag - sigma (one fp64
+ * rounding, on the host); x_k and y_k are unchanged; every multigrid level uses its own -2 (x_k,l + y_k,l) - sigma, the same sigma on
+ * every level, and the coarsest level's dense inverse is factored from the shifted matrix; the fp32 cycle rounds the shifted fp64
+ * constants to fp32.  Everything that applies the operator follows: mi355cg_apply / _apply_device / _get_true_residual,
+ * mi355cg_solve (both rules, diagnostics, fixed_iterations, the deferred x fold, graph replay), r0 = b - (A - sigma I) x0 of a warm
+ * start, mi355cg_apply_preconditioner, preconditioned CG of either kind and cycle, and the four mi355cg_solve_batch* entry points.
+ * sigma must be finite and >= 0 (the operator stays negative definite); anything else, a CSR handle (the caller owns that matrix), a
+ * slab / part handle (hence teams) and an MI355CG_F32_MIXED handle are refused with MI355CG_ERR_INVALID, the handle left as it was.
+ * set_shift(h, 0) gives bit for bit the handle that never had a shift.  A change of sigma drops the cached launch graphs of small
+ * grids and rebuilds the hierarchy's coefficients and coarse inverse in place (kind, cycle and level count are unchanged; if the
+ * rebuild fails, MI355CG_ERR_HIP, the old hierarchy and the old sigma stay).  The batch workspace stays: it holds vectors only.  The
+ * last x and r, the handle's b and u and a pending guess stay too; mi355cg_set_preconditioner* after mi355cg_set_shift builds the
+ * shifted hierarchy, and the two call orders give the same bits.  mi355cg_get_rhs, mi355cg_get_true_solution and the exact-error test
+ * of the MSG rule keep referring to the caller's or the generated vectors: whether u solves the shifted system is the caller's
+ * business.
+ * mi355cg_time_steps: nsteps steps of the theta scheme for u_t = A u - g, g = the handle's right-hand side at the time of the call
+ * (the steady state is the handle's Poisson problem); theta = 1 is implicit Euler, 0.5 Crank-Nicolson.  With sigma = 1 / (theta *
+ * tau) a step solves (A - sigma I) u+ = b_step, b_step = -sigma u - ((1 - theta) / theta) A u + g / theta (A unshifted), built by
+ * one kernel in one pass over u and g.  The state u is the handle's x: the starting state is the pending guess of
+ * mi355cg_set_initial_guess*, or of mi355cg_use_solution_as_initial_guess; without one, MI355CG_ERR_STATE.  Every step warm-starts
+ * from u in place through mi355cg_solve's own path, plain or preconditioned, with the warm start's semantics (REL_2NORM relative
+ * to ||b_step||_2, a start that meets the rule takes 0 iterations); no packed vector crosses PCIe between steps.  The shift is set
+ * to sigma if it is not already exactly sigma and is LEFT SET, so repeated calls with the same (tau, theta) pay the hierarchy
+ * rebuild once, and later solves on the handle see A - sigma I until mi355cg_set_shift(h, 0).  out[k] is step k's results.
+ * Stepping ends after the first step whose solve does not converge (iteration cap or stop request): *steps_done counts the converged
+ * steps, out[steps_done] describes the unfinished one, x holds its last iterate, and the call still returns MI355CG_OK.  One call
+ * with nsteps = k and k calls with nsteps = 1, each continued with mi355cg_use_solution_as_initial_guess, give the same bits.
+ * nsteps = 0 is MI355CG_OK and does nothing (it needs no starting state and leaves the shift alone).  Memory: one vector of the
+ * handle's storage size for b_step, allocated by the first call, freed by mi355cg_destroy; the handle's own b is bit for bit what
+ * it was.  MI355CG_ERR_INVALID, before anything is written: a null argument (stop_flag may be null), tau not finite or <= 0, theta
+ * outside (0, 1], nsteps < 0, params->diagnostics != 0 or use_true_solution != 0 (no callbacks, no per-step exact solution; note
+ * that mi355cg_default_params sets use_true_solution = 1), and the handles that refuse a shift.
+ * mi355cg_get_solution_device: mi355cg_get_solution into device memory of the handle's GPU (packed order), complete on return.   */
+int  mi355cg_set_shift(mi355cg_handle h, double sigma);
+int  mi355cg_get_shift(mi355cg_handle h, double *sigma);
+int  mi355cg_time_steps(mi355cg_handle h, const mi355cg_params *params, double tau, double theta, int nsteps,
+                        const volatile int *stop_flag, mi355cg_results *out /* nsteps */, int *steps_done);
+int  mi355cg_get_solution_device(mi355cg_handle h, double *x_dev);   /* packed, device memory of the handle's GPU */
 
 /* ---- measurement hooks (bench.py) ------------------------------------------------------------ */
 /* Per-kernel device time of the last mi355cg_solve, measured with HIP events on the solve

@@ -33,6 +33,7 @@ EXPORTS = [
     "mi355cg_solve_batch", "mi355cg_solve_batch_device", "mi355cg_batch_release", "mi355cg_get_xfold",
     "mi355cg_set_initial_guess", "mi355cg_set_initial_guess_device", "mi355cg_use_solution_as_initial_guess",
     "mi355cg_solve_batch_from", "mi355cg_solve_batch_device_from",
+    "mi355cg_set_shift", "mi355cg_get_shift", "mi355cg_time_steps", "mi355cg_get_solution_device",
 ]
 DECOMP_ROWS, DECOMP_2D = 0, 1
 PRECOND_NONE, PRECOND_MG, PRECOND_MG_ANY = 0, 1, 2
@@ -179,6 +180,11 @@ def load():
     L.mi355cg_use_solution_as_initial_guess.argtypes = [H]
     L.mi355cg_solve_batch_from.argtypes = [H, C.POINTER(Params), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Results)]
     L.mi355cg_solve_batch_device_from.argtypes = [H, C.POINTER(Params), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Results)]
+    # diagonal shift and the device-resident stepper
+    L.mi355cg_set_shift.argtypes = [H, C.c_double]
+    L.mi355cg_get_shift.argtypes = [H, DBP]
+    L.mi355cg_time_steps.argtypes = [H, C.POINTER(Params), C.c_double, C.c_double, C.c_int, C.c_void_p, C.POINTER(Results), IP]
+    L.mi355cg_get_solution_device.argtypes = [H, C.c_void_p]
     if hasattr(L, "mi355cg_get_xfold"):          # absent from an older build loaded through MI355CG_LIB
         L.mi355cg_get_xfold.argtypes = [H, IP, IP]
     _lib = L

@@ -9,6 +9,7 @@
 #include "mg_kernels.h"
 #include "mg_batch_kernels.h"
 #include "mg_kernels_f32.h"
+#include "step_kernels.h"
 
 #include <algorithm>
 #include <cfloat>
@@ -154,6 +155,10 @@ struct mi355cg_ctx {
     bool x_is_guess = false;            // x was overwritten by a guess since the last solve: x and r are not a solution and its residual
     double* guess_part = nullptr;       // (b, b) partial pairs of k_init_guess (hi, then lo, strideB each), then ||r0||_2 and ||b||_2 (k_guess_state)
     double* guess_norms_h = nullptr;    // pinned copy of those two norms
+    // Diagonal shift (mi355cg_set_shift): the operator is A - sigma I.  g.A = gp.A - sigma and every multigrid
+    // level's diagonal carry it; gp.A stays the Laplacian's.
+    double sigma = 0.0;
+    double* step_b = nullptr;           // mi355cg_time_steps: the right-hand side of a step, allocated by the first call
     // generic CSR handle (mi355cg_create_csr): vectors are plain length-n arrays, the operator is this matrix
     bool is_csr = false;
     long long csr_n = 0, csr_nnz = 0;
@@ -922,8 +927,9 @@ int mg_shape(int kind, int n, std::vector<int>* ns) {
     return MI355CG_OK;
 }
 
-// build_geom's storage layout for a whole grid of N intervals (base0 = 0) with the level's 5-point coefficients
-Geom mg_geom(int N, double hx, double hy, long long* len) {
+// build_geom's storage layout for a whole grid of N intervals (base0 = 0) with the level's 5-point coefficients, the diagonal
+// shifted by sigma
+Geom mg_geom(int N, double hx, double hy, double sigma, long long* len) {
     Geom g{};
     g.N = N; g.half = N / 2;
     g.Pu = (int)round_up(N + 1, 32); g.cb = g.half & ~31; g.Pb = g.Pu - g.cb;
@@ -931,7 +937,7 @@ Geom mg_geom(int N, double hx, double hy, long long* len) {
     g.y_lo = 1; g.y_hi = N - 1; g.base0 = 0;
     g.own_begin = phys_start(g, 1); g.own_len = phys_end(g, N - 1) - g.own_begin;
     g.xk = 1 / (hx * hx); g.yk = 1 / (hy * hy);               // grid_system.cpp:316-318 with the level's steps
-    g.A = -2 * (g.xk + g.yk);
+    g.A = -2 * (g.xk + g.yk) - sigma;                         // the same sigma on every level (mi355cg_set_shift); - 0.0 changes no bit
     *len = phys_end(g, N);
     return g;
 }
@@ -1016,7 +1022,7 @@ int mg_build(mi355cg_ctx* c, int kind, MgHier** out, int cycle = MI355CG_CYCLE_F
         MgLevel& L = H->lv[l];
         if (l > 0 && ns[l - 1] == 2 * ns[l]) { hx = std::ldexp(hx, 1); hy = std::ldexp(hy, 1); }   // nested: exactly doubled
         else if (l > 0) { hx = hx * ns[l - 1] / ns[l]; hy = hy * ns[l - 1] / ns[l]; }              // non-nested: same domain
-        L.g = mg_geom(ns[l], hx, hy, &L.len);
+        L.g = mg_geom(ns[l], hx, hy, c->sigma, &L.len);
         L.grid = std::min(L.g.N - 1, kMgMaxGrid);
         if (!f64) continue;                                     // the fp32 cycle has its own vectors (mg_build32)
         if (l > 0) { if (int rc = alloc_vec(&L.rhs, L.len)) return bail(rc); if (int rc = alloc_vec(&L.out, L.len)) return bail(rc); }
@@ -1729,6 +1735,7 @@ void mi355cg_destroy(mi355cg_handle c) {
     if (c->stop_h) hipHostFree(c->stop_h);
     if (c->guess_part) hipFree(c->guess_part);
     if (c->guess_norms_h) hipHostFree(c->guess_norms_h);
+    if (c->step_b) hipFree(c->step_b);
     clear_graphs(c);
     mg_batch_free(c);
     mg_free(c->mg);
@@ -2123,6 +2130,136 @@ int mi355cg_use_solution_as_initial_guess(mi355cg_handle c) {
     if (!c->solved || c->x_is_guess) return fail(MI355CG_ERR_STATE, "no solve has run on this handle: there is no solution to start from");
     c->x_is_guess = true;                                          // x is complete when a solve returns (k_fold_x / k_flush_x ran): nothing to flush
     c->guess_pending = true;
+    return MI355CG_OK;
+}
+
+// ---- diagonal shift and implicit time steps ---------------------------------------------------------------
+// what a shift, and with it the stepper, refuses: the handles whose operator is not the single-GPU fp64 grid stencil
+static int shift_check(mi355cg_ctx* c) {
+    if (!c) return fail(MI355CG_ERR_INVALID, "null handle");
+    if (c->is_csr) return fail(MI355CG_ERR_INVALID, "a shift changes the grid operator's diagonal: a CSR handle's matrix is the caller's");
+    if (c->is_slab) return fail(MI355CG_ERR_INVALID, "a shift is single-GPU only: this handle owns one part of a decomposed grid");
+    if (c->dtype != MI355CG_F64) return fail(MI355CG_ERR_INVALID, "a shift is fp64 only: this handle was created with MI355CG_F32_MIXED");
+    return MI355CG_OK;
+}
+
+// The operator becomes A - sigma I.  Everything that can fail (the upload of the refactored coarse inverse) happens before the
+// handle is touched, so a failure leaves the old hierarchy and the old sigma.
+int mi355cg_set_shift(mi355cg_handle c, double sigma) {
+    if (int rc = shift_check(c)) return rc;
+    if (!std::isfinite(sigma) || sigma < 0.0) return fail(MI355CG_ERR_INVALID, "shift %g rejected: sigma must be finite and >= 0 (A - sigma I stays negative definite)", sigma);
+    if (sigma == c->sigma) return MI355CG_OK;
+    HIPCK(hipSetDevice(c->device));
+    HIPCK(hipStreamSynchronize(c->stream));                        // nothing in flight reads the coefficients or the inverse
+    if (MgHier* H = c->mg) {
+        Geom gc = H->lv.back().g;
+        gc.A = -2 * (gc.xk + gc.yk) - sigma;
+        std::vector<double> inv;
+        std::vector<int> off;
+        mg_coarse_inverse(gc, inv, off);                           // off: the layout's, unchanged
+        void* fresh = nullptr;
+        if (H->cycle == MI355CG_CYCLE_F32) {
+            std::vector<float> inv32(inv.begin(), inv.end());
+            if (hipMalloc(&fresh, sizeof(float) * inv32.size()) != hipSuccess ||
+                hipMemcpy(fresh, inv32.data(), sizeof(float) * inv32.size(), hipMemcpyHostToDevice) != hipSuccess) {
+                if (fresh) hipFree(fresh);
+                (void)hipGetLastError();
+                return fail(MI355CG_ERR_HIP, "coarse inverse upload failed: the shift stays %g", c->sigma);
+            }
+            hipFree(H->inv32); H->inv32 = (float*)fresh;
+        } else {
+            if (hipMalloc(&fresh, sizeof(double) * inv.size()) != hipSuccess ||
+                hipMemcpy(fresh, inv.data(), sizeof(double) * inv.size(), hipMemcpyHostToDevice) != hipSuccess) {
+                if (fresh) hipFree(fresh);
+                (void)hipGetLastError();
+                return fail(MI355CG_ERR_HIP, "coarse inverse upload failed: the shift stays %g", c->sigma);
+            }
+            hipFree(H->inv); H->inv = (double*)fresh;
+        }
+        for (size_t l = 0; l < H->lv.size(); ++l) {
+            Geom& g = H->lv[l].g;
+            g.A = -2 * (g.xk + g.yk) - sigma;                      // mg_geom's expression
+            if (l < H->lv32.size()) H->lv32[l].c.A = (float)g.A;
+        }
+    }
+    c->sigma = sigma;
+    c->g.A = c->gp.A - sigma;
+    c->pg.g.A = c->g.A;
+    clear_graphs(c);                                               // their kernel arguments hold the old Geom
+    return MI355CG_OK;
+}
+
+int mi355cg_get_shift(mi355cg_handle c, double* sigma) {
+    if (!c || !sigma) return fail(MI355CG_ERR_INVALID, "null argument");
+    *sigma = c->sigma;
+    return MI355CG_OK;
+}
+
+int mi355cg_get_solution_device(mi355cg_handle c, double* x_dev) {
+    if (!c || !x_dev) return fail(MI355CG_ERR_INVALID, "null argument");
+    if (c->x_is_guess) return fail(MI355CG_ERR_STATE, "an initial guess was set after the last solve: x holds the guess, not a solution");
+    if (!c->solved) return fail(MI355CG_ERR_STATE, "no solve has run on this handle");
+    HIPCK(hipSetDevice(c->device));
+    if (c->is_csr) {
+        HIPCK(hipMemcpyAsync(x_dev, c->x, sizeof(double) * c->pk_len, hipMemcpyDeviceToDevice, c->stream));
+    } else {
+        if (c->is_slab) HIPCK(hipDeviceSynchronize());
+        if (c->pk_len > 0) hipLaunchKernelGGL((k_pack<double>), dim3(flat_grid(c->pk_len)), dim3(kBlock), 0, c->stream, c->pg, (const double*)c->x, x_dev);
+        HIPCK(hipGetLastError());
+    }
+    HIPCK(hipStreamSynchronize(c->stream));
+    return MI355CG_OK;
+}
+
+// b_step = g / theta - sigma u - ((1 - theta) / theta) A u from the state u = x and the handle's g = b, into step_b
+static void launch_step_rhs(mi355cg_ctx* c, double sigma, double theta) {
+    StepRhsArgs a{};
+    a.g = c->g;
+    a.A0 = c->gp.A; a.xk = c->gp.x_k; a.yk = c->gp.y_k;
+    a.sigma = sigma; a.theta = theta; a.c1 = (1.0 - theta) / theta;
+    a.u = c->x; a.rhs = c->b; a.out = c->step_b;
+    a.tiles_per_row = (c->g.N + kStepTileCols) / kStepTileCols;                    // columns 0 .. N
+    a.tiles = (long long)(c->g.N - 1) * a.tiles_per_row;
+    const int grid = (int)std::min<long long>(a.tiles, 1 << 20);
+    if (theta < 1.0) hipLaunchKernelGGL((k_step_rhs<true>), dim3(grid), dim3(kBlock), 0, c->stream, a);
+    else hipLaunchKernelGGL((k_step_rhs<false>), dim3(grid), dim3(kBlock), 0, c->stream, a);
+}
+
+// nsteps steps of the theta scheme for u_t = A u - g, the state in x, no packed vector over PCIe.  Each step is mi355cg_solve's warm
+// start on the handle with the step's right-hand side in the place of b; the handle's own b is never written.
+int mi355cg_time_steps(mi355cg_handle c, const mi355cg_params* prm, double tau, double theta, int nsteps,
+                       const volatile int* stop_flag, mi355cg_results* out, int* steps_done) {
+    if (!c || !prm || !out || !steps_done) return fail(MI355CG_ERR_INVALID, "null argument");
+    if (int rc = shift_check(c)) return rc;
+    if (!std::isfinite(tau) || !(tau > 0.0)) return fail(MI355CG_ERR_INVALID, "time step %g rejected: tau must be finite and > 0", tau);
+    if (!(theta > 0.0 && theta <= 1.0)) return fail(MI355CG_ERR_INVALID, "theta %g rejected: the scheme needs 0 < theta <= 1", theta);
+    if (nsteps < 0) return fail(MI355CG_ERR_INVALID, "nsteps %d rejected: it must be >= 0", nsteps);
+    if (prm->rule != MI355CG_RULE_MSG_MAXNORM && prm->rule != MI355CG_RULE_REL_2NORM) return fail(MI355CG_ERR_INVALID, "unknown rule %d", prm->rule);
+    if (prm->diagnostics) return fail(MI355CG_ERR_INVALID, "the stepper has no callbacks: diagnostics must be 0");
+    if (prm->use_true_solution) return fail(MI355CG_ERR_INVALID, "a step has no exact solution: use_true_solution must be 0");
+    const double sigma = 1.0 / (theta * tau);
+    if (!std::isfinite(sigma)) return fail(MI355CG_ERR_INVALID, "time step %g rejected: 1 / (theta tau) is not finite", tau);
+    if (nsteps == 0) { *steps_done = 0; return MI355CG_OK; }
+    if (!c->guess_pending) return fail(MI355CG_ERR_STATE, "no starting state: set it with mi355cg_set_initial_guess* or mi355cg_use_solution_as_initial_guess");
+    *steps_done = 0;
+    HIPCK(hipSetDevice(c->device));
+    if (!c->step_b) {
+        if (int rc = alloc_vec(&c->step_b, c->storage_len)) { (void)hipGetLastError(); c->step_b = nullptr; return rc; }
+        HIPCK(hipDeviceSynchronize());                             // the zero-fill ran on the NULL stream
+    }
+    if (int rc = mi355cg_set_shift(c, sigma)) return rc;           // a no-op when it is already exactly sigma
+    for (int k = 0; k < nsteps; ++k) {
+        if (k > 0) { c->x_is_guess = true; c->guess_pending = true; }     // mi355cg_use_solution_as_initial_guess
+        launch_step_rhs(c, sigma, theta);
+        HIPCK(hipGetLastError());
+        double* const own_b = c->b;
+        c->b = c->step_b;
+        const int rc = mi355cg_solve(c, prm, nullptr, nullptr, stop_flag, &out[k]);
+        c->b = own_b;
+        if (rc) return rc;
+        if (!out[k].converged) break;                              // the iteration cap or a stop request: x holds that step's last iterate
+        ++*steps_done;
+    }
     return MI355CG_OK;
 }
 

@@ -168,6 +168,36 @@ class _Handle:
         its iteration cap this continues it (mi355cg_use_solution_as_initial_guess)."""
         self._guess_rc(self._lib.mi355cg_use_solution_as_initial_guess(self._h))
 
+    def set_shift(self, sigma: float):
+        """Extension (no reference twin): the handle's operator becomes A - sigma I, for apply(), every solve, the preconditioner
+        and the batched solves (mi355cg_set_shift).  sigma is finite and >= 0; 0 restores the Laplacian bit for bit.  ValueError
+        if refused (a bad sigma; CSR, slab and F32_MIXED handles); the handle then keeps what it had."""
+        self._guess_rc(self._lib.mi355cg_set_shift(self._h, float(sigma)))
+
+    def get_shift(self) -> float:
+        s = C.c_double()
+        _capi.check(self._lib.mi355cg_get_shift(self._h, C.byref(s)))
+        return s.value
+
+    def solution_device(self, out):
+        """The x of the last solve into `out`, a contiguous CUDA float64 tensor [size] on the handle's device
+        (mi355cg_get_solution_device); complete on return."""
+        _capi.check(self._lib.mi355cg_get_solution_device(self._h, out.data_ptr()))
+        return out
+
+    def time_steps(self, params: _capi.Params, tau: float, theta: float, nsteps: int, stop_flag: Optional[C.c_int] = None):
+        """nsteps theta-scheme steps of u_t = A u - g from the pending starting state (mi355cg_time_steps).  Returns
+        ([Results of the steps taken, the unfinished one included], steps_done)."""
+        n = int(nsteps)
+        res = (_capi.Results * max(n, 1))()
+        done = C.c_int(0)
+        sp = C.cast(C.pointer(stop_flag), C.c_void_p) if stop_flag is not None else None
+        rc = self._lib.mi355cg_time_steps(self._h, C.byref(params), float(tau), float(theta), n, sp, res, C.byref(done))
+        if rc == _capi.ERR_INVALID:
+            raise ValueError(self._lib.mi355cg_last_error().decode())
+        _capi.check(rc)
+        return list(res[:min(n, done.value + 1)]), done.value
+
     def solve(self, params: _capi.Params, callback=None, stop_flag: Optional[C.c_int] = None) -> _capi.Results:
         res = _capi.Results()
         cb = _capi.ITER_CB(lambda user, it, p, r, e: callback(it, p, r, e)) if callback else _capi.ITER_CB()
@@ -353,6 +383,45 @@ class MatrixFreeSystem:
     def preconditioner_info(self):
         """(kind, cycle, levels) of the preconditioner that is set; (PRECOND_NONE, CYCLE_F64, 0) without one."""
         return self._handle.preconditioner_info()
+
+    def set_shift(self, sigma: float):
+        """Extension (no reference twin): this system's operator becomes A - sigma I (sigma finite, >= 0) for apply() and for every
+        solver built on it, preconditioned and batched solves included; 0 restores the Laplacian bit for bit."""
+        self._handle.set_shift(sigma)
+
+    @property
+    def shift(self) -> float:
+        """The sigma that is set (0.0 without one)."""
+        return self._handle.get_shift()
+
+    def time_steps(self, u0, tau: float, theta: float = 1.0, nsteps: int = 1, eps: float = 1e-8, max_iterations: int = 10000,
+                   rule: int = _capi.RULE_REL_2NORM, params=None):
+        """Extension (no reference twin): nsteps steps of the theta scheme (1: implicit Euler, 0.5: Crank-Nicolson) for
+        u_t = A u - g from the state u0, g = this system's right-hand side as it stands; the state stays on the device between
+        steps and every step warm-starts from the previous one (mi355cg_time_steps).  The shift is left at 1 / (theta * tau).
+        u0: NumPy [size()] float64 or a contiguous CUDA torch tensor; returns (u of u0's kind, [Results per step taken],
+        steps_done).  Stepping ends after the first step that does not converge; u is then that step's last iterate.  eps,
+        max_iterations, rule as in solve_batch; params, if given, is used as it is (use_true_solution and diagnostics 0)."""
+        h = self._handle
+        on_device = h._check_guess(u0, h.size)
+        if params is None:
+            params = default_params(rule)
+            params.max_iterations = max_iterations
+            params.eps_rel = params.eps_precision = params.eps_residual = eps
+            params.use_true_solution = 0
+        h.set_initial_guess(u0)
+        try:
+            res, done = h.time_steps(params, tau, theta, nsteps)
+        except Exception:
+            h.set_initial_guess(None)                             # a refused call takes no state with it
+            raise
+        if int(nsteps) == 0:
+            h.set_initial_guess(None)
+            return (u0.clone() if on_device else np.array(u0, dtype=np.float64, copy=True)), res, done
+        if on_device:
+            import torch
+            return h.solution_device(torch.empty_like(u0)), res, done
+        return h.solution(), res, done
 
     def solve_batch(self, b, eps: float = 1e-6, max_iterations: int = 10000, rule: int = _capi.RULE_REL_2NORM, params=None, x0=None):
         """Extension (no reference twin): many right-hand sides on this grid by one multigrid-preconditioned CG loop (needs
