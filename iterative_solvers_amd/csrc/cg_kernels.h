@@ -22,16 +22,13 @@
 #include <cfloat>
 #include <cmath>
 #include "solve_loop.h"               // CgState, HistEntry, kHist, kRing: what the host loop reads back
+#include "item_table.h"               // kBlock, kWave, kWaves; Panel, WorkList (host); ItemDesc, ItemSeq: the tables the kernels read
 
 namespace mi355cg {
 
-constexpr int kBlock = 256;           // threads per workgroup = 4 wave64
-constexpr int kWave = 64;
-constexpr int kWaves = kBlock / kWave;
-constexpr int kMaxPanels = 8;
-
 // ---- per-wave timing probe (diagnostic build only: -DMI355CG_WAVE_TIMING, tools/wave_timing.py) -------------------
-// Every wave of the two iteration kernels records wall_clock64() (100 MHz) at entry, after the prologue and at exit.
+// Every wave of the two iteration kernels records wall_clock64() (100 MHz) at entry (before its item sequence is fetched), when
+// the state is there (1), after reduce + decide (2), after the first DEPTH rows are requested (3), after the prologue and at exit.
 #ifdef MI355CG_WAVE_TIMING
 constexpr int kWtWaves = 16384, kWtStamps = 6;
 __device__ unsigned long long g_wave_dbg[2][kWtStamps * kWtWaves];
@@ -69,32 +66,6 @@ __host__ __device__ inline bool node_interior(const Geom& g, int x, int y) {
     return y >= 1 && y <= g.N - 1 && x <= g.N - 1 && x >= (y <= g.half ? g.half + 1 : 1);
 }
 
-// A panel is a rectangle of owned rows x column strips, cut into row chunks; one (chunk, strip)
-// pair is one work item = one wave marching `ty` rows of a 64*VEC-column strip.
-// gc (2-D decomposition): bit 0 = the column left of the panel's first strip belongs to another part (a ghost
-// column of this part), bit 1 = the same on the right of its last strip.
-struct Panel { int y0, y1, s0, ns, ty, nchunks, item0, gc; };
-// XCD classes: workgroups land on XCD blockIdx % 8, and every XCD has its own L2.  With ncls == 8 the items are cut into
-// eight contiguous ranges [cls0[k], cls0[k+1]) -- whole bands of chunk rows -- and range k is served by the workgroups with
-// blockIdx % 8 == k only: the strips left and right of a workgroup (whose edge columns it reads) and the chunk rows above and
-// below (whose halo rows it reads) are then work of the SAME XCD and those reads hit its L2 instead of going to the fabric
-// (PMC: read traffic of the stencil launch 1.10 x -> see profiles/r02_tune_notes.md).  A wrong guess about the placement costs
-// those hits, never correctness.
-constexpr int kXcds = 8;
-struct WorkList { Panel p[kMaxPanels]; int np; int nitems; int ncls; int cls0[kXcds + 1]; };
-// the item indices a wave takes: first, first + step, ... < end
-struct ItemSeq { int first, step, begin, end; };
-__device__ inline ItemSeq item_seq(const WorkList& wl, int wave) {
-    if (wl.ncls == kXcds) {
-        const int cls = blockIdx.x % kXcds, nb = (gridDim.x - cls + kXcds - 1) / kXcds;
-        int begin = wl.cls0[0], end = wl.cls0[1];
-#pragma unroll
-        for (int k = 1; k < kXcds; ++k) if (k == cls) { begin = wl.cls0[k]; end = wl.cls0[k + 1]; }     // constant indices only
-        return ItemSeq{begin + (int)(blockIdx.x / kXcds) * kWaves + wave, nb * kWaves, begin, end};
-    }
-    return ItemSeq{(int)blockIdx.x * kWaves + wave, (int)gridDim.x * kWaves, 0, wl.nitems};
-}
-
 // What every wave needs from the state, fetched with SCALAR loads (s_load through the constant address space, one
 // request per scalar cache instead of one per wave).  Copying the whole struct made hipcc fetch half of it with
 // per-lane global loads of one address: ~4000 waves x 3 loads of the same line queued at one L2 channel and the
@@ -105,6 +76,18 @@ struct StateLite { double alpha, rr, rr_prev, rz, r0norm; int it, done, first, s
 template <typename V> __device__ inline V scalar_load(const V* p) {
     return *(const __attribute__((address_space(4))) V*)p;
 }
+// The two tables of a launch shape (item_table.h), in device memory and never written while a handle lives: one ItemDesc per
+// item index, one ItemSeq per wave of the launch.  A wave fetches its entry with ONE 16-byte scalar load at a wave-uniform
+// index.  (The panel list used to travel by value: 856 bytes of kernel arguments that every wave searched through a chain of
+// some 60 dependent scalar loads, three times, before it could request its first row; profiles/launch_head.txt.)
+struct ItemTab { const ItemDesc* items; const ItemSeq* seq; int nitems; };
+typedef int int4_t __attribute__((ext_vector_type(4)));
+template <typename V> __device__ inline V scalar_load16(const V* p) {         // one s_load_dwordx4
+    static_assert(sizeof(V) == 16 && alignof(V) == 16, "scalar_load16: a 16-byte entry");
+    return __builtin_bit_cast(V, scalar_load(reinterpret_cast<const int4_t*>(p)));
+}
+__device__ inline ItemSeq item_seq(const ItemTab& t, int wave) { return scalar_load16(t.seq + (blockIdx.x * kWaves + wave)); }
+
 // State object -> state object, by the one thread of the grid that forwards it.  Not inlined: hipcc otherwise hoists
 // the loads in front of the branch that selects that thread, and every wave of the grid fetches all 128 bytes.
 __device__ __attribute__((noinline)) void copy_state(CgState* dst, const CgState* src) { *dst = *src; }
@@ -582,7 +565,7 @@ __device__ inline int queue_take(int* q, int lane) {
 template <typename T>
 struct StencilArgs {
     Geom g;
-    WorkList wl;
+    ItemTab tab;
     const T* r;          // FUSED: residual (with ghost rows / columns); PLAIN: unused
     const T* pin;        // FUSED: previous direction; PLAIN: the vector to apply the operator to
     T* pout;             // FUSED: new direction (ping-pong partner of pin)
@@ -672,21 +655,23 @@ template <typename T, int VEC> __device__ inline int edge_off(const Geom& g, int
 // of one round therefore work inside one compact band of rows: at N = 16384 / 32768, where a row is 131 / 262 KB, that
 // keeps concurrent accesses within a few MB per stream and measured +17-18 % over 2 048 independent waves each marching
 // one tall item down the whole grid (tools/hbm_probe.hip, profiles/r02_hbm_probe_*.txt).
-struct Item { int strip, ya, yb, gc; };
-__device__ inline Item decode_item(const WorkList& wl, int item) {
-    // constant indices only: a run-time index into the by-value argument struct makes hipcc spill the whole work
-    // list into per-thread LDS
-    Panel P = wl.p[0];
-#pragma unroll
-    for (int k = 1; k < kMaxPanels; ++k) if (k < wl.np && item >= wl.p[k].item0) P = wl.p[k];
-    const int local = item - P.item0;
-    const int chunk = local / P.ns;
-    Item it;
-    it.strip = P.s0 + (local - chunk * P.ns);
-    it.ya = P.y0 + chunk * P.ty;
-    it.yb = min(P.y1, it.ya + P.ty - 1);
-    it.gc = (it.strip == P.s0 ? (P.gc & 1) : 0) | (it.strip == P.s0 + P.ns - 1 ? (P.gc & 2) : 0);
-    return it;
+typedef ItemDesc Item;
+__device__ inline Item decode_item(const ItemTab& t, int item) { return scalar_load16(t.items + item); }      // item: wave-uniform, in [0, nitems)
+
+// prefetch_parts / prefetch_max through range-checked buffer loads: a thread beyond `n` carries an out-of-range offset and gets 0,
+// so the loads stand in no exec-masked region.  The lean prologues issue them BEFORE the first row requests -- vector memory
+// results return in order, so the wait for them is a counted vmcnt(N) that leaves the rows in flight.  lo_off: bytes from the hi
+// words of a field to its lo words.
+__device__ inline int part_voff(int i, int n, int es) { return i < n ? i * es * (int)sizeof(double) : kOob; }
+__device__ inline PreParts prefetch_parts_buf(rsrc_t rs, int field_off, int lo_off, int n, int es) {
+    const int v0 = part_voff(threadIdx.x, n, es), v1 = part_voff(threadIdx.x + kBlock, n, es);
+    PreParts p;
+    p.hi0 = buf_load<double>(rs, v0, field_off); p.lo0 = buf_load<double>(rs, v0, field_off + lo_off);
+    p.hi1 = buf_load<double>(rs, v1, field_off); p.lo1 = buf_load<double>(rs, v1, field_off + lo_off);
+    return p;
+}
+__device__ inline PreMax prefetch_max_buf(rsrc_t rs, int field_off, int n, int es) {
+    return PreMax{buf_load<double>(rs, part_voff(threadIdx.x, n, es), field_off), buf_load<double>(rs, part_voff(threadIdx.x + kBlock, n, es), field_off)};
 }
 
 // Addressing data of one work item, constant while the item is marched (wave-uniform unless noted).  It is computed
@@ -729,7 +714,11 @@ __device__ inline ItemAddr item_addr(const Geom& g, const Item& it, int lane) {
 // NOAP: A p is only reduced into (Ap, p), not stored -- the update phase recomputes it from the stored direction.
 // GC (2-D decomposition): the strips at the left / right end of this part also store the new direction of the ghost
 // COLUMN beside them (the edge lanes compute it anyway), so the direction never crosses ranks in x either.
-template <typename T, int VEC, bool FUSED, bool MSG, int DEPTH, bool NOAP, bool GC>
+// TEAM: the launch belongs to a team (csrc/team.h): the other parts' records are gathered in the prologue and the partials also go
+// out flagged.  QUEUE: the items may come from the run-time queues (QueueSpec).  The launchers choose both from what they know
+// (the records' mailbox, the flag spec, the queue counters); a single-context static-deal launch gets code without either path
+// -- no record array in LDS, no polling loops, no ticket atomic in the march -- and a prologue in another order (LEAN below).
+template <typename T, int VEC, bool FUSED, bool MSG, int DEPTH, bool NOAP, bool GC, bool TEAM, bool QUEUE>
 __global__ __launch_bounds__(kBlock) void k_stencil(const StencilArgs<T> a) {
     static_assert(DEPTH >= 1 && DEPTH <= 3, "the compute cursor takes its item from the fetch cursor: DEPTH <= rows fetched per item (>= 3)");
     typedef typename VecOf<T, VEC>::type vec_t;
@@ -737,9 +726,26 @@ __global__ __launch_bounds__(kBlock) void k_stencil(const StencilArgs<T> a) {
     const Geom& g = a.g;
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);   // wave-uniform -> SGPR item decode
-    const ItemSeq seq = item_seq(a.wl, wave);
     MI355CG_WT_BEGIN
+    const ItemSeq seq = item_seq(a.tab, wave);
     struct Raw { vec_t r, p; T re, pe; };
+
+    // LEAN prologue order: the small loads first.  The state (scalar loads) and this thread's two partial pairs are requested
+    // before the rows, so they are not queued behind a chip-wide burst of row loads, and the reduction runs while the rows land.
+    constexpr bool LEAN = FUSED && !TEAM;
+    StateLite s_lean{};
+    PreParts pre_lean{0.0, 0.0, 0.0, 0.0};
+    PreMax pmax_lean[3] = {{0, 0}, {0, 0}, {0, 0}};
+    if (LEAN) {
+        s_lean = load_state_lite(a.s_in);
+        const rsrc_t rs_part = make_rsrc(a.partB);
+        const int fb = a.strideB * (int)sizeof(double);
+        pre_lean = prefetch_parts_buf(rs_part, FB_RR * fb, FB_LO * fb, a.nB, a.esB);
+        if (MSG) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) pmax_lean[k] = prefetch_max_buf(rs_part, (FB_RMAX + k) * fb, a.nB, a.esB);
+        }
+    }
 
     // ---- fetch cursor ----
     int f_item = seq.first;
@@ -748,19 +754,19 @@ __global__ __launch_bounds__(kBlock) void k_stencil(const StencilArgs<T> a) {
     int f_idx = 0, f_so = 0, f_y = 0;
     rsrc_t rs_p = make_rsrc(a.pin), rs_r = make_rsrc(a.pin);
     const int dq_nsub = min(kQueueSubs, (int)(gridDim.x / kXcds)), dq_sub = (int)(blockIdx.x / kXcds) % dq_nsub;      // (every sub-group has a workgroup)
-    int* const dq = a.dq.mine ? a.dq.mine + ((int)(blockIdx.x % kXcds) * kQueueSubs + dq_sub) * kQueuePitch : nullptr;
-    if (a.dq.other && blockIdx.x == 0 && threadIdx.x < kXcds * kQueueSubs) a.dq.other[threadIdx.x * kQueuePitch] = 0;
+    int* const dq = (QUEUE && a.dq.mine) ? a.dq.mine + ((int)(blockIdx.x % kXcds) * kQueueSubs + dq_sub) * kQueuePitch : nullptr;
+    if (QUEUE && a.dq.other && blockIdx.x == 0 && threadIdx.x < kXcds * kQueueSubs) a.dq.other[threadIdx.x * kQueuePitch] = 0;
     int dq_ticket = 0;                                          // lane 0: this wave's next ticket of its group's queue
     auto enter = [&](int item) {
-        if (dq) dq_ticket = queue_take(dq, lane);               // asked for now, needed at the next switch
-        F = item_addr<T, VEC, false>(g, decode_item(a.wl, item), lane);
+        if (QUEUE && dq) dq_ticket = queue_take(dq, lane);      // asked for now, needed at the next switch
+        F = item_addr<T, VEC, false>(g, decode_item(a.tab, item), lane);
         rs_p = make_rsrc(a.pin + F.base_el);
         rs_r = make_rsrc(FUSED ? a.r + F.base_el : a.pin + F.base_el);
         f_idx = -1; f_so = F.so_first; f_y = F.ystart - 1;
     };
     auto fetch = [&]() -> Raw {
         if (f_have && f_idx > F.nrows) {                         // lazily: the compute cursor may still need F (see promote)
-            f_item = dq ? seq.begin + seq.step + __builtin_amdgcn_readfirstlane(dq_ticket) * dq_nsub + dq_sub : f_item + seq.step;
+            f_item = (QUEUE && dq) ? seq.begin + seq.step + __builtin_amdgcn_readfirstlane(dq_ticket) * dq_nsub + dq_sub : f_item + seq.step;
             f_have = f_item < seq.end;
             if (f_have) enter(f_item);
         }
@@ -806,9 +812,19 @@ __global__ __launch_bounds__(kBlock) void k_stencil(const StencilArgs<T> a) {
     Raw q[DEPTH];
 #pragma unroll
     for (int k = 0; k < DEPTH; ++k) q[k] = fetch();
+    MI355CG_WT_STAMP(3)
 
     T beta = (T)0;
-    if (FUSED && a.src.mbox) {
+    if (LEAN) {
+        const StateLite& s = s_lean;
+        if (s.done) { if (blockIdx.x == 0 && threadIdx.x == 0) copy_state(a.s_out, a.s_in); return; }
+        MI355CG_WT_STAMP(1)
+        const Decision d = reduce_and_decide(s, a.rp, a.partB, a.nB, a.strideB, a.esB, a.want_diag, lds, &pre_lean, MSG ? pmax_lean : nullptr);
+        MI355CG_WT_STAMP(2)
+        if (blockIdx.x == 0 && threadIdx.x == 0) write_state_after_decision(a.s_out, a.hist, a.s_in, s, d);
+        if (d.done) return;
+        beta = (T)d.beta;
+    } else if (FUSED && a.src.mbox) {
         // team: this part's share of the sums comes from its own partials (as on a single GPU), the other parts' from their records
         __shared__ double recs[kMaxRecDst * kRecWords];
         const PreParts pre = prefetch_parts(a.partB + FB_RR * a.strideB, a.partB + (FB_RR + FB_LO) * a.strideB, a.nB, 1);
@@ -923,7 +939,7 @@ __global__ __launch_bounds__(kBlock) void k_stencil(const StencilArgs<T> a) {
         const int b = a.slotA + blockIdx.x, st = a.strideA;
         a.partA[FA_PAP * st + b] = tp.hi; a.partA[(FA_PAP + FA_LO) * st + b] = tp.lo;
         a.partA[FA_RZ * st + b] = tz.hi;  a.partA[(FA_RZ + FA_LO) * st + b] = tz.lo;
-        if (FUSED && a.fl.part) { const double v[FA_COUNT] = {tp.hi, tz.hi, tp.lo, tz.lo}; store_flagged(a.fl, b, FA_COUNT, v); }     // field order FA_*
+        if (FUSED && TEAM && a.fl.part) { const double v[FA_COUNT] = {tp.hi, tz.hi, tp.lo, tz.lo}; store_flagged(a.fl, b, FA_COUNT, v); }     // field order FA_*
     }
 }
 
@@ -1191,7 +1207,7 @@ __global__ __launch_bounds__(kBlock) void k_guess_state(const double* partB, int
 template <typename T>
 struct UpdateStArgs {
     Geom g;
-    WorkList wl;
+    ItemTab tab;
     const T* p;          // current direction, ghost rows / columns valid
     const T* pprev[kRing - 1];   // XM >= 2: the directions of the 1, 2, ... iterations before (the other buffers of the ring)
     T* r; T* x; const T* u;
@@ -1209,7 +1225,8 @@ struct UpdateStArgs {
     int fold_mask;
 };
 
-template <typename T, int VEC, int XM, bool HAS_U, int DEPTH, bool DESC>
+// TEAM, QUEUE: see k_stencil.
+template <typename T, int VEC, int XM, bool HAS_U, int DEPTH, bool DESC, bool TEAM, bool QUEUE>
 __global__ __launch_bounds__(kBlock) void k_update_st(const UpdateStArgs<T> a) {
     static_assert(DEPTH >= 1 && DEPTH <= 3, "see k_stencil");
     typedef typename VecOf<T, VEC>::type vec_t;
@@ -1217,8 +1234,8 @@ __global__ __launch_bounds__(kBlock) void k_update_st(const UpdateStArgs<T> a) {
     const Geom& g = a.g;
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
-    const ItemSeq seq = item_seq(a.wl, wave);
     MI355CG_WT_BEGIN
+    const ItemSeq seq = item_seq(a.tab, wave);
     // the stop request (a pinned HOST word) is sampled once per iteration by block 0 -- a scalar load issued here and consumed
     // in the epilogue, so its PCIe round trip runs under the whole launch
     int stop_word = 0;
@@ -1226,6 +1243,17 @@ __global__ __launch_bounds__(kBlock) void k_update_st(const UpdateStArgs<T> a) {
     constexpr bool FULL = XM == 1;
     constexpr int NP = XM >= 2 ? XM - 1 : 0;          // earlier directions folded into this launch's x update
     struct Raw { vec_t p, r, x, u, pp[NP > 0 ? NP : 1]; T pe; };
+
+    // the small loads first (see k_stencil): state and this thread's partial pairs, before the rows
+    StateLite s{};
+    PreParts pre_lean{0.0, 0.0, 0.0, 0.0}, pre_rz_lean{0.0, 0.0, 0.0, 0.0};
+    if (!TEAM) {
+        s = load_state_lite(a.s_in);
+        const rsrc_t rs_part = make_rsrc(a.partA);
+        const int fa = a.strideA * (int)sizeof(double);
+        pre_lean = prefetch_parts_buf(rs_part, FA_PAP * fa, FA_LO * fa, a.nA, a.esA);
+        if (FULL) pre_rz_lean = prefetch_parts_buf(rs_part, FA_RZ * fa, FA_LO * fa, a.nA, a.esA);
+    }
 
     // ---- fetch cursor (see k_stencil) ----
     int f_item = seq.first;
@@ -1235,12 +1263,12 @@ __global__ __launch_bounds__(kBlock) void k_update_st(const UpdateStArgs<T> a) {
     rsrc_t rs_p = make_rsrc(a.p), rs_r = rs_p, rs_x = rs_p, rs_u = rs_p;
     rsrc_t rs_pp[NP > 0 ? NP : 1] = {rs_p};
     const int dq_nsub = min(kQueueSubs, (int)(gridDim.x / kXcds)), dq_sub = (int)(blockIdx.x / kXcds) % dq_nsub;      // (every sub-group has a workgroup)
-    int* const dq = a.dq.mine ? a.dq.mine + ((int)(blockIdx.x % kXcds) * kQueueSubs + dq_sub) * kQueuePitch : nullptr;
-    if (a.dq.other && blockIdx.x == 0 && threadIdx.x < kXcds * kQueueSubs) a.dq.other[threadIdx.x * kQueuePitch] = 0;
+    int* const dq = (QUEUE && a.dq.mine) ? a.dq.mine + ((int)(blockIdx.x % kXcds) * kQueueSubs + dq_sub) * kQueuePitch : nullptr;
+    if (QUEUE && a.dq.other && blockIdx.x == 0 && threadIdx.x < kXcds * kQueueSubs) a.dq.other[threadIdx.x * kQueuePitch] = 0;
     int dq_ticket = 0;
     auto enter = [&](int idx) {
-        if (dq) dq_ticket = queue_take(dq, lane);
-        F = item_addr<T, VEC, DESC>(g, decode_item(a.wl, a.reverse ? seq.end - 1 - (idx - seq.begin) : idx), lane);   // reversed within the wave's class
+        if (QUEUE && dq) dq_ticket = queue_take(dq, lane);
+        F = item_addr<T, VEC, DESC>(g, decode_item(a.tab, a.reverse ? seq.end - 1 - (idx - seq.begin) : idx), lane);   // reversed within the wave's class
         rs_p = make_rsrc(a.p + F.base_el);
         rs_r = make_rsrc(a.r + F.base_el);
         rs_x = make_rsrc(XM != 0 ? a.x + F.base_el : a.p + F.base_el);
@@ -1252,7 +1280,7 @@ __global__ __launch_bounds__(kBlock) void k_update_st(const UpdateStArgs<T> a) {
     // `own`: the row is one of this item's rows (its r / x / u / previous direction are needed, and its edge element)
     auto fetch = [&]() -> Raw {
         if (f_have && f_idx > F.nrows) {
-            f_item = dq ? seq.begin + seq.step + __builtin_amdgcn_readfirstlane(dq_ticket) * dq_nsub + dq_sub : f_item + seq.step;
+            f_item = (QUEUE && dq) ? seq.begin + seq.step + __builtin_amdgcn_readfirstlane(dq_ticket) * dq_nsub + dq_sub : f_item + seq.step;
             f_have = f_item < seq.end;
             if (f_have) enter(f_item);
         }
@@ -1295,10 +1323,22 @@ __global__ __launch_bounds__(kBlock) void k_update_st(const UpdateStArgs<T> a) {
     Raw q[DEPTH];
 #pragma unroll
     for (int k = 0; k < DEPTH; ++k) q[k] = fetch();
+    MI355CG_WT_STAMP(3)
 
     double alpha_d, rz = 0.0;
-    StateLite s;
-    if (a.src.mbox) {
+    if (!TEAM) {
+        if (s.done) { if (blockIdx.x == 0 && threadIdx.x == 0) copy_state(a.s_out, a.s_in); return; }
+        MI355CG_WT_STAMP(1)
+        const double pap = dd_value(reduce_parts_dd_pre(pre_lean, a.partA + FA_PAP * a.strideA, a.partA + (FA_PAP + FA_LO) * a.strideA, a.nA, a.esA, lds));
+        if (a.rule == 0) {
+            rz = FULL ? dd_value(reduce_parts_dd_pre(pre_rz_lean, a.partA + FA_RZ * a.strideA, a.partA + (FA_RZ + FA_LO) * a.strideA, a.nA, a.esA, lds))
+                      : dd_value(reduce_parts_dd(a.partA + FA_RZ * a.strideA, a.partA + (FA_RZ + FA_LO) * a.strideA, a.nA, a.esA, lds));
+            alpha_d = rz / pap;                       // msg_solver.cpp:102
+        } else {
+            alpha_d = s.rr / pap;                     // matrix_free_system.cpp:419
+        }
+        MI355CG_WT_STAMP(2)
+    } else if (a.src.mbox) {
         __shared__ double recs[kMaxRecDst * kRecWords];
         const PreParts pre = prefetch_parts(a.partA + FA_PAP * a.strideA, a.partA + (FA_PAP + FA_LO) * a.strideA, a.nA, 1);
         PreParts pre_rz{0, 0, 0, 0};
@@ -1428,7 +1468,7 @@ __global__ __launch_bounds__(kBlock) void k_update_st(const UpdateStArgs<T> a) {
         a.partB[FB_D2 * st + b] = t_d2.hi; a.partB[(FB_D2 + FB_LO) * st + b] = t_d2.lo;
         a.partB[FB_E2 * st + b] = t_e2.hi; a.partB[(FB_E2 + FB_LO) * st + b] = t_e2.lo;
         a.partB[FB_RMAX * st + b] = t_rmax; a.partB[FB_DMAX * st + b] = t_dmax; a.partB[FB_EMAX * st + b] = t_emax;
-        if (a.fl.part) {                                                  // field order FB_*, then the stop request this launch sampled
+        if (TEAM && a.fl.part) {                                          // field order FB_*, then the stop request this launch sampled
             const double v[FB_LL_COUNT] = {t_rr.hi, t_d2.hi, t_e2.hi, t_rr.lo, t_d2.lo, t_e2.lo, t_rmax, t_dmax, t_emax, (blockIdx.x == 0 && stop_word) ? 1.0 : 0.0};
             store_flagged(a.fl, b, FB_LL_COUNT, v);
         }
@@ -1470,12 +1510,12 @@ __global__ __launch_bounds__(kBlock) void k_check(const CheckArgs a) {
 // part's own cells, x = ((x + a[0] p[0]) + a[1] p[1]) + ..., oldest step first.
 template <typename T> struct FlushArgs { const T* p[kRing - 1]; T a[kRing - 1]; int n; };
 template <typename T, int VEC>
-__global__ __launch_bounds__(kBlock) void k_flush_x(const Geom g, const WorkList wl, T* x, const FlushArgs<T> f) {
+__global__ __launch_bounds__(kBlock) void k_flush_x(const Geom g, const ItemTab tab, T* x, const FlushArgs<T> f) {
     typedef typename VecOf<T, VEC>::type vec_t;
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
-    for (int item = blockIdx.x * kWaves + wave; item < wl.nitems; item += gridDim.x * kWaves) {
-        const Item it = decode_item(wl, item);
+    for (int item = blockIdx.x * kWaves + wave; item < tab.nitems; item += gridDim.x * kWaves) {
+        const Item it = decode_item(tab, item);
         const int x0 = it.strip * (kWave * VEC) + lane * VEC;
         if (x0 < (it.ya <= g.half ? g.cb : 0) || x0 >= g.xlim) continue;
         for (int y = it.ya; y <= it.yb; ++y) {
@@ -1556,14 +1596,14 @@ __global__ __launch_bounds__(kBlock) void k_fold_x(const FoldArgs a) {
 // (fields: 0 sum hi, 1 sum lo, 2 squares hi, 3 squares lo; field stride = gridDim.x).  Lets tests compare decompositions
 // of grids whose vectors are too large to bring to the host.
 template <typename T, int VEC>
-__global__ __launch_bounds__(kBlock) void k_checksum(const Geom g, const WorkList wl, const T* v, double* part) {
+__global__ __launch_bounds__(kBlock) void k_checksum(const Geom g, const ItemTab tab, const T* v, double* part) {
     typedef typename VecOf<T, VEC>::type vec_t;
     __shared__ double lds[2 * kWaves];
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
     dd s1 = dd_zero(), s2 = dd_zero();
-    for (int item = blockIdx.x * kWaves + wave; item < wl.nitems; item += gridDim.x * kWaves) {
-        const Item it = decode_item(wl, item);
+    for (int item = blockIdx.x * kWaves + wave; item < tab.nitems; item += gridDim.x * kWaves) {
+        const Item it = decode_item(tab, item);
         const int x0 = it.strip * (kWave * VEC) + lane * VEC;
         if (x0 < (it.ya <= g.half ? g.cb : 0) || x0 >= g.xlim) continue;
         for (int y = it.ya; y <= it.yb; ++y) {

@@ -65,9 +65,6 @@ struct EventPool {
     void destroy() { for (auto e : ev) hipEventDestroy(e); ev.clear(); used = 0; }
 };
 
-// One launch shape: the work items of a set of rows x strips and the persistent grid that marches them.
-struct Plan { WorkList wl{}; int grid = 0; int ty = 0; };
-
 // Geometric multigrid preconditioner (mi355cg_set_preconditioner; kernels in mg_kernels.h).  Level 0 is the handle's grid; level
 // l + 1 has 2 floor(N_l / 4) intervals (mg_shape) and the steps that keep the domain.  Per level: the right-hand side of its cycle
 // (level 0: the caller's vector), a work vector and the cycle's result (level 0: the caller's output); the coarsest level keeps
@@ -119,6 +116,7 @@ struct mi355cg_ctx {
     long long storage_len = 0;          // elements per vector incl. ghost rows
     long long pk_begin = 0, pk_len = 0; // owned cells in the part's packed order (pk_begin: global packed index of the first; row slabs are contiguous)
     PackGeom pg{};
+    // (Plan: item_table.h.  Every plan carries its two item tables in device memory: 16 B per item and per wave of its launch.)
     Plan whole, interior, edge;         // whole part; rows / strips that need no ghost data; the rest (first + last row, edge strips)
     Plan whole32;                       // fp32 kernels (VEC = 4, 256-column strips): the whole grid, or a row slab of full width
     int depth = 2;                      // raw rows in flight per wave (env MI355CG_DEPTH: 2 or 3)
@@ -239,7 +237,6 @@ void build_geom(mi355cg_ctx* c, int vec, int y_lo, int y_hi) {
 
 // Rows [ya, yb] x strips [sa, sb) as up to two rectangles (bottom-right block rows, upper block rows) with their
 // ghost-column flags (bit 0: a part to the left, bit 1: a part to the right).
-struct Rect { int y0, y1, s0, s1, gc; };
 int region_rects(const GridParams& gp, int vec, int ya, int yb, int sa, int sb, Rect out[2]) {
     const int ns_all = strips_total(gp, vec), s0b = first_bottom_strip(gp, vec);
     int nr = 0;
@@ -253,76 +250,15 @@ int region_rects(const GridParams& gp, int vec, int ya, int yb, int sa, int sb, 
     return nr;
 }
 
-// Append rows [y0, y1] x strips [s0, s1) cut into items of ~ty rows.  Returns the strip-rows added (ty <= 0: only count).
-long long add_panel(WorkList& wl, int y0, int y1, int s0, int s1, int ty, int gc) {
-    const int rows = y1 - y0 + 1, ns = s1 - s0;
-    if (rows <= 0 || ns <= 0) return 0;
-    if (ty <= 0) return (long long)rows * ns;
-    if (wl.np >= kMaxPanels) return 0;
-    Panel& P = wl.p[wl.np++];
-    P.y0 = y0; P.y1 = y1; P.s0 = s0; P.ns = ns; P.gc = gc;
-    P.nchunks = (rows + ty - 1) / ty;
-    P.ty = (rows + P.nchunks - 1) / P.nchunks;            // rebalance
-    P.nchunks = (rows + P.ty - 1) / P.ty;
-    P.item0 = wl.nitems;
-    wl.nitems += P.ns * P.nchunks;
-    return (long long)rows * ns;
+// add_panel, make_plan: item_table.h.  The knobs of a plan as the environment sets them.
+PlanKnobs env_knobs() {
+    PlanKnobs kn;
+    kn.target_waves = env_int("MI355CG_WAVES", 2048); kn.max_blocks = env_int("MI355CG_BLOCKS", 512);
+    { const char* v = getenv("MI355CG_ITEM_ROWS"); kn.item_rows = (v && *v) ? std::max(1, atoi(v)) : 0; }
+    kn.xcd_classes = env_int("MI355CG_XCD_CLASSES", 1);
+    return kn;
 }
-
-// Launch shape for a list of rectangles.  2 048 resident waves (2 workgroups per CU: 8 waves per CU already saturate the
-// memory system, round 1) take the items round-robin.  Measured (tools/tune.py, profiles/r02_tune_notes.md): one round of
-// items "as tall as it takes" is the best fp64 shape up to ~800 rows per item (N <= 16384 on one GPU); taller items (3 136 rows
-// of a 262 KB pitch at N = 32768: every wave sweeps 0.8 GB per stream) lose 14-16 %, so the height is capped and the rest
-// becomes further rounds -- which cost nothing since the load pipeline no longer drains between items.  The fp32 kernels
-// (256-column strips) like 64 rows.  The height is then nudged so that the items fill a whole number of rounds: a last
-// round with a few items would run at a fraction of the chip.
-Plan make_plan(const std::vector<Rect>& rects, int max_rows, int fixed_ty = 0, int dyn_rows = 0) {
-    Plan pl{};
-    const int target_waves = std::max(kWaves, env_int("MI355CG_WAVES", 2048));
-    const int max_blocks = std::max(1, env_int("MI355CG_BLOCKS", 512));
-    const int waves = std::min(target_waves, max_blocks * kWaves);
-    const long long item_rows = std::max(1, env_int("MI355CG_ITEM_ROWS", max_rows));
-    long long strip_rows = 0;
-    WorkList dry{};
-    for (auto& r : rects) strip_rows += add_panel(dry, r.y0, r.y1, r.s0, r.s1, 0, 0);
-    if (strip_rows == 0) return pl;
-    // XCD classes (see WorkList): only for launches that fill the chip, never for the single-row edge launches
-    const bool classes = env_int("MI355CG_XCD_CLASSES", 1) != 0 && fixed_ty == 0 && max_blocks >= kXcds && strip_rows >= 4LL * waves;
-    auto build = [&](int ty) {
-        WorkList wl{};
-        wl.ncls = 1;
-        for (auto& r : rects) add_panel(wl, r.y0, r.y1, r.s0, r.s1, ty, r.gc);
-        if (classes) {
-            wl.ncls = kXcds;
-            for (int k = 0; k <= kXcds; ++k) wl.cls0[k] = (int)((long long)wl.nitems * k / kXcds);
-        }
-        return wl;
-    };
-    auto fits = [&](const WorkList& wl, long long rounds) {
-        if (wl.ncls == kXcds) { for (int k = 0; k < kXcds; ++k) if (wl.cls0[k + 1] - wl.cls0[k] > rounds * (waves / kXcds)) return false; return true; }
-        return wl.nitems <= rounds * waves;
-    };
-    int ty = fixed_ty;
-    if (ty <= 0 && dyn_rows > 0 && classes) {
-        // dynamic queues: short items, several per wave; no need to fill whole rounds -- whoever is early takes more
-        ty = dyn_rows;
-        pl.wl = build(ty);
-    } else if (ty <= 0) {
-        const long long rounds = std::max<long long>(1, (strip_rows + waves * item_rows - 1) / (waves * item_rows));
-        ty = (int)std::max<long long>(std::min<long long>(8, item_rows), (strip_rows + rounds * waves - 1) / (rounds * waves));
-        for (int tries = 0; tries < 64; ++tries) {
-            pl.wl = build(ty);
-            if (fits(pl.wl, rounds)) break;
-            ++ty;
-        }
-    } else {
-        pl.wl = build(ty);
-    }
-    pl.ty = ty;
-    pl.grid = std::max(1, std::min(max_blocks, (pl.wl.nitems + kWaves - 1) / kWaves));
-    if (pl.wl.ncls == kXcds) pl.grid = std::min(max_blocks / kXcds * kXcds, (pl.grid + kXcds - 1) / kXcds * kXcds);      // the classes take turns over the workgroups
-    return pl;
-}
+Plan make_plan(const std::vector<Rect>& rects, int max_rows, int fixed_ty = 0, int dyn_rows = 0) { return make_plan(rects, env_knobs(), max_rows, fixed_ty, dyn_rows); }
 constexpr int kMaxRowsF64 = 800, kMaxRowsF32 = 64;
 
 void build_plans(mi355cg_ctx* c) {
@@ -383,6 +319,29 @@ void build_plans(mi355cg_ctx* c) {
     c->nB_own = c->whole.grid;
 }
 
+// The item tables of every plan (item_table.h), built and uploaded once, when the handle is created; mi355cg_destroy frees them.
+// No launch and no captured chunk allocates or copies anything for them.
+int upload_item_tables(mi355cg_ctx* c) {
+    for (Plan* pl : {&c->whole, &c->interior, &c->edge, &c->whole32}) {
+        if (pl->wl.nitems == 0 || pl->grid == 0) continue;
+        const std::vector<ItemDesc> items = build_item_table(pl->wl);
+        const std::vector<ItemSeq> seq = build_seq_table(pl->wl, pl->grid);
+        HIPCK(hipMalloc((void**)&pl->d_items, sizeof(ItemDesc) * items.size()));
+        HIPCK(hipMalloc((void**)&pl->d_seq, sizeof(ItemSeq) * seq.size()));
+        HIPCK(hipMemcpy(pl->d_items, items.data(), sizeof(ItemDesc) * items.size(), hipMemcpyHostToDevice));
+        HIPCK(hipMemcpy(pl->d_seq, seq.data(), sizeof(ItemSeq) * seq.size(), hipMemcpyHostToDevice));
+    }
+    return MI355CG_OK;
+}
+void free_item_tables(mi355cg_ctx* c) {
+    for (Plan* pl : {&c->whole, &c->interior, &c->edge, &c->whole32}) {
+        if (pl->d_items) hipFree(pl->d_items);
+        if (pl->d_seq) hipFree(pl->d_seq);
+        pl->d_items = nullptr; pl->d_seq = nullptr;
+    }
+}
+ItemTab item_tab(const Plan& pl) { return ItemTab{pl.d_items, pl.d_seq, pl.wl.nitems}; }
+
 int flat_grid(long long n) { return (int)std::max<long long>(1, std::min<long long>(2048, (n + kBlock - 1) / kBlock)); }
 
 // ---- launchers -------------------------------------------------------------------------------------
@@ -403,9 +362,9 @@ template <typename T, int VEC>
 void launch_apply(const mi355cg_ctx* c, const T* v, T* out, const Where& w) {
     if (w.plan->wl.nitems == 0) return;
     StencilArgs<T> a{};
-    a.g = kernel_geom<T, VEC>(c); a.wl = w.plan->wl;
+    a.g = kernel_geom<T, VEC>(c); a.tab = item_tab(*w.plan);
     a.pin = v; a.ap = out; a.partA = nullptr;
-    hipLaunchKernelGGL((k_stencil<T, VEC, false, false, 2, false, false>), dim3(w.plan->grid), dim3(kBlock), 0, w.stream, a);
+    hipLaunchKernelGGL((k_stencil<T, VEC, false, false, 2, false, false, false, false>), dim3(w.plan->grid), dim3(kBlock), 0, w.stream, a);
 }
 
 struct IterCfg { RuleParams rp; int want_diag; bool has_u; bool x2 = false; bool fold = false; };     // fold: x2 with the x steps deferred to k_fold_x
@@ -415,7 +374,7 @@ template <typename T, int VEC>
 void launch_iteration_stencil(mi355cg_ctx* c, const IterCfg& cfg, const T* r, T* const p[kRing], const Where& w, const PartSrc& pb, const FlagSpec* fl = nullptr) {
     if (w.plan->wl.nitems == 0) return;
     StencilArgs<T> a{};
-    a.g = kernel_geom<T, VEC>(c); a.wl = w.plan->wl;
+    a.g = kernel_geom<T, VEC>(c); a.tab = item_tab(*w.plan);
     a.r = r; a.pin = p[c->cur]; a.pout = p[(c->cur + 1) % c->xsteps]; a.ap = nullptr;
     a.partB = pb.ptr; a.nB = pb.n; a.strideB = pb.fstride; a.esB = pb.estride; a.src = pb.rec;
     a.partA = c->partA; a.strideA = c->strideA; a.slotA = w.slot;
@@ -425,7 +384,12 @@ void launch_iteration_stencil(mi355cg_ctx* c, const IterCfg& cfg, const T* r, T*
     if (VEC == 2 && c->dyn_rows > 0 && w.plan == &c->whole) a.dq = QueueSpec{c->qctr, c->qctr + kXcds * kQueueSubs * kQueuePitch};
     const dim3 grid(w.plan->grid), block(kBlock);
     const bool msg = cfg.rp.rule == MI355CG_RULE_MSG_MAXNORM, gc = c->has_gc, d3 = c->depth == 3;
-#define MI355CG_ST(MSG, D, GC) hipLaunchKernelGGL((k_stencil<T, VEC, true, MSG, D, true, GC>), grid, block, 0, w.stream, a)
+    // A team launch (records to gather, flagged partials to store) runs the code with both paths, as ever; a single-context launch
+    // gets the instantiation without the team path, and without the queue path unless its items are dealt at run time.
+    const bool team = pb.rec.mbox != nullptr || (fl && fl->part), queue = a.dq.mine != nullptr;
+#define MI355CG_ST(MSG, D, GC) do { if (team) hipLaunchKernelGGL((k_stencil<T, VEC, true, MSG, D, true, GC, true, VEC == 2>), grid, block, 0, w.stream, a); \
+                                    else if (VEC == 2 && queue) hipLaunchKernelGGL((k_stencil<T, VEC, true, MSG, D, true, GC, false, VEC == 2>), grid, block, 0, w.stream, a); \
+                                    else hipLaunchKernelGGL((k_stencil<T, VEC, true, MSG, D, true, GC, false, false>), grid, block, 0, w.stream, a); } while (0)
     if constexpr (VEC == 2) {
         if (msg) { if (gc) { if (d3) MI355CG_ST(true, 3, true); else MI355CG_ST(true, 2, true); } else { if (d3) MI355CG_ST(true, 3, false); else MI355CG_ST(true, 2, false); } }
         else     { if (gc) { if (d3) MI355CG_ST(false, 3, true); else MI355CG_ST(false, 2, true); } else { if (d3) MI355CG_ST(false, 3, false); else MI355CG_ST(false, 2, false); } }
@@ -441,7 +405,7 @@ template <typename T, int VEC>
 void launch_iteration_update(mi355cg_ctx* c, const IterCfg& cfg, T* x, T* r, T* const p[kRing], const T* u, const Where& w, const PartSrc& pa, const FlagSpec* fl = nullptr) {
     if (w.plan->wl.nitems == 0) return;
     UpdateStArgs<T> a{};
-    a.g = kernel_geom<T, VEC>(c); a.wl = w.plan->wl;
+    a.g = kernel_geom<T, VEC>(c); a.tab = item_tab(*w.plan);
     a.p = p[c->cur]; a.r = r; a.x = x; a.u = u;
     for (int i = 0; i < kRing - 1; ++i) a.pprev[i] = p[(c->cur + 2 * kRing * c->xsteps - 1 - i) % c->xsteps];      // directions of iterations k-1, k-2, ...
     a.partA = pa.ptr; a.nA = pa.n; a.strideA = pa.fstride; a.esA = pa.estride; a.src = pa.rec;
@@ -453,13 +417,17 @@ void launch_iteration_update(mi355cg_ctx* c, const IterCfg& cfg, T* x, T* r, T* 
     a.stop_req = w.slot == 0 ? c->stop_dev : nullptr;   // block 0 samples the pinned stop word once per iteration (of a phase in two launches: the one that runs last and owns slot 0)
     const dim3 grid(w.plan->grid), block(kBlock);
     const bool d3 = c->depth == 3 && !(cfg.x2 && c->cur == 0 && c->xsteps == 8);
-#define MI355CG_UST(XM, HASU) do { if (d3) hipLaunchKernelGGL((k_update_st<T, VEC, XM, HASU, 3, true>), grid, block, 0, w.stream, a); \
-                                   else hipLaunchKernelGGL((k_update_st<T, VEC, XM, HASU, 2, true>), grid, block, 0, w.stream, a); } while (0)
+    const bool team = pa.rec.mbox != nullptr || (fl && fl->part), queue = a.dq.mine != nullptr;      // see launch_iteration_stencil
+#define MI355CG_UST_D(XM, HASU, D) do { if (team) hipLaunchKernelGGL((k_update_st<T, VEC, XM, HASU, D, true, true, VEC == 2>), grid, block, 0, w.stream, a); \
+                                        else if (VEC == 2 && queue) hipLaunchKernelGGL((k_update_st<T, VEC, XM, HASU, D, true, false, VEC == 2>), grid, block, 0, w.stream, a); \
+                                        else hipLaunchKernelGGL((k_update_st<T, VEC, XM, HASU, D, true, false, false>), grid, block, 0, w.stream, a); } while (0)
+#define MI355CG_UST(XM, HASU) do { if (d3) MI355CG_UST_D(XM, HASU, 3); else MI355CG_UST_D(XM, HASU, 2); } while (0)
     if (cfg.x2) {                    // iterations k = 0 mod M carry all M x steps (c->cur = k % M)
         if (c->cur != 0 || cfg.fold) MI355CG_UST(0, false); else if (c->xsteps == 8) MI355CG_UST(8, false); else if (c->xsteps == 4) MI355CG_UST(4, false); else MI355CG_UST(2, false);
     }
     else if constexpr (VEC == 2) { if (cfg.has_u) MI355CG_UST(1, true); else MI355CG_UST(1, false); }
 #undef MI355CG_UST
+#undef MI355CG_UST_D
 }
 
 // Flat pass over the owned rows: state initialisation (x = 0, r = b: norms of r0) or the resume step of the mixed path.
@@ -486,7 +454,7 @@ void launch_flush_x(const mi355cg_ctx* c, const Plan& plan, T* x, T* const p[kRi
     f.n = pending;
     for (int j = 0; j < pending; ++j) { const int k = fin.it - pending + 1 + j; f.p[j] = p[k % c->xsteps]; f.a[j] = (T)fin.alpha_hist[k & (kRing - 1)]; }
     hipLaunchKernelGGL((k_flush_x<T, VEC>), dim3(std::max(1, std::min(1024, (plan.wl.nitems + kWaves - 1) / kWaves))), dim3(kBlock), 0, stream,
-                       kernel_geom<T, VEC>(c), plan.wl, x, f);
+                       kernel_geom<T, VEC>(c), item_tab(plan), x, f);
 }
 
 // Deferred x fold.  flush_it < 0: after the update launch of an iteration k = 0 mod R, the R steps up to k (unless that launch's
@@ -1564,6 +1532,7 @@ static int create_impl(int n, int m, double a, double b, double c_, double d, in
     int rc = MI355CG_OK;
     auto cleanup = [&]() { mi355cg_destroy(c); return rc; };
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { rc = fail(MI355CG_ERR_HIP, "hipStreamCreate failed"); return cleanup(); }
+    if ((rc = upload_item_tables(c))) return cleanup();
     const long long L = c->storage_len;
     // x is folded every M-th iteration: 4 by default.  8 saves another 0.125 words per iteration and measured +0.2-0.7 % for
     // four more vectors (fp64 only: the fp32 8-step launch needs 262 VGPRs and would halve the resident waves)
@@ -1726,6 +1695,7 @@ void mi355cg_destroy(mi355cg_handle c) {
                    c->packed, c->partA, c->partB, c->partR, c->sumsA, c->sumsB, c->sA, c->sB, c->summary, c->hist, c->qctr};
     for (void* p : dev) if (p) hipFree(p);
     free_fold_ring(c);
+    free_item_tables(c);
     if (c->csr_row_map) hipFree(c->csr_row_map);
     if (c->csr_entries) hipFree(c->csr_entries);
     if (c->csr_values) hipFree(c->csr_values);
@@ -2440,7 +2410,7 @@ int ctx_checksum(mi355cg_ctx* c, int which, hdd out[2]) {
     if (c->is_slab) HIPCK(hipDeviceSynchronize());
     if (which == 3) if (int rc = ensure_u_on_device(c)) return rc;
     const int grid = 512;
-    hipLaunchKernelGGL((k_checksum<double, 2>), dim3(grid), dim3(kBlock), 0, c->stream, kernel_geom<double, 2>(c), c->whole.wl, v, c->partR);
+    hipLaunchKernelGGL((k_checksum<double, 2>), dim3(grid), dim3(kBlock), 0, c->stream, kernel_geom<double, 2>(c), item_tab(c->whole), v, c->partR);
     HIPCK(hipGetLastError());
     HIPCK(hipMemcpyAsync(c->partR_h, c->partR, sizeof(double) * 4 * grid, hipMemcpyDeviceToHost, c->stream));
     HIPCK(hipStreamSynchronize(c->stream));

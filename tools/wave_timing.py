@@ -31,8 +31,13 @@ for k, name in enumerate(("stencil", "update")):
     print(f"   percentiles          min      5     25     50     75     95    max")
     print(f"   wave start      {q(start)}")
     print(f"   prologue length {q(mid - start)}")
+    # stamps: 0 kernel entry (before the wave's item sequence is fetched), 3 the first DEPTH rows are requested, 1 the state is
+    # there, 2 reduced and decided, 4 end of the prologue
+    if w[:, 3].max() > 0:
+        print(f"     rows requested{q((w[:, 3] - w[:, 0]) / 100.0)}    (entry -> item sequence, first item, DEPTH row requests issued)")
     if w[:, 1].max() > 0:
-        print(f"     state loaded  {q((w[:, 1] - w[:, 0]) / 100.0)}")
+        since = 3 if w[:, 3].max() > 0 else 0
+        print(f"     state loaded  {q((w[:, 1] - w[:, since]) / 100.0)}")
         print(f"     reduce+decide {q((w[:, 2] - w[:, 1]) / 100.0)}")
         print(f"     rest          {q((w[:, 4] - w[:, 2]) / 100.0)}")
     print(f"   main loop length{q(end - mid)}")
