@@ -1,6 +1,6 @@
 // mg_batch_kernels.h -- HIP kernels (gfx950 / CDNA4, wave64) of the batched multigrid-preconditioned CG
-// (mi355cg_solve_batch / mi355cg_solve_batch_device): the kernels of mg_kernels.h with a second grid
-// dimension over the systems of a batch that are still iterating.
+// (mi355cg_solve_batch / mi355cg_solve_batch_device): a second grid dimension over the systems of a batch
+// that are still iterating.
 //
 //   blockIdx.x, gridDim.x   exactly as in the single-system launch (MgLevel::grid): the rows a block takes, and with them the
 //                           order of every sum, do not depend on the batch
@@ -9,10 +9,13 @@
 //   partials                [system][field][block]; k_mgb_reduce sums a field's blocks left to right in one wave per
 //                           (position, field) -- the sum solve_mg makes on the host -- into [position][field]
 //
-// Per system every element-wise expression and every reduction tree is the one of mg_kernels.h, so system s of a batch gets the
-// bits a single solve gives it.  Systems never meet in a sum.  No kernel here writes a vector of a system that is not in the
-// active list: a finished system stays frozen.  Plain fp64 arithmetic (no FMA contraction: -ffp-contract=off), no atomics, no
-// LDS beyond the block reduction.
+// k_mgb_smooth, _restrict, _prolong, _residual, _restrict_nn, _prolong_nn, _dir_apply and _dot call the __device__ bodies of
+// mg_kernels.h (mg_smooth ... mg_dot) on their system's vectors: there is one expression and one reduction tree, so system s of
+// a batch gets the bits a single solve gives it.  The others are kernels of their own: k_mgb_coarse walks the active list,
+// k_mgb_update and k_mgb_init[_guess] have their own partial fields, k_mgb_reduce, k_mgb_pack and k_mgb_unpack have no single
+// twin.  Systems never meet in a sum.  No kernel here writes a vector of a system that is not in the active list: a finished
+// system stays frozen.  Plain fp64 arithmetic (no FMA contraction: -ffp-contract=off), no atomics, no LDS beyond the block
+// reduction.
 #pragma once
 #include "mg_kernels.h"
 
@@ -25,115 +28,44 @@ struct MgbAct { long long stride; int n; int sys[kMgBatchMax]; };    // elements
 struct MgbScal { double v[kMgBatchMax]; };                           // one scalar per active position
 
 #define MGB_SYS(ACT) ((long long)(ACT).sys[blockIdx.y] * (ACT).stride)
-#define MGB_FOR_INTERIOR(G, XI, YI)                                                                \
-    for (int YI = 1 + (int)blockIdx.x; YI <= (G).N - 1; YI += (int)gridDim.x)                      \
-        for (int XI = mg_x0((G), YI) + (int)threadIdx.x; XI <= (G).N - 1; XI += kBlock)
+#define MGB_SLOT(ACT) ((long long)(ACT).sys[blockIdx.y] * gridDim.x + blockIdx.x)      // of part[system][0][block]
 
-// k_mg_smooth per active system; DOT: partials of (r, t) into part[system][0][block]
+// The bodies of mg_kernels.h on the vectors of blockIdx.y's system
 template <bool FIRST, bool DOT>
 __global__ __launch_bounds__(kBlock) void k_mgb_smooth(const MgbAct act, const Geom g, double omega, const double* __restrict__ r_,
                                                        const double* __restrict__ u_, double* __restrict__ t_, double* __restrict__ part) {
-    __shared__ double lds[2 * kWaves];
     const long long so = MGB_SYS(act);
-    const double* __restrict__ r = r_ + so;
-    const double* __restrict__ u = FIRST ? nullptr : u_ + so;
-    double* __restrict__ t = t_ + so;
-    double s = 0.0;
-    MGB_FOR_INTERIOR(g, x, y) {
-        const long long o = mg_off(g, x, y);
-        const double rv = r[o];
-        double tv;
-        if (FIRST) tv = omega * (rv / g.A);
-        else tv = u[o] + omega * ((rv - mg_Av(g, u, x, y)) / g.A);
-        t[o] = tv;
-        if (DOT) s += rv * tv;
-    }
-    if (DOT) {
-        const double b = block_reduce<false>(s, lds);
-        if (threadIdx.x == 0) part[(long long)act.sys[blockIdx.y] * gridDim.x + blockIdx.x] = b;
-    }
+    mg_smooth<FIRST, DOT>(g, omega, r_ + so, FIRST ? nullptr : u_ + so, t_ + so, DOT ? part + MGB_SLOT(act) : nullptr);
 }
 
 __global__ __launch_bounds__(kBlock) void k_mgb_restrict(const MgbAct act, const Geom gf, const Geom gc, const double* __restrict__ r_,
                                                          const double* __restrict__ u_, double* __restrict__ rc_) {
     const long long so = MGB_SYS(act);
-    const double* __restrict__ r = r_ + so;
-    const double* __restrict__ u = u_ + so;
-    double* __restrict__ rc = rc_ + so;
-    MGB_FOR_INTERIOR(gc, X, Y) {
-        const int x = 2 * X, y = 2 * Y;
-        const double s00 = mg_fine_residual(gf, r, u, x, y);
-        const double sl = mg_fine_residual(gf, r, u, x - 1, y), sr = mg_fine_residual(gf, r, u, x + 1, y);
-        const double sd = mg_fine_residual(gf, r, u, x, y - 1), su = mg_fine_residual(gf, r, u, x, y + 1);
-        const double sld = mg_fine_residual(gf, r, u, x - 1, y - 1), srd = mg_fine_residual(gf, r, u, x + 1, y - 1);
-        const double slu = mg_fine_residual(gf, r, u, x - 1, y + 1), sru = mg_fine_residual(gf, r, u, x + 1, y + 1);
-        rc[mg_off(gc, X, Y)] = 0.0625 * (4.0 * s00 + 2.0 * (sl + sr + sd + su) + (sld + srd + slu + sru));
-    }
+    mg_restrict(gf, gc, r_ + so, u_ + so, rc_ + so);
 }
 
 __global__ __launch_bounds__(kBlock) void k_mgb_prolong(const MgbAct act, const Geom gf, const Geom gc, const double* __restrict__ e_,
                                                         double* __restrict__ u_) {
     const long long so = MGB_SYS(act);
-    const double* __restrict__ e = e_ + so;
-    double* __restrict__ u = u_ + so;
-    MGB_FOR_INTERIOR(gf, x, y) {
-        const int cx = x >> 1, cy = y >> 1;
-        const double e00 = mg_at(gc, e, cx, cy);
-        double corr;
-        if ((x & 1) && (y & 1)) corr = 0.25 * (e00 + mg_at(gc, e, cx + 1, cy) + mg_at(gc, e, cx, cy + 1) + mg_at(gc, e, cx + 1, cy + 1));
-        else if (x & 1) corr = 0.5 * (e00 + mg_at(gc, e, cx + 1, cy));
-        else if (y & 1) corr = 0.5 * (e00 + mg_at(gc, e, cx, cy + 1));
-        else corr = e00;
-        const long long o = mg_off(gf, x, y);
-        u[o] = u[o] + corr;
-    }
+    mg_prolong(gf, gc, e_ + so, u_ + so);
 }
 
 __global__ __launch_bounds__(kBlock) void k_mgb_residual(const MgbAct act, const Geom g, const double* __restrict__ r_,
                                                          const double* __restrict__ u_, double* __restrict__ s_) {
     const long long so = MGB_SYS(act);
-    const double* __restrict__ r = r_ + so;
-    const double* __restrict__ u = u_ + so;
-    double* __restrict__ s = s_ + so;
-    MGB_FOR_INTERIOR(g, x, y) {
-        const long long o = mg_off(g, x, y);
-        s[o] = r[o] - mg_Av(g, u, x, y);
-    }
+    mg_residual(g, r_ + so, u_ + so, s_ + so);
 }
 
 __global__ __launch_bounds__(kBlock) void k_mgb_restrict_nn(const MgbAct act, const Geom gf, const Geom gc, double scale,
                                                             const double* __restrict__ s_, double* __restrict__ rc_) {
     const long long so = MGB_SYS(act);
-    const double* __restrict__ s = s_ + so;
-    double* __restrict__ rc = rc_ + so;
-    const int Nf = gf.N, Nc = gc.N;
-    MGB_FOR_INTERIOR(gc, X, Y) {
-        const int x_lo = (int)((long long)(X - 1) * Nf / Nc) + 1, x_hi = (int)(((long long)(X + 1) * Nf - 1) / Nc);
-        const int y_lo = (int)((long long)(Y - 1) * Nf / Nc) + 1, y_hi = (int)(((long long)(Y + 1) * Nf - 1) / Nc);
-        double acc = 0.0;
-        for (int y = y_lo; y <= y_hi; ++y) {
-            const double wy = mg_w(y, Y, Nf, Nc);
-            for (int x = x_lo; x <= x_hi; ++x) acc += (wy * mg_w(x, X, Nf, Nc)) * mg_at(gf, s, x, y);
-        }
-        rc[mg_off(gc, X, Y)] = scale * acc;
-    }
+    mg_restrict_nn(gf, gc, scale, s_ + so, rc_ + so);
 }
 
 __global__ __launch_bounds__(kBlock) void k_mgb_prolong_nn(const MgbAct act, const Geom gf, const Geom gc, const double* __restrict__ e_,
                                                            double* __restrict__ u_) {
     const long long so = MGB_SYS(act);
-    const double* __restrict__ e = e_ + so;
-    double* __restrict__ u = u_ + so;
-    const int Nf = gf.N, Nc = gc.N;
-    MGB_FOR_INTERIOR(gf, x, y) {
-        const int X0 = (int)((long long)x * Nc / Nf), Y0 = (int)((long long)y * Nc / Nf);
-        const double wx0 = mg_w(x, X0, Nf, Nc), wx1 = mg_w(x, X0 + 1, Nf, Nc);
-        const double wy0 = mg_w(y, Y0, Nf, Nc), wy1 = mg_w(y, Y0 + 1, Nf, Nc);
-        const double corr = wy0 * (wx0 * mg_at(gc, e, X0, Y0) + wx1 * mg_at(gc, e, X0 + 1, Y0)) +
-                            wy1 * (wx0 * mg_at(gc, e, X0, Y0 + 1) + wx1 * mg_at(gc, e, X0 + 1, Y0 + 1));
-        const long long o = mg_off(gf, x, y);
-        u[o] = u[o] + corr;
-    }
+    mg_prolong_nn(gf, gc, e_ + so, u_ + so);
 }
 
 // Coarsest level, z = A_L^-1 r for every active system in one launch: block i owns row i of the inverse, keeps its lane-strided
@@ -166,32 +98,13 @@ __global__ __launch_bounds__(kBlock) void k_mgb_coarse(const MgbAct act, int n, 
     }
 }
 
-// k_mg_dir_apply per active system, beta by position; partials of (p, q) into part[system][0][block]
+// beta by position; partials of (p, q) into part[system][0][block]
 template <bool FIRST>
 __global__ __launch_bounds__(kBlock) void k_mgb_dir_apply(const MgbAct act, const MgbScal betas, const Geom g, const double* __restrict__ z_,
                                                           const double* __restrict__ po_, double* __restrict__ p_,
                                                           double* __restrict__ q_, double* __restrict__ part) {
-    __shared__ double lds[2 * kWaves];
     const long long so = MGB_SYS(act);
-    const double beta = betas.v[blockIdx.y];
-    const double* __restrict__ z = z_ + so;
-    const double* __restrict__ po = FIRST ? nullptr : po_ + so;
-    double* __restrict__ p = p_ + so;
-    double* __restrict__ q = q_ + so;
-    double s = 0.0;
-    MGB_FOR_INTERIOR(g, x, y) {
-        const long long o = mg_off(g, x, y);
-        auto dir = [&](int xx, int yy) {
-            return FIRST ? mg_at(g, z, xx, yy) : mg_at(g, z, xx, yy) + beta * mg_at(g, po, xx, yy);
-        };
-        const double pc = FIRST ? z[o] : z[o] + beta * po[o];
-        const double qv = g.A * pc + g.xk * (dir(x - 1, y) + dir(x + 1, y)) + g.yk * (dir(x, y - 1) + dir(x, y + 1));
-        p[o] = pc;
-        q[o] = qv;
-        s += pc * qv;
-    }
-    const double b = block_reduce<false>(s, lds);
-    if (threadIdx.x == 0) part[(long long)act.sys[blockIdx.y] * gridDim.x + blockIdx.x] = b;
+    mg_dir_apply<FIRST>(g, betas.v[blockIdx.y], z_ + so, FIRST ? nullptr : po_ + so, p_ + so, q_ + so, part + MGB_SLOT(act));
 }
 
 // k_mg_update per active system, alpha by position; partials part[(system * MGB_NFIELDS + field) * gridDim.x + block] of (r, r),
@@ -207,7 +120,7 @@ __global__ __launch_bounds__(kBlock) void k_mgb_update(const MgbAct act, const M
     const double* __restrict__ p = p_ + so;
     const double* __restrict__ q = q_ + so;
     double rr = 0, rmax = 0, dmax = 0;
-    MGB_FOR_INTERIOR(g, xx, y) {
+    MG_FOR_INTERIOR(g, xx, y) {
         const long long o = mg_off(g, xx, y);
         const double xo = x[o];
         const double xn = xo + alpha * p[o];
@@ -234,7 +147,7 @@ __global__ __launch_bounds__(kBlock) void k_mgb_init(const MgbAct act, const Geo
     double* __restrict__ x = x_ + so;
     const double* __restrict__ r = r_ + so;
     double rr = 0, rmax = 0;
-    MGB_FOR_INTERIOR(g, xx, y) {
+    MG_FOR_INTERIOR(g, xx, y) {
         const long long o = mg_off(g, xx, y);
         const double rn = r[o];
         x[o] = 0.0;
@@ -260,7 +173,7 @@ __global__ __launch_bounds__(kBlock) void k_mgb_init_guess(const MgbAct act, con
     const double* __restrict__ x = x_ + so;
     double* __restrict__ r = r_ + so;
     double rr = 0, bb = 0, rmax = 0;
-    MGB_FOR_INTERIOR(g, xx, y) {
+    MG_FOR_INTERIOR(g, xx, y) {
         const long long o = mg_off(g, xx, y);
         double v = g.A * x[o];
         v = v + g.xk * x[o - 1];
@@ -280,17 +193,11 @@ __global__ __launch_bounds__(kBlock) void k_mgb_init_guess(const MgbAct act, con
     t = block_reduce<true>(rmax, lds); if (threadIdx.x == 0) { part[base + MGBG_RMAX * n] = t; part[base + MGBG_DMAX * n] = 0.0; }
 }
 
-// k_mg_dot per active system (the (r, z) of a one-level hierarchy)
+// the (r, z) of a one-level hierarchy
 __global__ __launch_bounds__(kBlock) void k_mgb_dot(const MgbAct act, const Geom g, const double* __restrict__ a_, const double* __restrict__ b_,
                                                     double* __restrict__ part) {
-    __shared__ double lds[2 * kWaves];
     const long long so = MGB_SYS(act);
-    const double* __restrict__ a = a_ + so;
-    const double* __restrict__ b = b_ + so;
-    double s = 0.0;
-    MGB_FOR_INTERIOR(g, x, y) { const long long o = mg_off(g, x, y); s += a[o] * b[o]; }
-    const double t = block_reduce<false>(s, lds);
-    if (threadIdx.x == 0) part[(long long)act.sys[blockIdx.y] * gridDim.x + blockIdx.x] = t;
+    mg_dot(g, a_ + so, b_ + so, part + MGB_SLOT(act));
 }
 
 // red[position][field] = the field's nblocks partials of the position's system summed (fields >= first_max: maxed) serially in
@@ -344,7 +251,8 @@ __global__ __launch_bounds__(kBlock) void k_mgb_pack(const PackGeom pg, long lon
     for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < pg.pk_len; i += step) dst[i] = src[packed_to_storage(pg, i)];
 }
 
-#undef MGB_FOR_INTERIOR
+#undef MG_FOR_INTERIOR
+#undef MGB_SLOT
 #undef MGB_SYS
 
 }  // namespace mi355cg

@@ -18,6 +18,11 @@
 // stencil can name that is not stored is (x, N_l/2) with x < cb (left of the bottom block's storage), which mg_at reads as 0.
 // All reductions have a fixed order (a fixed grid, a fixed tree per block, the blocks summed by the host in index order), so
 // the same inputs give the same bits on every run.  Plain fp64 arithmetic (no FMA contraction: -ffp-contract=off).
+//
+// The element-wise loops of smooth, restrict, prolong, residual, restrict_nn, prolong_nn, dir_apply and dot are written once, as
+// the __device__ functions mg_smooth ... mg_dot: they take the level geometry, the vectors of one system and the address of the
+// block's partial slot.  k_mg_X passes its arguments through; k_mgb_X (mg_batch_kernels.h) offsets every vector to its system.
+// They take Geom by value, as the kernels do: by reference the compiler gives mg_restrict_nn's two kernels two VGPRs more.
 #pragma once
 #include "cg_kernels.h"
 
@@ -40,13 +45,15 @@ __device__ inline double mg_Av(const Geom& g, const double* __restrict__ v, int 
 __device__ inline int mg_x0(const Geom& g, int y) { return y <= g.half ? g.half + 1 : 1; }    // first interior column of row y
 
 // The row loops: block b takes interior rows 1 + b, 1 + b + gridDim.x, ...; its threads stride the row's interior columns.
+// (mg_batch_kernels.h uses the macro too and undefines it.)
 #define MG_FOR_INTERIOR(G, XI, YI)                                                                 \
     for (int YI = 1 + (int)blockIdx.x; YI <= (G).N - 1; YI += (int)gridDim.x)                      \
         for (int XI = mg_x0((G), YI) + (int)threadIdx.x; XI <= (G).N - 1; XI += kBlock)
 
+// slot (DOT): where this block's partial of (r, t) goes
 template <bool FIRST, bool DOT>
-__global__ __launch_bounds__(kBlock) void k_mg_smooth(const Geom g, double omega, const double* __restrict__ r,
-                                                      const double* __restrict__ u, double* __restrict__ t, double* __restrict__ part) {
+__device__ __forceinline__ void mg_smooth(const Geom g, double omega, const double* __restrict__ r, const double* __restrict__ u,
+                                          double* __restrict__ t, double* __restrict__ slot) {
     __shared__ double lds[2 * kWaves];
     double s = 0.0;
     MG_FOR_INTERIOR(g, x, y) {
@@ -60,16 +67,21 @@ __global__ __launch_bounds__(kBlock) void k_mg_smooth(const Geom g, double omega
     }
     if (DOT) {
         const double b = block_reduce<false>(s, lds);
-        if (threadIdx.x == 0) part[blockIdx.x] = b;
+        if (threadIdx.x == 0) *slot = b;
     }
+}
+template <bool FIRST, bool DOT>
+__global__ __launch_bounds__(kBlock) void k_mg_smooth(const Geom g, double omega, const double* __restrict__ r,
+                                                      const double* __restrict__ u, double* __restrict__ t, double* __restrict__ part) {
+    mg_smooth<FIRST, DOT>(g, omega, r, u, t, DOT ? part + blockIdx.x : nullptr);
 }
 
 // coarse interior node (X, Y) <- full weighting of s = r - A u around fine node (2X, 2Y); s = 0 off the fine interior
 __device__ inline double mg_fine_residual(const Geom& gf, const double* __restrict__ r, const double* __restrict__ u, int x, int y) {
     return node_interior(gf, x, y) ? r[mg_off(gf, x, y)] - mg_Av(gf, u, x, y) : 0.0;
 }
-__global__ __launch_bounds__(kBlock) void k_mg_restrict(const Geom gf, const Geom gc, const double* __restrict__ r,
-                                                        const double* __restrict__ u, double* __restrict__ rc) {
+__device__ __forceinline__ void mg_restrict(const Geom gf, const Geom gc, const double* __restrict__ r, const double* __restrict__ u,
+                                            double* __restrict__ rc) {
     MG_FOR_INTERIOR(gc, X, Y) {
         const int x = 2 * X, y = 2 * Y;
         const double s00 = mg_fine_residual(gf, r, u, x, y);
@@ -80,10 +92,11 @@ __global__ __launch_bounds__(kBlock) void k_mg_restrict(const Geom gf, const Geo
         rc[mg_off(gc, X, Y)] = 0.0625 * (4.0 * s00 + 2.0 * (sl + sr + sd + su) + (sld + srd + slu + sru));
     }
 }
+__global__ __launch_bounds__(kBlock) void k_mg_restrict(const Geom gf, const Geom gc, const double* __restrict__ r,
+                                                        const double* __restrict__ u, double* __restrict__ rc) { mg_restrict(gf, gc, r, u, rc); }
 
 // fine interior node (x, y): u += bilinear interpolation of the coarse correction e (0 on the coarse boundary)
-__global__ __launch_bounds__(kBlock) void k_mg_prolong(const Geom gf, const Geom gc, const double* __restrict__ e,
-                                                       double* __restrict__ u) {
+__device__ __forceinline__ void mg_prolong(const Geom gf, const Geom gc, const double* __restrict__ e, double* __restrict__ u) {
     MG_FOR_INTERIOR(gf, x, y) {
         const int cx = x >> 1, cy = y >> 1;
         const double e00 = mg_at(gc, e, cx, cy);
@@ -96,6 +109,8 @@ __global__ __launch_bounds__(kBlock) void k_mg_prolong(const Geom gf, const Geom
         u[o] = u[o] + corr;
     }
 }
+__global__ __launch_bounds__(kBlock) void k_mg_prolong(const Geom gf, const Geom gc, const double* __restrict__ e,
+                                                       double* __restrict__ u) { mg_prolong(gf, gc, e, u); }
 
 // ---- non-nested levels (MI355CG_PRECOND_MG_ANY, N_f % 4 == 2, N_c = 2 floor(N_f / 4) = (N_f - 2) / 2) -------------------------
 // 1-D bilinear weight of coarse node X at fine node x: the hat of coarse width around X at x's physical place x / N_f, i.e.
@@ -108,18 +123,19 @@ __host__ __device__ inline double mg_w(int x, int X, int Nf, int Nc) {
 }
 
 // s = r - A u at fine interior nodes; nothing else is written, so s keeps the zero boundary of the level's vectors
-__global__ __launch_bounds__(kBlock) void k_mg_residual(const Geom g, const double* __restrict__ r, const double* __restrict__ u,
-                                                        double* __restrict__ s) {
+__device__ __forceinline__ void mg_residual(const Geom g, const double* __restrict__ r, const double* __restrict__ u, double* __restrict__ s) {
     MG_FOR_INTERIOR(g, x, y) {
         const long long o = mg_off(g, x, y);
         s[o] = r[o] - mg_Av(g, u, x, y);
     }
 }
+__global__ __launch_bounds__(kBlock) void k_mg_residual(const Geom g, const double* __restrict__ r, const double* __restrict__ u,
+                                                        double* __restrict__ s) { mg_residual(g, r, u, s); }
 
 // coarse interior node (X, Y) <- scale * sum over fine nodes y ascending, then x ascending, of w(y, Y) w(x, X) s(x, y), scale =
 // (N_c / N_f)^2.  The support |x N_c - X N_f| < N_f is x_lo..x_hi below, <= 5 nodes wide and inside 1..N_f - 1 for 1 <= X <= N_c - 1.
-__global__ __launch_bounds__(kBlock) void k_mg_restrict_nn(const Geom gf, const Geom gc, double scale, const double* __restrict__ s,
-                                                           double* __restrict__ rc) {
+__device__ __forceinline__ void mg_restrict_nn(const Geom gf, const Geom gc, double scale, const double* __restrict__ s,
+                                               double* __restrict__ rc) {
     const int Nf = gf.N, Nc = gc.N;
     MG_FOR_INTERIOR(gc, X, Y) {
         const int x_lo = (int)((long long)(X - 1) * Nf / Nc) + 1, x_hi = (int)(((long long)(X + 1) * Nf - 1) / Nc);
@@ -132,10 +148,11 @@ __global__ __launch_bounds__(kBlock) void k_mg_restrict_nn(const Geom gf, const 
         rc[mg_off(gc, X, Y)] = scale * acc;
     }
 }
+__global__ __launch_bounds__(kBlock) void k_mg_restrict_nn(const Geom gf, const Geom gc, double scale, const double* __restrict__ s,
+                                                           double* __restrict__ rc) { mg_restrict_nn(gf, gc, scale, s, rc); }
 
 // fine interior node (x, y): u += sum of w(x, X) w(y, Y) e(X, Y) over the coarse nodes X0 = floor(x N_c / N_f), X0 + 1 (same in y)
-__global__ __launch_bounds__(kBlock) void k_mg_prolong_nn(const Geom gf, const Geom gc, const double* __restrict__ e,
-                                                          double* __restrict__ u) {
+__device__ __forceinline__ void mg_prolong_nn(const Geom gf, const Geom gc, const double* __restrict__ e, double* __restrict__ u) {
     const int Nf = gf.N, Nc = gc.N;
     MG_FOR_INTERIOR(gf, x, y) {
         const int X0 = (int)((long long)x * Nc / Nf), Y0 = (int)((long long)y * Nc / Nf);
@@ -147,6 +164,8 @@ __global__ __launch_bounds__(kBlock) void k_mg_prolong_nn(const Geom gf, const G
         u[o] = u[o] + corr;
     }
 }
+__global__ __launch_bounds__(kBlock) void k_mg_prolong_nn(const Geom gf, const Geom gc, const double* __restrict__ e,
+                                                          double* __restrict__ u) { mg_prolong_nn(gf, gc, e, u); }
 
 // z[off[i]] = sum_j inv[i][j] r[off[j]]: block-strided rows, each summed lane-strided and by the fixed block tree
 __global__ __launch_bounds__(kBlock) void k_mg_coarse(int n, const double* __restrict__ inv, const int* __restrict__ off,
@@ -163,9 +182,8 @@ __global__ __launch_bounds__(kBlock) void k_mg_coarse(int n, const double* __res
 // p = z + beta * p_old (first iteration: p = z) evaluated at the node and its four neighbours, q = A p, partials of (p, q).
 // p_old and p are different buffers: a neighbour's p_old must still be there when this node reads it.
 template <bool FIRST>
-__global__ __launch_bounds__(kBlock) void k_mg_dir_apply(const Geom g, double beta, const double* __restrict__ z,
-                                                         const double* __restrict__ po, double* __restrict__ p,
-                                                         double* __restrict__ q, double* __restrict__ part) {
+__device__ __forceinline__ void mg_dir_apply(const Geom g, double beta, const double* __restrict__ z, const double* __restrict__ po,
+                                             double* __restrict__ p, double* __restrict__ q, double* __restrict__ slot) {
     __shared__ double lds[2 * kWaves];
     double s = 0.0;
     MG_FOR_INTERIOR(g, x, y) {
@@ -180,7 +198,13 @@ __global__ __launch_bounds__(kBlock) void k_mg_dir_apply(const Geom g, double be
         s += pc * qv;
     }
     const double b = block_reduce<false>(s, lds);
-    if (threadIdx.x == 0) part[blockIdx.x] = b;
+    if (threadIdx.x == 0) *slot = b;
+}
+template <bool FIRST>
+__global__ __launch_bounds__(kBlock) void k_mg_dir_apply(const Geom g, double beta, const double* __restrict__ z,
+                                                         const double* __restrict__ po, double* __restrict__ p,
+                                                         double* __restrict__ q, double* __restrict__ part) {
+    mg_dir_apply<FIRST>(g, beta, z, po, p, q, part + blockIdx.x);
 }
 
 // x += alpha p, r -= alpha q; partials (field-major, part[f * gridDim.x + block]) of the MG_* fields.  u == nullptr: no error norms.
@@ -212,14 +236,15 @@ __global__ __launch_bounds__(kBlock) void k_mg_update(const Geom g, double alpha
 }
 
 // partials of (a, b) over the interior
-__global__ __launch_bounds__(kBlock) void k_mg_dot(const Geom g, const double* __restrict__ a, const double* __restrict__ b,
-                                                   double* __restrict__ part) {
+__device__ __forceinline__ void mg_dot(const Geom g, const double* __restrict__ a, const double* __restrict__ b, double* __restrict__ slot) {
     __shared__ double lds[2 * kWaves];
     double s = 0.0;
     MG_FOR_INTERIOR(g, x, y) { const long long o = mg_off(g, x, y); s += a[o] * b[o]; }
     const double t = block_reduce<false>(s, lds);
-    if (threadIdx.x == 0) part[blockIdx.x] = t;
+    if (threadIdx.x == 0) *slot = t;
 }
+__global__ __launch_bounds__(kBlock) void k_mg_dot(const Geom g, const double* __restrict__ a, const double* __restrict__ b,
+                                                   double* __restrict__ part) { mg_dot(g, a, b, part + blockIdx.x); }
 
 // partials of ||b - A x||^2 (REL_2NORM diagnostics: the true residual, matrix_free_system.cpp:457-463)
 __global__ __launch_bounds__(kBlock) void k_mg_resid2(const Geom g, const double* __restrict__ b, const double* __restrict__ x,
@@ -230,7 +255,5 @@ __global__ __launch_bounds__(kBlock) void k_mg_resid2(const Geom g, const double
     const double t = block_reduce<false>(s, lds);
     if (threadIdx.x == 0) part[blockIdx.x] = t;
 }
-
-#undef MG_FOR_INTERIOR
 
 }  // namespace mi355cg

@@ -1021,34 +1021,58 @@ int mg_build(mi355cg_ctx* c, int kind, MgHier** out, int cycle = MI355CG_CYCLE_F
     return MI355CG_OK;
 }
 
+// The fp64 V-cycle of a single solve (act == nullptr) or of the active systems of a batch.  The two differ in how a launch goes
+// out and in where a level keeps its vectors, and in nothing else:
+//   single   k_mg_X on dim3(blocks); the vectors of MgLevel
+//   batch    k_mgb_X, whose arguments are k_mg_X's behind act, on dim3(blocks, act->n): a row of blocks per active system; the
+//            vectors of system 0 in MgBatchWs (the kernels add a system's stride)
+struct MgVecs { double *rhs, *a, *out; };
+struct MgCycle {
+    mi355cg_ctx* c;
+    const MgbAct* act;
+    template <class... K, class... A>
+    void launch(void (*single)(K...), void (*batched)(MgbAct, K...), int blocks, A... args) const {
+        if (act) hipLaunchKernelGGL(batched, dim3(blocks, act->n), dim3(kBlock), 0, c->stream, *act, static_cast<K>(args)...);
+        else hipLaunchKernelGGL(single, dim3(blocks), dim3(kBlock), 0, c->stream, static_cast<K>(args)...);
+    }
+    MgVecs vecs(int l) const {                                   // a level has no vector it does not need: nullptr
+        if (!act) return {c->mg->lv[l].rhs, c->mg->lv[l].a, c->mg->lv[l].out};
+        const MgBatchWs& W = *c->batch;
+        auto at = [&](long long off) { return off < 0 ? nullptr : W.base + off; };
+        return {at(W.lv[l].rhs), at(W.lv[l].a), at(W.lv[l].out)};
+    }
+};
+
 // out = V(rhs, l) on level l's vectors.  dot != nullptr (level 0): the last launch also leaves the partials of (rhs, out) there.
-void mg_vcycle(mi355cg_ctx* c, int l, const double* rhs, double* out, double* dot) {
-    const MgHier& H = *c->mg;
+void mg_vcycle(const MgCycle& cy, int l, const double* rhs, double* out, double* dot) {
+    const MgHier& H = *cy.c->mg;
     const MgLevel& L = H.lv[l];
-    const hipStream_t st = c->stream;
-    const dim3 grid(L.grid), blk(kBlock);
-    if (l + 1 == (int)H.lv.size()) {
-        hipLaunchKernelGGL(k_mg_coarse, dim3(H.ncoarse), blk, 0, st, H.ncoarse, (const double*)H.inv, (const int*)H.coff, rhs, out);
-        if (dot) hipLaunchKernelGGL(k_mg_dot, grid, blk, 0, st, L.g, rhs, (const double*)out, dot);
+    if (l + 1 == (int)H.lv.size()) {                             // k_mgb_coarse walks the active list itself: one row of blocks
+        const dim3 grid(H.ncoarse), blk(kBlock);
+        if (cy.act) hipLaunchKernelGGL(k_mgb_coarse, grid, blk, 0, cy.c->stream, *cy.act, H.ncoarse, (const double*)H.inv, (const int*)H.coff, rhs, out);
+        else hipLaunchKernelGGL(k_mg_coarse, grid, blk, 0, cy.c->stream, H.ncoarse, (const double*)H.inv, (const int*)H.coff, rhs, out);
+        if (dot) cy.launch(k_mg_dot, k_mgb_dot, L.grid, L.g, rhs, out, dot);
         return;
     }
     const MgLevel& C = H.lv[l + 1];
+    double* const a = cy.vecs(l).a;
+    const MgVecs cv = cy.vecs(l + 1);
     const bool nested = L.g.N == 2 * C.g.N;
-    hipLaunchKernelGGL((k_mg_smooth<true, false>), grid, blk, 0, st, L.g, kMgOmega, rhs, (const double*)nullptr, L.a, (double*)nullptr);
-    hipLaunchKernelGGL((k_mg_smooth<false, false>), grid, blk, 0, st, L.g, kMgOmega, rhs, (const double*)L.a, out, (double*)nullptr);
+    cy.launch(k_mg_smooth<true, false>, k_mgb_smooth<true, false>, L.grid, L.g, kMgOmega, rhs, nullptr, a, nullptr);
+    cy.launch(k_mg_smooth<false, false>, k_mgb_smooth<false, false>, L.grid, L.g, kMgOmega, rhs, a, out, nullptr);
     if (nested) {
-        hipLaunchKernelGGL(k_mg_restrict, dim3(C.grid), blk, 0, st, L.g, C.g, rhs, (const double*)out, C.rhs);
-    } else {                            // L.a is free until the first post-sweep: it holds s = rhs - A out for the gather
+        cy.launch(k_mg_restrict, k_mgb_restrict, C.grid, L.g, C.g, rhs, out, cv.rhs);
+    } else {                            // a is free until the first post-sweep: it holds s = rhs - A out for the gather
         const double scale = (double)((long long)C.g.N * C.g.N) / (double)((long long)L.g.N * L.g.N);
-        hipLaunchKernelGGL(k_mg_residual, grid, blk, 0, st, L.g, rhs, (const double*)out, L.a);
-        hipLaunchKernelGGL(k_mg_restrict_nn, dim3(C.grid), blk, 0, st, L.g, C.g, scale, (const double*)L.a, C.rhs);
+        cy.launch(k_mg_residual, k_mgb_residual, L.grid, L.g, rhs, out, a);
+        cy.launch(k_mg_restrict_nn, k_mgb_restrict_nn, C.grid, L.g, C.g, scale, a, cv.rhs);
     }
-    mg_vcycle(c, l + 1, C.rhs, C.out, nullptr);
-    if (nested) hipLaunchKernelGGL(k_mg_prolong, grid, blk, 0, st, L.g, C.g, (const double*)C.out, out);
-    else hipLaunchKernelGGL(k_mg_prolong_nn, grid, blk, 0, st, L.g, C.g, (const double*)C.out, out);
-    hipLaunchKernelGGL((k_mg_smooth<false, false>), grid, blk, 0, st, L.g, kMgOmega, rhs, (const double*)out, L.a, (double*)nullptr);
-    if (dot) hipLaunchKernelGGL((k_mg_smooth<false, true>), grid, blk, 0, st, L.g, kMgOmega, rhs, (const double*)L.a, out, dot);
-    else hipLaunchKernelGGL((k_mg_smooth<false, false>), grid, blk, 0, st, L.g, kMgOmega, rhs, (const double*)L.a, out, (double*)nullptr);
+    mg_vcycle(cy, l + 1, cv.rhs, cv.out, nullptr);
+    if (nested) cy.launch(k_mg_prolong, k_mgb_prolong, L.grid, L.g, C.g, cv.out, out);
+    else cy.launch(k_mg_prolong_nn, k_mgb_prolong_nn, L.grid, L.g, C.g, cv.out, out);
+    cy.launch(k_mg_smooth<false, false>, k_mgb_smooth<false, false>, L.grid, L.g, kMgOmega, rhs, out, a, nullptr);
+    if (dot) cy.launch(k_mg_smooth<false, true>, k_mgb_smooth<false, true>, L.grid, L.g, kMgOmega, rhs, a, out, dot);
+    else cy.launch(k_mg_smooth<false, false>, k_mgb_smooth<false, false>, L.grid, L.g, kMgOmega, rhs, a, out, nullptr);
 }
 
 // ---- the fp32 V-cycle (MI355CG_CYCLE_F32; kernels in mg_kernels_f32.h) -----------------------------------
@@ -1227,7 +1251,7 @@ int solve_mg(mi355cg_ctx* c, const mi355cg_params* prm, mi355cg_iter_cb cb, void
         double rz = 0, pq = 0;
         if (H.cycle == MI355CG_CYCLE_F32) { if (int rc = mg_apply32(c, c->r, H.z, nm[MG_RMAX])) return rc; }   // nm: of the last update
         else
-        mg_vcycle(c, 0, c->r, H.z, H.part);                                                  // z = M r, partials of (r, z)
+        mg_vcycle(MgCycle{c, nullptr}, 0, c->r, H.z, H.part);                                // z = M r, partials of (r, z)
         if (int rc = fetch(1, &rz)) return rc;
         const double beta = it == 0 ? 0.0 : rz / rho;
         rho = rz;
@@ -1325,40 +1349,6 @@ int mg_batch_ensure(mi355cg_ctx* c, int nsys, int stage_sys) {
     return MI355CG_OK;
 }
 
-// mg_vcycle for the active systems: the same launches in the same order, each with a row of blocks per active system
-void mg_vcycle_batch(mi355cg_ctx* c, const MgbAct& act, int l, long long rhs, long long out, double* dot) {
-    const MgHier& H = *c->mg;
-    const MgBatchWs& W = *c->batch;
-    const MgLevel& L = H.lv[l];
-    const hipStream_t st = c->stream;
-    const dim3 grid(L.grid, act.n), blk(kBlock);
-    double* const B = W.base;
-    if (l + 1 == (int)H.lv.size()) {
-        hipLaunchKernelGGL(k_mgb_coarse, dim3(H.ncoarse), blk, 0, st, act, H.ncoarse, (const double*)H.inv, (const int*)H.coff, (const double*)(B + rhs), B + out);
-        if (dot) hipLaunchKernelGGL(k_mgb_dot, grid, blk, 0, st, act, L.g, (const double*)(B + rhs), (const double*)(B + out), dot);
-        return;
-    }
-    const MgLevel& C = H.lv[l + 1];
-    const dim3 cgrid(C.grid, act.n);
-    const long long La = W.lv[l].a, Crhs = W.lv[l + 1].rhs, Cout = W.lv[l + 1].out;
-    const bool nested = L.g.N == 2 * C.g.N;
-    hipLaunchKernelGGL((k_mgb_smooth<true, false>), grid, blk, 0, st, act, L.g, kMgOmega, (const double*)(B + rhs), (const double*)nullptr, B + La, (double*)nullptr);
-    hipLaunchKernelGGL((k_mgb_smooth<false, false>), grid, blk, 0, st, act, L.g, kMgOmega, (const double*)(B + rhs), (const double*)(B + La), B + out, (double*)nullptr);
-    if (nested) {
-        hipLaunchKernelGGL(k_mgb_restrict, cgrid, blk, 0, st, act, L.g, C.g, (const double*)(B + rhs), (const double*)(B + out), B + Crhs);
-    } else {
-        const double scale = (double)((long long)C.g.N * C.g.N) / (double)((long long)L.g.N * L.g.N);
-        hipLaunchKernelGGL(k_mgb_residual, grid, blk, 0, st, act, L.g, (const double*)(B + rhs), (const double*)(B + out), B + La);
-        hipLaunchKernelGGL(k_mgb_restrict_nn, cgrid, blk, 0, st, act, L.g, C.g, scale, (const double*)(B + La), B + Crhs);
-    }
-    mg_vcycle_batch(c, act, l + 1, Crhs, Cout, nullptr);
-    if (nested) hipLaunchKernelGGL(k_mgb_prolong, grid, blk, 0, st, act, L.g, C.g, (const double*)(B + Cout), B + out);
-    else hipLaunchKernelGGL(k_mgb_prolong_nn, grid, blk, 0, st, act, L.g, C.g, (const double*)(B + Cout), B + out);
-    hipLaunchKernelGGL((k_mgb_smooth<false, false>), grid, blk, 0, st, act, L.g, kMgOmega, (const double*)(B + rhs), (const double*)(B + out), B + La, (double*)nullptr);
-    if (dot) hipLaunchKernelGGL((k_mgb_smooth<false, true>), grid, blk, 0, st, act, L.g, kMgOmega, (const double*)(B + rhs), (const double*)(B + La), B + out, dot);
-    else hipLaunchKernelGGL((k_mgb_smooth<false, false>), grid, blk, 0, st, act, L.g, kMgOmega, (const double*)(B + rhs), (const double*)(B + La), B + out, (double*)nullptr);
-}
-
 // solve_mg for nrhs systems at once.  b_dev, x_dev: packed vectors in device memory (they may be the same buffer: b is consumed
 // before x is written).  Every system runs solve_mg's tests on its own numbers in solve_mg's order; one that stops leaves the
 // active list and no later launch touches its vectors.  Three host waits per iteration, as there.
@@ -1433,7 +1423,7 @@ int solve_mg_batch(mi355cg_ctx* c, const mi355cg_params* prm, int nrhs, const do
         if (n == 0) break;
         if (stop_flag && *stop_flag) { for (int k = 0; k < n; ++k) S[act.sys[k]].interrupted = true; break; }
         const dim3 grid(G, n);
-        mg_vcycle_batch(c, act, 0, W.r, W.z, W.part);             // z = M r, partials of (r, z)
+        mg_vcycle(MgCycle{c, &act}, 0, B + W.r, B + W.z, W.part); // z = M r, partials of (r, z)
         if (int rc = fetch(1, 1)) return rc;
         for (int k = 0; k < n; ++k) {
             Sys& s = S[act.sys[k]];
@@ -2333,7 +2323,7 @@ int mi355cg_apply_preconditioner(mi355cg_handle c, const double* r, double* z) {
         for (long long i = 0; i < c->pk_len; ++i) rmax = std::max(rmax, std::fabs(r[i]));
         if (int rc = mg_apply32(c, c->mg->q, c->mg->z, rmax)) return rc;
     } else
-    mg_vcycle(c, 0, c->mg->q, c->mg->z, nullptr);
+    mg_vcycle(MgCycle{c, nullptr}, 0, c->mg->q, c->mg->z, nullptr);
     HIPCK(hipGetLastError());
     return download_packed<double>(c, c->mg->z, z);
 }

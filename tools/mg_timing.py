@@ -20,9 +20,9 @@ Usage: python tools/mg_timing.py [N ...]      (default 256 1024 4096 8192; write
 --batch: batched solves (mi355cg_solve_batch_device) against one solve per right-hand side, MG_ANY, fp64 cycle, REL_2NORM 1e-8, seeded
 standard-normal right-hand sides.  Per N and nrhs: one warm-up of each path, then three repetitions alternating {nrhs single solves, one
 batch}; reported are the best sum of the single solves' wall times (set_rhs / get_solution not timed) and the best wall time of the batch
-call on vectors that are already in device memory.  --baseline-tree DIR adds the single solves of another built checkout (the commit
-before the feature) in a child process of the same job: the yardstick.
-       python tools/mg_timing.py --batch [--baseline-tree DIR] [N ...]
+call on vectors that are already in device memory.  --baseline-tree DIR adds the same measurement of another built checkout (the
+commit before a change) in a child process of the same job: the yardstick.  Its single solves, and its batch call if it has one.
+       python tools/mg_timing.py --batch [--baseline-tree DIR] [--nrhs 4,16] [--out FILE] [N ...]
                                                      (default 100 258 1000 2002 4096, nrhs 4 16 64, at N >= 4096 only 4;
                                                       writes profiles/mg_batch_time_to_solution.txt)"""
 import json
@@ -180,8 +180,11 @@ def main_f32(ns, baseline_tree):
     print("wrote", OUT_F32)
 
 
+NRHS = None                                          # --nrhs: these counts at every N
+
+
 def batch_counts(n):
-    return [4] if n >= 4096 else [4, 16, 64]
+    return NRHS or ([4] if n >= 4096 else [4, 16, 64])
 
 
 def batch_rhs(n, size, nrhs):
@@ -206,29 +209,49 @@ def sequential_solves(h, rhs, p):
     return total, its
 
 
+def batch_best_of_three(h, rhs, with_batch=True):
+    """One warm-up of each path, then three repetitions alternating {the single solves, one batch on device vectors}: the best sum
+    of the single solves' wall times, the best wall time of the batch call (None without one) and the iteration counts."""
+    import torch
+    p = batch_params()
+    dev = torch.from_numpy(rhs).cuda() if with_batch else None
+    sequential_solves(h, rhs, p)
+    if with_batch:
+        h.solve_batch(p, dev)
+    seq, bat, its = [], [], None
+    for _ in range(3):
+        t, its = sequential_solves(h, rhs, p)
+        seq.append(t)
+        if with_batch:
+            t0 = time.perf_counter()
+            _, res = h.solve_batch(p, dev)
+            bat.append(time.perf_counter() - t0)
+            assert [r.iterations for r in res] == its
+    if with_batch:
+        del dev
+        h.batch_release()
+    return min(seq), (min(bat) if with_batch else None), its
+
+
 def batch_baseline_worker(ns):
-    """Child process of --batch --baseline-tree: the other checkout's package, which has no batched solve.  Prints one JSON line:
-    {N: {nrhs: best sum of wall times}}."""
+    """Child process of --batch --baseline-tree: the other checkout's package, which may have no batched solve.  Prints one JSON line:
+    {N: {nrhs: [best sum of wall times, best wall time of the batch call or null]}}."""
     out = {}
     for n in ns:
         s = isa.MatrixFreeSystem(n, n, 1.0, 2.0, 1.0, 2.0)
         s.set_preconditioner(isa.PRECOND_MG_ANY)
-        out[n] = {}
-        for nrhs in batch_counts(n):
-            rhs = batch_rhs(n, s.size(), nrhs)
-            sequential_solves(s._handle, rhs, batch_params())
-            out[n][nrhs] = min(sequential_solves(s._handle, rhs, batch_params())[0] for _ in range(3))
-        s._handle.close()
+        h = s._handle
+        out[n] = {nrhs: batch_best_of_three(h, batch_rhs(n, s.size(), nrhs), hasattr(h, "solve_batch"))[:2] for nrhs in batch_counts(n)}
+        h.close()
     print("BASELINE " + json.dumps(out), flush=True)
 
 
-def main_batch(ns, baseline_tree):
-    import torch
+def main_batch(ns, baseline_tree, out_path):
     base = None
     if baseline_tree:
         env = dict(os.environ, MG_TIMING_TREE=os.path.abspath(baseline_tree))
-        txt = subprocess.run([sys.executable, os.path.abspath(__file__), "--batch-baseline-worker"] + [str(n) for n in ns], env=env,
-                             check=True, capture_output=True, text=True, timeout=900).stdout
+        cmd = [sys.executable, os.path.abspath(__file__), "--batch-baseline-worker"] + (["--nrhs", ",".join(map(str, NRHS))] if NRHS else [])
+        txt = subprocess.run(cmd + [str(n) for n in ns], env=env, check=True, capture_output=True, text=True, timeout=900).stdout
         base = json.loads([l for l in txt.splitlines() if l.startswith("BASELINE ")][-1][len("BASELINE "):])
     lines = ["# time to solution of nrhs right-hand sides on one MI355X: one batched solve (mi355cg_solve_batch_device) against nrhs single "
              "solves (tools/mg_timing.py --batch)",
@@ -236,44 +259,35 @@ def main_batch(ns, baseline_tree):
              "repetitions alternating, the best of each",
              "# seq = sum of the wall times of mi355cg_solve (set_rhs / get_solution not timed); batch = wall time of the batch call, "
              "vectors already in device memory",
-             "# base_seq = seq of the --baseline-tree checkout (the commit before the feature) in a child process of the same job"
-             if base else "# no --baseline-tree: base_seq not measured",
-             f"# {'N':>5} {'nrhs':>4} {'iters':>7} {'base_seq_ms':>11} {'seq_ms':>9} {'batch_ms':>9} {'batch/base':>10} {'batch/seq':>9} {'seq/base':>8}"]
+             "# base_seq, base_batch = seq and batch of the --baseline-tree checkout (the commit before the change; '-': it has no batched "
+             "solve) in a child process of the same job"
+             if base else "# no --baseline-tree: base_seq and base_batch not measured",
+             f"# {'N':>5} {'nrhs':>4} {'iters':>7} {'base_seq_ms':>11} {'seq_ms':>9} {'batch_ms':>9} {'batch/base':>10} {'batch/seq':>9} {'seq/base':>8} "
+             f"{'base_batch_ms':>13} {'batch/base_batch':>16}"]
     print("\n".join(lines), flush=True)
+    num = lambda v, w, scale=1.0, prec=3: f"{v * scale:>{w}.{prec}f}" if v is not None else f"{'-':>{w}}"      # noqa: E731
     for n in ns:
         s = isa.MatrixFreeSystem(n, n, 1.0, 2.0, 1.0, 2.0)
         s.set_preconditioner(isa.PRECOND_MG_ANY)
-        h = s._handle
         for nrhs in batch_counts(n):
-            rhs = batch_rhs(n, s.size(), nrhs)
-            dev = torch.from_numpy(rhs).cuda()
-            p = batch_params()
-            sequential_solves(h, rhs, p)
-            h.solve_batch(p, dev)
-            seq, bat, its = [], [], None
-            for _ in range(3):
-                t, its = sequential_solves(h, rhs, p)
-                seq.append(t)
-                t0 = time.perf_counter()
-                _, res = h.solve_batch(p, dev)
-                bat.append(time.perf_counter() - t0)
-                assert [r.iterations for r in res] == its
-            b = base[str(n)][str(nrhs)] if base else None
-            line = (f"  {n:>5} {nrhs:>4} {f'{min(its)}..{max(its)}':>7} " + (f"{b * 1e3:>11.3f}" if base else f"{'-':>11}") +
-                    f" {min(seq) * 1e3:>9.3f} {min(bat) * 1e3:>9.3f} " + (f"{min(bat) / b:>10.3f}" if base else f"{'-':>10}") +
-                    f" {min(bat) / min(seq):>9.3f} " + (f"{min(seq) / b:>8.3f}" if base else f"{'-':>8}"))
+            seq, bat, its = batch_best_of_three(s._handle, batch_rhs(n, s.size(), nrhs))
+            b, bb = base[str(n)][str(nrhs)] if base else (None, None)
+            line = (f"  {n:>5} {nrhs:>4} {f'{min(its)}..{max(its)}':>7} {num(b, 11, 1e3)} {seq * 1e3:>9.3f} {bat * 1e3:>9.3f} "
+                    f"{num(b and bat / b, 10)} {bat / seq:>9.3f} {num(b and seq / b, 8)} {num(bb, 13, 1e3)} {num(bb and bat / bb, 16)}")
             lines.append(line)
             print(line, flush=True)
-            del dev
-            h.batch_release()
-        h.close()
-    with open(OUT_BATCH, "w") as f:
+        s._handle.close()
+    with open(out_path, "w") as f:
         f.write("\n".join(lines) + "\n")
-    print("wrote", OUT_BATCH)
+    print("wrote", out_path)
 
 
 if __name__ == "__main__":
     args = sys.argv[1:]
+    if "--nrhs" in args:
+        i = args.index("--nrhs")
+        NRHS = [int(v) for v in args[i + 1].split(",")]
+        del args[i:i + 2]
     if args and args[0] == "--baseline-worker":
         baseline_worker([int(a) for a in args[1:]])
         sys.exit(0)
@@ -281,7 +295,11 @@ if __name__ == "__main__":
         batch_baseline_worker([int(a) for a in args[1:]])
         sys.exit(0)
     kind = "mg"
-    cycle, baseline_tree = "f64", None
+    cycle, baseline_tree, out_path = "f64", None, OUT_BATCH
+    if "--out" in args:
+        i = args.index("--out")
+        out_path = os.path.abspath(args[i + 1])
+        del args[i:i + 2]
     batch = "--batch" in args
     if batch:
         args.remove("--batch")
@@ -302,7 +320,7 @@ if __name__ == "__main__":
         if kind not in OUT:
             sys.exit(f"--kind must be one of {sorted(OUT)}")
     if batch:
-        main_batch([int(a) for a in args] or SIZES_BATCH, baseline_tree)
+        main_batch([int(a) for a in args] or SIZES_BATCH, baseline_tree, out_path)
     elif cycle == "f32":
         if kind != "any":
             sys.exit("--cycle f32 goes with --kind any")
