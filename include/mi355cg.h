@@ -34,6 +34,10 @@
  *   mi355cg_set_shift / _get_shift the operator becomes A - sigma I (implicit time steps, screened Poisson, shift-and-invert)
  *   mi355cg_time_steps             theta-scheme steps of u_t = A u - g with the state kept on the device
  *   mi355cg_get_solution_device    the x of the last solve into device memory
+ *   mi355cg_eigs / _eigs_device    the lowest eigenpairs by a block iteration preconditioned with the V-cycle
+ *   mi355cg_eigs_release           free the workspace the eigen solves keep on the handle
+ *   mi355cg_block_gram / _combine  the block kernels of that iteration on host vectors
+ *   mi355cg_rayleigh_ritz          its Rayleigh-Ritz step (pure host arithmetic, no GPU needed)
  *
  * Plain pointers and sizes only; no C++/torch types.  All host vectors are in the reference's
  * PACKED unknown order (bottom-right block row-major, then the upper block row-major;
@@ -300,6 +304,67 @@ int  mi355cg_get_shift(mi355cg_handle h, double *sigma);
 int  mi355cg_time_steps(mi355cg_handle h, const mi355cg_params *params, double tau, double theta, int nsteps,
                         const volatile int *stop_flag, mi355cg_results *out /* nsteps */, int *steps_done);
 int  mi355cg_get_solution_device(mi355cg_handle h, double *x_dev);   /* packed, device memory of the handle's GPU */
+
+/* ---- lowest eigenpairs of the operator (extension: the reference solves linear systems only) ------------------------------
+ * mi355cg_eigs: the nev lowest eigenpairs of K = -(A - sigma I), sigma the handle's shift, by a locally optimal block
+ * preconditioned iteration (LOBPCG) whose preconditioner is one fp64 V-cycle of the handle's multigrid hierarchy: per iteration
+ * one V-cycle and one operator apply per active column and no inner solve.  Sign convention: lambda[j] > 0 ascending and
+ * (A - sigma I) v_j = -lambda[j] v_j, so with sigma = 0 the lambda are the Laplacian's eigenvalues in the usual positive sense and
+ * with a shift they are the unshifted ones + sigma.  x holds `block` packed vectors, nev <= block <= MI355CG_EIG_BLOCK_MAX: the
+ * start block on entry (any linearly independent vectors; the columns past nev are guard vectors that speed up the last wanted
+ * pairs), the Ritz vectors on return, the first nev of them the eigenvectors, orthonormal in the Euclidean inner product of
+ * packed vectors up to rounding.  lambda and resid have `block` entries: the Ritz values and res_j = ||K v_j - lambda_j v_j||_2 /
+ * (lambda_j ||v_j||_2) of the returned vectors.  The iteration stops when res_j <= tol for all j < nev (CONVERGED, converged = 1),
+ * at max_iterations (ITERATIONS) or when *stop_flag is non-zero (INTERRUPTED; read once per iteration, after the two other
+ * tests).  Locking rule: a column, guard columns included, whose res_j <= tol gets no new search direction and no V-cycle in that
+ * iteration (soft locking: it stays in the Rayleigh-Ritz basis, so it keeps being rotated with the others); without it a full
+ * block of converged directions makes the basis singular.  The Rayleigh-Ritz step (mi355cg_rayleigh_ritz) runs on the host on the
+ * <= 48 x 48 Gram matrices the device reduces in a fixed order; a basis [X, W, P] it refuses is retried once as [X, W] (counted in
+ * p_drops), and if that is refused too the call ends with stop_reason BREAKDOWN, the last good vectors and MI355CG_OK.  Two calls
+ * with the same input give the same bits.  The handle's right-hand side, last solution and residual, a pending guess and the shift
+ * are untouched.  MI355CG_ERR_INVALID, before anything is allocated or written: a null argument (stop_flag may be null), nev < 1,
+ * block < nev, block > MI355CG_EIG_BLOCK_MAX, block > mi355cg_size(h), tol not finite or <= 0, max_iterations < 1, a preconditioner
+ * set with MI355CG_CYCLE_F32.  MI355CG_ERR_STATE: no preconditioner is set (CSR, slab / part and MI355CG_F32_MIXED handles cannot
+ * have one).  Workspace: allocated by the first call, kept on the handle, regrown for a larger block, freed by
+ * mi355cg_eigs_release, by every mi355cg_set_preconditioner* call that is not refused and by mi355cg_destroy; a failed allocation
+ * returns MI355CG_ERR_HIP, leaks nothing and leaves the handle usable.  Memory per column of the block (computed from the layout,
+ * not measured): 11 storage vectors (X, A X, P, A P twice, R, Z, A W) plus the V-cycle's vectors of one system (level 0's work
+ * vector and three vectors per coarser level: 2.04 storage vectors at n = 1000), rounded up to whole storage vectors: 14 x 8 B x
+ * the padded storage length for a hierarchy of two or more levels (11 for one level), 88 MB per column at n = 1000 and 1.4 GB for a
+ * block of 16; besides that <= 38 MB of reduction partials.  The host entry point adds `block` packed vectors of staging.
+ * mi355cg_eigs_device: the same with x in device memory of the handle's GPU (lambda, resid and out stay host memory).
+ * mi355cg_block_gram: c[i * nb + j] = (a_i, b_j) for na and nb <= 48 packed host vectors, each entry summed in a fixed order (two
+ * calls give the same bits); mi355cg_block_gram_indexed: the same for the vectors ia[0 .. nia) of a and ib[0 .. nib) of b (c is
+ * nia x nib; a null list = all vectors in order) -- the device addresses subsets through such lists, never through copies.
+ * mi355cg_block_combine: y_j = sum_i s_i coef[i * m + j], k <= 48 inputs, m <= 16 outputs, i ascending, unfused.  These are the
+ * kernels the iteration is built from, on a temporary buffer; they need a whole-grid handle (not CSR, not a slab / part:
+ * MI355CG_ERR_INVALID) but no preconditioner.
+ * mi355cg_rayleigh_ritz (pure host arithmetic, no GPU needed): for the k x k pair G = S^T S, H = S^T K S (row-major, k <= 48; both
+ * are symmetrised) theta ascending and coef (k x k, row-major, column j = Ritz vector j) with coef^T G coef = I, coef^T H coef =
+ * diag(theta): D = diag(G)^-1/2, Cholesky D G D = L L^T, a cyclic Jacobi iteration on L^-1 D H D L^-T, coef = D L^-T Y.
+ * MI355CG_ERR_STATE for a refused basis: a diagonal entry of G not positive and finite, a failed Cholesky, min diag(L) < 1e-6.  */
+#define MI355CG_EIG_BLOCK_MAX 16
+#define MI355CG_EIG_CONVERGED   0
+#define MI355CG_EIG_ITERATIONS  1
+#define MI355CG_EIG_INTERRUPTED 2
+#define MI355CG_EIG_BREAKDOWN   3
+typedef struct mi355cg_eig_results {
+    int iterations;        /* Rayleigh-Ritz steps on [X, W, P] that were taken                                   */
+    int converged;         /* 1: res_j <= tol for all j < nev                                                    */
+    int stop_reason;       /* MI355CG_EIG_*                                                                      */
+    int p_drops;           /* iterations that fell back to the basis [X, W]                                      */
+    double solve_seconds;  /* wall time of the call's iteration, transfers of the device entry point included    */
+} mi355cg_eig_results;
+int  mi355cg_eigs(mi355cg_handle h, int nev, int block, double tol, int max_iterations, double *x, double *lambda, double *resid,
+                  const volatile int *stop_flag, mi355cg_eig_results *out);
+int  mi355cg_eigs_device(mi355cg_handle h, int nev, int block, double tol, int max_iterations, double *x_dev, double *lambda,
+                         double *resid, const volatile int *stop_flag, mi355cg_eig_results *out);
+int  mi355cg_eigs_release(mi355cg_handle h);
+int  mi355cg_block_gram(mi355cg_handle h, int na, const double *a, int nb, const double *b, double *c);
+int  mi355cg_block_gram_indexed(mi355cg_handle h, int na, const double *a, int nia, const int *ia, int nb, const double *b,
+                                int nib, const int *ib, double *c);
+int  mi355cg_block_combine(mi355cg_handle h, int k, const double *s, int m, const double *coef, double *y);
+int  mi355cg_rayleigh_ritz(int k, const double *g, const double *hmat, double *theta, double *coef);
 
 /* ---- measurement hooks (bench.py) ------------------------------------------------------------ */
 /* Per-kernel device time of the last mi355cg_solve, measured with HIP events on the solve

@@ -34,11 +34,16 @@ EXPORTS = [
     "mi355cg_set_initial_guess", "mi355cg_set_initial_guess_device", "mi355cg_use_solution_as_initial_guess",
     "mi355cg_solve_batch_from", "mi355cg_solve_batch_device_from",
     "mi355cg_set_shift", "mi355cg_get_shift", "mi355cg_time_steps", "mi355cg_get_solution_device",
+    "mi355cg_eigs", "mi355cg_eigs_device", "mi355cg_eigs_release", "mi355cg_block_gram", "mi355cg_block_gram_indexed",
+    "mi355cg_block_combine", "mi355cg_rayleigh_ritz",
 ]
 DECOMP_ROWS, DECOMP_2D = 0, 1
 PRECOND_NONE, PRECOND_MG, PRECOND_MG_ANY = 0, 1, 2
 CYCLE_F64, CYCLE_F32 = 0, 1
 BATCH_MAX = 64          # MI355CG_BATCH_MAX
+EIG_BLOCK_MAX = 16      # MI355CG_EIG_BLOCK_MAX
+EIG_BASIS_MAX = 48      # vectors of a Rayleigh-Ritz basis, and of a group of block_gram
+EIG_CONVERGED, EIG_ITERATIONS, EIG_INTERRUPTED, EIG_BREAKDOWN = range(4)
 
 
 class Params(C.Structure):
@@ -56,6 +61,11 @@ class Results(C.Structure):
                 ("final_error_norm", C.c_double), ("r_norm2", C.c_double),
                 ("initial_r_norm2", C.c_double), ("solve_seconds", C.c_double),
                 ("refine_true_rel", C.c_double), ("refine_outer", C.c_int), ("loop_seconds", C.c_double)]
+
+
+class EigResults(C.Structure):
+    _fields_ = [("iterations", C.c_int), ("converged", C.c_int), ("stop_reason", C.c_int), ("p_drops", C.c_int),
+                ("solve_seconds", C.c_double)]
 
 
 class HaloMsg(C.Structure):
@@ -185,6 +195,15 @@ def load():
     L.mi355cg_get_shift.argtypes = [H, DBP]
     L.mi355cg_time_steps.argtypes = [H, C.POINTER(Params), C.c_double, C.c_double, C.c_int, C.c_void_p, C.POINTER(Results), IP]
     L.mi355cg_get_solution_device.argtypes = [H, C.c_void_p]
+    if hasattr(L, "mi355cg_eigs"):               # absent from an older build loaded through MI355CG_LIB
+        # block eigensolver: vectors as plain addresses (host arrays for _eigs, device memory for _eigs_device)
+        for fn in (L.mi355cg_eigs, L.mi355cg_eigs_device):
+            fn.argtypes = [H, C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(EigResults)]
+        L.mi355cg_eigs_release.argtypes = [H]
+        L.mi355cg_block_gram.argtypes = [H, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.mi355cg_block_gram_indexed.argtypes = [H, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.mi355cg_block_combine.argtypes = [H, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.mi355cg_rayleigh_ritz.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     if hasattr(L, "mi355cg_get_xfold"):          # absent from an older build loaded through MI355CG_LIB
         L.mi355cg_get_xfold.argtypes = [H, IP, IP]
     _lib = L

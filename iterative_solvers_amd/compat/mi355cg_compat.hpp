@@ -24,6 +24,7 @@
 #include <iostream>
 #include <limits>
 #include <memory>
+#include <random>
 #include <sstream>
 #include <stdexcept>
 #include <string>
@@ -454,6 +455,46 @@ public:
         return x;
     }
     void batchRelease() { mi355cg_compat::check(mi355cg_batch_release(ctx_->h)); }
+    // Extension: the nev lowest eigenpairs of this system's operator by a block preconditioned iteration with one multigrid V-cycle
+    // per vector and iteration (mi355cg_eigs; needs setPreconditioner with the fp64 cycle first).  lambda > 0 ascending with
+    // A v = -lambda v, the vectors orthonormal.  block = 0: min(16, nev + max(2, nev / 4)), capped by size(); the extra columns are
+    // guard vectors.  x0: the start block (block vectors); nullptr: standard-normal numbers from std::mt19937_64(seed) (the Python
+    // binding draws from NumPy's generator, so the two start blocks differ).  residuals and ritz_values cover all block columns.
+    // std::invalid_argument for a start block of the wrong shape and for what the library refuses as invalid;
+    // std::runtime_error without a preconditioner.
+    struct EigsResult {
+        std::vector<double> lambda;                    // nev
+        std::vector<std::vector<double>> vectors;      // nev x size()
+        std::vector<double> residuals, ritz_values;    // block
+        mi355cg_eig_results info{};
+    };
+    EigsResult eigs(int nev, int block = 0, double tol = 1e-8, int max_iterations = 200, const std::vector<std::vector<double>>* x0 = nullptr,
+                    unsigned long long seed = 0, const volatile int* stop_flag = nullptr) {
+        const size_t n = rhs.size();
+        if (block == 0) block = (int)std::min<size_t>(n, (size_t)std::min(MI355CG_EIG_BLOCK_MAX, nev + std::max(2, nev / 4)));
+        if (nev < 1 || block < nev || block > MI355CG_EIG_BLOCK_MAX) throw std::invalid_argument("eigs: 1 <= nev <= block <= MI355CG_EIG_BLOCK_MAX is required");
+        std::vector<double> xp(n * (size_t)block);
+        if (x0) {
+            if (x0->size() != (size_t)block) throw std::invalid_argument("eigs: the start block does not have `block` vectors");
+            for (int j = 0; j < block; ++j) {
+                if ((*x0)[(size_t)j].size() != n) throw std::invalid_argument("eigs: vector size does not match the system");
+                std::copy((*x0)[(size_t)j].begin(), (*x0)[(size_t)j].end(), xp.begin() + (std::ptrdiff_t)((size_t)j * n));
+            }
+        } else {
+            std::mt19937_64 gen(seed);
+            std::normal_distribution<double> normal(0.0, 1.0);
+            for (double& v : xp) v = normal(gen);
+        }
+        EigsResult r;
+        r.ritz_values.resize((size_t)block);
+        r.residuals.resize((size_t)block);
+        mi355cg_compat::check(mi355cg_eigs(ctx_->h, nev, block, tol, max_iterations, xp.data(), r.ritz_values.data(), r.residuals.data(), stop_flag, &r.info));
+        r.lambda.assign(r.ritz_values.begin(), r.ritz_values.begin() + nev);
+        r.vectors.resize((size_t)nev);
+        for (int j = 0; j < nev; ++j) r.vectors[(size_t)j].assign(xp.begin() + (std::ptrdiff_t)((size_t)j * n), xp.begin() + (std::ptrdiff_t)((size_t)(j + 1) * n));
+        return r;
+    }
+    void eigsRelease() { mi355cg_compat::check(mi355cg_eigs_release(ctx_->h)); }
     const std::shared_ptr<mi355cg_compat::Context>& context() const { return ctx_; }
     friend std::ostream& operator<<(std::ostream& os, const MatrixFreeSystem& s) {
         return os << "MatrixFreeSystem Information:\n  Dimensions: " << s.ctx_->n << "x" << s.ctx_->m << "\n  System size: " << s.size() << "\n";

@@ -251,7 +251,6 @@ __global__ __launch_bounds__(kBlock) void k_mgb_pack(const PackGeom pg, long lon
     for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < pg.pk_len; i += step) dst[i] = src[packed_to_storage(pg, i)];
 }
 
-#undef MG_FOR_INTERIOR
 #undef MGB_SLOT
 #undef MGB_SYS
 

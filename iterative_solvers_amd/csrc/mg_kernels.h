@@ -45,7 +45,7 @@ __device__ inline double mg_Av(const Geom& g, const double* __restrict__ v, int 
 __device__ inline int mg_x0(const Geom& g, int y) { return y <= g.half ? g.half + 1 : 1; }    // first interior column of row y
 
 // The row loops: block b takes interior rows 1 + b, 1 + b + gridDim.x, ...; its threads stride the row's interior columns.
-// (mg_batch_kernels.h uses the macro too and undefines it.)
+// (mg_batch_kernels.h and eig_kernels.h use the macro too; the last of them undefines it.)
 #define MG_FOR_INTERIOR(G, XI, YI)                                                                 \
     for (int YI = 1 + (int)blockIdx.x; YI <= (G).N - 1; YI += (int)gridDim.x)                      \
         for (int XI = mg_x0((G), YI) + (int)threadIdx.x; XI <= (G).N - 1; XI += kBlock)

@@ -8,6 +8,7 @@
 #include "grid_setup.h"
 #include "mg_kernels.h"
 #include "mg_batch_kernels.h"
+#include "eig_kernels.h"
 #include "mg_kernels_f32.h"
 #include "step_kernels.h"
 
@@ -104,6 +105,25 @@ struct MgBatchWs {
     int stage_cap = 0;
 };
 
+// Workspace of the block eigensolver (mi355cg_eigs*; kernels in eig_kernels.h): one allocation, column-major
+// like the batch workspace.  Column j of the block keeps its vectors in slots of `vlen` doubles at base + (j * slots + slot) * vlen:
+// X, A X, P, A P twice (ping-pong: a Rayleigh-Ritz step writes the set it does not read), the residual R (after the cycle: the
+// projected W), the cycle's result Z (after the projection: the copy mg_dir_apply keeps of its direction), A W, and from EIG_CYC
+// on what mg_vcycle needs per system -- the offsets of `cyc`, an MgBatchWs that owns nothing.
+enum { EIG_X = 0, EIG_AX = 2, EIG_P = 4, EIG_AP = 6, EIG_R = 8, EIG_Z = 9, EIG_AW = 10, EIG_CYC = 11 };
+struct EigWs {
+    int cap = 0;                        // columns the vectors hold
+    long long vlen = 0;                 // doubles per slot: the storage length rounded up to 32 (256 B)
+    int slots = 0;                      // slots per column
+    double* base = nullptr;
+    MgBatchWs cyc;                      // base, stride and the levels' offsets as mg_vcycle reads them
+    double* part = nullptr;             // block partials of the widest launch: a full symmetric gram of 48 vectors
+    double* mat = nullptr;              // two reduced matrices (48 x 48), then the coefficients of a combine (48 x 16)
+    double* mat_h = nullptr;            // pinned copy
+    double* red = nullptr;              // [column][field] sums of k_eig_resid
+    double* stage = nullptr;            // packed vectors of the host entry point, cap x pk_len
+};
+
 }  // namespace
 
 struct mi355cg_ctx {
@@ -184,6 +204,7 @@ struct mi355cg_ctx {
     hipEvent_t ev_loop[2] = {nullptr, nullptr};   // brackets the iterations of the last solve (mi355cg_results::loop_seconds)
     MgHier* mg = nullptr;               // opt-in preconditioner (mi355cg_set_preconditioner): mi355cg_solve runs solve_mg while set
     MgBatchWs* batch = nullptr;         // workspace of mi355cg_solve_batch*, nullptr until the first batch
+    EigWs* eig = nullptr;               // workspace of mi355cg_eigs*, nullptr until the first eigen solve
     bool profiling = false;
     EventPool events;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pairs[2];
@@ -1030,6 +1051,7 @@ struct MgVecs { double *rhs, *a, *out; };
 struct MgCycle {
     mi355cg_ctx* c;
     const MgbAct* act;
+    const MgBatchWs* ws = nullptr;      // the systems' vectors if they are not the batch workspace's (the eigensolver's columns)
     template <class... K, class... A>
     void launch(void (*single)(K...), void (*batched)(MgbAct, K...), int blocks, A... args) const {
         if (act) hipLaunchKernelGGL(batched, dim3(blocks, act->n), dim3(kBlock), 0, c->stream, *act, static_cast<K>(args)...);
@@ -1037,7 +1059,7 @@ struct MgCycle {
     }
     MgVecs vecs(int l) const {                                   // a level has no vector it does not need: nullptr
         if (!act) return {c->mg->lv[l].rhs, c->mg->lv[l].a, c->mg->lv[l].out};
-        const MgBatchWs& W = *c->batch;
+        const MgBatchWs& W = ws ? *ws : *c->batch;
         auto at = [&](long long off) { return off < 0 ? nullptr : W.base + off; };
         return {at(W.lv[l].rhs), at(W.lv[l].a), at(W.lv[l].out)};
     }
@@ -1482,6 +1504,367 @@ int batch_check(mi355cg_ctx* c, const mi355cg_params* prm, int nrhs, const void*
     return MI355CG_OK;
 }
 
+
+// ---- block eigensolver (mi355cg_eigs*; kernels in eig_kernels.h) --------------------------------------------
+// The Rayleigh-Ritz step on the host (k <= 48): theta ascending and coef (k x k, row-major, column j = Ritz vector j in the basis)
+// with coef^T G coef = I and coef^T H coef = diag(theta).  G and H are symmetrised on the way in.  nullptr: done; otherwise why
+// the basis is refused.
+const char* rr_solve(int k, const double* G, const double* Hm, double* theta, double* coef) {
+    const size_t kk = (size_t)k * k;
+    std::vector<double> d(k), Gs(kk), Hs(kk), L(kk, 0.0), Y(kk), M(kk), V(kk, 0.0);
+    for (int i = 0; i < k; ++i) {
+        const double gii = G[(size_t)i * k + i];
+        if (!(gii > 0.0) || !std::isfinite(gii)) return "a diagonal entry of the Gram matrix is not positive and finite";
+        d[i] = 1.0 / std::sqrt(gii);
+    }
+    for (int i = 0; i < k; ++i)
+        for (int j = 0; j < k; ++j) {
+            Gs[(size_t)i * k + j] = d[i] * (0.5 * (G[(size_t)i * k + j] + G[(size_t)j * k + i])) * d[j];
+            Hs[(size_t)i * k + j] = d[i] * (0.5 * (Hm[(size_t)i * k + j] + Hm[(size_t)j * k + i])) * d[j];
+            if (!std::isfinite(Gs[(size_t)i * k + j]) || !std::isfinite(Hs[(size_t)i * k + j])) return "an entry of the pair is not finite";
+        }
+    double lmin = DBL_MAX;
+    for (int j = 0; j < k; ++j) {                                  // G^ = L L^T
+        double v = Gs[(size_t)j * k + j];
+        for (int p = 0; p < j; ++p) v -= L[(size_t)j * k + p] * L[(size_t)j * k + p];
+        if (!(v > 0.0)) return "the Cholesky factorisation of the scaled Gram matrix failed";
+        const double ljj = std::sqrt(v);
+        L[(size_t)j * k + j] = ljj;
+        lmin = std::min(lmin, ljj);
+        for (int i = j + 1; i < k; ++i) {
+            double w = Gs[(size_t)i * k + j];
+            for (int p = 0; p < j; ++p) w -= L[(size_t)i * k + p] * L[(size_t)j * k + p];
+            L[(size_t)i * k + j] = w / ljj;
+        }
+    }
+    if (lmin < 1e-6) return "the basis is numerically dependent (min diag(L) < 1e-6)";
+    for (int c = 0; c < k; ++c)                                    // Y = L^-1 H^
+        for (int i = 0; i < k; ++i) {
+            double v = Hs[(size_t)i * k + c];
+            for (int p = 0; p < i; ++p) v -= L[(size_t)i * k + p] * Y[(size_t)p * k + c];
+            Y[(size_t)i * k + c] = v / L[(size_t)i * k + i];
+        }
+    for (int r = 0; r < k; ++r)                                    // M = Y L^-T, row by row
+        for (int i = 0; i < k; ++i) {
+            double v = Y[(size_t)r * k + i];
+            for (int p = 0; p < i; ++p) v -= L[(size_t)i * k + p] * M[(size_t)r * k + p];
+            M[(size_t)r * k + i] = v / L[(size_t)i * k + i];
+        }
+    for (int i = 0; i < k; ++i)
+        for (int j = i + 1; j < k; ++j) M[(size_t)i * k + j] = M[(size_t)j * k + i] = 0.5 * (M[(size_t)i * k + j] + M[(size_t)j * k + i]);
+    // cyclic Jacobi: M <- J^T M J until a sweep finds nothing to rotate, V <- V J
+    for (int i = 0; i < k; ++i) V[(size_t)i * k + i] = 1.0;
+    for (int sweep = 0; sweep < 64; ++sweep) {
+        int rotations = 0;
+        for (int p = 0; p < k - 1; ++p)
+            for (int q = p + 1; q < k; ++q) {
+                const double apq = M[(size_t)p * k + q];
+                const double app = M[(size_t)p * k + p], aqq = M[(size_t)q * k + q];
+                if (apq == 0.0 || std::fabs(apq) <= 0.25 * DBL_EPSILON * std::sqrt(std::fabs(app) * std::fabs(aqq))) continue;
+                ++rotations;
+                const double th = (aqq - app) / (2.0 * apq);
+                const double t = (th >= 0.0 ? 1.0 : -1.0) / (std::fabs(th) + std::sqrt(th * th + 1.0));
+                const double cs = 1.0 / std::sqrt(t * t + 1.0), sn = t * cs;
+                for (int r = 0; r < k; ++r) {                      // columns p and q
+                    const double arp = M[(size_t)r * k + p], arq = M[(size_t)r * k + q];
+                    M[(size_t)r * k + p] = cs * arp - sn * arq;
+                    M[(size_t)r * k + q] = sn * arp + cs * arq;
+                    const double vrp = V[(size_t)r * k + p], vrq = V[(size_t)r * k + q];
+                    V[(size_t)r * k + p] = cs * vrp - sn * vrq;
+                    V[(size_t)r * k + q] = sn * vrp + cs * vrq;
+                }
+                for (int r = 0; r < k; ++r) {                      // rows p and q
+                    const double apr = M[(size_t)p * k + r], aqr = M[(size_t)q * k + r];
+                    M[(size_t)p * k + r] = cs * apr - sn * aqr;
+                    M[(size_t)q * k + r] = sn * apr + cs * aqr;
+                }
+                M[(size_t)p * k + q] = M[(size_t)q * k + p] = 0.0;
+            }
+        if (!rotations) break;
+    }
+    std::vector<int> order(k);
+    for (int i = 0; i < k; ++i) order[i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return M[(size_t)a * k + a] < M[(size_t)b * k + b]; });
+    for (int c = 0; c < k; ++c) {                                  // coef = D L^-T V, columns in ascending order of theta
+        const int src = order[c];
+        theta[c] = M[(size_t)src * k + src];
+        if (!std::isfinite(theta[c])) return "a Ritz value is not finite";
+        for (int i = k - 1; i >= 0; --i) {
+            double v = V[(size_t)i * k + src];
+            for (int p = i + 1; p < k; ++p) v -= L[(size_t)p * k + i] * Y[(size_t)p * k + c];
+            Y[(size_t)i * k + c] = v / L[(size_t)i * k + i];      // Y is free: it holds L^-T V now
+        }
+        for (int i = 0; i < k; ++i) coef[(size_t)i * k + c] = d[i] * Y[(size_t)i * k + c];
+    }
+    return nullptr;
+}
+
+constexpr int kEigMatLen = 2 * kEigBasisMax * kEigBasisMax;       // EigWs::mat: two reduced matrices ...
+constexpr int kEigCoefLen = kEigBasisMax * kEigBlockMax;          // ... then the coefficients of a combine
+constexpr int kEigGramTilesMax = (kEigBasisMax / kEigTile) * (kEigBasisMax / kEigTile);
+
+void eig_free(mi355cg_ctx* c) {
+    EigWs* W = c->eig;
+    if (!W) return;
+    if (c->stream) hipStreamSynchronize(c->stream);
+    for (double* v : {W->base, W->part, W->mat, W->red, W->stage}) if (v) hipFree(v);
+    if (W->mat_h) hipHostFree(W->mat_h);
+    delete W;
+    c->eig = nullptr;
+}
+
+// Vectors for a block of m columns on the handle's hierarchy (stage: the host entry point's packed staging too).  A workspace that
+// is large enough is kept; a larger one replaces it only once it is complete, so a failure leaves the handle as it was.
+int eig_ensure(mi355cg_ctx* c, int m, bool stage) {
+    const MgHier& H = *c->mg;
+    if (!c->eig || c->eig->cap < m) {
+        EigWs* W = new EigWs();
+        auto bail = [&](const char* what) {
+            for (double* v : {W->base, W->part, W->mat, W->red}) if (v) hipFree(v);
+            if (W->mat_h) hipHostFree(W->mat_h);
+            delete W;
+            (void)hipGetLastError();
+            return fail(MI355CG_ERR_HIP, "eigensolver workspace for a block of %d: %s allocation failed", m, what);
+        };
+        W->vlen = round_up(H.lv[0].len, 32);
+        long long off = (long long)EIG_CYC * W->vlen;
+        auto take = [&](long long len) { const long long o = off; off += round_up(len, 32); return o; };
+        const int nl = (int)H.lv.size();
+        W->cyc.lv.resize(nl);
+        for (int l = 0; l < nl; ++l) {                             // the vectors mg_build gives a level
+            if (l > 0) { W->cyc.lv[l].rhs = take(H.lv[l].len); W->cyc.lv[l].out = take(H.lv[l].len); }
+            if (l + 1 < nl) W->cyc.lv[l].a = take(H.lv[l].len);
+        }
+        W->slots = (int)(round_up(off, W->vlen) / W->vlen);
+        W->cyc.stride = (long long)W->slots * W->vlen;
+        W->cap = m;
+        const int G = H.lv[0].grid;
+        const size_t bytes = sizeof(double) * (size_t)W->cyc.stride * m;
+        if (hipMalloc((void**)&W->base, bytes) != hipSuccess) return bail("vector");
+        W->cyc.base = W->base;
+        if (hipMalloc((void**)&W->part, sizeof(double) * kEigGramTilesMax * kEigTileEntries * G) != hipSuccess) return bail("partials");
+        if (hipMalloc((void**)&W->mat, sizeof(double) * (kEigMatLen + kEigCoefLen)) != hipSuccess) return bail("matrix");
+        if (hipMalloc((void**)&W->red, sizeof(double) * 2 * kEigBlockMax) != hipSuccess) return bail("sums");
+        if (hipHostMalloc((void**)&W->mat_h, sizeof(double) * (kEigMatLen + kEigCoefLen + 2 * kEigBlockMax)) != hipSuccess) return bail("pinned matrix");
+        // boundary nodes and pads hold 0 for good: the kernels write interior nodes only
+        if (hipMemsetAsync(W->base, 0, bytes, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return bail("zero-filled vector");
+        eig_free(c);                                               // the staging goes with it: it was sized for the smaller block
+        c->eig = W;
+    }
+    EigWs* W = c->eig;
+    if (stage && !W->stage) {
+        if (hipMalloc((void**)&W->stage, sizeof(double) * c->pk_len * W->cap) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(MI355CG_ERR_HIP, "eigensolver staging for %d packed vectors: allocation failed", W->cap);
+        }
+    }
+    return MI355CG_OK;
+}
+
+// C = A^T B for two lists of vectors of one base: partials, then the ordered sums into c_dev (row-major la.n x lb.n)
+template <bool SYM>
+void launch_gram(hipStream_t st, const Geom& g, int G, const EigList& la, const EigList& lb, const double* base, double* part, double* c_dev) {
+    const int tiles = eig_tiles(la.n) * eig_tiles(lb.n);
+    hipLaunchKernelGGL((k_eig_gram<SYM>), dim3(G, tiles), dim3(kBlock), 0, st, g, la, base, lb, base, part);
+    hipLaunchKernelGGL((k_eig_reduce<SYM>), dim3(kEigTileEntries, tiles), dim3(kWave), 0, st, la.n, lb.n, G, (const double*)part, c_dev);
+}
+
+// The iteration of DESIGN section 10.7 on a block of m columns.  x_dev: m packed vectors in device memory, the start block on
+// entry and the Ritz vectors on return.  What the kernels hold is A X, A W, A P and R' = A X + theta X = -(K X - theta X), K = -A:
+// H = S^T K S is minus the gram of S and A S, and W = T R = M R' with M the V-cycle.
+int solve_eigs(mi355cg_ctx* c, int nev, int m, double tol, int max_iterations, double* x_dev, double* lambda, double* resid,
+               const volatile int* stop_flag, mi355cg_eig_results* out) {
+    const MgHier& H = *c->mg;
+    EigWs& W = *c->eig;
+    const Geom& g = H.lv[0].g;
+    const int G = H.lv[0].grid;
+    const hipStream_t st = c->stream;
+    const dim3 blk(kBlock);
+    const auto t0 = std::chrono::steady_clock::now();
+    const long long cs = W.cyc.stride;
+    auto slot = [&](int s) { return W.base + (long long)s * W.vlen; };                    // of column 0
+    auto list = [&](EigList& L, int s, const int* cols, int n) { for (int k = 0; k < n; ++k) L.idx[L.n++] = cols[k] * W.slots + s; };
+    int all[kEigBlockMax];
+    for (int j = 0; j < m; ++j) all[j] = j;
+    double* const mat_h = W.mat_h;
+    double* const coef_h = W.mat_h + kEigMatLen;
+    double* const red_h = coef_h + kEigCoefLen;
+    double* const coef_d = W.mat + kEigMatLen;
+    MgbAct act{};
+    act.stride = cs;
+    const MgbScal zero{};
+    // q = A v for the listed columns; mg_dir_apply's copy of its direction goes to Z, which is free whenever this runs
+    auto apply_A = [&](int src, int dst) {
+        hipLaunchKernelGGL((k_mgb_dir_apply<true>), dim3(G, act.n), blk, 0, st, act, zero, g, (const double*)slot(src), (const double*)nullptr,
+                           slot(EIG_Z), slot(dst), W.part);
+    };
+    // G = S^T S and H = -(S^T A S) of the lists -> the host; then the Rayleigh-Ritz step
+    std::vector<double> Gm, Hm, th(kEigBasisMax), C((size_t)kEigBasisMax * kEigBasisMax);
+    auto fetch_pair = [&](const EigList& ls, const EigList& las) -> int {
+        const int k = ls.n;
+        launch_gram<true>(st, g, G, ls, ls, W.base, W.part, W.mat);
+        launch_gram<true>(st, g, G, ls, las, W.base, W.part, W.mat + (size_t)k * k);
+        HIPCK(hipGetLastError());
+        HIPCK(hipMemcpyAsync(mat_h, W.mat, sizeof(double) * 2 * k * k, hipMemcpyDeviceToHost, st));
+        HIPCK(hipStreamSynchronize(st));
+        Gm.assign(mat_h, mat_h + (size_t)k * k);
+        Hm.resize((size_t)k * k);
+        for (size_t i = 0; i < (size_t)k * k; ++i) Hm[i] = -mat_h[(size_t)k * k + i];
+        return MI355CG_OK;
+    };
+    // Y_j = sum_i S_i coef[i][j] for the m columns of slot `dst`; coef_h rows [row0, row0 + ls.n) x m are already on the device
+    auto combine = [&](const EigList& ls, int row0, int dst) {
+        EigList ly{W.vlen, 0, {}};
+        list(ly, dst, all, m);
+        hipLaunchKernelGGL((k_eig_combine<false>), dim3(G), blk, 0, st, g, ls, (const double*)W.base, (const double*)(coef_d + (size_t)row0 * m), m,
+                           ly, W.base, ly, (const double*)W.base);
+    };
+    auto tail = [&](const EigList& L, int from) { EigList T{L.stride, 0, {}}; for (int i = from; i < L.n; ++i) T.idx[T.n++] = L.idx[i]; return T; };
+
+    std::vector<double> theta(m, 0.0), res(m, HUGE_VAL);
+    int it = 0, reason = MI355CG_EIG_ITERATIONS, p_drops = 0, cur = 0, pc = 0;
+    bool have_p = false, converged = false;
+    // X = the start block, A X, and the first Rayleigh-Ritz step on S = [X]
+    hipLaunchKernelGGL(k_mgb_unpack, dim3(flat_grid(c->pk_len), m), blk, 0, st, c->pg, cs, (const double*)x_dev, slot(EIG_X));
+    act.n = m;
+    for (int j = 0; j < m; ++j) act.sys[j] = j;
+    apply_A(EIG_X, EIG_AX);
+    {
+        EigList ls{W.vlen, 0, {}}, las{W.vlen, 0, {}};
+        list(ls, EIG_X, all, m); list(las, EIG_AX, all, m);
+        if (int rc = fetch_pair(ls, las)) return rc;
+        if (rr_solve(m, Gm.data(), Hm.data(), th.data(), C.data())) {
+            reason = MI355CG_EIG_BREAKDOWN;                        // the start block itself is refused: it goes back as it came
+            for (int j = 0; j < m; ++j) { const double gj = Gm[(size_t)j * m + j]; theta[j] = gj > 0.0 ? Hm[(size_t)j * m + j] / gj : 0.0; }
+        } else {
+            for (int i = 0; i < m; ++i) for (int j = 0; j < m; ++j) coef_h[(size_t)i * m + j] = C[(size_t)i * m + j];
+            HIPCK(hipMemcpyAsync(coef_d, coef_h, sizeof(double) * m * m, hipMemcpyHostToDevice, st));
+            combine(ls, 0, EIG_X + 1);
+            combine(las, 0, EIG_AX + 1);
+            cur = 1;
+            for (int j = 0; j < m; ++j) theta[j] = th[j];
+        }
+    }
+    while (reason != MI355CG_EIG_BREAKDOWN) {
+        // R' = A X + theta X with the norms of R' and X, for all m columns
+        MgbScal ths{};
+        for (int j = 0; j < m; ++j) ths.v[j] = theta[j];
+        hipLaunchKernelGGL(k_eig_resid, dim3(G, m), blk, 0, st, ths, g, cs, (const double*)slot(EIG_X + cur), (const double*)slot(EIG_AX + cur),
+                           slot(EIG_R), W.part);
+        act.n = m;
+        for (int j = 0; j < m; ++j) act.sys[j] = j;
+        hipLaunchKernelGGL(k_mgb_reduce, dim3(2, m), dim3(kWave), 0, st, act, 2, 2, G, (const double*)W.part, W.red);
+        HIPCK(hipGetLastError());
+        HIPCK(hipMemcpyAsync(red_h, W.red, sizeof(double) * 2 * m, hipMemcpyDeviceToHost, st));
+        HIPCK(hipStreamSynchronize(st));
+        bool done = true;
+        for (int j = 0; j < m; ++j) {
+            res[j] = std::sqrt(red_h[2 * j]) / (theta[j] * std::sqrt(red_h[2 * j + 1]));
+            if (j < nev && !(res[j] <= tol)) done = false;
+        }
+        if (done) { converged = true; reason = MI355CG_EIG_CONVERGED; break; }
+        if (it >= max_iterations) { reason = MI355CG_EIG_ITERATIONS; break; }
+        if (stop_flag && *stop_flag) { reason = MI355CG_EIG_INTERRUPTED; break; }
+        int na = 0, cols[kEigBlockMax];                            // soft locking: only columns that have not converged get a W and a P
+        for (int j = 0; j < m; ++j) if (!(res[j] <= tol)) cols[na++] = j;
+        act.n = na;
+        for (int k = 0; k < na; ++k) act.sys[k] = cols[k];
+        mg_vcycle(MgCycle{c, &act, &W.cyc}, 0, slot(EIG_R), slot(EIG_Z), nullptr);        // Z = M R' = T R
+        // W = Z - X (X^T Z), into R's slots
+        EigList lx{W.vlen, 0, {}}, lz{W.vlen, 0, {}}, lw{W.vlen, 0, {}};
+        list(lx, EIG_X + cur, all, m); list(lz, EIG_Z, cols, na); list(lw, EIG_R, cols, na);
+        launch_gram<false>(st, g, G, lx, lz, W.base, W.part, W.mat);
+        HIPCK(hipGetLastError());
+        HIPCK(hipMemcpyAsync(mat_h, W.mat, sizeof(double) * m * na, hipMemcpyDeviceToHost, st));
+        HIPCK(hipStreamSynchronize(st));
+        for (int i = 0; i < m * na; ++i) coef_h[i] = -mat_h[i];
+        HIPCK(hipMemcpyAsync(coef_d, coef_h, sizeof(double) * m * na, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL((k_eig_combine<true>), dim3(G), blk, 0, st, g, lx, (const double*)W.base, (const double*)coef_d, na, lw, W.base, lz,
+                           (const double*)W.base);
+        apply_A(EIG_R, EIG_AW);
+        // S = [X, W, P_act]
+        EigList ls = lx, las{W.vlen, 0, {}};
+        list(las, EIG_AX + cur, all, m);
+        list(ls, EIG_R, cols, na); list(las, EIG_AW, cols, na);
+        if (have_p) { list(ls, EIG_P + pc, cols, na); list(las, EIG_AP + pc, cols, na); }
+        if (int rc = fetch_pair(ls, las)) return rc;
+        int k = ls.n;
+        const char* why = rr_solve(k, Gm.data(), Hm.data(), th.data(), C.data());
+        if (why && have_p) {                                       // drop P for this iteration: [X, W] is the leading block of the pair
+            ++p_drops;
+            const int k2 = m + na;
+            std::vector<double> G2((size_t)k2 * k2), H2((size_t)k2 * k2);
+            for (int i = 0; i < k2; ++i) for (int j = 0; j < k2; ++j) { G2[(size_t)i * k2 + j] = Gm[(size_t)i * k + j]; H2[(size_t)i * k2 + j] = Hm[(size_t)i * k + j]; }
+            ls.n = las.n = k = k2;
+            why = rr_solve(k, G2.data(), H2.data(), th.data(), C.data());
+        }
+        if (why) { reason = MI355CG_EIG_BREAKDOWN; break; }
+        for (int i = 0; i < k; ++i) for (int j = 0; j < m; ++j) coef_h[(size_t)i * m + j] = C[(size_t)i * k + j];
+        HIPCK(hipMemcpyAsync(coef_d, coef_h, sizeof(double) * k * m, hipMemcpyHostToDevice, st));
+        combine(ls, 0, EIG_X + (cur ^ 1));
+        combine(las, 0, EIG_AX + (cur ^ 1));
+        const int pn = have_p ? pc ^ 1 : pc;                       // P+ = S C with the X rows left out
+        combine(tail(ls, m), m, EIG_P + pn);
+        combine(tail(las, m), m, EIG_AP + pn);
+        HIPCK(hipGetLastError());
+        cur ^= 1; pc = pn; have_p = true;
+        for (int j = 0; j < m; ++j) theta[j] = th[j];
+        ++it;
+    }
+    hipLaunchKernelGGL(k_mgb_pack, dim3(flat_grid(c->pk_len), m), blk, 0, st, c->pg, cs, (const double*)slot(EIG_X + cur), x_dev);
+    HIPCK(hipGetLastError());
+    HIPCK(hipStreamSynchronize(st));
+    for (int j = 0; j < m; ++j) { lambda[j] = theta[j]; resid[j] = res[j]; }
+    out->iterations = it;
+    out->converged = converged ? 1 : 0;
+    out->stop_reason = reason;
+    out->p_drops = p_drops;
+    out->solve_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return MI355CG_OK;
+}
+
+// what both entry points refuse before anything is allocated or written
+int eig_check(mi355cg_ctx* c, int nev, int block, double tol, int max_iterations, const void* x, const void* lambda, const void* resid,
+              const mi355cg_eig_results* out) {
+    if (!c || !x || !lambda || !resid || !out) return fail(MI355CG_ERR_INVALID, "null argument");
+    if (nev < 1) return fail(MI355CG_ERR_INVALID, "nev = %d: at least one eigenpair", nev);
+    if (block < nev || block > MI355CG_EIG_BLOCK_MAX)
+        return fail(MI355CG_ERR_INVALID, "a block has nev .. %d columns, not %d (nev = %d)", MI355CG_EIG_BLOCK_MAX, block, nev);
+    if (block > c->gp.size) return fail(MI355CG_ERR_INVALID, "a block of %d is larger than the system (%lld unknowns)", block, (long long)c->gp.size);
+    if (!std::isfinite(tol) || !(tol > 0.0)) return fail(MI355CG_ERR_INVALID, "tol must be finite and > 0");
+    if (max_iterations < 1) return fail(MI355CG_ERR_INVALID, "max_iterations = %d: at least 1", max_iterations);
+    if (!c->mg) return fail(MI355CG_ERR_STATE, "no preconditioner is set on this handle (mi355cg_set_preconditioner): the eigen iteration is multigrid-preconditioned");
+    if (c->mg->cycle != MI355CG_CYCLE_F64) return fail(MI355CG_ERR_INVALID, "the eigen iteration runs the fp64 V-cycle: this handle's preconditioner was set with MI355CG_CYCLE_F32");
+    return MI355CG_OK;
+}
+
+// the block utilities: n packed host vectors -> zero-padded storage vectors of a temporary buffer, vector i at i * vlen
+struct BlockTmp {
+    double *packed = nullptr, *vec = nullptr, *part = nullptr, *mat = nullptr;
+    ~BlockTmp() { for (double* v : {packed, vec, part, mat}) if (v) hipFree(v); }
+};
+int block_check(mi355cg_ctx* c) {
+    if (c->is_csr) return fail(MI355CG_ERR_INVALID, "the block utilities need the grid operator's storage layout: a CSR handle has no grid");
+    if (c->is_slab) return fail(MI355CG_ERR_INVALID, "the block utilities are single-GPU only: this handle owns one part of a decomposed grid");
+    return MI355CG_OK;
+}
+int block_upload(mi355cg_ctx* c, BlockTmp& T, int n, int n_out, const double* const* src, const int* counts, int nsrc, long long vlen) {
+    if (hipMalloc((void**)&T.packed, sizeof(double) * c->pk_len * std::max(n, n_out)) != hipSuccess ||
+        hipMalloc((void**)&T.vec, sizeof(double) * vlen * (n + n_out)) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(MI355CG_ERR_HIP, "block utility: allocation of %d vectors failed", n + n_out);
+    }
+    HIPCK(hipMemsetAsync(T.vec, 0, sizeof(double) * vlen * (n + n_out), c->stream));
+    long long at = 0;
+    for (int s = 0; s < nsrc; ++s) {
+        HIPCK(hipMemcpyAsync(T.packed + at * c->pk_len, src[s], sizeof(double) * c->pk_len * counts[s], hipMemcpyHostToDevice, c->stream));
+        at += counts[s];
+    }
+    hipLaunchKernelGGL(k_mgb_unpack, dim3(flat_grid(c->pk_len), n), dim3(kBlock), 0, c->stream, c->pg, vlen, (const double*)T.packed, T.vec);
+    HIPCK(hipGetLastError());
+    return MI355CG_OK;
+}
+
 }  // namespace
 
 // ====================================================================================================
@@ -1698,6 +2081,7 @@ void mi355cg_destroy(mi355cg_handle c) {
     if (c->step_b) hipFree(c->step_b);
     clear_graphs(c);
     mg_batch_free(c);
+    eig_free(c);
     mg_free(c->mg);
     c->events.destroy();
     for (hipEvent_t e : c->ev_loop) if (e) hipEventDestroy(e);
@@ -2281,6 +2665,7 @@ int mi355cg_set_preconditioner_ex(mi355cg_handle c, int kind, int cycle) {
     HIPCK(hipSetDevice(c->device));
     if (kind == MI355CG_PRECOND_NONE) {
         mg_batch_free(c);                                          // the batch workspace belongs to the hierarchy it was built for
+        eig_free(c);                                               // and so does the eigensolver's
         if (c->mg) { HIPCK(hipStreamSynchronize(c->stream)); mg_free(c->mg); c->mg = nullptr; }
         return MI355CG_OK;
     }
@@ -2292,6 +2677,7 @@ int mi355cg_set_preconditioner_ex(mi355cg_handle c, int kind, int cycle) {
     if (cycle != MI355CG_CYCLE_F64 && cycle != MI355CG_CYCLE_F32)
         return fail(MI355CG_ERR_INVALID, "unknown V-cycle precision %d (MI355CG_CYCLE_F64 = 0, MI355CG_CYCLE_F32 = 1)", cycle);
     mg_batch_free(c);                                              // accepted: the batch workspace goes, a refused call above keeps it
+    eig_free(c);
     if (c->mg && c->mg->cycle == cycle) { c->mg->kind = kind; return MI355CG_OK; }   // both kinds have a hierarchy here: it is the same one
     if (!c->mg) return mg_build(c, kind, &c->mg, cycle);
     // another precision: the levels' vectors and the coarse inverse change type.  Built first, so a failure keeps the old one.
@@ -2380,6 +2766,110 @@ int mi355cg_batch_release(mi355cg_handle c) {
     if (!c->batch) return MI355CG_OK;
     HIPCK(hipSetDevice(c->device));
     mg_batch_free(c);
+    return MI355CG_OK;
+}
+
+// ---- lowest eigenpairs by a block multigrid-preconditioned iteration ------------------------------------------
+int mi355cg_eigs_device(mi355cg_handle c, int nev, int block, double tol, int max_iterations, double* x_dev, double* lambda, double* resid,
+                        const volatile int* stop_flag, mi355cg_eig_results* out) {
+    if (int rc = eig_check(c, nev, block, tol, max_iterations, x_dev, lambda, resid, out)) return rc;
+    HIPCK(hipSetDevice(c->device));
+    if (int rc = eig_ensure(c, block, false)) return rc;
+    return solve_eigs(c, nev, block, tol, max_iterations, x_dev, lambda, resid, stop_flag, out);
+}
+
+int mi355cg_eigs(mi355cg_handle c, int nev, int block, double tol, int max_iterations, double* x, double* lambda, double* resid,
+                 const volatile int* stop_flag, mi355cg_eig_results* out) {
+    if (int rc = eig_check(c, nev, block, tol, max_iterations, x, lambda, resid, out)) return rc;
+    HIPCK(hipSetDevice(c->device));
+    if (int rc = eig_ensure(c, block, true)) return rc;
+    double* stage = c->eig->stage;                                 // the start block goes up and the Ritz vectors come down through it
+    const size_t bytes = sizeof(double) * (size_t)c->pk_len * (size_t)block;
+    HIPCK(hipMemcpyAsync(stage, x, bytes, hipMemcpyHostToDevice, c->stream));
+    if (int rc = solve_eigs(c, nev, block, tol, max_iterations, stage, lambda, resid, stop_flag, out)) return rc;
+    HIPCK(hipMemcpyAsync(x, stage, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(hipStreamSynchronize(c->stream));
+    return MI355CG_OK;
+}
+
+int mi355cg_eigs_release(mi355cg_handle c) {
+    if (!c) return fail(MI355CG_ERR_INVALID, "null handle");
+    if (!c->eig) return MI355CG_OK;
+    HIPCK(hipSetDevice(c->device));
+    eig_free(c);
+    return MI355CG_OK;
+}
+
+int mi355cg_rayleigh_ritz(int k, const double* g, const double* hmat, double* theta, double* coef) {
+    if (!g || !hmat || !theta || !coef) return fail(MI355CG_ERR_INVALID, "null argument");
+    if (k < 1 || k > kEigBasisMax) return fail(MI355CG_ERR_INVALID, "a Rayleigh-Ritz basis has 1 .. %d vectors, not %d", kEigBasisMax, k);
+    if (const char* why = rr_solve(k, g, hmat, theta, coef)) return fail(MI355CG_ERR_STATE, "basis refused: %s", why);
+    return MI355CG_OK;
+}
+
+int mi355cg_block_gram_indexed(mi355cg_handle c, int na, const double* a, int nia, const int* ia, int nb, const double* b, int nib, const int* ib,
+                               double* out) {
+    if (!c || !a || !b || !out) return fail(MI355CG_ERR_INVALID, "null argument");
+    if (na < 1 || na > kEigBasisMax || nb < 1 || nb > kEigBasisMax)
+        return fail(MI355CG_ERR_INVALID, "a group has 1 .. %d vectors, not %d and %d", kEigBasisMax, na, nb);
+    if ((ia && (nia < 1 || nia > kEigBasisMax)) || (ib && (nib < 1 || nib > kEigBasisMax)))
+        return fail(MI355CG_ERR_INVALID, "an index list has 1 .. %d entries, not %d and %d", kEigBasisMax, nia, nib);
+    for (int i = 0; ia && i < nia; ++i) if (ia[i] < 0 || ia[i] >= na) return fail(MI355CG_ERR_INVALID, "index %d of the first list is outside 0 .. %d", ia[i], na - 1);
+    for (int i = 0; ib && i < nib; ++i) if (ib[i] < 0 || ib[i] >= nb) return fail(MI355CG_ERR_INVALID, "index %d of the second list is outside 0 .. %d", ib[i], nb - 1);
+    if (int rc = block_check(c)) return rc;
+    HIPCK(hipSetDevice(c->device));
+    const long long vlen = round_up(c->storage_len, 32);
+    const int G = std::min(c->g.N - 1, kMgMaxGrid);
+    EigList la{vlen, 0, {}}, lb{vlen, 0, {}};
+    for (int i = 0; i < (ia ? nia : na); ++i) la.idx[la.n++] = ia ? ia[i] : i;
+    for (int i = 0; i < (ib ? nib : nb); ++i) lb.idx[lb.n++] = na + (ib ? ib[i] : i);
+    BlockTmp T;
+    const double* src[2] = {a, b};
+    const int counts[2] = {na, nb};
+    if (int rc = block_upload(c, T, na + nb, 0, src, counts, 2, vlen)) return rc;
+    const int tiles = eig_tiles(la.n) * eig_tiles(lb.n);
+    if (hipMalloc((void**)&T.part, sizeof(double) * tiles * kEigTileEntries * G) != hipSuccess ||
+        hipMalloc((void**)&T.mat, sizeof(double) * la.n * lb.n) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(MI355CG_ERR_HIP, "block gram: allocation of the partials failed");
+    }
+    launch_gram<false>(c->stream, c->g, G, la, lb, T.vec, T.part, T.mat);
+    HIPCK(hipGetLastError());
+    HIPCK(hipMemcpyAsync(out, T.mat, sizeof(double) * la.n * lb.n, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(hipStreamSynchronize(c->stream));
+    return MI355CG_OK;
+}
+
+int mi355cg_block_gram(mi355cg_handle c, int na, const double* a, int nb, const double* b, double* out) {
+    return mi355cg_block_gram_indexed(c, na, a, 0, nullptr, nb, b, 0, nullptr, out);
+}
+
+int mi355cg_block_combine(mi355cg_handle c, int k, const double* s, int m, const double* coef, double* y) {
+    if (!c || !s || !coef || !y) return fail(MI355CG_ERR_INVALID, "null argument");
+    if (k < 1 || k > kEigBasisMax) return fail(MI355CG_ERR_INVALID, "a combination has 1 .. %d inputs, not %d", kEigBasisMax, k);
+    if (m < 1 || m > kEigBlockMax) return fail(MI355CG_ERR_INVALID, "a combination has 1 .. %d outputs, not %d", kEigBlockMax, m);
+    if (int rc = block_check(c)) return rc;
+    HIPCK(hipSetDevice(c->device));
+    const long long vlen = round_up(c->storage_len, 32);
+    const int G = std::min(c->g.N - 1, kMgMaxGrid);
+    EigList ls{vlen, 0, {}}, ly{vlen, 0, {}};
+    for (int i = 0; i < k; ++i) ls.idx[ls.n++] = i;
+    for (int j = 0; j < m; ++j) ly.idx[ly.n++] = k + j;
+    BlockTmp T;
+    const double* src[1] = {s};
+    const int counts[1] = {k};
+    if (int rc = block_upload(c, T, k, m, src, counts, 1, vlen)) return rc;
+    if (hipMalloc((void**)&T.mat, sizeof(double) * k * m) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(MI355CG_ERR_HIP, "block combine: allocation of the coefficients failed");
+    }
+    HIPCK(hipMemcpyAsync(T.mat, coef, sizeof(double) * k * m, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL((k_eig_combine<false>), dim3(G), dim3(kBlock), 0, c->stream, c->g, ls, (const double*)T.vec, (const double*)T.mat, m, ly, T.vec, ly,
+                       (const double*)T.vec);
+    hipLaunchKernelGGL(k_mgb_pack, dim3(flat_grid(c->pk_len), m), dim3(kBlock), 0, c->stream, c->pg, vlen, (const double*)(T.vec + (long long)k * vlen), T.packed);
+    HIPCK(hipGetLastError());
+    HIPCK(hipMemcpyAsync(y, T.packed, sizeof(double) * c->pk_len * m, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(hipStreamSynchronize(c->stream));
     return MI355CG_OK;
 }
 

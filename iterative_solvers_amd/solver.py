@@ -297,6 +297,90 @@ class _Handle:
         """Free the workspace solve_batch keeps on the handle (nothing to free is fine)."""
         _capi.check(self._lib.mi355cg_batch_release(self._h))
 
+    @staticmethod
+    def _check_block(v, size, most, what):
+        """A group of packed vectors for the block utilities: NumPy [n, size] float64, 1 <= n <= most, C-contiguous on return."""
+        if not isinstance(v, np.ndarray):
+            raise ValueError(f"{what} is a NumPy array, not {type(v).__name__}")
+        if v.dtype != np.float64:
+            raise ValueError(f"{what} has dtype {v.dtype}, expected float64")
+        if v.ndim != 2 or v.shape[1] != size:
+            raise ValueError(f"{what} has shape {tuple(v.shape)}, expected (n, {size})")
+        if not 1 <= v.shape[0] <= most:
+            raise ValueError(f"{what} has 1 .. {most} vectors, not {v.shape[0]}")
+        return np.ascontiguousarray(v)
+
+    def eigs(self, nev: int, block: int, tol: float, max_iterations: int, x, stop_flag: Optional[C.c_int] = None):
+        """The nev lowest eigenpairs by the block multigrid-preconditioned iteration (mi355cg_eigs; needs set_preconditioner
+        first).  x: the start block, NumPy [block, size] float64 (a new array comes back) or a contiguous CUDA torch tensor
+        on the handle's device (mi355cg_eigs_device; a new tensor comes back).  Returns (lambda[block], Ritz vectors
+        [block, size], resid[block], _capi.EigResults)."""
+        nev, block = int(nev), int(block)
+        on_device = not isinstance(x, np.ndarray)
+        if on_device:
+            if not (type(x).__module__.split(".")[0] == "torch" and hasattr(x, "data_ptr")):
+                raise ValueError(f"a start block is a NumPy array or a CUDA torch tensor, not {type(x).__name__}")
+            import torch
+            if not x.is_cuda:
+                raise ValueError("a torch start block must be in device memory (a CPU tensor: pass tensor.numpy())")
+            if x.dtype != torch.float64:
+                raise ValueError(f"start block has dtype {x.dtype}, expected torch.float64")
+            if x.device.index != self._device:
+                raise ValueError(f"start block is on {x.device}, the handle on device {self._device}")
+        elif x.dtype != np.float64:
+            raise ValueError(f"start block has dtype {x.dtype}, expected float64")
+        if tuple(x.shape) != (block, self.size):
+            raise ValueError(f"start block has shape {tuple(x.shape)}, expected ({block}, {self.size})")
+        lam, res = np.zeros(max(block, 1)), np.zeros(max(block, 1))
+        out = _capi.EigResults()
+        sp = C.cast(C.pointer(stop_flag), C.c_void_p) if stop_flag is not None else None
+        if on_device:
+            v = x.contiguous().clone()
+            torch.cuda.current_stream(x.device).synchronize()        # the library works on its own stream
+            rc = self._lib.mi355cg_eigs_device(self._h, nev, block, float(tol), int(max_iterations), v.data_ptr(), lam.ctypes.data,
+                                               res.ctypes.data, sp, C.byref(out))
+        else:
+            v = np.array(x, dtype=np.float64, order="C", copy=True)
+            rc = self._lib.mi355cg_eigs(self._h, nev, block, float(tol), int(max_iterations), v.ctypes.data, lam.ctypes.data,
+                                        res.ctypes.data, sp, C.byref(out))
+        if rc == _capi.ERR_INVALID:
+            raise ValueError(self._lib.mi355cg_last_error().decode())
+        _capi.check(rc)
+        return lam[:block], v, res[:block], out
+
+    def eigs_release(self):
+        """Free the workspace eigs keeps on the handle (nothing to free is fine)."""
+        _capi.check(self._lib.mi355cg_eigs_release(self._h))
+
+    def block_gram(self, a, b, rows=None, cols=None):
+        """C[i, j] = a[i] . b[j] on the device in a fixed summation order (mi355cg_block_gram).  rows / cols: index lists into a
+        and b; the result then has the listed rows and columns only (mi355cg_block_gram_indexed)."""
+        a = self._check_block(a, self.size, _capi.EIG_BASIS_MAX, "a")
+        b = self._check_block(b, self.size, _capi.EIG_BASIS_MAX, "b")
+        ia = None if rows is None else np.ascontiguousarray(rows, dtype=np.int32)
+        ib = None if cols is None else np.ascontiguousarray(cols, dtype=np.int32)
+        out = np.empty((a.shape[0] if ia is None else ia.size, b.shape[0] if ib is None else ib.size))
+        rc = self._lib.mi355cg_block_gram_indexed(self._h, a.shape[0], a.ctypes.data, 0 if ia is None else ia.size,
+                                                  None if ia is None else ia.ctypes.data, b.shape[0], b.ctypes.data,
+                                                  0 if ib is None else ib.size, None if ib is None else ib.ctypes.data, out.ctypes.data)
+        if rc == _capi.ERR_INVALID:
+            raise ValueError(self._lib.mi355cg_last_error().decode())
+        _capi.check(rc)
+        return out
+
+    def block_combine(self, s, coef):
+        """y[j] = sum_i s[i] * coef[i, j], i ascending, unfused (mi355cg_block_combine); s: [k, size], coef: [k, m] -> [m, size]."""
+        s = self._check_block(s, self.size, _capi.EIG_BASIS_MAX, "s")
+        coef = np.ascontiguousarray(coef, dtype=np.float64)
+        if coef.ndim != 2 or coef.shape[0] != s.shape[0] or not 1 <= coef.shape[1] <= _capi.EIG_BLOCK_MAX:
+            raise ValueError(f"coef has shape {tuple(coef.shape)}, expected ({s.shape[0]}, 1 .. {_capi.EIG_BLOCK_MAX})")
+        y = np.empty((coef.shape[1], self.size))
+        rc = self._lib.mi355cg_block_combine(self._h, s.shape[0], s.ctypes.data, coef.shape[1], coef.ctypes.data, y.ctypes.data)
+        if rc == _capi.ERR_INVALID:
+            raise ValueError(self._lib.mi355cg_last_error().decode())
+        _capi.check(rc)
+        return y
+
     def setup_on_device(self):
         """Opt-in: regenerate b and u on the GPU (<= 1 ulp from the host values)."""
         _capi.check(self._lib.mi355cg_setup_on_device(self._h))
@@ -350,6 +434,24 @@ def mg_hierarchy(n: int, kind: int = _capi.PRECOND_MG_ANY):
         raise ValueError(lib.mi355cg_last_error().decode())
     _capi.check(rc)
     return tuple(buf[:L.value])
+
+
+def rayleigh_ritz(g, h):
+    """The Rayleigh-Ritz step of eigs on the host (mi355cg_rayleigh_ritz, no GPU): for the k x k pair G = S^T S, H = S^T K S
+    (k <= 48) returns (theta[k] ascending, coef[k, k]) with coef.T @ G @ coef = I and coef.T @ H @ coef = diag(theta).
+    ValueError for a bad shape; Mi355cgError (code ERR_STATE) for a basis that is refused as numerically dependent."""
+    g = np.ascontiguousarray(g, dtype=np.float64)
+    h = np.ascontiguousarray(h, dtype=np.float64)
+    if g.ndim != 2 or g.shape[0] != g.shape[1] or h.shape != g.shape:
+        raise ValueError(f"G and H are square matrices of one size, not {tuple(g.shape)} and {tuple(h.shape)}")
+    k = g.shape[0]
+    theta, coef = np.empty(max(k, 1)), np.empty((max(k, 1), max(k, 1)))
+    lib = _capi.load()
+    rc = lib.mi355cg_rayleigh_ritz(k, g.ctypes.data, h.ctypes.data, theta.ctypes.data, coef.ctypes.data)
+    if rc == _capi.ERR_INVALID:
+        raise ValueError(lib.mi355cg_last_error().decode())
+    _capi.check(rc)
+    return theta, coef
 
 
 # ---------------------------------------------------------------------------------------------
@@ -440,6 +542,43 @@ class MatrixFreeSystem:
     def batch_release(self):
         """Free the device workspace solve_batch keeps on this system."""
         self._handle.batch_release()
+
+    def eigs(self, nev: int, block: Optional[int] = None, tol: float = 1e-8, max_iterations: int = 200, x0=None, seed: int = 0,
+             stop_flag: Optional[C.c_int] = None):
+        """Extension (no reference twin): the nev lowest eigenpairs of this system's operator by a block preconditioned
+        iteration (LOBPCG) with one multigrid V-cycle per vector and iteration (needs set_preconditioner with the fp64 cycle).
+        Returns (lam[nev], V[nev, size()], info): lam > 0 ascending with A v = -lam v (with set_shift(sigma): (A - sigma I) v =
+        -lam v, i.e. the unshifted values + sigma), the rows of V orthonormal.  block: vectors iterated, nev <= block <= 16; the
+        extra ones are guard vectors (default min(16, nev + max(2, nev // 4)), capped by size()).  x0: the start block,
+        [block, size()] float64, NumPy or a CUDA torch tensor (V is then a tensor too); without it
+        numpy.random.default_rng(seed).standard_normal((block, size())).  info: iterations, converged, stop_reason
+        (_capi.EIG_CONVERGED / EIG_ITERATIONS / EIG_INTERRUPTED / EIG_BREAKDOWN), p_drops, solve_seconds, residuals (the relative
+        residuals of all block columns), ritz_values (all block Ritz values).  The system's right-hand side, last solution and
+        shift are untouched."""
+        nev = int(nev)
+        if block is None:
+            block = min(_capi.EIG_BLOCK_MAX, nev + max(2, nev // 4), self.size())
+        block = int(block)
+        if x0 is None:
+            if not 1 <= nev <= block <= _capi.EIG_BLOCK_MAX:
+                raise ValueError(f"1 <= nev <= block <= {_capi.EIG_BLOCK_MAX} is required, not nev = {nev}, block = {block}")
+            x0 = np.random.default_rng(seed).standard_normal((block, self.size()))
+        lam, v, res, out = self._handle.eigs(nev, block, tol, max_iterations, x0, stop_flag)
+        info = {"iterations": out.iterations, "converged": bool(out.converged), "stop_reason": out.stop_reason, "p_drops": out.p_drops,
+                "solve_seconds": out.solve_seconds, "residuals": res, "ritz_values": lam}
+        return lam[:nev].copy(), v[:nev], info
+
+    def eigs_release(self):
+        """Free the device workspace eigs keeps on this system."""
+        self._handle.eigs_release()
+
+    def block_gram(self, a, b, rows=None, cols=None):
+        """a @ b.T for two groups of <= 48 packed vectors, summed on the device in a fixed order (two calls: the same bits)."""
+        return self._handle.block_gram(a, b, rows, cols)
+
+    def block_combine(self, s, coef):
+        """coef.T @ s for <= 48 packed vectors s and <= 16 output columns, as an ascending sum of unfused multiply-adds."""
+        return self._handle.block_combine(s, coef)
 
 
 class GridSystem(MatrixFreeSystem):
