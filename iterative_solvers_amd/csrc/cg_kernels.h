@@ -22,7 +22,7 @@
 #include <cfloat>
 #include <cmath>
 #include "solve_loop.h"               // CgState, HistEntry, kHist, kRing: what the host loop reads back
-#include "item_table.h"               // kBlock, kWave, kWaves; Panel, WorkList (host); ItemDesc, ItemSeq: the tables the kernels read
+#include "item_table.h"               // kBlock, kWave, kWaves; Geom, row_off; Panel, WorkList (host); ItemDesc, ItemUni, StartRec: the tables the kernels read
 
 namespace mi355cg {
 
@@ -44,28 +44,6 @@ __device__ unsigned long long g_wave_dbg[2][kWtStamps * kWtWaves];
 #define MI355CG_WT_END(K)
 #endif
 
-// ---- storage layout -------------------------------------------------------------------------------
-// Node (x, y) of the (N+1)x(N+1) bounding grid lives at  row_off(y) + x - base0.  Rows y <= N/2
-// (bottom-right block + its boundary row 0) only store columns [cb, cb+Pb), cb = N/2 rounded down
-// to 32; rows above store columns [0, Pu).  Pb, Pu, cb are multiples of 32 elements so every row
-// starts 256-B aligned.  Boundary nodes and pads hold 0 and stay 0; Dirichlet data is in the RHS.
-struct Geom {
-    int N, half, cb, xlim;            // xlim: columns [0, xlim) are touched by the stencil strips
-    int Pb, Pu;                       // row pitches (elements) of bottom / upper rows
-    int y_lo, y_hi;                   // owned rows (inclusive); rows y_lo-1 and y_hi+1 are ghosts
-    long long base0;                  // physical offset of the first stored element (row y_lo-1)
-    long long own_begin, own_len;     // flat [begin, begin+len) of the owned rows, local offsets
-    double A, xk, yk;                 // stencil coefficients (grid_system.cpp:316-318)
-};
-
-__host__ __device__ inline long long row_off(const Geom& g, int y) {
-    return y <= g.half ? (long long)y * g.Pb - g.cb
-                       : (long long)(g.half + 1) * g.Pb + (long long)(y - g.half - 1) * g.Pu;
-}
-__host__ __device__ inline bool node_interior(const Geom& g, int x, int y) {
-    return y >= 1 && y <= g.N - 1 && x <= g.N - 1 && x >= (y <= g.half ? g.half + 1 : 1);
-}
-
 // What every wave needs from the state, fetched with SCALAR loads (s_load through the constant address space, one
 // request per scalar cache instead of one per wave).  Copying the whole struct made hipcc fetch half of it with
 // per-lane global loads of one address: ~4000 waves x 3 loads of the same line queued at one L2 channel and the
@@ -76,17 +54,23 @@ struct StateLite { double alpha, rr, rr_prev, rz, r0norm; int it, done, first, s
 template <typename V> __device__ inline V scalar_load(const V* p) {
     return *(const __attribute__((address_space(4))) V*)p;
 }
-// The two tables of a launch shape (item_table.h), in device memory and never written while a handle lives: one ItemDesc per
-// item index, one ItemSeq per wave of the launch.  A wave fetches its entry with ONE 16-byte scalar load at a wave-uniform
-// index.  (The panel list used to travel by value: 856 bytes of kernel arguments that every wave searched through a chain of
-// some 60 dependent scalar loads, three times, before it could request its first row; profiles/launch_head.txt.)
-struct ItemTab { const ItemDesc* items; const ItemSeq* seq; int nitems; };
+// The tables of a launch shape (item_table.h), in device memory and never written while a handle lives: one ItemDesc per item index,
+// one StartRec per wave of the launch and march direction.  A wave fetches its start record with ONE 64-byte scalar load at a
+// wave-uniform index and has its item sequence and the addressing of its first item; a later item costs one 16-byte scalar load
+// (decode_item) and item_uniform.  (The panel list used to travel by value: 856 bytes of kernel arguments that every wave searched
+// through a chain of some 60 dependent scalar loads, three times, before it could request its first row; then the chain
+// arguments -> sequence -> item -> row offsets stood in front of the first row request; profiles/launch_head.txt, launch_boundary.txt.)
+struct ItemTab { const ItemDesc* items; const StartRec* start; const StartRec* start_rev; int nitems; };
 typedef int int4_t __attribute__((ext_vector_type(4)));
+typedef int int16_t_ __attribute__((ext_vector_type(16)));
 template <typename V> __device__ inline V scalar_load16(const V* p) {         // one s_load_dwordx4
     static_assert(sizeof(V) == 16 && alignof(V) == 16, "scalar_load16: a 16-byte entry");
     return __builtin_bit_cast(V, scalar_load(reinterpret_cast<const int4_t*>(p)));
 }
-__device__ inline ItemSeq item_seq(const ItemTab& t, int wave) { return scalar_load16(t.seq + (blockIdx.x * kWaves + wave)); }
+__device__ inline StartRec start_rec(const StartRec* t, int wave) {            // one s_load_dwordx16
+    static_assert(alignof(StartRec) == 64, "start_rec: a 64-byte entry");
+    return __builtin_bit_cast(StartRec, scalar_load(reinterpret_cast<const int16_t_*>(t + (blockIdx.x * kWaves + wave))));
+}
 
 // State object -> state object, by the one thread of the grid that forwards it.  Not inlined: hipcc otherwise hoists
 // the loads in front of the branch that selects that thread, and every wave of the grid fetches all 128 bytes.
@@ -609,17 +593,24 @@ template <typename V> __device__ inline V buf_load(rsrc_t r, int voff, int soff)
 // vdata: 1 wait state) and hipcc pads it for FLAT stores and for MUBUF stores WITHOUT a register soffset; with the soffset in
 // an SGPR (every store here: the row offset) it pads nothing.  The empty asm below keeps the data registers alive across two
 // wait states after the store, so nothing can be scheduled into that window that writes them.
-template <typename V> __device__ inline void buf_store(V v, rsrc_t r, int voff, int soff) {
+// POLICY: the cache-policy bits of the store (the builtin's aux operand on gfx950).  Every flavour writes its bytes back to memory; plain
+// and nt stores keep the line in the writing XCD's L2, sc1 (write-through) stores drop it.
+constexpr int kStPlain = 0, kStNt = 2, kStSc1 = 16;
+template <int POLICY = kStPlain, typename V> __device__ inline void buf_store(V v, rsrc_t r, int voff, int soff) {
     typedef unsigned int u4 __attribute__((ext_vector_type(4)));
     typedef unsigned int u2 __attribute__((ext_vector_type(2)));
     if constexpr (sizeof(V) == 16) {
         u4 d = __builtin_bit_cast(u4, v);
-        __builtin_amdgcn_raw_buffer_store_b128(d, r, voff, soff, 0);
+        __builtin_amdgcn_raw_buffer_store_b128(d, r, voff, soff, POLICY);
         asm volatile("s_nop 1" : "+v"(d));
     }
-    else if constexpr (sizeof(V) == 8) __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u2, v), r, voff, soff, 0);
-    else { static_assert(sizeof(V) == 4, "buf_store: 4, 8 or 16 bytes"); __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned int, v), r, voff, soff, 0); }
+    else if constexpr (sizeof(V) == 8) __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u2, v), r, voff, soff, POLICY);
+    else { static_assert(sizeof(V) == 4, "buf_store: 4, 8 or 16 bytes"); __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned int, v), r, voff, soff, POLICY); }
 }
+// The two bulk row stores of the iteration: the new direction (k_stencil) nontemporal, the residual (k_update_st) write-through.  Measured
+// against the default policy and the other seven combinations, alternating on one box (profiles/launch_boundary.txt): +1.7 to +4.1 % at
+// N = 4096, +1.4 % at N = 8192, +1.0 % at N = 16384; write-through on the direction loses what nontemporal gains.
+constexpr int kStorePnew = kStNt, kStoreR = kStSc1;
 // value of the lane below (lane - 1) / above (lane + 1); lane 0 / lane 63 get 0 and are overridden by the caller
 __device__ inline int dpp_from_below(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x138 /*wave_shr:1*/, 0xf, 0xf, false); }
 __device__ inline int dpp_from_above(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x130 /*wave_shl:1*/, 0xf, 0xf, false); }
@@ -674,10 +665,10 @@ __device__ inline PreMax prefetch_max_buf(rsrc_t rs, int field_off, int n, int e
     return PreMax{buf_load<double>(rs, part_voff(threadIdx.x, n, es), field_off), buf_load<double>(rs, part_voff(threadIdx.x + kBlock, n, es), field_off)};
 }
 
-// Addressing data of one work item, constant while the item is marched (wave-uniform unless noted).  It is computed
-// when the FETCH cursor of a wave enters the item and handed to the COMPUTE cursor when that gets there: the fetch
-// cursor runs DEPTH rows ahead of the compute cursor ACROSS item boundaries, so the load pipeline never drains between
-// items (round 1 refilled it per item, which is what made short items lose there).
+// Addressing data of one work item, constant while the item is marched: the wave-uniform ItemUni (item_table.h) and what the
+// lanes add to it.  It is computed when the FETCH cursor of a wave enters the item and handed to the COMPUTE cursor when that gets
+// there: the fetch cursor runs DEPTH rows ahead of the compute cursor ACROSS item boundaries, so the load pipeline never drains
+// between items (round 1 refilled it per item, which is what made short items lose there).
 struct ItemAddr {
     int nrows, ystart;          // rows of the item; its first row in march order
     long long base_el;          // element offset of row y0 = ya - 1 from the start of a vector
@@ -687,22 +678,16 @@ struct ItemAddr {
     int vo_own, ve_own, vo_first, vo_last;        // per lane: byte offsets within a row (lane_off / edge_off)
 };
 template <typename T, int VEC, bool DESC>
-__device__ inline ItemAddr item_addr(const Geom& g, const Item& it, int lane) {
+__device__ inline ItemAddr item_addr(const Geom& g, const ItemUni& u, int lane) {
     constexpr int DIR = DESC ? -1 : 1;
     ItemAddr A;
-    A.x = it.strip * (kWave * VEC) + lane * VEC;
-    A.nrows = it.yb - it.ya + 1;
-    A.ystart = DESC ? it.yb : it.ya;
-    const int y0 = it.ya - 1;                                   // lowest row the item touches (halo)
-    A.base_el = row_off(g, y0) - g.base0;
-    A.bot = it.ya <= g.half;                                    // all own rows lie in one block of the L
+    A.nrows = u.nrows; A.ystart = u.ystart; A.base_el = u.base_el; A.so_first = u.so_first; A.so_c0 = u.so_c0; A.gc = u.gc;
+    A.bot = u.bot != 0;                                         // all own rows lie in one block of the L
+    A.x = u.strip * (kWave * VEC) + lane * VEC;
     A.vo_own = lane_off<T>(g, A.x, A.bot);                      // the item's own rows (loads and stores)
     A.ve_own = edge_off<T, VEC>(g, A.x, lane, A.bot);
     A.vo_first = lane_off<T>(g, A.x, A.ystart - DIR <= g.half); // the halo row behind the first own row
     A.vo_last = lane_off<T>(g, A.x, A.ystart + DIR * A.nrows <= g.half);   // the halo row ahead of the last one
-    A.so_first = DESC ? (int)((row_off(g, it.yb + 1) - row_off(g, y0)) * (long long)sizeof(T)) : 0;
-    A.so_c0 = DESC ? (int)((row_off(g, it.yb) - row_off(g, y0)) * (long long)sizeof(T)) : row_step<T>(g, y0);
-    A.gc = it.gc;
     return A;
 }
 
@@ -727,7 +712,8 @@ __global__ __launch_bounds__(kBlock) void k_stencil(const StencilArgs<T> a) {
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);   // wave-uniform -> SGPR item decode
     MI355CG_WT_BEGIN
-    const ItemSeq seq = item_seq(a.tab, wave);
+    const StartRec rec = start_rec(a.tab.start, wave);
+    const ItemSeq seq = rec.seq;
     struct Raw { vec_t r, p; T re, pe; };
 
     // LEAN prologue order: the small loads first.  The state (scalar loads) and this thread's two partial pairs are requested
@@ -757,18 +743,20 @@ __global__ __launch_bounds__(kBlock) void k_stencil(const StencilArgs<T> a) {
     int* const dq = (QUEUE && a.dq.mine) ? a.dq.mine + ((int)(blockIdx.x % kXcds) * kQueueSubs + dq_sub) * kQueuePitch : nullptr;
     if (QUEUE && a.dq.other && blockIdx.x == 0 && threadIdx.x < kXcds * kQueueSubs) a.dq.other[threadIdx.x * kQueuePitch] = 0;
     int dq_ticket = 0;                                          // lane 0: this wave's next ticket of its group's queue
-    auto enter = [&](int item) {
+    auto enter = [&](const ItemUni& u) {
         if (QUEUE && dq) dq_ticket = queue_take(dq, lane);      // asked for now, needed at the next switch
-        F = item_addr<T, VEC, false>(g, decode_item(a.tab, item), lane);
+        F = item_addr<T, VEC, false>(g, u, lane);
         rs_p = make_rsrc(a.pin + F.base_el);
         rs_r = make_rsrc(FUSED ? a.r + F.base_el : a.pin + F.base_el);
         f_idx = -1; f_so = F.so_first; f_y = F.ystart - 1;
     };
-    auto fetch = [&]() -> Raw {
-        if (f_have && f_idx > F.nrows) {                         // lazily: the compute cursor may still need F (see promote)
+    // may_switch = false: the first DEPTH fetches of a launch stay in the first item (DEPTH <= 3 <= nrows + 2), so no switch -- and no
+    // dependent item load -- stands in front of the first row requests
+    auto fetch = [&](bool may_switch = true) -> Raw {
+        if (may_switch && f_have && f_idx > F.nrows) {           // lazily: the compute cursor may still need F (see promote)
             f_item = (QUEUE && dq) ? seq.begin + seq.step + __builtin_amdgcn_readfirstlane(dq_ticket) * dq_nsub + dq_sub : f_item + seq.step;
             f_have = f_item < seq.end;
-            if (f_have) enter(f_item);
+            if (f_have) enter(item_uniform<false>(g, decode_item(a.tab, f_item), (int)sizeof(T)));
         }
         const bool own = f_idx >= 0 && f_idx < F.nrows;
         int vo = own ? F.vo_own : (f_idx < 0 ? F.vo_first : F.vo_last);
@@ -808,10 +796,10 @@ __global__ __launch_bounds__(kBlock) void k_stencil(const StencilArgs<T> a) {
 
     // The first rows are requested BEFORE the prologue: they do not depend on beta, and the state load and the
     // reduction of the partials then run under their latency instead of in front of it.
-    if (f_have) { enter(f_item); promote(); }
+    if (f_have) { enter(rec.u); promote(); }                    // the first item comes ready made
     Raw q[DEPTH];
 #pragma unroll
-    for (int k = 0; k < DEPTH; ++k) q[k] = fetch();
+    for (int k = 0; k < DEPTH; ++k) q[k] = fetch(false);
     MI355CG_WT_STAMP(3)
 
     T beta = (T)0;
@@ -917,7 +905,7 @@ __global__ __launch_bounds__(kBlock) void k_stencil(const StencilArgs<T> a) {
                         if (MSG) dd_acc_prod(acc_rz, (double)r_c[j], (double)c);
                     }
                     if (!NOAP) buf_store(out, rs_ap, C.vo_own, c_so);
-                    if (FUSED) buf_store(pn_c, rs_po, C.vo_own, c_so);
+                    if (FUSED) buf_store<kStorePnew>(pn_c, rs_po, C.vo_own, c_so);
                     if (FUSED && GC) buf_store(pne_c, rs_po, c_ve_gc, c_so);   // new direction of the ghost column beside the part
                     c_so += row_step<T>(g, c_y); ++c_y;
                     pn_b = pn_c; pn_c = pn; pne_c = pne; r_c = w.r;
@@ -1216,7 +1204,8 @@ struct UpdateStArgs {
     double* partB; int strideB, slotB;
     const CgState* s_in; CgState* s_out;
     int rule;
-    int reverse;         // take the items from the last to the first (start where the stencil launch ended)
+    int reverse;         // take the items from the last to the first (start where the stencil launch ended); selects the start records of the
+                         // reversed descending march, so it goes with DESC = true (launch_iteration_update sets both)
     const int* stop_req; // pinned host word, sampled once per iteration by block 0 -> CgState::stop (msg_solver.cpp:82-87) and, in a team, -> the
                          // part's record (every part ORs its own sample with the other parts' records, so all decide alike); may be null
     FlagSpec fl;         // team: every block also stores its partials flagged, for the reducer launch that runs beside this one
@@ -1235,11 +1224,8 @@ __global__ __launch_bounds__(kBlock) void k_update_st(const UpdateStArgs<T> a) {
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
     MI355CG_WT_BEGIN
-    const ItemSeq seq = item_seq(a.tab, wave);
-    // the stop request (a pinned HOST word) is sampled once per iteration by block 0 -- a scalar load issued here and consumed
-    // in the epilogue, so its PCIe round trip runs under the whole launch
-    int stop_word = 0;
-    if (blockIdx.x == 0 && a.stop_req) stop_word = scalar_load(a.stop_req);
+    const StartRec rec = start_rec(a.reverse ? a.tab.start_rev : a.tab.start, wave);
+    const ItemSeq seq = rec.seq;
     constexpr bool FULL = XM == 1;
     constexpr int NP = XM >= 2 ? XM - 1 : 0;          // earlier directions folded into this launch's x update
     struct Raw { vec_t p, r, x, u, pp[NP > 0 ? NP : 1]; T pe; };
@@ -1266,9 +1252,9 @@ __global__ __launch_bounds__(kBlock) void k_update_st(const UpdateStArgs<T> a) {
     int* const dq = (QUEUE && a.dq.mine) ? a.dq.mine + ((int)(blockIdx.x % kXcds) * kQueueSubs + dq_sub) * kQueuePitch : nullptr;
     if (QUEUE && a.dq.other && blockIdx.x == 0 && threadIdx.x < kXcds * kQueueSubs) a.dq.other[threadIdx.x * kQueuePitch] = 0;
     int dq_ticket = 0;
-    auto enter = [&](int idx) {
+    auto enter = [&](const ItemUni& u) {
         if (QUEUE && dq) dq_ticket = queue_take(dq, lane);
-        F = item_addr<T, VEC, DESC>(g, decode_item(a.tab, a.reverse ? seq.end - 1 - (idx - seq.begin) : idx), lane);   // reversed within the wave's class
+        F = item_addr<T, VEC, DESC>(g, u, lane);
         rs_p = make_rsrc(a.p + F.base_el);
         rs_r = make_rsrc(a.r + F.base_el);
         rs_x = make_rsrc(XM != 0 ? a.x + F.base_el : a.p + F.base_el);
@@ -1278,11 +1264,11 @@ __global__ __launch_bounds__(kBlock) void k_update_st(const UpdateStArgs<T> a) {
         f_idx = -1; f_so = F.so_first; f_y = DESC ? F.ystart + 1 : F.ystart - 1;
     };
     // `own`: the row is one of this item's rows (its r / x / u / previous direction are needed, and its edge element)
-    auto fetch = [&]() -> Raw {
-        if (f_have && f_idx > F.nrows) {
+    auto fetch = [&](bool may_switch = true) -> Raw {           // see k_stencil
+        if (may_switch && f_have && f_idx > F.nrows) {
             f_item = (QUEUE && dq) ? seq.begin + seq.step + __builtin_amdgcn_readfirstlane(dq_ticket) * dq_nsub + dq_sub : f_item + seq.step;
             f_have = f_item < seq.end;
-            if (f_have) enter(f_item);
+            if (f_have) enter(item_uniform<DESC>(g, decode_item(a.tab, a.reverse ? seq.end - 1 - (f_item - seq.begin) : f_item), (int)sizeof(T)));   // reversed within the wave's class
         }
         const bool own = f_have && f_idx >= 0 && f_idx < F.nrows;
         int vo = own ? F.vo_own : (f_idx < 0 ? F.vo_first : F.vo_last);
@@ -1319,11 +1305,15 @@ __global__ __launch_bounds__(kBlock) void k_update_st(const UpdateStArgs<T> a) {
         for (int j = 0; j < VEC; ++j) in_j[j] = (C.x + j >= xint0) && (C.x + j <= g.N - 1);
     };
 
-    if (f_have) { enter(f_item); promote(); }
+    if (f_have) { enter(rec.u); promote(); }                    // the first item comes ready made
     Raw q[DEPTH];
 #pragma unroll
-    for (int k = 0; k < DEPTH; ++k) q[k] = fetch();
+    for (int k = 0; k < DEPTH; ++k) q[k] = fetch(false);
     MI355CG_WT_STAMP(3)
+    // the stop request (a pinned HOST word) is sampled once per iteration by block 0 -- a scalar load issued behind the first row
+    // requests (the next wait for a scalar is a PCIe round trip long) and consumed in the epilogue
+    int stop_word = 0;
+    if (blockIdx.x == 0 && a.stop_req) stop_word = scalar_load(a.stop_req);
 
     double alpha_d, rz = 0.0;
     if (!TEAM) {
@@ -1443,7 +1433,7 @@ __global__ __launch_bounds__(kBlock) void k_update_st(const UpdateStArgs<T> a) {
                             }
                         }
                     }
-                    buf_store(rn, rs_ro, C.vo_own, c_so);
+                    buf_store<kStoreR>(rn, rs_ro, C.vo_own, c_so);
                     if (XM != 0) buf_store(xn, rs_xo, C.vo_own, c_so);
                     if (DESC) { c_so -= row_step<T>(g, c_y - 1); --c_y; } else { c_so += row_step<T>(g, c_y); ++c_y; }
                     p_b = c.p; c = w;

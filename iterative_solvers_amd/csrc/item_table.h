@@ -1,16 +1,45 @@
-// item_table.h -- the work items of a launch and who takes them: plan arithmetic and the two tables the kernels read.
+// item_table.h -- the work items of a launch and who takes them: plan arithmetic, the storage layout and the tables the kernels read.
 //
-// Host only, free of HIP includes (tests/cpp/item_table_driver.cpp compiles it with the host compiler alone).  A launch covers
+// Free of HIP includes (tests/cpp/item_table_driver.cpp and tests/cpp/start_record_driver.cpp compile it with the host compiler alone).  A launch covers
 // a list of panels (rows x column strips, cut into row chunks); one (chunk, strip) pair is one work item.  The kernels used to get
 // the panel list by value and searched it in their prologue; now every plan is expanded ONCE, when it is made, into
-//   * an ItemDesc per item index, in the enumeration order (panel by panel, chunk-major, strip fastest), and
-//   * an ItemSeq per wave of the launch: the item indices that wave takes,
-// 16 bytes each, which a wave fetches with one scalar load at a wave-uniform index (cg_kernels.h: decode_item, item_seq).
+//   * an ItemDesc per item index, in the enumeration order (panel by panel, chunk-major, strip fastest): 16 bytes, and
+//   * a StartRec per wave of the launch and march direction: the item indices that wave takes (its ItemSeq) and the addressing
+//     of its FIRST item, ready made: 64 bytes,
+// each of which a wave fetches with one scalar load at a wave-uniform index (cg_kernels.h: decode_item, start_rec).
 #pragma once
 #include <algorithm>
 #include <vector>
 
+#ifdef __HIP__
+#define MI355CG_HD __attribute__((host)) __attribute__((device))
+#else
+#define MI355CG_HD
+#endif
+
 namespace mi355cg {
+
+// ---- storage layout -------------------------------------------------------------------------------
+// Node (x, y) of the (N+1)x(N+1) bounding grid lives at  row_off(y) + x - base0.  Rows y <= N/2
+// (bottom-right block + its boundary row 0) only store columns [cb, cb+Pb), cb = N/2 rounded down
+// to 32; rows above store columns [0, Pu).  Pb, Pu, cb are multiples of 32 elements so every row
+// starts 256-B aligned.  Boundary nodes and pads hold 0 and stay 0; Dirichlet data is in the RHS.
+struct Geom {
+    int N, half, cb, xlim;            // xlim: columns [0, xlim) are touched by the stencil strips
+    int Pb, Pu;                       // row pitches (elements) of bottom / upper rows
+    int y_lo, y_hi;                   // owned rows (inclusive); rows y_lo-1 and y_hi+1 are ghosts
+    long long base0;                  // physical offset of the first stored element (row y_lo-1)
+    long long own_begin, own_len;     // flat [begin, begin+len) of the owned rows, local offsets
+    double A, xk, yk;                 // stencil coefficients (grid_system.cpp:316-318)
+};
+
+MI355CG_HD inline long long row_off(const Geom& g, int y) {
+    return y <= g.half ? (long long)y * g.Pb - g.cb
+                       : (long long)(g.half + 1) * g.Pb + (long long)(y - g.half - 1) * g.Pu;
+}
+MI355CG_HD inline bool node_interior(const Geom& g, int x, int y) {
+    return y >= 1 && y <= g.N - 1 && x <= g.N - 1 && x >= (y <= g.half ? g.half + 1 : 1);
+}
 
 constexpr int kBlock = 256;           // threads per workgroup = 4 wave64
 constexpr int kWave = 64;
@@ -36,6 +65,37 @@ struct alignas(16) ItemDesc { int strip, ya, yb, gc; };
 // the item indices a wave takes: first, first + step, ... < end (begin: first index of the wave's class, for the reversed march and the queues)
 struct alignas(16) ItemSeq { int first, step, begin, end; };
 
+// The wave-uniform addressing data of one work item, constant while the item is marched (what the lanes add: cg_kernels.h,
+// ItemAddr).  Written once, for both sides: the host expands it into the start records, a wave evaluates it for its later items.
+// DESC: the item is marched from its last row down (the update launches).  elem: bytes per element.
+struct ItemUni {
+    long long base_el;          // element offset of row y0 = ya - 1 (the lowest row the item touches) from the start of a vector
+    int so_first, so_c0;        // byte offsets from row y0 of the halo row behind the first own row / of the first own row
+    int nrows, ystart;          // rows of the item; its first row in march order
+    int strip;
+    int bot;                    // 1: all own rows lie in the bottom block of the L
+    int gc;
+};
+template <bool DESC>
+MI355CG_HD inline ItemUni item_uniform(const Geom& g, const ItemDesc& it, int elem) {
+    ItemUni u;
+    const int y0 = it.ya - 1;
+    u.nrows = it.yb - it.ya + 1;
+    u.ystart = DESC ? it.yb : it.ya;
+    u.base_el = row_off(g, y0) - g.base0;
+    u.so_first = DESC ? (int)((row_off(g, it.yb + 1) - row_off(g, y0)) * (long long)elem) : 0;
+    u.so_c0 = DESC ? (int)((row_off(g, it.yb) - row_off(g, y0)) * (long long)elem) : (y0 + 1 <= g.half ? g.Pb : g.Pu) * elem;
+    u.strip = it.strip;
+    u.bot = it.ya <= g.half ? 1 : 0;
+    u.gc = it.gc;
+    return u;
+}
+// What a wave starts a launch from: its item sequence and the ItemUni of its first item (have == 0: the wave has no item, u is 0).
+// Ascending launches (stencil) start on item seq.first, the reversed descending march (update) on seq.end - 1 - (seq.first - seq.begin);
+// a launch with run-time queues starts every wave on the same static first item.
+struct alignas(64) StartRec { ItemSeq seq; ItemUni u; int have; int pad; };
+static_assert(sizeof(StartRec) == 64, "StartRec: one 64-byte scalar load");
+
 // Rows [y0, y1] x strips [s0, s1) with their ghost-column flags
 struct Rect { int y0, y1, s0, s1, gc; };
 
@@ -59,8 +119,9 @@ inline long long add_panel(WorkList& wl, int y0, int y1, int s0, int s1, int ty,
 // the handle: uploaded when the plans are built, freed with it) the two tables of that shape.
 struct Plan {
     WorkList wl{}; int grid = 0; int ty = 0;
+    int elem = 8;                     // bytes per element of the kernels that march this plan (the start records hold byte offsets)
     ItemDesc* d_items = nullptr;      // wl.nitems entries
-    ItemSeq* d_seq = nullptr;         // grid * kWaves entries
+    StartRec* d_start[2] = {nullptr, nullptr};     // grid * kWaves entries each: ascending march, reversed descending march
 };
 
 // What the environment may override (MI355CG_WAVES, MI355CG_BLOCKS, MI355CG_ITEM_ROWS, MI355CG_XCD_CLASSES)
@@ -148,6 +209,21 @@ inline std::vector<ItemSeq> build_seq_table(const WorkList& wl, int grid) {
             s = ItemSeq{wl.cls0[cls] + b / kXcds * kWaves, nb * kWaves, wl.cls0[cls], wl.cls0[cls + 1]};
         }
         for (int w = 0; w < kWaves; ++w) { t[(size_t)b * kWaves + w] = s; t[(size_t)b * kWaves + w].first += w; }
+    }
+    return t;
+}
+
+// Entry b * kWaves + w: the start record of wave w of workgroup b.  reversed: for the update launches (see StartRec).
+inline std::vector<StartRec> build_start_table(const WorkList& wl, int grid, const Geom& g, int elem, bool reversed) {
+    const std::vector<ItemDesc> items = build_item_table(wl);
+    const std::vector<ItemSeq> seq = build_seq_table(wl, grid);
+    std::vector<StartRec> t(seq.size(), StartRec{});
+    for (size_t w = 0; w < seq.size(); ++w) {
+        const ItemSeq& s = seq[w];
+        t[w].seq = s;
+        if (s.first >= s.end) continue;
+        t[w].have = 1;
+        t[w].u = reversed ? item_uniform<true>(g, items[(size_t)(s.end - 1 - (s.first - s.begin))], elem) : item_uniform<false>(g, items[(size_t)s.first], elem);
     }
     return t;
 }

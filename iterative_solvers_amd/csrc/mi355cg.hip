@@ -346,22 +346,25 @@ int upload_item_tables(mi355cg_ctx* c) {
     for (Plan* pl : {&c->whole, &c->interior, &c->edge, &c->whole32}) {
         if (pl->wl.nitems == 0 || pl->grid == 0) continue;
         const std::vector<ItemDesc> items = build_item_table(pl->wl);
-        const std::vector<ItemSeq> seq = build_seq_table(pl->wl, pl->grid);
         HIPCK(hipMalloc((void**)&pl->d_items, sizeof(ItemDesc) * items.size()));
-        HIPCK(hipMalloc((void**)&pl->d_seq, sizeof(ItemSeq) * seq.size()));
         HIPCK(hipMemcpy(pl->d_items, items.data(), sizeof(ItemDesc) * items.size(), hipMemcpyHostToDevice));
-        HIPCK(hipMemcpy(pl->d_seq, seq.data(), sizeof(ItemSeq) * seq.size(), hipMemcpyHostToDevice));
+        pl->elem = pl == &c->whole32 ? (int)sizeof(float) : (int)sizeof(double);
+        for (int rev = 0; rev < 2; ++rev) {      // the start records of the ascending (stencil, apply) and of the reversed descending march (update)
+            const std::vector<StartRec> start = build_start_table(pl->wl, pl->grid, c->g, pl->elem, rev != 0);
+            HIPCK(hipMalloc((void**)&pl->d_start[rev], sizeof(StartRec) * start.size()));
+            HIPCK(hipMemcpy(pl->d_start[rev], start.data(), sizeof(StartRec) * start.size(), hipMemcpyHostToDevice));
+        }
     }
     return MI355CG_OK;
 }
 void free_item_tables(mi355cg_ctx* c) {
     for (Plan* pl : {&c->whole, &c->interior, &c->edge, &c->whole32}) {
         if (pl->d_items) hipFree(pl->d_items);
-        if (pl->d_seq) hipFree(pl->d_seq);
-        pl->d_items = nullptr; pl->d_seq = nullptr;
+        for (int rev = 0; rev < 2; ++rev) { if (pl->d_start[rev]) hipFree(pl->d_start[rev]); pl->d_start[rev] = nullptr; }
+        pl->d_items = nullptr;
     }
 }
-ItemTab item_tab(const Plan& pl) { return ItemTab{pl.d_items, pl.d_seq, pl.wl.nitems}; }
+ItemTab item_tab(const Plan& pl) { return ItemTab{pl.d_items, pl.d_start[0], pl.d_start[1], pl.wl.nitems}; }
 
 int flat_grid(long long n) { return (int)std::max<long long>(1, std::min<long long>(2048, (n + kBlock - 1) / kBlock)); }
 
