@@ -25,8 +25,9 @@
  *                                  set, mi355cg_solve runs preconditioned CG (same stop rules, callbacks, stop flag, results)
  *   mi355cg_set_preconditioner_ex  the same with the precision of the V-cycle: MI355CG_CYCLE_F64 or MI355CG_CYCLE_F32
  *   mi355cg_preconditioner_info    kind, cycle precision and number of levels of what is set
+ *   mi355cg_set_smoother / _get_smoother   the smoother of the fp64 V-cycle: damped point Jacobi, or line Jacobi for stretched domains
  *   mi355cg_apply_preconditioner   z = M r on host vectors (packed order)
- *   mi355cg_mg_levels              the hierarchy a grid gets (pure host arithmetic, no GPU needed)
+ *   mi355cg_mg_levels            the hierarchy a grid gets (pure host arithmetic, no GPU needed)
  *   mi355cg_mg_hierarchy           every level's N of either multigrid kind (pure host arithmetic, no GPU needed)
  *   mi355cg_solve_batch            many right-hand sides on one grid by one preconditioned CG loop (host vectors)
  *   mi355cg_solve_batch_device     the same with the vectors in device memory
@@ -203,6 +204,30 @@ int  mi355cg_mg_hierarchy(int kind, int n, int max_levels, int *levels, int *lev
 #define MI355CG_CYCLE_F32 1   /* the V-cycle in fp32 inside the fp64 PCG */
 int  mi355cg_set_preconditioner_ex(mi355cg_handle h, int kind, int cycle);
 int  mi355cg_preconditioner_info(mi355cg_handle h, int *kind, int *cycle, int *levels);
+
+/* Smoother of the fp64 V-cycle.  The interface takes n == m, so every domain that is not a square has
+ * hx != hy and an operator that is anisotropic by (hx / hy)^2; damped point Jacobi stops smoothing the weakly coupled direction
+ * and the iteration count of the preconditioned CG grows with the stretch and with n.  A line smoother replaces the point sweep
+ * by  t = u + omega T^-1 (r - A u), omega = 0.8,  T = the level's operator along the lines (its diagonal, shift included, and the
+ * two neighbours in the line direction), solved exactly per line.  Lines are the maximal runs of interior nodes of the L-shape.
+ * Schedule, transfer operators and coarse inverse are unchanged, T is symmetric, so M stays symmetric negative definite.
+ * The default is MI355CG_SMOOTHER_JACOBI: a handle that never calls mi355cg_set_smoother runs the launches it always ran.
+ * mi355cg_set_smoother may be called before or after mi355cg_set_preconditioner* and mi355cg_set_shift, with the same result:
+ * with a hierarchy present it builds or frees the per-level line tables (2 N_l doubles per level) in place and takes effect at
+ * once; without one the value is kept for the next mi355cg_set_preconditioner*.  Everything that runs the fp64 cycle follows it
+ * (mi355cg_apply_preconditioner, mi355cg_solve, mi355cg_solve_batch*, mi355cg_time_steps, mi355cg_eigs*); the batch and eigen
+ * workspaces, x, r, b, u and a pending guess stay.  MI355CG_SMOOTHER_JACOBI after a line smoother gives the bits of a handle that
+ * never had one.  On one-level grids (n <= 32) the cycle is the dense inverse: every smoother gives the same bits.
+ * MI355CG_ERR_INVALID, the handle left as it was: a null handle, an unknown value, a CSR, slab / part or MI355CG_F32_MIXED
+ * handle, a line smoother while the preconditioner is set with MI355CG_CYCLE_F32 -- and, the other way round,
+ * mi355cg_set_preconditioner_ex(.., MI355CG_CYCLE_F32) while a line smoother is set.
+ * mi355cg_get_smoother: the value as set, and the direction it means on this handle (0 none, 1 x, 2 y); null out-pointers are skipped. */
+#define MI355CG_SMOOTHER_JACOBI    0   /* the default: damped point Jacobi */
+#define MI355CG_SMOOTHER_LINE_X    1   /* lines along x (rows)    */
+#define MI355CG_SMOOTHER_LINE_Y    2   /* lines along y (columns) */
+#define MI355CG_SMOOTHER_LINE_AUTO 3   /* y-lines if level 0 has y_k > x_k, else x-lines; one decision for all levels */
+int  mi355cg_set_smoother(mi355cg_handle h, int smoother);
+int  mi355cg_get_smoother(mi355cg_handle h, int *smoother, int *direction);
 
 /* Batched solves: nrhs right-hand sides on one handle that has a multigrid preconditioner set (fp64 cycle), solved together by
  * one preconditioned CG loop whose every launch carries all systems that are still iterating, so the launches and the three

@@ -36,10 +36,12 @@ EXPORTS = [
     "mi355cg_set_shift", "mi355cg_get_shift", "mi355cg_time_steps", "mi355cg_get_solution_device",
     "mi355cg_eigs", "mi355cg_eigs_device", "mi355cg_eigs_release", "mi355cg_block_gram", "mi355cg_block_gram_indexed",
     "mi355cg_block_combine", "mi355cg_rayleigh_ritz",
+    "mi355cg_set_smoother", "mi355cg_get_smoother",
 ]
 DECOMP_ROWS, DECOMP_2D = 0, 1
 PRECOND_NONE, PRECOND_MG, PRECOND_MG_ANY = 0, 1, 2
 CYCLE_F64, CYCLE_F32 = 0, 1
+SMOOTHER_JACOBI, SMOOTHER_LINE_X, SMOOTHER_LINE_Y, SMOOTHER_LINE_AUTO = 0, 1, 2, 3
 BATCH_MAX = 64          # MI355CG_BATCH_MAX
 EIG_BLOCK_MAX = 16      # MI355CG_EIG_BLOCK_MAX
 EIG_BASIS_MAX = 48      # vectors of a Rayleigh-Ritz basis, and of a group of block_gram
@@ -204,7 +206,10 @@ def load():
         L.mi355cg_block_gram_indexed.argtypes = [H, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.mi355cg_block_combine.argtypes = [H, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.mi355cg_rayleigh_ritz.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    if hasattr(L, "mi355cg_get_xfold"):          # absent from an older build loaded through MI355CG_LIB
+    if hasattr(L, "mi355cg_set_smoother"):       # absent from an older build loaded through MI355CG_LIB
+        L.mi355cg_set_smoother.argtypes = [H, C.c_int]
+        L.mi355cg_get_smoother.argtypes = [H, IP, IP]
+    if hasattr(L, "mi355cg_get_xfold"):         # absent from an older build loaded through MI355CG_LIB
         L.mi355cg_get_xfold.argtypes = [H, IP, IP]
     _lib = L
     return L

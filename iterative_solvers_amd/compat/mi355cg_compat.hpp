@@ -433,6 +433,9 @@ public:
     // returns to plain CG.  std::invalid_argument for PRECOND_MG on a grid without a nested hierarchy.
     // cycle: MI355CG_CYCLE_F32 runs the V-cycle in fp32 inside the fp64 PCG (mi355cg_set_preconditioner_ex).
     void setPreconditioner(int kind, int cycle = MI355CG_CYCLE_F64) { mi355cg_compat::check(mi355cg_set_preconditioner_ex(ctx_->h, kind, cycle)); }
+    // Extension: the smoother of the fp64 V-cycle (mi355cg_set_smoother): MI355CG_SMOOTHER_JACOBI (the default), or line Jacobi
+    // MI355CG_SMOOTHER_LINE_X / _LINE_Y / _LINE_AUTO for a stretched domain.  Before or after setPreconditioner.
+    void setSmoother(int smoother) { mi355cg_compat::check(mi355cg_set_smoother(ctx_->h, smoother)); }
     // Extension: every b[s] solved by one multigrid-preconditioned CG loop (mi355cg_solve_batch; needs setPreconditioner first).
     // x[s] and results[s] have the bits a single solve of b[s] on this system gives.  params.use_true_solution and
     // params.diagnostics must be 0 (mi355cg_default_params sets the former to 1).  std::invalid_argument for an empty batch, more

@@ -9,6 +9,7 @@
 #include "mg_kernels.h"
 #include "mg_batch_kernels.h"
 #include "eig_kernels.h"
+#include "mg_line_kernels.h"
 #include "mg_kernels_f32.h"
 #include "step_kernels.h"
 
@@ -70,13 +71,17 @@ struct EventPool {
 // l + 1 has 2 floor(N_l / 4) intervals (mg_shape) and the steps that keep the domain.  Per level: the right-hand side of its cycle
 // (level 0: the caller's vector), a work vector and the cycle's result (level 0: the caller's output); the coarsest level keeps
 // its dense inverse.
-struct MgLevel { Geom g{}; long long len = 0; int grid = 0; double *rhs = nullptr, *a = nullptr, *out = nullptr; };
+struct MgLevel {
+    Geom g{}; long long len = 0; int grid = 0; double *rhs = nullptr, *a = nullptr, *out = nullptr;
+    double* tab = nullptr;              // line smoother: the level's Thomas factors, 2 N doubles (mg_line_kernels.h); nullptr without one
+};
 // The same three vectors of a level in fp32 (MI355CG_CYCLE_F32; level 0 too: r32, the work vector, the iterate) with the level's
 // constants rounded to fp32; vec: columns per lane of its kernels (mg_kernels_f32.h)
 struct MgLevel32 { float *rhs = nullptr, *a = nullptr, *out = nullptr; MgCoef32 c{}; float scale = 0.f; int vec = 1; };
 struct MgHier {
     int kind = 0;                       // MI355CG_PRECOND_MG or _MG_ANY: the kind last set (where both have a hierarchy it is this one)
     int cycle = MI355CG_CYCLE_F64;      // precision of the V-cycle; F32 keeps lv32 / inv32 instead of the levels' fp64 vectors and inv
+    int line_dir = 0;                   // 0: damped point Jacobi; MG_LINE_X / MG_LINE_Y: line Jacobi along it, the levels keep `tab`
     std::vector<MgLevel> lv;
     std::vector<MgLevel32> lv32;
     float* inv32 = nullptr;             // A_L^-1 rounded to fp32
@@ -176,6 +181,7 @@ struct mi355cg_ctx {
     // Diagonal shift (mi355cg_set_shift): the operator is A - sigma I.  g.A = gp.A - sigma and every multigrid
     // level's diagonal carry it; gp.A stays the Laplacian's.
     double sigma = 0.0;
+    int smoother = MI355CG_SMOOTHER_JACOBI;   // as given to mi355cg_set_smoother; kept while there is no hierarchy
     double* step_b = nullptr;           // mi355cg_time_steps: the right-hand side of a step, allocated by the first call
     // generic CSR handle (mi355cg_create_csr): vectors are plain length-n arrays, the operator is this matrix
     bool is_csr = false;
@@ -936,7 +942,7 @@ Geom mg_geom(int N, double hx, double hy, double sigma, long long* len) {
 
 void mg_free(MgHier* H) {
     if (!H) return;
-    for (auto& L : H->lv) for (double* v : {L.rhs, L.a, L.out}) if (v) hipFree(v);
+    for (auto& L : H->lv) for (double* v : {L.rhs, L.a, L.out, L.tab}) if (v) hipFree(v);
     for (double* v : {H->inv, H->z, H->p[0], H->p[1], H->q, H->part}) if (v) hipFree(v);
     for (auto& L : H->lv32) for (float* v : {L.rhs, L.a, L.out}) if (v) hipFree(v);
     if (H->inv32) hipFree(H->inv32);
@@ -999,6 +1005,60 @@ void mg_coarse_inverse(const Geom& g, std::vector<double>& inv, std::vector<int>
 
 int mg_build32(MgHier* H, const std::vector<double>& inv);
 
+// ---- line smoother (mi355cg_set_smoother; kernels in mg_line_kernels.h) -------------------------------------
+// The direction a smoother value means on this handle.  AUTO looks at level 0 alone: the coarser levels keep the ratio of the steps.
+int mg_line_direction(const mi355cg_ctx* c, int smoother) {
+    if (smoother == MI355CG_SMOOTHER_LINE_X) return MG_LINE_X;
+    if (smoother == MI355CG_SMOOTHER_LINE_Y) return MG_LINE_Y;
+    if (smoother == MI355CG_SMOOTHER_LINE_AUTO) return c->g.yk > c->g.xk ? MG_LINE_Y : MG_LINE_X;
+    return 0;
+}
+
+// The Thomas factors of a level's lines (mg_line_kernels.h): tab[i] = inv_i, tab[N + i] = cp_i for 1 <= i <= N - 1
+std::vector<double> mg_line_table(const Geom& g, int dir) {
+    const double k = dir == MG_LINE_X ? g.xk : g.yk;
+    std::vector<double> tab((size_t)2 * g.N, 0.0);
+    double cp = 0.0;
+    for (int i = 1; i <= g.N - 1; ++i) {
+        const double inv = 1.0 / (g.A - k * cp);               // i = 1: A - k * 0 = A
+        cp = k * inv;
+        tab[i] = inv;
+        tab[(size_t)g.N + i] = cp;
+    }
+    return tab;
+}
+
+// The tables of direction dir (dir == 0: none) for every smoothing level of H with the diagonal shifted by sigma, uploaded into
+// fresh[level]; H is not touched.
+int mg_make_line_tables(const MgHier* H, int dir, double sigma, std::vector<double*>& fresh) {
+    const int nl = (int)H->lv.size();
+    fresh.assign(nl, nullptr);
+    for (int l = 0; dir && l + 1 < nl; ++l) {                      // the coarsest level does not smooth
+        Geom g = H->lv[l].g;
+        g.A = -2 * (g.xk + g.yk) - sigma;                          // mg_geom's expression
+        const std::vector<double> tab = mg_line_table(g, dir);
+        if (hipMalloc((void**)&fresh[l], sizeof(double) * tab.size()) != hipSuccess ||
+            hipMemcpy(fresh[l], tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice) != hipSuccess) {
+            for (double* v : fresh) if (v) hipFree(v);
+            (void)hipGetLastError();
+            fresh.assign(nl, nullptr);
+            return fail(MI355CG_ERR_HIP, "line smoother table upload failed");
+        }
+    }
+    return MI355CG_OK;
+}
+// ... and dir becomes H's smoother with them.  The caller has made sure that nothing in flight reads the old tables.
+void mg_install_line_tables(MgHier* H, int dir, const std::vector<double*>& fresh) {
+    for (size_t l = 0; l < H->lv.size(); ++l) { if (H->lv[l].tab) hipFree(H->lv[l].tab); H->lv[l].tab = fresh[l]; }
+    H->line_dir = dir;
+}
+int mg_set_line_tables(MgHier* H, int dir, double sigma) {
+    std::vector<double*> fresh;
+    if (int rc = mg_make_line_tables(H, dir, sigma, fresh)) return rc;
+    mg_install_line_tables(H, dir, fresh);
+    return MI355CG_OK;
+}
+
 int mg_build(mi355cg_ctx* c, int kind, MgHier** out, int cycle = MI355CG_CYCLE_F64) {
     std::vector<int> ns;
     if (int rc = mg_shape(kind, c->gp.n, &ns)) return rc;
@@ -1041,6 +1101,7 @@ int mg_build(mi355cg_ctx* c, int kind, MgHier** out, int cycle = MI355CG_CYCLE_F
         return bail(fail(MI355CG_ERR_HIP, "coarse inverse upload failed"));
     // the zero-fills ran on the NULL stream; the context's stream does not order with them (see create_impl)
     if (hipDeviceSynchronize() != hipSuccess) return bail(fail(MI355CG_ERR_HIP, "hipDeviceSynchronize failed"));
+    if (f64) if (int rc = mg_set_line_tables(H, mg_line_direction(c, c->smoother), c->sigma)) return bail(rc);   // the smoother set before the hierarchy
     *out = H;
     return MI355CG_OK;
 }
@@ -1068,6 +1129,25 @@ struct MgCycle {
     }
 };
 
+// One sweep of the hierarchy's smoother on level L: t = S(rhs, u).  first: u = 0.  dot != nullptr: + the partials of (rhs, t), one per
+// block of L.grid.  Point Jacobi goes out exactly as before there was a choice.
+template <int DIR>
+void mg_line_sweep(const MgCycle& cy, const MgLevel& L, bool first, const double* rhs, const double* u, double* t, double* dot) {
+    const int blocks = mg_line_blocks(L.g.N);
+    const double* tab = L.tab;
+    if (dot) cy.launch(k_mg_line<DIR, false, true>, k_mgb_line<DIR, false, true>, L.grid, L.g, kMgOmega, tab, rhs, u, t, dot);
+    else if (first) cy.launch(k_mg_line<DIR, true, false>, k_mgb_line<DIR, true, false>, blocks, L.g, kMgOmega, tab, rhs, nullptr, t, nullptr);
+    else cy.launch(k_mg_line<DIR, false, false>, k_mgb_line<DIR, false, false>, blocks, L.g, kMgOmega, tab, rhs, u, t, nullptr);
+}
+void mg_sweep(const MgCycle& cy, const MgLevel& L, bool first, const double* rhs, const double* u, double* t, double* dot) {
+    const int dir = cy.c->mg->line_dir;
+    if (dir == MG_LINE_X) return mg_line_sweep<MG_LINE_X>(cy, L, first, rhs, u, t, dot);
+    if (dir == MG_LINE_Y) return mg_line_sweep<MG_LINE_Y>(cy, L, first, rhs, u, t, dot);
+    if (dot) cy.launch(k_mg_smooth<false, true>, k_mgb_smooth<false, true>, L.grid, L.g, kMgOmega, rhs, u, t, dot);
+    else if (first) cy.launch(k_mg_smooth<true, false>, k_mgb_smooth<true, false>, L.grid, L.g, kMgOmega, rhs, nullptr, t, nullptr);
+    else cy.launch(k_mg_smooth<false, false>, k_mgb_smooth<false, false>, L.grid, L.g, kMgOmega, rhs, u, t, nullptr);
+}
+
 // out = V(rhs, l) on level l's vectors.  dot != nullptr (level 0): the last launch also leaves the partials of (rhs, out) there.
 void mg_vcycle(const MgCycle& cy, int l, const double* rhs, double* out, double* dot) {
     const MgHier& H = *cy.c->mg;
@@ -1083,8 +1163,8 @@ void mg_vcycle(const MgCycle& cy, int l, const double* rhs, double* out, double*
     double* const a = cy.vecs(l).a;
     const MgVecs cv = cy.vecs(l + 1);
     const bool nested = L.g.N == 2 * C.g.N;
-    cy.launch(k_mg_smooth<true, false>, k_mgb_smooth<true, false>, L.grid, L.g, kMgOmega, rhs, nullptr, a, nullptr);
-    cy.launch(k_mg_smooth<false, false>, k_mgb_smooth<false, false>, L.grid, L.g, kMgOmega, rhs, a, out, nullptr);
+    mg_sweep(cy, L, true, rhs, nullptr, a, nullptr);
+    mg_sweep(cy, L, false, rhs, a, out, nullptr);
     if (nested) {
         cy.launch(k_mg_restrict, k_mgb_restrict, C.grid, L.g, C.g, rhs, out, cv.rhs);
     } else {                            // a is free until the first post-sweep: it holds s = rhs - A out for the gather
@@ -1095,9 +1175,8 @@ void mg_vcycle(const MgCycle& cy, int l, const double* rhs, double* out, double*
     mg_vcycle(cy, l + 1, cv.rhs, cv.out, nullptr);
     if (nested) cy.launch(k_mg_prolong, k_mgb_prolong, L.grid, L.g, C.g, cv.out, out);
     else cy.launch(k_mg_prolong_nn, k_mgb_prolong_nn, L.grid, L.g, C.g, cv.out, out);
-    cy.launch(k_mg_smooth<false, false>, k_mgb_smooth<false, false>, L.grid, L.g, kMgOmega, rhs, out, a, nullptr);
-    if (dot) cy.launch(k_mg_smooth<false, true>, k_mgb_smooth<false, true>, L.grid, L.g, kMgOmega, rhs, a, out, dot);
-    else cy.launch(k_mg_smooth<false, false>, k_mgb_smooth<false, false>, L.grid, L.g, kMgOmega, rhs, a, out, nullptr);
+    mg_sweep(cy, L, false, rhs, out, a, nullptr);
+    mg_sweep(cy, L, false, rhs, a, out, dot);
 }
 
 // ---- the fp32 V-cycle (MI355CG_CYCLE_F32; kernels in mg_kernels_f32.h) -----------------------------------
@@ -2504,12 +2583,15 @@ int mi355cg_set_shift(mi355cg_handle c, double sigma) {
         std::vector<double> inv;
         std::vector<int> off;
         mg_coarse_inverse(gc, inv, off);                           // off: the layout's, unchanged
+        std::vector<double*> tabs;                                 // the lines' factors hold the diagonal too
+        if (int rc = mg_make_line_tables(H, H->line_dir, sigma, tabs)) return rc;
         void* fresh = nullptr;
         if (H->cycle == MI355CG_CYCLE_F32) {
             std::vector<float> inv32(inv.begin(), inv.end());
             if (hipMalloc(&fresh, sizeof(float) * inv32.size()) != hipSuccess ||
                 hipMemcpy(fresh, inv32.data(), sizeof(float) * inv32.size(), hipMemcpyHostToDevice) != hipSuccess) {
                 if (fresh) hipFree(fresh);
+                for (double* v : tabs) if (v) hipFree(v);
                 (void)hipGetLastError();
                 return fail(MI355CG_ERR_HIP, "coarse inverse upload failed: the shift stays %g", c->sigma);
             }
@@ -2518,6 +2600,7 @@ int mi355cg_set_shift(mi355cg_handle c, double sigma) {
             if (hipMalloc(&fresh, sizeof(double) * inv.size()) != hipSuccess ||
                 hipMemcpy(fresh, inv.data(), sizeof(double) * inv.size(), hipMemcpyHostToDevice) != hipSuccess) {
                 if (fresh) hipFree(fresh);
+                for (double* v : tabs) if (v) hipFree(v);
                 (void)hipGetLastError();
                 return fail(MI355CG_ERR_HIP, "coarse inverse upload failed: the shift stays %g", c->sigma);
             }
@@ -2528,6 +2611,7 @@ int mi355cg_set_shift(mi355cg_handle c, double sigma) {
             g.A = -2 * (g.xk + g.yk) - sigma;                      // mg_geom's expression
             if (l < H->lv32.size()) H->lv32[l].c.A = (float)g.A;
         }
+        mg_install_line_tables(H, H->line_dir, tabs);
     }
     c->sigma = sigma;
     c->g.A = c->gp.A - sigma;
@@ -2679,6 +2763,9 @@ int mi355cg_set_preconditioner_ex(mi355cg_handle c, int kind, int cycle) {
     if (int rc = mg_shape(kind, c->gp.n, &ns)) return rc;          // refused: the handle keeps what it had
     if (cycle != MI355CG_CYCLE_F64 && cycle != MI355CG_CYCLE_F32)
         return fail(MI355CG_ERR_INVALID, "unknown V-cycle precision %d (MI355CG_CYCLE_F64 = 0, MI355CG_CYCLE_F32 = 1)", cycle);
+    if (cycle == MI355CG_CYCLE_F32 && c->smoother != MI355CG_SMOOTHER_JACOBI)
+        return fail(MI355CG_ERR_INVALID, "the fp32 V-cycle smooths with point Jacobi only: this handle has line smoother %d "
+                    "(mi355cg_set_smoother(h, MI355CG_SMOOTHER_JACOBI) first)", c->smoother);
     mg_batch_free(c);                                              // accepted: the batch workspace goes, a refused call above keeps it
     eig_free(c);
     if (c->mg && c->mg->cycle == cycle) { c->mg->kind = kind; return MI355CG_OK; }   // both kinds have a hierarchy here: it is the same one
@@ -2689,6 +2776,37 @@ int mi355cg_set_preconditioner_ex(mi355cg_handle c, int kind, int cycle) {
     if (int rc = mg_build(c, kind, &H, cycle)) return rc;
     mg_free(c->mg);
     c->mg = H;
+    return MI355CG_OK;
+}
+
+// The smoother of the fp64 V-cycle.  With a hierarchy the levels' line tables are built or freed in place;
+// without one the value waits for the next mi355cg_set_preconditioner*.  A refusal or a failed upload leaves the handle as it was.
+int mi355cg_set_smoother(mi355cg_handle c, int smoother) {
+    if (!c) return fail(MI355CG_ERR_INVALID, "null handle");
+    if (smoother != MI355CG_SMOOTHER_JACOBI && smoother != MI355CG_SMOOTHER_LINE_X && smoother != MI355CG_SMOOTHER_LINE_Y &&
+        smoother != MI355CG_SMOOTHER_LINE_AUTO)
+        return fail(MI355CG_ERR_INVALID, "unknown smoother %d (MI355CG_SMOOTHER_JACOBI = 0, _LINE_X = 1, _LINE_Y = 2, _LINE_AUTO = 3)", smoother);
+    if (c->is_csr) return fail(MI355CG_ERR_INVALID, "the smoother belongs to the multigrid preconditioner: a CSR handle has no grid");
+    if (c->is_slab) return fail(MI355CG_ERR_INVALID, "the multigrid preconditioner is single-GPU only: this handle owns one part of a decomposed grid");
+    if (c->dtype != MI355CG_F64) return fail(MI355CG_ERR_INVALID, "the multigrid preconditioner is fp64 only: this handle was created with MI355CG_F32_MIXED");
+    if (smoother != MI355CG_SMOOTHER_JACOBI && c->mg && c->mg->cycle == MI355CG_CYCLE_F32)
+        return fail(MI355CG_ERR_INVALID, "the fp32 V-cycle smooths with point Jacobi only: this handle's preconditioner was set with MI355CG_CYCLE_F32");
+    if (c->mg && c->mg->cycle == MI355CG_CYCLE_F64) {
+        const int dir = mg_line_direction(c, smoother);
+        if (dir != c->mg->line_dir) {
+            HIPCK(hipSetDevice(c->device));
+            HIPCK(hipStreamSynchronize(c->stream));                // nothing in flight reads the tables
+            if (int rc = mg_set_line_tables(c->mg, dir, c->sigma)) return rc;
+        }
+    }
+    c->smoother = smoother;
+    return MI355CG_OK;
+}
+
+int mi355cg_get_smoother(mi355cg_handle c, int* smoother, int* direction) {
+    if (!c) return fail(MI355CG_ERR_INVALID, "null handle");
+    if (smoother) *smoother = c->smoother;
+    if (direction) *direction = mg_line_direction(c, c->smoother);
     return MI355CG_OK;
 }
 

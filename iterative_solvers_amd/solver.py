@@ -225,6 +225,21 @@ class _Handle:
         _capi.check(self._lib.mi355cg_preconditioner_info(self._h, C.byref(k), C.byref(cy), C.byref(lv)))
         return k.value, cy.value, lv.value
 
+    def set_smoother(self, smoother: int):
+        """Extension (no reference twin): the smoother of the fp64 V-cycle, _capi.SMOOTHER_JACOBI (the default) or line Jacobi
+        _capi.SMOOTHER_LINE_X / _LINE_Y / _LINE_AUTO for stretched domains (include/mi355cg.h, mi355cg_set_smoother).  Before or
+        after set_preconditioner.  ValueError if refused; the handle then keeps what it had."""
+        rc = self._lib.mi355cg_set_smoother(self._h, int(smoother))
+        if rc == _capi.ERR_INVALID:
+            raise ValueError(self._lib.mi355cg_last_error().decode())
+        _capi.check(rc)
+
+    def smoother_info(self):
+        """(smoother, direction): the smoother as set, and the line direction it means on this grid (0 none, 1 x, 2 y)."""
+        s, d = C.c_int(), C.c_int()
+        _capi.check(self._lib.mi355cg_get_smoother(self._h, C.byref(s), C.byref(d)))
+        return s.value, d.value
+
     def apply_preconditioner(self, r):
         """z = M r for a packed vector r (needs set_preconditioner(PRECOND_MG or PRECOND_MG_ANY) first)."""
         r = np.ascontiguousarray(r, dtype=np.float64)
@@ -485,6 +500,16 @@ class MatrixFreeSystem:
     def preconditioner_info(self):
         """(kind, cycle, levels) of the preconditioner that is set; (PRECOND_NONE, CYCLE_F64, 0) without one."""
         return self._handle.preconditioner_info()
+
+    def set_smoother(self, smoother: int):
+        """Extension (no reference twin): _capi.SMOOTHER_JACOBI (the default) or SMOOTHER_LINE_X / _LINE_Y / _LINE_AUTO, line
+        Jacobi along the strongly coupled direction of a stretched domain, for the fp64 V-cycle of this system's preconditioner
+        and everything built on it.  Before or after set_preconditioner."""
+        self._handle.set_smoother(smoother)
+
+    def smoother_info(self):
+        """(smoother, direction): the smoother as set, and the line direction it means on this grid (0 none, 1 x, 2 y)."""
+        return self._handle.smoother_info()
 
     def set_shift(self, sigma: float):
         """Extension (no reference twin): this system's operator becomes A - sigma I (sigma finite, >= 0) for apply() and for every

@@ -24,7 +24,17 @@ call on vectors that are already in device memory.  --baseline-tree DIR adds the
 commit before a change) in a child process of the same job: the yardstick.  Its single solves, and its batch call if it has one.
        python tools/mg_timing.py --batch [--baseline-tree DIR] [--nrhs 4,16] [--out FILE] [N ...]
                                                      (default 100 258 1000 2002 4096, nrhs 4 16 64, at N >= 4096 only 4;
-                                                      writes profiles/mg_batch_time_to_solution.txt)"""
+                                                      writes profiles/mg_batch_time_to_solution.txt)
+--smoother: the point smoother against the line smoother of the fp64 V-cycle (mi355cg_set_smoother, MI355CG_SMOOTHER_LINE_AUTO) on the
+square and on stretched domains: MG_ANY, REL_2NORM 1e-8, one seeded standard-normal right-hand side per N.  Per N and domain: one
+handle, one warm-up solve per smoother, then three timed solves of each alternating (set_smoother switches in place; the hierarchy's
+set-up is not timed), the best wall time of each.  --baseline-tree DIR adds the same point-smoother solves of another built checkout
+(the commit before the option) in child processes of the same job, one before and one after this build's solves: the yardstick.
+--traces DIR adds the device time of one level-0 sweep of each kind from rocprofv3 kernel traces found under DIR, each of
+`rocprofv3 --kernel-trace --stats --output-format csv -d DIR/NAME -- python tools/mg_timing.py --smoother-solve N a b c d {jacobi,line}`:
+the sweep that carries the (r, z) partials runs on level 0 only, so its kernel name tells level 0 from the coarser levels.
+       python tools/mg_timing.py --smoother [--baseline-tree DIR] [--traces DIR] [--out FILE] [N ...]
+                                                     (default 1024 4096; writes profiles/mg_line_time_to_solution.txt)"""
 import json
 import subprocess
 import os
@@ -180,6 +190,144 @@ def main_f32(ns, baseline_tree):
     print("wrote", OUT_F32)
 
 
+# ---- --smoother -------------------------------------------------------------------------------------------------------------------
+OUT_LINE = os.path.join(ROOT, "profiles", "mg_line_time_to_solution.txt")
+SIZES_LINE = [1024, 4096]
+DOMAINS_LINE = [(1.0, 2.0, 1.0, 2.0), (0.0, 3.0, 0.0, 1.0), (0.0, 10.0, 0.0, 1.0), (0.0, 1.0, 0.0, 10.0), (0.0, 32.0, 0.0, 1.0)]
+
+
+def dom_name(dom):
+    return "(" + ",".join(f"{v:g}" for v in dom) + ")"
+
+
+def line_system(n, dom):
+    """the handle of one (N, domain) with MG_ANY set and the seeded standard-normal right-hand side in place"""
+    s = isa.MatrixFreeSystem(n, n, *dom)
+    s.set_preconditioner(isa.PRECOND_MG_ANY)
+    b = np.random.default_rng(n).standard_normal(s.size())
+    s._handle.set_rhs(b)
+    return s, float(np.linalg.norm(b))
+
+
+def line_params():
+    p = params(_capi.RULE_REL_2NORM)
+    p.use_true_solution = 0
+    return p
+
+
+def line_best_of_three(h, settings, b_norm):
+    """best_of_three without the error norm: the right-hand side has no known solution"""
+    best = {}
+    for name, setp in settings.items():
+        setp()
+        h.solve(line_params())
+    for _ in range(3):
+        for name, setp in settings.items():
+            setp()
+            t0 = time.perf_counter()
+            res = h.solve(line_params())
+            wall = time.perf_counter() - t0
+            rel = float(np.linalg.norm(h.true_residual()) / b_norm)
+            if name not in best or wall < best[name][0]:
+                best[name] = (wall, res.iterations, res.stop_reason, res.converged, res.solve_seconds, rel)
+    return best
+
+
+def smoother_baseline_worker(ns):
+    """Child process of --smoother --baseline-tree: the other checkout's package, which has the point smoother only.  Prints one JSON
+    line: {N: {domain: [wall, iterations, stop, converged, solve_seconds, true_rel]}}."""
+    out = {}
+    for n in ns:
+        out[n] = {}
+        for dom in DOMAINS_LINE:
+            s, b_norm = line_system(n, dom)
+            out[n][dom_name(dom)] = line_best_of_three(s._handle, {"base": lambda: None}, b_norm)["base"]
+            s._handle.close()
+    print("BASELINE " + json.dumps(out), flush=True)
+
+
+def smoother_solve(args):
+    """one converged solve for a kernel trace: N a b c d {jacobi,line}"""
+    n, dom, which = int(args[0]), tuple(float(v) for v in args[1:5]), args[5]
+    s, _ = line_system(n, dom)
+    s.set_smoother(isa.SMOOTHER_LINE_AUTO if which == "line" else isa.SMOOTHER_JACOBI)
+    res = s._handle.solve(line_params())
+    print(json.dumps({"n": n, "domain": dom_name(dom), "smoother": which, "direction": s.smoother_info()[1],
+                      "iterations": res.iterations, "converged": res.converged}))
+    return 0 if res.converged else 1
+
+
+def sweep_times(traces):
+    """{trace name: {kernel: (launches, average us)}} of the level-0 sweeps with the (r, z) partials and of all sweeps by kernel name"""
+    import csv
+    import glob
+    import re
+    out = {}
+    for d in sorted(glob.glob(os.path.join(traces, "*"))):
+        dur = {}
+        for f in glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True):
+            with open(f, newline="") as fh:
+                for row in csv.DictReader(fh):
+                    m = re.search(r"k_mg_(smooth|line)<[^>]*>", row["Kernel_Name"])
+                    if m:
+                        dur.setdefault(m.group(0), []).append((int(row["End_Timestamp"]) - int(row["Start_Timestamp"])) / 1e3)
+        if dur:
+            out[os.path.basename(d)] = {k: (len(v), sum(v) / len(v)) for k, v in dur.items()}
+    return out
+
+
+def main_smoother(ns, baseline_tree, traces, out_path):
+    def base_pass():
+        env = dict(os.environ, MG_TIMING_TREE=os.path.abspath(baseline_tree))
+        txt = subprocess.run([sys.executable, os.path.abspath(__file__), "--smoother-baseline-worker"] + [str(n) for n in ns], env=env,
+                             check=True, capture_output=True, text=True, timeout=900).stdout
+        return json.loads([l for l in txt.splitlines() if l.startswith("BASELINE ")][-1][len("BASELINE "):])
+    lines = ["# time to solution on one MI355X: MG_ANY-preconditioned CG with damped point Jacobi against damped line Jacobi "
+             "(MI355CG_SMOOTHER_LINE_AUTO) in the fp64 V-cycle (tools/mg_timing.py --smoother)",
+             "# REL_2NORM 1e-8, b = numpy.random.default_rng(N).standard_normal(size); one handle per (N, domain), the hierarchy's set-up not "
+             "timed; one warm-up solve per smoother, then three timed solves of each alternating; wall = best host wall time of mi355cg_solve",
+             "# jacobi, line = this build; dir = the direction LINE_AUTO took (1 x, 2 y); true_rel = ||b - A x|| / ||b||",
+             "# base1, base2 = the point smoother of the --baseline-tree checkout (the commit before the option) in child processes of the same "
+             "job, one before and one after this build's solves" if baseline_tree else "# no --baseline-tree: the parent commit not measured",
+             "# ratio = wall / the better base wall" if baseline_tree else "# ratio = wall / wall of jacobi",
+             f"# {'N':>5} {'domain':<12} {'smoother':<8} {'dir':>3} {'iters':>5} {'conv':>4} {'wall_ms':>9} {'solve_ms':>9} {'ms_per_it':>9} {'true_rel':>9} {'ratio':>6}"]
+    print("\n".join(lines), flush=True)
+    base1 = base_pass() if baseline_tree else None
+    rows = []
+    for n in ns:
+        for dom in DOMAINS_LINE:
+            s, b_norm = line_system(n, dom)
+            settings = {"jacobi": lambda: s.set_smoother(isa.SMOOTHER_JACOBI), "line": lambda: s.set_smoother(isa.SMOOTHER_LINE_AUTO)}
+            best = line_best_of_three(s._handle, settings, b_norm)
+            s.set_smoother(isa.SMOOTHER_LINE_AUTO)
+            rows.append((n, dom, best, s.smoother_info()[1]))
+            s._handle.close()
+    base2 = base_pass() if baseline_tree else None
+    for n, dom, best, direction in rows:
+        named = {}
+        if baseline_tree:
+            named["base1"], named["base2"] = tuple(base1[str(n)][dom_name(dom)]), tuple(base2[str(n)][dom_name(dom)])
+        named.update(best)
+        ref_wall = min(named["base1"][0], named["base2"][0]) if baseline_tree else named["jacobi"][0]
+        for name, (w, it, stop, conv, ss, rel) in named.items():
+            line = (f"  {n:>5} {dom_name(dom):<12} {name:<8} {direction if name == 'line' else 0:>3} {it:>5} {conv:>4} {w * 1e3:>9.3f} {ss * 1e3:>9.3f} "
+                    f"{w * 1e3 / max(it, 1):>9.3f} {rel:>9.2e} {w / ref_wall:>6.3f}")
+            lines.append(line)
+            print(line, flush=True)
+    if traces:
+        first = len(lines)
+        lines += ["#", "# device time of the sweeps of one converged solve (rocprofv3 --kernel-trace of tools/mg_timing.py --smoother-solve): the sweep with",
+                  "# the (r, z) partials, <.., false, true>, runs on level 0 only -- one level-0 sweep; the other names average over all levels",
+                  f"# {'trace':<28} {'kernel':<34} {'launches':>8} {'avg_us':>9}"]
+        for name, ks in sweep_times(traces).items():
+            for k, (cnt, avg) in sorted(ks.items()):
+                lines.append(f"  {name:<28} {k:<34} {cnt:>8} {avg:>9.2f}")
+        print("\n".join(lines[first:]), flush=True)
+    with open(out_path, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    print("wrote", out_path)
+
+
 NRHS = None                                          # --nrhs: these counts at every N
 
 
@@ -294,11 +442,24 @@ if __name__ == "__main__":
     if args and args[0] == "--batch-baseline-worker":
         batch_baseline_worker([int(a) for a in args[1:]])
         sys.exit(0)
+    if args and args[0] == "--smoother-baseline-worker":
+        smoother_baseline_worker([int(a) for a in args[1:]])
+        sys.exit(0)
+    if args and args[0] == "--smoother-solve":
+        sys.exit(smoother_solve(args[1:]))
     kind = "mg"
-    cycle, baseline_tree, out_path = "f64", None, OUT_BATCH
+    cycle, baseline_tree, out_path = "f64", None, None
     if "--out" in args:
         i = args.index("--out")
         out_path = os.path.abspath(args[i + 1])
+        del args[i:i + 2]
+    smoother = "--smoother" in args
+    if smoother:
+        args.remove("--smoother")
+    traces = None
+    if "--traces" in args:
+        i = args.index("--traces")
+        traces = args[i + 1]
         del args[i:i + 2]
     batch = "--batch" in args
     if batch:
@@ -319,8 +480,10 @@ if __name__ == "__main__":
         del args[i:i + 2]
         if kind not in OUT:
             sys.exit(f"--kind must be one of {sorted(OUT)}")
-    if batch:
-        main_batch([int(a) for a in args] or SIZES_BATCH, baseline_tree, out_path)
+    if smoother:
+        main_smoother([int(a) for a in args] or SIZES_LINE, baseline_tree, traces, out_path or OUT_LINE)
+    elif batch:
+        main_batch([int(a) for a in args] or SIZES_BATCH, baseline_tree, out_path or OUT_BATCH)
     elif cycle == "f32":
         if kind != "any":
             sys.exit("--cycle f32 goes with --kind any")
