@@ -4,6 +4,7 @@
 // No CPU fallback: every compute entry point needs a working HIP device.
 #include "../../include/mi355cg.h"
 #include "cg_kernels.h"
+#include "device_buffer.h"
 #include "csr_kernels.h"
 #include "grid_setup.h"
 #include "mg_kernels.h"
@@ -22,6 +23,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <thread>
 #include <vector>
@@ -45,6 +47,31 @@ int fail(int code, const char* fmt, ...) {
         if (e_ != hipSuccess)                                                                        \
             return fail(MI355CG_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
     } while (0)
+
+}  // namespace
+
+// What Buf<T> (device_buffer.h) allocates and frees with: the only hipMalloc / hipHostMalloc / hipFree / hipHostFree of the file.
+namespace mi355cg {
+int mem_device_alloc(void** out, size_t bytes, bool zero, const char* what) {
+    void* p = nullptr;
+    hipError_t e = hipMalloc(&p, bytes);
+    if (e == hipSuccess && zero && (e = hipMemset(p, 0, bytes)) != hipSuccess) hipFree(p);
+    if (e == hipSuccess) { *out = p; return MI355CG_OK; }
+    (void)hipGetLastError();                     // a failed allocation leaves no sticky error behind
+    return what ? fail(MI355CG_ERR_HIP, "%s", what) : fail(MI355CG_ERR_HIP, "device allocation of %zu bytes failed: %s", bytes, hipGetErrorString(e));
+}
+void mem_device_free(void* p) { if (p) hipFree(p); }
+int mem_pinned_alloc(void** out, size_t bytes, const char* what) {
+    void* p = nullptr;
+    const hipError_t e = hipHostMalloc(&p, bytes);
+    if (e == hipSuccess) { *out = p; return MI355CG_OK; }
+    (void)hipGetLastError();
+    return what ? fail(MI355CG_ERR_HIP, "%s", what) : fail(MI355CG_ERR_HIP, "pinned allocation of %zu bytes failed: %s", bytes, hipGetErrorString(e));
+}
+void mem_pinned_free(void* p) { if (p) hipHostFree(p); }
+}  // namespace mi355cg
+
+namespace {
 
 int env_int(const char* name, int dflt) {
     const char* v = getenv(name);
@@ -72,25 +99,25 @@ struct EventPool {
 // (level 0: the caller's vector), a work vector and the cycle's result (level 0: the caller's output); the coarsest level keeps
 // its dense inverse.
 struct MgLevel {
-    Geom g{}; long long len = 0; int grid = 0; double *rhs = nullptr, *a = nullptr, *out = nullptr;
-    double* tab = nullptr;              // line smoother: the level's Thomas factors, 2 N doubles (mg_line_kernels.h); nullptr without one
+    Geom g{}; long long len = 0; int grid = 0; Buf<double> rhs, a, out;
+    Buf<double> tab;                    // line smoother: the level's Thomas factors, 2 N doubles (mg_line_kernels.h); nullptr without one
 };
 // The same three vectors of a level in fp32 (MI355CG_CYCLE_F32; level 0 too: r32, the work vector, the iterate) with the level's
 // constants rounded to fp32; vec: columns per lane of its kernels (mg_kernels_f32.h)
-struct MgLevel32 { float *rhs = nullptr, *a = nullptr, *out = nullptr; MgCoef32 c{}; float scale = 0.f; int vec = 1; };
+struct MgLevel32 { Buf<float> rhs, a, out; MgCoef32 c{}; float scale = 0.f; int vec = 1; };
 struct MgHier {
     int kind = 0;                       // MI355CG_PRECOND_MG or _MG_ANY: the kind last set (where both have a hierarchy it is this one)
     int cycle = MI355CG_CYCLE_F64;      // precision of the V-cycle; F32 keeps lv32 / inv32 instead of the levels' fp64 vectors and inv
     int line_dir = 0;                   // 0: damped point Jacobi; MG_LINE_X / MG_LINE_Y: line Jacobi along it, the levels keep `tab`
     std::vector<MgLevel> lv;
     std::vector<MgLevel32> lv32;
-    float* inv32 = nullptr;             // A_L^-1 rounded to fp32
+    Buf<float> inv32;                   // A_L^-1 rounded to fp32
     int ncoarse = 0;                    // unknowns of the coarsest level
-    double* inv = nullptr;              // A_L^-1, ncoarse x ncoarse, row-major (unknowns in packed order)
-    int* coff = nullptr;                // storage offset of every coarsest unknown
-    double *z = nullptr, *p[2] = {nullptr, nullptr}, *q = nullptr;    // PCG vectors of level 0 (p: ping-pong)
-    double* part = nullptr;             // per-block partials, MG_NFIELDS x kMgMaxGrid
-    double* part_h = nullptr;           // pinned copy
+    Buf<double> inv;                    // A_L^-1, ncoarse x ncoarse, row-major (unknowns in packed order)
+    Buf<int> coff;                      // storage offset of every coarsest unknown
+    Buf<double> z, p[2], q;             // PCG vectors of level 0 (p: ping-pong)
+    Buf<double> part;                   // per-block partials, MG_NFIELDS x kMgMaxGrid
+    Buf<double> part_h;                 // pinned copy
 };
 
 // Workspace of the batched solves (mi355cg_solve_batch*; kernels in mg_batch_kernels.h): one allocation, system-major.  System s
@@ -100,13 +127,13 @@ struct MgBatchLevel { long long rhs = -1, a = -1, out = -1; };
 struct MgBatchWs {
     int cap = 0;                        // systems the vectors hold
     long long stride = 0;               // doubles per system, a multiple of 32 (256 B)
-    double* base = nullptr;
+    Buf<double> base;                   // (the eigensolver's `cyc` borrows its workspace's)
     long long x = 0, r = 0, z = 0, p[2] = {0, 0}, q = 0;
     std::vector<MgBatchLevel> lv;
-    double* part = nullptr;             // [system][field][block], cap x MGBG_NFIELDS (the widest launch) x level 0's grid
-    double* red = nullptr;              // [position][field] sums of the last launch
-    double* red_h = nullptr;            // pinned copy
-    double* stage = nullptr;            // packed vectors of the host entry point, stage_cap x pk_len
+    Buf<double> part;                   // [system][field][block], cap x MGBG_NFIELDS (the widest launch) x level 0's grid
+    Buf<double> red;                    // [position][field] sums of the last launch
+    Buf<double> red_h;                  // pinned copy
+    Buf<double> stage;                  // packed vectors of the host entry point, stage_cap x pk_len
     int stage_cap = 0;
 };
 
@@ -120,13 +147,13 @@ struct EigWs {
     int cap = 0;                        // columns the vectors hold
     long long vlen = 0;                 // doubles per slot: the storage length rounded up to 32 (256 B)
     int slots = 0;                      // slots per column
-    double* base = nullptr;
+    Buf<double> base;
     MgBatchWs cyc;                      // base, stride and the levels' offsets as mg_vcycle reads them
-    double* part = nullptr;             // block partials of the widest launch: a full symmetric gram of 48 vectors
-    double* mat = nullptr;              // two reduced matrices (48 x 48), then the coefficients of a combine (48 x 16)
-    double* mat_h = nullptr;            // pinned copy
-    double* red = nullptr;              // [column][field] sums of k_eig_resid
-    double* stage = nullptr;            // packed vectors of the host entry point, cap x pk_len
+    Buf<double> part;                   // block partials of the widest launch: a full symmetric gram of 48 vectors
+    Buf<double> mat;                    // two reduced matrices (48 x 48), then the coefficients of a combine (48 x 16)
+    Buf<double> mat_h;                  // pinned copy
+    Buf<double> red;                    // [column][field] sums of k_eig_resid
+    Buf<double> stage;                  // packed vectors of the host entry point, cap x pk_len
 };
 
 }  // namespace
@@ -141,34 +168,37 @@ struct mi355cg_ctx {
     long long storage_len = 0;          // elements per vector incl. ghost rows
     long long pk_begin = 0, pk_len = 0; // owned cells in the part's packed order (pk_begin: global packed index of the first; row slabs are contiguous)
     PackGeom pg{};
-    // (Plan: item_table.h.  Every plan carries its two item tables in device memory: 16 B per item and per wave of its launch.)
+    // (Plan: item_table.h.  Every plan carries views of its two item tables in device memory: 16 B per item and per wave of its
+    // launch.  The handle owns them: plan_items / plan_start below, in the order whole, interior, edge, whole32.)
     Plan whole, interior, edge;         // whole part; rows / strips that need no ghost data; the rest (first + last row, edge strips)
     Plan whole32;                       // fp32 kernels (VEC = 4, 256-column strips): the whole grid, or a row slab of full width
+    Buf<ItemDesc> plan_items[4];
+    Buf<StartRec> plan_start[4][2];
     int depth = 2;                      // raw rows in flight per wave (env MI355CG_DEPTH: 2 or 3)
     bool has_gc = false;                // 2-D part with a neighbour in x: the stencil launches keep the ghost columns of the direction
     int nB_own = 0;                     // partB slots written by the last update-phase launch(es) of this context
     int strideA = 0, strideB = 0;
 
     // device vectors in storage layout (fp64 set always; fp32 set for F32_MIXED)
-    double *x = nullptr, *r = nullptr, *p[kRing] = {}, *ap = nullptr, *b = nullptr, *u = nullptr;
+    Buf<double> x, r, p[kRing], ap, b, u;        // (a team part of several: r borrows IPC-pool memory, team.h)
     int xsteps = 4;                     // M: the direction ring has M buffers, x is touched every M-th iteration (env MI355CG_XSTEPS: 2 | 4 | 8)
-    double* scratch[2] = {nullptr, nullptr};      // mi355cg_apply / true residual work space, allocated on first use: never a solver vector
-    float *xf = nullptr, *rf = nullptr, *pf[kRing] = {}, *apf = nullptr;
-    double* packed = nullptr;           // device scratch, pk_len doubles
-    double *partA = nullptr, *partB = nullptr, *partR = nullptr;
-    double *sumsA = nullptr, *sumsB = nullptr;   // slab mode: this rank's record = reduced partials [+ its two boundary rows] (feeds the all-gather)
+    Buf<double> scratch[2];             // mi355cg_apply / true residual work space, allocated on first use: never a solver vector
+    Buf<float> xf, rf, pf[kRing], apf;  // (a mixed team: rf borrows the memory of r)
+    Buf<double> packed;                 // device scratch, pk_len doubles
+    Buf<double> partA, partB, partR;
+    Buf<double> sumsA, sumsB;           // slab mode: this rank's record = reduced partials [+ its two boundary rows] (feeds the all-gather)
     int rec_width = 0;
     mi355cg_params dist_prm{};                    // slab mode: parameters given to mi355cg_dist_begin
     bool dist_active = false, is_slab = false;
-    CgState *sA = nullptr, *sB = nullptr, *summary = nullptr;
-    int* qctr = nullptr;                // dynamic item queues: kXcds * kQueueSubs counters of the stencil launches, then as many of the update launches (QueueSpec)
+    Buf<CgState> sA, sB, summary;
+    Buf<int> qctr;                      // dynamic item queues: kXcds * kQueueSubs counters of the stencil launches, then as many of the update launches (QueueSpec)
     int dyn_rows = 0;                   // > 0: the whole-part launches cut their items this short and deal them through the queues
-    int* stop_h = nullptr;              // pinned host word: a stop request, sampled by block 0 of every update launch (msg_solver.cpp:82-87)
+    Buf<int> stop_h;                    // pinned host word: a stop request, sampled by block 0 of every update launch (msg_solver.cpp:82-87)
     int* stop_dev = nullptr;            // the same word as the device addresses it (nullptr while no solve with a stop flag is running)
-    HistEntry* hist = nullptr;
-    CgState* summary_h = nullptr;       // pinned
-    HistEntry* hist_h = nullptr;        // pinned
-    double* partR_h = nullptr;          // pinned
+    Buf<HistEntry> hist;
+    Buf<CgState> summary_h;             // pinned
+    Buf<HistEntry> hist_h;              // pinned
+    Buf<double> partR_h;                // pinned
 
     std::vector<double> rhs_h, u_h;     // host copies (owned cells, the part's packed order)
     bool host_rhs_valid = true, host_u_valid = true;     // false after mi355cg_setup_on_device until somebody asks for the host copy
@@ -176,26 +206,27 @@ struct mi355cg_ctx {
     // Warm start (mi355cg_set_initial_guess*, mi355cg_use_solution_as_initial_guess): the guess lives in x itself.
     bool guess_pending = false;         // the next mi355cg_solve starts from x as it stands (one-shot)
     bool x_is_guess = false;            // x was overwritten by a guess since the last solve: x and r are not a solution and its residual
-    double* guess_part = nullptr;       // (b, b) partial pairs of k_init_guess (hi, then lo, strideB each), then ||r0||_2 and ||b||_2 (k_guess_state)
-    double* guess_norms_h = nullptr;    // pinned copy of those two norms
+    Buf<double> guess_part;             // (b, b) partial pairs of k_init_guess (hi, then lo, strideB each), then ||r0||_2 and ||b||_2 (k_guess_state)
+    Buf<double> guess_norms_h;          // pinned copy of those two norms
     // Diagonal shift (mi355cg_set_shift): the operator is A - sigma I.  g.A = gp.A - sigma and every multigrid
     // level's diagonal carry it; gp.A stays the Laplacian's.
     double sigma = 0.0;
     int smoother = MI355CG_SMOOTHER_JACOBI;   // as given to mi355cg_set_smoother; kept while there is no hierarchy
-    double* step_b = nullptr;           // mi355cg_time_steps: the right-hand side of a step, allocated by the first call
+    Buf<double> step_b;                 // mi355cg_time_steps: the right-hand side of a step, allocated by the first call
     // generic CSR handle (mi355cg_create_csr): vectors are plain length-n arrays, the operator is this matrix
     bool is_csr = false;
     long long csr_n = 0, csr_nnz = 0;
-    int *csr_row_map = nullptr, *csr_entries = nullptr; double* csr_values = nullptr;
+    Buf<int> csr_row_map, csr_entries; Buf<double> csr_values;
     int grid_csr = 0, grid_update = 0;
     int cur = 0;                        // p[cur] holds the current direction after the last stencil: cur = (iterations done) % xsteps
     int nA_dist = 0;                    // slab mode: stencil partial slots written by the last stencil phase
     // Deferred x fold (k_fold_x; single-context fp64 solves that would otherwise fold x every M-th iteration): a ring of R direction
     // buffers.  Slots 0 .. xsteps-1 are p[], the others are allocated by the first solve that folds (ensure_fold_ring).
     int xfold = 0;                      // R (16 | 32), 0 = the fused update (env MI355CG_XFOLD; unset: by size, see create_impl)
-    double* fold_p[kFoldMax] = {};      // the ring's slots: p_k lives in fold_p[k % R]
+    double* fold_p[kFoldMax] = {};      // the ring's slots: p_k lives in fold_p[k % R]; views of p[] and of fold_own[]
+    Buf<double> fold_own[kFoldMax];     // the slots beyond p[] (entries below xsteps stay empty)
     int fold_extra = 0;                 // buffers allocated beyond p[]: 0 until the first solve that folds, then R - xsteps
-    FoldTable* fold_tab = nullptr;      // device: the slots, and the step lengths of the last R iterations (written by the update launches)
+    Buf<FoldTable> fold_tab;            // device: the slots, and the step lengths of the last R iterations (written by the update launches)
     int fcur = 0;                       // fold mode: (iterations done) % R
     int fold_grid = 0;                  // workgroups of k_fold_x; 0 = one element pair per thread (env MI355CG_XFOLD_GRID)
     bool fold_nt = true;                // nontemporal loads of the once-read directions in k_fold_x (env MI355CG_XFOLD_NT, A/B runs)
@@ -208,9 +239,9 @@ struct mi355cg_ctx {
     int use_graph = -1;                 // env MI355CG_GRAPH: -1 auto (small grids), 0 off, 1 on
 
     hipEvent_t ev_loop[2] = {nullptr, nullptr};   // brackets the iterations of the last solve (mi355cg_results::loop_seconds)
-    MgHier* mg = nullptr;               // opt-in preconditioner (mi355cg_set_preconditioner): mi355cg_solve runs solve_mg while set
-    MgBatchWs* batch = nullptr;         // workspace of mi355cg_solve_batch*, nullptr until the first batch
-    EigWs* eig = nullptr;               // workspace of mi355cg_eigs*, nullptr until the first eigen solve
+    std::unique_ptr<MgHier> mg;         // opt-in preconditioner (mi355cg_set_preconditioner): mi355cg_solve runs solve_mg while set
+    std::unique_ptr<MgBatchWs> batch;   // workspace of mi355cg_solve_batch*, nullptr until the first batch
+    std::unique_ptr<EigWs> eig;         // workspace of mi355cg_eigs*, nullptr until the first eigen solve
     bool profiling = false;
     EventPool events;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pairs[2];
@@ -346,29 +377,35 @@ void build_plans(mi355cg_ctx* c) {
     c->nB_own = c->whole.grid;
 }
 
-// The item tables of every plan (item_table.h), built and uploaded once, when the handle is created; mi355cg_destroy frees them.
+// A host array in fresh device memory (blocking copy).  dst is replaced only once the copy is there: a failure leaves it as it was.
+template <typename T>
+int upload(const std::vector<T>& src, Buf<T>& dst, const char* what = nullptr) {
+    Buf<T> fresh;
+    if (int rc = Buf<T>::device(fresh, (long long)src.size(), what)) return rc;
+    if (hipMemcpy(fresh, src.data(), sizeof(T) * src.size(), hipMemcpyHostToDevice) != hipSuccess) {
+        const hipError_t e = hipGetLastError();
+        return what ? fail(MI355CG_ERR_HIP, "%s", what) : fail(MI355CG_ERR_HIP, "upload of %zu bytes failed: %s", sizeof(T) * src.size(), hipGetErrorString(e));
+    }
+    dst = std::move(fresh);
+    return MI355CG_OK;
+}
+
+// The item tables of every plan (item_table.h), built and uploaded once, when the handle is created, and owned by the handle.
 // No launch and no captured chunk allocates or copies anything for them.
 int upload_item_tables(mi355cg_ctx* c) {
+    int k = 0;
     for (Plan* pl : {&c->whole, &c->interior, &c->edge, &c->whole32}) {
+        const int slot = k++;
         if (pl->wl.nitems == 0 || pl->grid == 0) continue;
-        const std::vector<ItemDesc> items = build_item_table(pl->wl);
-        HIPCK(hipMalloc((void**)&pl->d_items, sizeof(ItemDesc) * items.size()));
-        HIPCK(hipMemcpy(pl->d_items, items.data(), sizeof(ItemDesc) * items.size(), hipMemcpyHostToDevice));
+        if (int rc = upload(build_item_table(pl->wl), c->plan_items[slot])) return rc;
+        pl->d_items = c->plan_items[slot];
         pl->elem = pl == &c->whole32 ? (int)sizeof(float) : (int)sizeof(double);
         for (int rev = 0; rev < 2; ++rev) {      // the start records of the ascending (stencil, apply) and of the reversed descending march (update)
-            const std::vector<StartRec> start = build_start_table(pl->wl, pl->grid, c->g, pl->elem, rev != 0);
-            HIPCK(hipMalloc((void**)&pl->d_start[rev], sizeof(StartRec) * start.size()));
-            HIPCK(hipMemcpy(pl->d_start[rev], start.data(), sizeof(StartRec) * start.size(), hipMemcpyHostToDevice));
+            if (int rc = upload(build_start_table(pl->wl, pl->grid, c->g, pl->elem, rev != 0), c->plan_start[slot][rev])) return rc;
+            pl->d_start[rev] = c->plan_start[slot][rev];
         }
     }
     return MI355CG_OK;
-}
-void free_item_tables(mi355cg_ctx* c) {
-    for (Plan* pl : {&c->whole, &c->interior, &c->edge, &c->whole32}) {
-        if (pl->d_items) hipFree(pl->d_items);
-        for (int rev = 0; rev < 2; ++rev) { if (pl->d_start[rev]) hipFree(pl->d_start[rev]); pl->d_start[rev] = nullptr; }
-        pl->d_items = nullptr;
-    }
 }
 ItemTab item_tab(const Plan& pl) { return ItemTab{pl.d_items, pl.d_start[0], pl.d_start[1], pl.wl.nitems}; }
 
@@ -401,7 +438,7 @@ struct IterCfg { RuleParams rp; int want_diag; bool has_u; bool x2 = false; bool
 
 // Phase A'.  Does NOT flip c->cur (a part's interior and edge launches share one direction pair).
 template <typename T, int VEC>
-void launch_iteration_stencil(mi355cg_ctx* c, const IterCfg& cfg, const T* r, T* const p[kRing], const Where& w, const PartSrc& pb, const FlagSpec* fl = nullptr) {
+void launch_iteration_stencil(mi355cg_ctx* c, const IterCfg& cfg, const T* r, const Buf<T> p[kRing], const Where& w, const PartSrc& pb, const FlagSpec* fl = nullptr) {
     if (w.plan->wl.nitems == 0) return;
     StencilArgs<T> a{};
     a.g = kernel_geom<T, VEC>(c); a.tab = item_tab(*w.plan);
@@ -432,7 +469,7 @@ void launch_iteration_stencil(mi355cg_ctx* c, const IterCfg& cfg, const T* r, T*
 // Phase B on the stencil's work items, marched the other way (it starts on what the stencil launch touched last).
 // c->cur was flipped after this iteration's stencil launch: it is the iteration number's parity.
 template <typename T, int VEC>
-void launch_iteration_update(mi355cg_ctx* c, const IterCfg& cfg, T* x, T* r, T* const p[kRing], const T* u, const Where& w, const PartSrc& pa, const FlagSpec* fl = nullptr) {
+void launch_iteration_update(mi355cg_ctx* c, const IterCfg& cfg, T* x, T* r, const Buf<T> p[kRing], const T* u, const Where& w, const PartSrc& pa, const FlagSpec* fl = nullptr) {
     if (w.plan->wl.nitems == 0) return;
     UpdateStArgs<T> a{};
     a.g = kernel_geom<T, VEC>(c); a.tab = item_tab(*w.plan);
@@ -443,7 +480,7 @@ void launch_iteration_update(mi355cg_ctx* c, const IterCfg& cfg, T* x, T* r, T* 
     a.s_in = c->sA; a.s_out = c->sB; a.rule = cfg.rp.rule; a.reverse = 1;
     if (fl) a.fl = *fl;
     if (VEC == 2 && c->dyn_rows > 0 && w.plan == &c->whole) a.dq = QueueSpec{c->qctr + kXcds * kQueueSubs * kQueuePitch, c->qctr};
-    if (cfg.fold) { a.fold_alpha = reinterpret_cast<double*>(reinterpret_cast<char*>(c->fold_tab) + offsetof(FoldTable, alpha)); a.fold_mask = c->xfold - 1; }
+    if (cfg.fold) { a.fold_alpha = reinterpret_cast<double*>(reinterpret_cast<char*>(c->fold_tab.get()) + offsetof(FoldTable, alpha)); a.fold_mask = c->xfold - 1; }
     a.stop_req = w.slot == 0 ? c->stop_dev : nullptr;   // block 0 samples the pinned stop word once per iteration (of a phase in two launches: the one that runs last and owns slot 0)
     const dim3 grid(w.plan->grid), block(kBlock);
     const bool d3 = c->depth == 3 && !(cfg.x2 && c->cur == 0 && c->xsteps == 8);
@@ -477,7 +514,7 @@ void launch_update_flat(mi355cg_ctx* c, const IterCfg& cfg, T* x, T* r, const T*
 
 // The x steps of the iterations after the last multiple of M (REL_2NORM folded update), oldest first.
 template <typename T, int VEC>
-void launch_flush_x(const mi355cg_ctx* c, const Plan& plan, T* x, T* const p[kRing], const CgState& fin, hipStream_t stream) {
+void launch_flush_x(const mi355cg_ctx* c, const Plan& plan, T* x, const Buf<T> p[kRing], const CgState& fin, hipStream_t stream) {
     const int pending = fin.it % c->xsteps;
     if (plan.wl.nitems == 0 || pending == 0) return;
     FlushArgs<T> f{};
@@ -499,8 +536,8 @@ void launch_fold_x(const mi355cg_ctx* c, int flush_it, hipStream_t stream) {
     else hipLaunchKernelGGL((k_fold_x<false>), dim3(grid), dim3(kBlock), 0, stream, a);
 }
 void free_fold_ring(mi355cg_ctx* c) {
-    for (int k = c->xsteps; k < kFoldMax; ++k) if (c->fold_p[k]) { hipFree(c->fold_p[k]); c->fold_p[k] = nullptr; }
-    if (c->fold_tab) { hipFree(c->fold_tab); c->fold_tab = nullptr; }
+    for (int k = c->xsteps; k < kFoldMax; ++k) { c->fold_own[k].reset(); c->fold_p[k] = nullptr; }
+    c->fold_tab.reset();
     c->fold_extra = 0;
 }
 // The ring of a handle that folds, allocated and zeroed once (pads, boundary and ghost cells of every slot must hold 0, as in p[]).
@@ -512,12 +549,12 @@ bool ensure_fold_ring(mi355cg_ctx* c) {
     bool ok = true;
     for (int k = 0; k < c->xfold && ok; ++k) {
         if (k < c->xsteps) { c->fold_p[k] = c->p[k]; continue; }
-        ok = hipMalloc((void**)&c->fold_p[k], bytes) == hipSuccess && hipMemsetAsync(c->fold_p[k], 0, bytes, c->stream) == hipSuccess;
-        if (!ok) c->fold_p[k] = nullptr;
+        ok = Buf<double>::device(c->fold_own[k], c->storage_len) == MI355CG_OK && hipMemsetAsync(c->fold_own[k], 0, bytes, c->stream) == hipSuccess;
+        c->fold_p[k] = c->fold_own[k];
     }
     FoldTable t{};
     for (int k = 0; k < c->xfold; ++k) t.p[k] = c->fold_p[k];
-    ok = ok && hipMalloc((void**)&c->fold_tab, sizeof(FoldTable)) == hipSuccess &&
+    ok = ok && Buf<FoldTable>::device(c->fold_tab, 1) == MI355CG_OK &&
          hipMemcpyAsync(c->fold_tab, &t, sizeof t, hipMemcpyHostToDevice, c->stream) == hipSuccess && hipStreamSynchronize(c->stream) == hipSuccess;
     if (!ok) {
         (void)hipGetLastError();                 // the failed allocation is not an error of the solve
@@ -586,12 +623,6 @@ int download_packed(mi355cg_ctx* c, const T* storage, double* host_packed) {
     return MI355CG_OK;
 }
 
-int alloc_vec(double** p, long long n) {
-    HIPCK(hipMalloc((void**)p, sizeof(double) * n));
-    HIPCK(hipMemset(*p, 0, sizeof(double) * n));
-    return MI355CG_OK;
-}
-
 int ensure_host_copies(mi355cg_ctx* c) {        // device-generated problem data: fetch the host copies on first use
     if (!c->host_rhs_valid) { c->rhs_h.resize(c->pk_len); if (int rc = download_packed<double>(c, c->b, c->rhs_h.data())) return rc; c->host_rhs_valid = true; }
     if (!c->host_u_valid) { c->u_h.resize(c->pk_len); if (int rc = download_packed<double>(c, c->u, c->u_h.data())) return rc; c->host_u_valid = true; }
@@ -603,12 +634,9 @@ int ensure_f32_vectors(mi355cg_ctx* c) {
     if (c->xsteps > 4) return fail(MI355CG_ERR_INVALID, "MI355CG_XSTEPS=8 is fp64 only");
     if (c->whole32.wl.nitems == 0) return fail(MI355CG_ERR_INVALID, "the fp32 kernels march 256-column strips: a part of a 2-D decomposition (cut on 128 columns) cannot run them; use row slabs");
     if (c->g.own_begin % 4 != 0 || c->g.own_len % 4 != 0) return fail(MI355CG_ERR_STATE, "a part's owned range is not a whole number of float4");
-    float** fv[] = {&c->xf, &c->apf, &c->pf[0], &c->pf[1], &c->pf[2], &c->pf[3]};
-    for (int k = 0; k < 2 + c->xsteps; ++k) {
-        if (*fv[k]) continue;
-        if (hipMalloc((void**)fv[k], sizeof(float) * c->storage_len) != hipSuccess || hipMemset(*fv[k], 0, sizeof(float) * c->storage_len) != hipSuccess)
-            return fail(MI355CG_ERR_HIP, "fp32 vector allocation failed");
-    }
+    Buf<float>* fv[] = {&c->xf, &c->apf, &c->pf[0], &c->pf[1], &c->pf[2], &c->pf[3]};
+    for (int k = 0; k < 2 + c->xsteps; ++k)
+        if (!*fv[k]) if (int rc = Buf<float>::device_zeroed(*fv[k], c->storage_len, "fp32 vector allocation failed")) return rc;
     HIPCK(hipDeviceSynchronize());
     return MI355CG_OK;
 }
@@ -623,7 +651,7 @@ int ensure_u_on_device(mi355cg_ctx* c) {
 // Work space of mi355cg_apply / mi355cg_get_true_residual.  The reference's apply is const and may be called from an
 // iteration callback in the middle of a solve, so it must never borrow a solver vector.
 int ensure_scratch(mi355cg_ctx* c) {
-    for (auto& s : c->scratch) if (!s) { if (int rc = alloc_vec(&s, c->storage_len)) return rc; }
+    for (auto& s : c->scratch) if (!s) { if (int rc = Buf<double>::device_zeroed(s, c->storage_len)) return rc; }
     HIPCK(hipDeviceSynchronize());      // the zero-fill ran on the NULL stream
     return MI355CG_OK;
 }
@@ -631,8 +659,8 @@ int ensure_scratch(mi355cg_ctx* c) {
 // Work space of a warm start on the plain path, allocated by the first one: k_init_guess's (b, b) partials and the two norms
 // k_guess_state leaves for the host.
 int ensure_guess_ws(mi355cg_ctx* c) {
-    if (!c->guess_part) HIPCK(hipMalloc((void**)&c->guess_part, sizeof(double) * (2 * (size_t)c->strideB + 2)));
-    if (!c->guess_norms_h) HIPCK(hipHostMalloc((void**)&c->guess_norms_h, sizeof(double) * 2));
+    if (!c->guess_part) if (int rc = Buf<double>::device(c->guess_part, 2 * (long long)c->strideB + 2)) return rc;
+    if (!c->guess_norms_h) if (int rc = Buf<double>::pinned(c->guess_norms_h, 2)) return rc;
     return MI355CG_OK;
 }
 
@@ -940,15 +968,17 @@ Geom mg_geom(int N, double hx, double hy, double sigma, long long* len) {
     return g;
 }
 
-void mg_free(MgHier* H) {
-    if (!H) return;
-    for (auto& L : H->lv) for (double* v : {L.rhs, L.a, L.out, L.tab}) if (v) hipFree(v);
-    for (double* v : {H->inv, H->z, H->p[0], H->p[1], H->q, H->part}) if (v) hipFree(v);
-    for (auto& L : H->lv32) for (float* v : {L.rhs, L.a, L.out}) if (v) hipFree(v);
-    if (H->inv32) hipFree(H->inv32);
-    if (H->coff) hipFree(H->coff);
-    if (H->part_h) hipHostFree(H->part_h);
-    delete H;
+// Which vectors a level keeps, written once: its right-hand side and its result from level 1 on (level 0's are the caller's), and a
+// work vector on every level but the coarsest.  f(level, which, length) allocates one or takes its offset; the first failure ends the walk.
+enum MgVecKind { MG_VEC_RHS, MG_VEC_OUT, MG_VEC_A };
+template <class F>
+int mg_for_level_vectors(const std::vector<MgLevel>& lv, F f) {
+    const int nl = (int)lv.size();
+    for (int l = 0; l < nl; ++l) {
+        if (l > 0) { if (int rc = f(l, MG_VEC_RHS, lv[l].len)) return rc; if (int rc = f(l, MG_VEC_OUT, lv[l].len)) return rc; }
+        if (l + 1 < nl) if (int rc = f(l, MG_VEC_A, lv[l].len)) return rc;
+    }
+    return MI355CG_OK;
 }
 
 // A_L^-1 of the coarsest level in its packed unknown order, from the Cholesky factor of -A_L (fp64, host), and the storage
@@ -1030,41 +1060,34 @@ std::vector<double> mg_line_table(const Geom& g, int dir) {
 
 // The tables of direction dir (dir == 0: none) for every smoothing level of H with the diagonal shifted by sigma, uploaded into
 // fresh[level]; H is not touched.
-int mg_make_line_tables(const MgHier* H, int dir, double sigma, std::vector<double*>& fresh) {
+int mg_make_line_tables(const MgHier* H, int dir, double sigma, std::vector<Buf<double>>& fresh) {
     const int nl = (int)H->lv.size();
-    fresh.assign(nl, nullptr);
+    fresh = std::vector<Buf<double>>(nl);
     for (int l = 0; dir && l + 1 < nl; ++l) {                      // the coarsest level does not smooth
         Geom g = H->lv[l].g;
         g.A = -2 * (g.xk + g.yk) - sigma;                          // mg_geom's expression
-        const std::vector<double> tab = mg_line_table(g, dir);
-        if (hipMalloc((void**)&fresh[l], sizeof(double) * tab.size()) != hipSuccess ||
-            hipMemcpy(fresh[l], tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice) != hipSuccess) {
-            for (double* v : fresh) if (v) hipFree(v);
-            (void)hipGetLastError();
-            fresh.assign(nl, nullptr);
-            return fail(MI355CG_ERR_HIP, "line smoother table upload failed");
-        }
+        if (int rc = upload(mg_line_table(g, dir), fresh[l], "line smoother table upload failed")) return rc;
     }
     return MI355CG_OK;
 }
 // ... and dir becomes H's smoother with them.  The caller has made sure that nothing in flight reads the old tables.
-void mg_install_line_tables(MgHier* H, int dir, const std::vector<double*>& fresh) {
-    for (size_t l = 0; l < H->lv.size(); ++l) { if (H->lv[l].tab) hipFree(H->lv[l].tab); H->lv[l].tab = fresh[l]; }
+void mg_install_line_tables(MgHier* H, int dir, std::vector<Buf<double>>& fresh) {
+    for (size_t l = 0; l < H->lv.size(); ++l) H->lv[l].tab = std::move(fresh[l]);
     H->line_dir = dir;
 }
 int mg_set_line_tables(MgHier* H, int dir, double sigma) {
-    std::vector<double*> fresh;
+    std::vector<Buf<double>> fresh;
     if (int rc = mg_make_line_tables(H, dir, sigma, fresh)) return rc;
     mg_install_line_tables(H, dir, fresh);
     return MI355CG_OK;
 }
 
-int mg_build(mi355cg_ctx* c, int kind, MgHier** out, int cycle = MI355CG_CYCLE_F64) {
+// The hierarchy is built in a local object: a failure returns and leaves *out as it was, success moves it there.
+int mg_build(mi355cg_ctx* c, int kind, std::unique_ptr<MgHier>& out, int cycle = MI355CG_CYCLE_F64) {
     std::vector<int> ns;
     if (int rc = mg_shape(kind, c->gp.n, &ns)) return rc;
     const int nl = (int)ns.size();
-    MgHier* H = new MgHier();
-    auto bail = [&](int rc) { mg_free(H); return rc; };
+    std::unique_ptr<MgHier> H(new MgHier());
     H->kind = kind;
     H->cycle = cycle;
     const bool f64 = cycle == MI355CG_CYCLE_F64;
@@ -1076,33 +1099,30 @@ int mg_build(mi355cg_ctx* c, int kind, MgHier** out, int cycle = MI355CG_CYCLE_F
         else if (l > 0) { hx = hx * ns[l - 1] / ns[l]; hy = hy * ns[l - 1] / ns[l]; }              // non-nested: same domain
         L.g = mg_geom(ns[l], hx, hy, c->sigma, &L.len);
         L.grid = std::min(L.g.N - 1, kMgMaxGrid);
-        if (!f64) continue;                                     // the fp32 cycle has its own vectors (mg_build32)
-        if (l > 0) { if (int rc = alloc_vec(&L.rhs, L.len)) return bail(rc); if (int rc = alloc_vec(&L.out, L.len)) return bail(rc); }
-        if (l + 1 < nl) if (int rc = alloc_vec(&L.a, L.len)) return bail(rc);
     }
+    if (f64)                                                    // the fp32 cycle has its own vectors (mg_build32)
+        if (int rc = mg_for_level_vectors(H->lv, [&](int l, MgVecKind which, long long len) {
+                MgLevel& L = H->lv[l];
+                return Buf<double>::device_zeroed(which == MG_VEC_RHS ? L.rhs : which == MG_VEC_OUT ? L.out : L.a, len);
+            })) return rc;
     const Geom& g0 = H->lv[0].g;
     if (H->lv[0].len != c->storage_len || g0.Pb != c->g.Pb || g0.Pu != c->g.Pu || g0.cb != c->g.cb || c->g.base0 != 0)
-        return bail(fail(MI355CG_ERR_STATE, "multigrid level 0 does not match the handle's storage layout"));
-    for (double** v : {&H->z, &H->p[0], &H->p[1], &H->q}) if (int rc = alloc_vec(v, c->storage_len)) return bail(rc);
-    if (int rc = alloc_vec(&H->part, (long long)MG_NFIELDS * kMgMaxGrid)) return bail(rc);
-    if (hipHostMalloc((void**)&H->part_h, sizeof(double) * MG_NFIELDS * kMgMaxGrid) != hipSuccess)
-        return bail(fail(MI355CG_ERR_HIP, "pinned partials allocation failed"));
+        return fail(MI355CG_ERR_STATE, "multigrid level 0 does not match the handle's storage layout");
+    for (Buf<double>* v : {&H->z, &H->p[0], &H->p[1], &H->q}) if (int rc = Buf<double>::device_zeroed(*v, c->storage_len)) return rc;
+    if (int rc = Buf<double>::device_zeroed(H->part, (long long)MG_NFIELDS * kMgMaxGrid)) return rc;
+    if (int rc = Buf<double>::pinned(H->part_h, (long long)MG_NFIELDS * kMgMaxGrid, "pinned partials allocation failed")) return rc;
     std::vector<double> inv;
     std::vector<int> off;
     mg_coarse_inverse(H->lv.back().g, inv, off);
     H->ncoarse = (int)off.size();
-    if (H->ncoarse > kMgMaxCoarse) return bail(fail(MI355CG_ERR_STATE, "coarsest grid has %d unknowns (> %d)", H->ncoarse, kMgMaxCoarse));
-    if (!f64) { if (int rc = mg_build32(H, inv)) return bail(rc); }
-    else if (hipMalloc((void**)&H->inv, sizeof(double) * inv.size()) != hipSuccess ||
-        hipMemcpy(H->inv, inv.data(), sizeof(double) * inv.size(), hipMemcpyHostToDevice) != hipSuccess)
-        return bail(fail(MI355CG_ERR_HIP, "coarse inverse upload failed"));
-    if (hipMalloc((void**)&H->coff, sizeof(int) * off.size()) != hipSuccess ||
-        hipMemcpy(H->coff, off.data(), sizeof(int) * off.size(), hipMemcpyHostToDevice) != hipSuccess)
-        return bail(fail(MI355CG_ERR_HIP, "coarse inverse upload failed"));
-    // the zero-fills ran on the NULL stream; the context's stream does not order with them (see create_impl)
-    if (hipDeviceSynchronize() != hipSuccess) return bail(fail(MI355CG_ERR_HIP, "hipDeviceSynchronize failed"));
-    if (f64) if (int rc = mg_set_line_tables(H, mg_line_direction(c, c->smoother), c->sigma)) return bail(rc);   // the smoother set before the hierarchy
-    *out = H;
+    if (H->ncoarse > kMgMaxCoarse) return fail(MI355CG_ERR_STATE, "coarsest grid has %d unknowns (> %d)", H->ncoarse, kMgMaxCoarse);
+    if (!f64) { if (int rc = mg_build32(H.get(), inv)) return rc; }
+    else if (int rc = upload(inv, H->inv, "coarse inverse upload failed")) return rc;
+    if (int rc = upload(off, H->coff, "coarse inverse upload failed")) return rc;
+    // the zero-fills ran on the NULL stream; the context's stream does not order with them (see create_state)
+    if (hipDeviceSynchronize() != hipSuccess) return fail(MI355CG_ERR_HIP, "hipDeviceSynchronize failed");
+    if (f64) if (int rc = mg_set_line_tables(H.get(), mg_line_direction(c, c->smoother), c->sigma)) return rc;   // the smoother set before the hierarchy
+    out = std::move(H);
     return MI355CG_OK;
 }
 
@@ -1186,11 +1206,6 @@ constexpr int kMg32VecMinN = 256;       // levels with at least this many interv
 int mg_build32(MgHier* H, const std::vector<double>& inv) {
     const int nl = (int)H->lv.size();
     H->lv32.resize(nl);
-    auto alloc32 = [](float** p, long long n) -> int {
-        HIPCK(hipMalloc((void**)p, sizeof(float) * n));
-        HIPCK(hipMemset(*p, 0, sizeof(float) * n));
-        return MI355CG_OK;
-    };
     for (int l = 0; l < nl; ++l) {
         const MgLevel& L = H->lv[l];
         MgLevel32& F = H->lv32[l];
@@ -1200,13 +1215,10 @@ int mg_build32(MgHier* H, const std::vector<double>& inv) {
             const Geom& C = H->lv[l + 1].g;
             F.scale = (float)((double)((long long)C.N * C.N) / (double)((long long)L.g.N * L.g.N));
         }
-        for (float** v : {&F.rhs, &F.out}) if (int rc = alloc32(v, L.len)) return rc;
-        if (l + 1 < nl) if (int rc = alloc32(&F.a, L.len)) return rc;
+        for (Buf<float>* v : {&F.rhs, &F.out}) if (int rc = Buf<float>::device_zeroed(*v, L.len)) return rc;
+        if (l + 1 < nl) if (int rc = Buf<float>::device_zeroed(F.a, L.len)) return rc;
     }
-    std::vector<float> inv32(inv.begin(), inv.end());
-    HIPCK(hipMalloc((void**)&H->inv32, sizeof(float) * inv32.size()));
-    HIPCK(hipMemcpy(H->inv32, inv32.data(), sizeof(float) * inv32.size(), hipMemcpyHostToDevice));
-    return MI355CG_OK;
+    return upload(std::vector<float>(inv.begin(), inv.end()), H->inv32);
 }
 
 // levels l >= 1: out = V(rhs, l) on the level's fp32 vectors
@@ -1392,13 +1404,9 @@ int solve_mg(mi355cg_ctx* c, const mi355cg_params* prm, mi355cg_iter_cb cb, void
 
 // ---- batched PCG (mi355cg_solve_batch*; kernels in mg_batch_kernels.h) ------------------------------------
 void mg_batch_free(mi355cg_ctx* c) {
-    MgBatchWs* W = c->batch;
-    if (!W) return;
+    if (!c->batch) return;
     if (c->stream) hipStreamSynchronize(c->stream);
-    for (double* v : {W->base, W->part, W->red, W->stage}) if (v) hipFree(v);
-    if (W->red_h) hipHostFree(W->red_h);
-    delete W;
-    c->batch = nullptr;
+    c->batch.reset();
 }
 
 // Vectors for nsys systems of the handle's hierarchy (and, stage_sys > 0, the host entry point's packed staging).  A workspace
@@ -1406,49 +1414,38 @@ void mg_batch_free(mi355cg_ctx* c) {
 int mg_batch_ensure(mi355cg_ctx* c, int nsys, int stage_sys) {
     const MgHier& H = *c->mg;
     if (!c->batch || c->batch->cap < nsys) {
-        MgBatchWs* W = new MgBatchWs();
-        auto bail = [&](const char* what) {
-            for (double* v : {W->base, W->part, W->red}) if (v) hipFree(v);
-            if (W->red_h) hipHostFree(W->red_h);
-            delete W;
-            (void)hipGetLastError();
-            return fail(MI355CG_ERR_HIP, "batch workspace for %d systems: %s allocation failed", nsys, what);
-        };
+        std::unique_ptr<MgBatchWs> W(new MgBatchWs());
+        auto failed = [&](const char* what) { return fail(MI355CG_ERR_HIP, "batch workspace for %d systems: %s allocation failed", nsys, what); };
         long long off = 0;
         auto take = [&](long long len) { const long long o = off; off += round_up(len, 32); return o; };
         const long long len0 = H.lv[0].len;
         W->x = take(len0); W->r = take(len0); W->z = take(len0); W->p[0] = take(len0); W->p[1] = take(len0); W->q = take(len0);
-        const int nl = (int)H.lv.size();
-        W->lv.resize(nl);
-        for (int l = 0; l < nl; ++l) {                             // the vectors mg_build gives a level
-            if (l > 0) { W->lv[l].rhs = take(H.lv[l].len); W->lv[l].out = take(H.lv[l].len); }
-            if (l + 1 < nl) W->lv[l].a = take(H.lv[l].len);
-        }
+        W->lv.resize(H.lv.size());
+        mg_for_level_vectors(H.lv, [&](int l, MgVecKind which, long long len) {
+            (which == MG_VEC_RHS ? W->lv[l].rhs : which == MG_VEC_OUT ? W->lv[l].out : W->lv[l].a) = take(len);
+            return MI355CG_OK;
+        });
         W->stride = off;
         W->cap = nsys;
         const int G = H.lv[0].grid;
-        if (hipMalloc((void**)&W->base, sizeof(double) * W->stride * nsys) != hipSuccess) return bail("vector");
+        if (Buf<double>::device(W->base, W->stride * nsys)) return failed("vector");
         constexpr int kFields = MGBG_NFIELDS > MGB_NFIELDS ? MGBG_NFIELDS : MGB_NFIELDS;      // the warm start's launch has one field more
-        if (hipMalloc((void**)&W->part, sizeof(double) * kFields * G * nsys) != hipSuccess) return bail("partials");
-        if (hipMalloc((void**)&W->red, sizeof(double) * kFields * kMgBatchMax) != hipSuccess) return bail("sums");
-        if (hipHostMalloc((void**)&W->red_h, sizeof(double) * kFields * kMgBatchMax) != hipSuccess) return bail("pinned sums");
+        if (Buf<double>::device(W->part, (long long)kFields * G * nsys)) return failed("partials");
+        if (Buf<double>::device(W->red, (long long)kFields * kMgBatchMax)) return failed("sums");
+        if (Buf<double>::pinned(W->red_h, (long long)kFields * kMgBatchMax)) return failed("pinned sums");
         // boundary nodes and pads hold 0 for good: the kernels write interior nodes only
         if (hipMemsetAsync(W->base, 0, sizeof(double) * W->stride * nsys, c->stream) != hipSuccess ||
-            hipStreamSynchronize(c->stream) != hipSuccess) return bail("zero-filled vector");
-        if (c->batch) { W->stage = c->batch->stage; W->stage_cap = c->batch->stage_cap; c->batch->stage = nullptr; }
+            hipStreamSynchronize(c->stream) != hipSuccess) { (void)hipGetLastError(); return failed("zero-filled vector"); }
+        if (c->batch) { W->stage = std::move(c->batch->stage); W->stage_cap = c->batch->stage_cap; }
         mg_batch_free(c);
-        c->batch = W;
+        c->batch = std::move(W);
     }
-    MgBatchWs* W = c->batch;
+    MgBatchWs* W = c->batch.get();
     if (stage_sys > W->stage_cap) {
-        double* st = nullptr;
         HIPCK(hipStreamSynchronize(c->stream));                    // nothing in flight reads the buffer that is replaced
-        if (hipMalloc((void**)&st, sizeof(double) * c->pk_len * stage_sys) != hipSuccess) {
-            (void)hipGetLastError();
+        if (Buf<double>::device(W->stage, (long long)c->pk_len * stage_sys))
             return fail(MI355CG_ERR_HIP, "batch staging for %d packed vectors: allocation failed", stage_sys);
-        }
-        if (W->stage) hipFree(W->stage);
-        W->stage = st; W->stage_cap = stage_sys;
+        W->stage_cap = stage_sys;
     }
     return MI355CG_OK;
 }
@@ -1686,13 +1683,9 @@ constexpr int kEigCoefLen = kEigBasisMax * kEigBlockMax;          // ... then th
 constexpr int kEigGramTilesMax = (kEigBasisMax / kEigTile) * (kEigBasisMax / kEigTile);
 
 void eig_free(mi355cg_ctx* c) {
-    EigWs* W = c->eig;
-    if (!W) return;
+    if (!c->eig) return;
     if (c->stream) hipStreamSynchronize(c->stream);
-    for (double* v : {W->base, W->part, W->mat, W->red, W->stage}) if (v) hipFree(v);
-    if (W->mat_h) hipHostFree(W->mat_h);
-    delete W;
-    c->eig = nullptr;
+    c->eig.reset();
 }
 
 // Vectors for a block of m columns on the handle's hierarchy (stage: the host entry point's packed staging too).  A workspace that
@@ -1700,46 +1693,39 @@ void eig_free(mi355cg_ctx* c) {
 int eig_ensure(mi355cg_ctx* c, int m, bool stage) {
     const MgHier& H = *c->mg;
     if (!c->eig || c->eig->cap < m) {
-        EigWs* W = new EigWs();
-        auto bail = [&](const char* what) {
-            for (double* v : {W->base, W->part, W->mat, W->red}) if (v) hipFree(v);
-            if (W->mat_h) hipHostFree(W->mat_h);
-            delete W;
-            (void)hipGetLastError();
-            return fail(MI355CG_ERR_HIP, "eigensolver workspace for a block of %d: %s allocation failed", m, what);
-        };
+        std::unique_ptr<EigWs> W(new EigWs());
+        auto failed = [&](const char* what) { return fail(MI355CG_ERR_HIP, "eigensolver workspace for a block of %d: %s allocation failed", m, what); };
         W->vlen = round_up(H.lv[0].len, 32);
         long long off = (long long)EIG_CYC * W->vlen;
         auto take = [&](long long len) { const long long o = off; off += round_up(len, 32); return o; };
-        const int nl = (int)H.lv.size();
-        W->cyc.lv.resize(nl);
-        for (int l = 0; l < nl; ++l) {                             // the vectors mg_build gives a level
-            if (l > 0) { W->cyc.lv[l].rhs = take(H.lv[l].len); W->cyc.lv[l].out = take(H.lv[l].len); }
-            if (l + 1 < nl) W->cyc.lv[l].a = take(H.lv[l].len);
-        }
+        W->cyc.lv.resize(H.lv.size());
+        mg_for_level_vectors(H.lv, [&](int l, MgVecKind which, long long len) {
+            (which == MG_VEC_RHS ? W->cyc.lv[l].rhs : which == MG_VEC_OUT ? W->cyc.lv[l].out : W->cyc.lv[l].a) = take(len);
+            return MI355CG_OK;
+        });
         W->slots = (int)(round_up(off, W->vlen) / W->vlen);
         W->cyc.stride = (long long)W->slots * W->vlen;
         W->cap = m;
         const int G = H.lv[0].grid;
-        const size_t bytes = sizeof(double) * (size_t)W->cyc.stride * m;
-        if (hipMalloc((void**)&W->base, bytes) != hipSuccess) return bail("vector");
-        W->cyc.base = W->base;
-        if (hipMalloc((void**)&W->part, sizeof(double) * kEigGramTilesMax * kEigTileEntries * G) != hipSuccess) return bail("partials");
-        if (hipMalloc((void**)&W->mat, sizeof(double) * (kEigMatLen + kEigCoefLen)) != hipSuccess) return bail("matrix");
-        if (hipMalloc((void**)&W->red, sizeof(double) * 2 * kEigBlockMax) != hipSuccess) return bail("sums");
-        if (hipHostMalloc((void**)&W->mat_h, sizeof(double) * (kEigMatLen + kEigCoefLen + 2 * kEigBlockMax)) != hipSuccess) return bail("pinned matrix");
+        const long long count = W->cyc.stride * m;
+        if (Buf<double>::device(W->base, count)) return failed("vector");
+        W->cyc.base.borrow(W->base);
+        if (Buf<double>::device(W->part, (long long)kEigGramTilesMax * kEigTileEntries * G)) return failed("partials");
+        if (Buf<double>::device(W->mat, kEigMatLen + kEigCoefLen)) return failed("matrix");
+        if (Buf<double>::device(W->red, 2 * kEigBlockMax)) return failed("sums");
+        if (Buf<double>::pinned(W->mat_h, kEigMatLen + kEigCoefLen + 2 * kEigBlockMax)) return failed("pinned matrix");
         // boundary nodes and pads hold 0 for good: the kernels write interior nodes only
-        if (hipMemsetAsync(W->base, 0, bytes, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return bail("zero-filled vector");
-        eig_free(c);                                               // the staging goes with it: it was sized for the smaller block
-        c->eig = W;
-    }
-    EigWs* W = c->eig;
-    if (stage && !W->stage) {
-        if (hipMalloc((void**)&W->stage, sizeof(double) * c->pk_len * W->cap) != hipSuccess) {
+        if (hipMemsetAsync(W->base, 0, sizeof(double) * (size_t)count, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
             (void)hipGetLastError();
-            return fail(MI355CG_ERR_HIP, "eigensolver staging for %d packed vectors: allocation failed", W->cap);
+            return failed("zero-filled vector");
         }
+        eig_free(c);                                               // the staging goes with it: it was sized for the smaller block
+        c->eig = std::move(W);
     }
+    EigWs* W = c->eig.get();
+    if (stage && !W->stage)
+        if (Buf<double>::device(W->stage, (long long)c->pk_len * W->cap))
+            return fail(MI355CG_ERR_HIP, "eigensolver staging for %d packed vectors: allocation failed", W->cap);
     return MI355CG_OK;
 }
 
@@ -1921,21 +1907,15 @@ int eig_check(mi355cg_ctx* c, int nev, int block, double tol, int max_iterations
 }
 
 // the block utilities: n packed host vectors -> zero-padded storage vectors of a temporary buffer, vector i at i * vlen
-struct BlockTmp {
-    double *packed = nullptr, *vec = nullptr, *part = nullptr, *mat = nullptr;
-    ~BlockTmp() { for (double* v : {packed, vec, part, mat}) if (v) hipFree(v); }
-};
+struct BlockTmp { Buf<double> packed, vec, part, mat; };
 int block_check(mi355cg_ctx* c) {
     if (c->is_csr) return fail(MI355CG_ERR_INVALID, "the block utilities need the grid operator's storage layout: a CSR handle has no grid");
     if (c->is_slab) return fail(MI355CG_ERR_INVALID, "the block utilities are single-GPU only: this handle owns one part of a decomposed grid");
     return MI355CG_OK;
 }
 int block_upload(mi355cg_ctx* c, BlockTmp& T, int n, int n_out, const double* const* src, const int* counts, int nsrc, long long vlen) {
-    if (hipMalloc((void**)&T.packed, sizeof(double) * c->pk_len * std::max(n, n_out)) != hipSuccess ||
-        hipMalloc((void**)&T.vec, sizeof(double) * vlen * (n + n_out)) != hipSuccess) {
-        (void)hipGetLastError();
+    if (Buf<double>::device(T.packed, (long long)c->pk_len * std::max(n, n_out)) || Buf<double>::device(T.vec, vlen * (n + n_out)))
         return fail(MI355CG_ERR_HIP, "block utility: allocation of %d vectors failed", n + n_out);
-    }
     HIPCK(hipMemsetAsync(T.vec, 0, sizeof(double) * vlen * (n + n_out), c->stream));
     long long at = 0;
     for (int s = 0; s < nsrc; ++s) {
@@ -1954,6 +1934,21 @@ extern "C" {
 
 const char* mi355cg_last_error(void) { return g_err.c_str(); }
 const char* mi355cg_version(void) { return "mi355cg 0.2 (gfx950)"; }
+
+// What every handle keeps, grid or CSR: the partials of the two phases and of the flat reductions, the device-side CG state with
+// its history, and their pinned copies.  The zero-fills run on the NULL stream and are asynchronous to the host; the context's own
+// stream is non-blocking and does not order with them.  Without the callers' device-wide wait after it a delayed memset can land
+// AFTER the first upload or kernel of the context and wipe it (seen as a right-hand side of zeros -> "converged" at iteration 0).
+static int create_state(mi355cg_ctx* c, const char* what) {
+    if (int rc = Buf<double>::device_zeroed(c->partA, (long long)FA_COUNT * c->strideA)) return rc;
+    if (int rc = Buf<double>::device_zeroed(c->partB, (long long)FB_COUNT * c->strideB)) return rc;
+    if (int rc = Buf<double>::device_zeroed(c->partR, 2048)) return rc;
+    for (Buf<CgState>* s : {&c->sA, &c->sB, &c->summary}) if (int rc = Buf<CgState>::device_zeroed(*s, 1, what)) return rc;
+    if (int rc = Buf<HistEntry>::device_zeroed(c->hist, kHist, what)) return rc;
+    if (int rc = Buf<CgState>::pinned(c->summary_h, 1, what)) return rc;
+    if (int rc = Buf<HistEntry>::pinned(c->hist_h, kHist, what)) return rc;
+    return Buf<double>::pinned(c->partR_h, 2048, what);
+}
 
 static int create_impl(int n, int m, double a, double b, double c_, double d, int dtype, int device,
                        int y_lo, int y_hi, int s_lo, int s_hi, bool part, mi355cg_handle* out) {
@@ -2007,40 +2002,21 @@ static int create_impl(int n, int m, double a, double b, double c_, double d, in
         c->fold_grid = std::max(0, env_int("MI355CG_XFOLD_GRID", 0));
         c->fold_nt = env_int("MI355CG_XFOLD_NT", 1) != 0;
     }
-    double** vecs[] = {&c->x, &c->r, &c->p[0], &c->p[1], &c->ap, &c->b, &c->u, &c->p[2], &c->p[3], &c->p[4], &c->p[5], &c->p[6], &c->p[7]};
-    for (int k = 0; k < 7 + (c->xsteps - 2); ++k) if ((rc = alloc_vec(vecs[k], L))) return cleanup();
+    Buf<double>* vecs[] = {&c->x, &c->r, &c->p[0], &c->p[1], &c->ap, &c->b, &c->u, &c->p[2], &c->p[3], &c->p[4], &c->p[5], &c->p[6], &c->p[7]};
+    for (int k = 0; k < 7 + (c->xsteps - 2); ++k) if ((rc = Buf<double>::device_zeroed(*vecs[k], L))) return cleanup();
     if (dtype == MI355CG_F32_MIXED) {
-        float** fv[] = {&c->xf, &c->rf, &c->pf[0], &c->pf[1], &c->apf, &c->pf[2], &c->pf[3], &c->pf[4], &c->pf[5], &c->pf[6], &c->pf[7]};
-        const int nfv = 5 + (c->xsteps - 2);
-        for (int k = 0; k < nfv; ++k) {
-            float** v = fv[k];
-            if (hipMalloc((void**)v, sizeof(float) * L) != hipSuccess || hipMemset(*v, 0, sizeof(float) * L) != hipSuccess) {
-                rc = fail(MI355CG_ERR_HIP, "fp32 vector allocation failed"); return cleanup();
-            }
-        }
+        Buf<float>* fv[] = {&c->xf, &c->rf, &c->pf[0], &c->pf[1], &c->apf, &c->pf[2], &c->pf[3], &c->pf[4], &c->pf[5], &c->pf[6], &c->pf[7]};
+        for (int k = 0; k < 5 + (c->xsteps - 2); ++k) if ((rc = Buf<float>::device_zeroed(*fv[k], L, "fp32 vector allocation failed"))) return cleanup();
     }
-    if ((rc = alloc_vec(&c->packed, std::max<long long>(c->pk_len, 1)))) return cleanup();
-    if ((rc = alloc_vec(&c->partA, (long long)FA_COUNT * c->strideA))) return cleanup();
-    if ((rc = alloc_vec(&c->partB, (long long)FB_COUNT * c->strideB))) return cleanup();
-    if ((rc = alloc_vec(&c->partR, 2048))) return cleanup();
+    if ((rc = Buf<double>::device_zeroed(c->packed, std::max<long long>(c->pk_len, 1)))) return cleanup();
+    if ((rc = create_state(c, "state allocation failed"))) return cleanup();
     c->rec_width = kRecHeader + 2 * c->g.Pu;            // [sums | first owned row | last owned row]
-    if ((rc = alloc_vec(&c->sumsA, c->rec_width))) return cleanup();
-    if ((rc = alloc_vec(&c->sumsB, c->rec_width))) return cleanup();
-    if (hipMalloc((void**)&c->sA, sizeof(CgState)) != hipSuccess || hipMalloc((void**)&c->sB, sizeof(CgState)) != hipSuccess ||
-        hipMalloc((void**)&c->summary, sizeof(CgState)) != hipSuccess || hipMalloc((void**)&c->hist, sizeof(HistEntry) * kHist) != hipSuccess ||
-        hipHostMalloc((void**)&c->summary_h, sizeof(CgState)) != hipSuccess || hipHostMalloc((void**)&c->hist_h, sizeof(HistEntry) * kHist) != hipSuccess ||
-        hipHostMalloc((void**)&c->partR_h, sizeof(double) * 2048) != hipSuccess) {
-        rc = fail(MI355CG_ERR_HIP, "state allocation failed"); return cleanup();
-    }
-    hipMemset(c->sA, 0, sizeof(CgState)); hipMemset(c->sB, 0, sizeof(CgState)); hipMemset(c->summary, 0, sizeof(CgState));
-    hipMemset(c->hist, 0, sizeof(HistEntry) * kHist);
-    if (hipMalloc((void**)&c->qctr, sizeof(int) * 2 * kXcds * kQueueSubs * kQueuePitch) != hipSuccess || hipMemset(c->qctr, 0, sizeof(int) * 2 * kXcds * kQueueSubs * kQueuePitch) != hipSuccess) { rc = fail(MI355CG_ERR_HIP, "queue counter allocation failed"); return cleanup(); }
-    if (hipHostMalloc((void**)&c->stop_h, sizeof(int)) != hipSuccess) { rc = fail(MI355CG_ERR_HIP, "stop word allocation failed"); return cleanup(); }
+    if ((rc = Buf<double>::device_zeroed(c->sumsA, c->rec_width))) return cleanup();
+    if ((rc = Buf<double>::device_zeroed(c->sumsB, c->rec_width))) return cleanup();
+    if ((rc = Buf<int>::device_zeroed(c->qctr, 2 * kXcds * kQueueSubs * kQueuePitch, "queue counter allocation failed"))) return cleanup();
+    if ((rc = Buf<int>::pinned(c->stop_h, 1, "stop word allocation failed"))) return cleanup();
     *c->stop_h = 0;
-    // The zero-fills above run on the NULL stream and are asynchronous to the host; the context's own stream is
-    // non-blocking and does not order with them.  Without this wait a delayed memset can land AFTER the first upload
-    // or kernel of the context and wipe it (seen as a right-hand side of zeros -> "converged" at iteration 0).
-    HIPCK(hipDeviceSynchronize());
+    if (hipDeviceSynchronize() != hipSuccess) { rc = fail(MI355CG_ERR_HIP, "hipDeviceSynchronize failed"); return cleanup(); }      // the zero-fills: see create_state
 
     if (env_int("MI355CG_DEVICE_SETUP", 0)) {
         // opt-in: b and u generated on the device, no host pass and no upload; <= 1 ulp from the host values
@@ -2101,30 +2077,16 @@ int mi355cg_create_csr(long long nrows, const int* row_map, const int* entries, 
     int rc = MI355CG_OK;
     auto cleanup = [&]() { mi355cg_destroy(c); return rc; };
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { rc = fail(MI355CG_ERR_HIP, "hipStreamCreate failed"); return cleanup(); }
-    double** vecs[] = {&c->x, &c->r, &c->p[0], &c->p[1], &c->ap, &c->b, &c->u};
-    for (auto v : vecs) if ((rc = alloc_vec(v, nrows))) return cleanup();
-    if ((rc = alloc_vec(&c->partA, (long long)FA_COUNT * c->strideA))) return cleanup();
-    if ((rc = alloc_vec(&c->partB, (long long)FB_COUNT * c->strideB))) return cleanup();
-    if ((rc = alloc_vec(&c->partR, 2048))) return cleanup();
-    if (hipMalloc((void**)&c->csr_row_map, sizeof(int) * (nrows + 1)) != hipSuccess || hipMalloc((void**)&c->csr_entries, sizeof(int) * std::max<long long>(nnz, 1)) != hipSuccess ||
-        hipMalloc((void**)&c->csr_values, sizeof(double) * std::max<long long>(nnz, 1)) != hipSuccess ||
-        hipMalloc((void**)&c->sA, sizeof(CgState)) != hipSuccess || hipMalloc((void**)&c->sB, sizeof(CgState)) != hipSuccess ||
-        hipMalloc((void**)&c->summary, sizeof(CgState)) != hipSuccess || hipMalloc((void**)&c->hist, sizeof(HistEntry) * kHist) != hipSuccess ||
-        hipHostMalloc((void**)&c->summary_h, sizeof(CgState)) != hipSuccess || hipHostMalloc((void**)&c->hist_h, sizeof(HistEntry) * kHist) != hipSuccess ||
-        hipHostMalloc((void**)&c->partR_h, sizeof(double) * 2048) != hipSuccess) {
-        rc = fail(MI355CG_ERR_HIP, "allocation failed"); return cleanup();
-    }
+    for (Buf<double>* v : {&c->x, &c->r, &c->p[0], &c->p[1], &c->ap, &c->b, &c->u}) if ((rc = Buf<double>::device_zeroed(*v, nrows))) return cleanup();
+    if ((rc = create_state(c, "allocation failed"))) return cleanup();
+    if ((rc = Buf<int>::device(c->csr_row_map, nrows + 1, "allocation failed")) || (rc = Buf<int>::device(c->csr_entries, std::max<long long>(nnz, 1), "allocation failed")) ||
+        (rc = Buf<double>::device(c->csr_values, std::max<long long>(nnz, 1), "allocation failed"))) return cleanup();
     if (hipMemcpy(c->csr_row_map, row_map, sizeof(int) * (nrows + 1), hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(c->csr_entries, entries, sizeof(int) * nnz, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(c->csr_values, values, sizeof(double) * nnz, hipMemcpyHostToDevice) != hipSuccess) {
         rc = fail(MI355CG_ERR_HIP, "CSR upload failed"); return cleanup();
     }
-    hipMemset(c->sA, 0, sizeof(CgState)); hipMemset(c->sB, 0, sizeof(CgState)); hipMemset(c->summary, 0, sizeof(CgState));
-    hipMemset(c->hist, 0, sizeof(HistEntry) * kHist);
-    // The zero-fills above run on the NULL stream and are asynchronous to the host; the context's own stream is
-    // non-blocking and does not order with them.  Without this wait a delayed memset can land AFTER the first upload
-    // or kernel of the context and wipe it (seen as a right-hand side of zeros -> "converged" at iteration 0).
-    HIPCK(hipDeviceSynchronize());
+    if (hipDeviceSynchronize() != hipSuccess) { rc = fail(MI355CG_ERR_HIP, "hipDeviceSynchronize failed"); return cleanup(); }      // the zero-fills: see create_state
     c->rhs_h.assign(nrows, 0.0); c->u_h.assign(nrows, 0.0);
     *out = c;
     return MI355CG_OK;
@@ -2145,30 +2107,13 @@ void mi355cg_destroy(mi355cg_handle c) {
     if (!c) return;
     hipSetDevice(c->device);
     if (c->stream) hipStreamSynchronize(c->stream);
-    void* dev[] = {c->x, c->r, c->p[0], c->p[1], c->p[2], c->p[3], c->p[4], c->p[5], c->p[6], c->p[7], c->ap, c->b, c->u, c->scratch[0], c->scratch[1], c->xf, c->rf,
-                   c->pf[0], c->pf[1], c->pf[2], c->pf[3], c->pf[4], c->pf[5], c->pf[6], c->pf[7], c->apf,
-                   c->packed, c->partA, c->partB, c->partR, c->sumsA, c->sumsB, c->sA, c->sB, c->summary, c->hist, c->qctr};
-    for (void* p : dev) if (p) hipFree(p);
-    free_fold_ring(c);
-    free_item_tables(c);
-    if (c->csr_row_map) hipFree(c->csr_row_map);
-    if (c->csr_entries) hipFree(c->csr_entries);
-    if (c->csr_values) hipFree(c->csr_values);
-    if (c->summary_h) hipHostFree(c->summary_h);
-    if (c->hist_h) hipHostFree(c->hist_h);
-    if (c->partR_h) hipHostFree(c->partR_h);
-    if (c->stop_h) hipHostFree(c->stop_h);
-    if (c->guess_part) hipFree(c->guess_part);
-    if (c->guess_norms_h) hipHostFree(c->guess_norms_h);
-    if (c->step_b) hipFree(c->step_b);
     clear_graphs(c);
     mg_batch_free(c);
     eig_free(c);
-    mg_free(c->mg);
     c->events.destroy();
     for (hipEvent_t e : c->ev_loop) if (e) hipEventDestroy(e);
     if (c->stream) hipStreamDestroy(c->stream);
-    delete c;
+    delete c;                                   // every buffer goes with its member (device_buffer.h)
 }
 
 long long mi355cg_size(mi355cg_handle c) { return c ? c->gp.size : -1; }
@@ -2389,9 +2334,9 @@ int mi355cg_solve(mi355cg_handle c, const mi355cg_params* prm, mi355cg_iter_cb c
                 hipEvent_t e0 = nullptr;
                 // Fold mode: the direction pair of this iteration sits in ring slots fcur and fcur + 1.  The launchers address p[] by
                 // c->cur, so they are handed a table with those two slots at cur and cur + 1 (the update launch is XM = 0: no pprev).
-                double* pp[kRing] = {};
-                if (fold) { pp[c->cur] = c->fold_p[c->fcur]; pp[(c->cur + 1) % c->xsteps] = c->fold_p[(c->fcur + 1) % c->xfold]; }
-                double* const* ring = fold ? pp : c->p;
+                Buf<double> pp[kRing];
+                if (fold) { pp[c->cur].borrow(c->fold_p[c->fcur]); pp[(c->cur + 1) % c->xsteps].borrow(c->fold_p[(c->fcur + 1) % c->xfold]); }
+                const Buf<double>* ring = fold ? pp : c->p;
                 prof_begin(c, &e0);
                 launch_iteration_stencil<double, 2>(c, cfg, c->r, ring, whole_part(c), own_partB(c));
                 c->cur = (c->cur + 1) % c->xsteps;
@@ -2577,35 +2522,17 @@ int mi355cg_set_shift(mi355cg_handle c, double sigma) {
     if (sigma == c->sigma) return MI355CG_OK;
     HIPCK(hipSetDevice(c->device));
     HIPCK(hipStreamSynchronize(c->stream));                        // nothing in flight reads the coefficients or the inverse
-    if (MgHier* H = c->mg) {
+    if (MgHier* H = c->mg.get()) {
         Geom gc = H->lv.back().g;
         gc.A = -2 * (gc.xk + gc.yk) - sigma;
         std::vector<double> inv;
         std::vector<int> off;
         mg_coarse_inverse(gc, inv, off);                           // off: the layout's, unchanged
-        std::vector<double*> tabs;                                 // the lines' factors hold the diagonal too
+        std::vector<Buf<double>> tabs;                             // the lines' factors hold the diagonal too
         if (int rc = mg_make_line_tables(H, H->line_dir, sigma, tabs)) return rc;
-        void* fresh = nullptr;
-        if (H->cycle == MI355CG_CYCLE_F32) {
-            std::vector<float> inv32(inv.begin(), inv.end());
-            if (hipMalloc(&fresh, sizeof(float) * inv32.size()) != hipSuccess ||
-                hipMemcpy(fresh, inv32.data(), sizeof(float) * inv32.size(), hipMemcpyHostToDevice) != hipSuccess) {
-                if (fresh) hipFree(fresh);
-                for (double* v : tabs) if (v) hipFree(v);
-                (void)hipGetLastError();
-                return fail(MI355CG_ERR_HIP, "coarse inverse upload failed: the shift stays %g", c->sigma);
-            }
-            hipFree(H->inv32); H->inv32 = (float*)fresh;
-        } else {
-            if (hipMalloc(&fresh, sizeof(double) * inv.size()) != hipSuccess ||
-                hipMemcpy(fresh, inv.data(), sizeof(double) * inv.size(), hipMemcpyHostToDevice) != hipSuccess) {
-                if (fresh) hipFree(fresh);
-                for (double* v : tabs) if (v) hipFree(v);
-                (void)hipGetLastError();
-                return fail(MI355CG_ERR_HIP, "coarse inverse upload failed: the shift stays %g", c->sigma);
-            }
-            hipFree(H->inv); H->inv = (double*)fresh;
-        }
+        // the last step that can fail: upload replaces the inverse only once the new one is on the device
+        if (H->cycle == MI355CG_CYCLE_F32 ? upload(std::vector<float>(inv.begin(), inv.end()), H->inv32) : upload(inv, H->inv))
+            return fail(MI355CG_ERR_HIP, "coarse inverse upload failed: the shift stays %g", c->sigma);
         for (size_t l = 0; l < H->lv.size(); ++l) {
             Geom& g = H->lv[l].g;
             g.A = -2 * (g.xk + g.yk) - sigma;                      // mg_geom's expression
@@ -2675,7 +2602,7 @@ int mi355cg_time_steps(mi355cg_handle c, const mi355cg_params* prm, double tau, 
     *steps_done = 0;
     HIPCK(hipSetDevice(c->device));
     if (!c->step_b) {
-        if (int rc = alloc_vec(&c->step_b, c->storage_len)) { (void)hipGetLastError(); c->step_b = nullptr; return rc; }
+        if (int rc = Buf<double>::device_zeroed(c->step_b, c->storage_len)) return rc;
         HIPCK(hipDeviceSynchronize());                             // the zero-fill ran on the NULL stream
     }
     if (int rc = mi355cg_set_shift(c, sigma)) return rc;           // a no-op when it is already exactly sigma
@@ -2683,10 +2610,9 @@ int mi355cg_time_steps(mi355cg_handle c, const mi355cg_params* prm, double tau, 
         if (k > 0) { c->x_is_guess = true; c->guess_pending = true; }     // mi355cg_use_solution_as_initial_guess
         launch_step_rhs(c, sigma, theta);
         HIPCK(hipGetLastError());
-        double* const own_b = c->b;
-        c->b = c->step_b;
+        std::swap(c->b, c->step_b);                                // the step's right-hand side in the place of b ...
         const int rc = mi355cg_solve(c, prm, nullptr, nullptr, stop_flag, &out[k]);
-        c->b = own_b;
+        std::swap(c->b, c->step_b);                                // ... and back, whatever the solve returned
         if (rc) return rc;
         if (!out[k].converged) break;                              // the iteration cap or a stop request: x holds that step's last iterate
         ++*steps_done;
@@ -2753,7 +2679,7 @@ int mi355cg_set_preconditioner_ex(mi355cg_handle c, int kind, int cycle) {
     if (kind == MI355CG_PRECOND_NONE) {
         mg_batch_free(c);                                          // the batch workspace belongs to the hierarchy it was built for
         eig_free(c);                                               // and so does the eigensolver's
-        if (c->mg) { HIPCK(hipStreamSynchronize(c->stream)); mg_free(c->mg); c->mg = nullptr; }
+        if (c->mg) { HIPCK(hipStreamSynchronize(c->stream)); c->mg.reset(); }
         return MI355CG_OK;
     }
     if (c->is_csr) return fail(MI355CG_ERR_INVALID, "the multigrid preconditioner needs the grid operator: a CSR handle has no grid");
@@ -2769,14 +2695,10 @@ int mi355cg_set_preconditioner_ex(mi355cg_handle c, int kind, int cycle) {
     mg_batch_free(c);                                              // accepted: the batch workspace goes, a refused call above keeps it
     eig_free(c);
     if (c->mg && c->mg->cycle == cycle) { c->mg->kind = kind; return MI355CG_OK; }   // both kinds have a hierarchy here: it is the same one
-    if (!c->mg) return mg_build(c, kind, &c->mg, cycle);
-    // another precision: the levels' vectors and the coarse inverse change type.  Built first, so a failure keeps the old one.
-    HIPCK(hipStreamSynchronize(c->stream));
-    MgHier* H = nullptr;
-    if (int rc = mg_build(c, kind, &H, cycle)) return rc;
-    mg_free(c->mg);
-    c->mg = H;
-    return MI355CG_OK;
+    // another precision: the levels' vectors and the coarse inverse change type.  mg_build replaces the old hierarchy only once
+    // the new one is complete, so a failure keeps it.
+    if (c->mg) HIPCK(hipStreamSynchronize(c->stream));
+    return mg_build(c, kind, c->mg, cycle);
 }
 
 // The smoother of the fp64 V-cycle.  With a hierarchy the levels' line tables are built or freed in place;
@@ -2796,7 +2718,7 @@ int mi355cg_set_smoother(mi355cg_handle c, int smoother) {
         if (dir != c->mg->line_dir) {
             HIPCK(hipSetDevice(c->device));
             HIPCK(hipStreamSynchronize(c->stream));                // nothing in flight reads the tables
-            if (int rc = mg_set_line_tables(c->mg, dir, c->sigma)) return rc;
+            if (int rc = mg_set_line_tables(c->mg.get(), dir, c->sigma)) return rc;
         }
     }
     c->smoother = smoother;
@@ -2949,11 +2871,8 @@ int mi355cg_block_gram_indexed(mi355cg_handle c, int na, const double* a, int ni
     const int counts[2] = {na, nb};
     if (int rc = block_upload(c, T, na + nb, 0, src, counts, 2, vlen)) return rc;
     const int tiles = eig_tiles(la.n) * eig_tiles(lb.n);
-    if (hipMalloc((void**)&T.part, sizeof(double) * tiles * kEigTileEntries * G) != hipSuccess ||
-        hipMalloc((void**)&T.mat, sizeof(double) * la.n * lb.n) != hipSuccess) {
-        (void)hipGetLastError();
+    if (Buf<double>::device(T.part, (long long)tiles * kEigTileEntries * G) || Buf<double>::device(T.mat, (long long)la.n * lb.n))
         return fail(MI355CG_ERR_HIP, "block gram: allocation of the partials failed");
-    }
     launch_gram<false>(c->stream, c->g, G, la, lb, T.vec, T.part, T.mat);
     HIPCK(hipGetLastError());
     HIPCK(hipMemcpyAsync(out, T.mat, sizeof(double) * la.n * lb.n, hipMemcpyDeviceToHost, c->stream));
@@ -2980,10 +2899,7 @@ int mi355cg_block_combine(mi355cg_handle c, int k, const double* s, int m, const
     const double* src[1] = {s};
     const int counts[1] = {k};
     if (int rc = block_upload(c, T, k, m, src, counts, 1, vlen)) return rc;
-    if (hipMalloc((void**)&T.mat, sizeof(double) * k * m) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(MI355CG_ERR_HIP, "block combine: allocation of the coefficients failed");
-    }
+    if (int rc = Buf<double>::device(T.mat, (long long)k * m, "block combine: allocation of the coefficients failed")) return rc;
     HIPCK(hipMemcpyAsync(T.mat, coef, sizeof(double) * k * m, hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL((k_eig_combine<false>), dim3(G), dim3(kBlock), 0, c->stream, c->g, ls, (const double*)T.vec, (const double*)T.mat, m, ly, T.vec, ly,
                        (const double*)T.vec);

@@ -403,8 +403,8 @@ void team_free(mi355cg_team_s* t) {
     for (auto& p : t->parts) {
         if (p.c) hipSetDevice(p.c->device);
         if (p.slab) ipc_pool().release(p.slab);
-        if (p.c && p.c->rf == (float*)p.c->r) p.c->rf = nullptr;           // F32_MIXED: an alias of r
-        if (p.r_pooled && p.c) { ipc_pool().release(p.c->r); p.c->r = nullptr; }
+        if (p.c && p.c->rf == (float*)p.c->r.get()) p.c->rf.reset();       // F32_MIXED: a borrow of r
+        if (p.r_pooled && p.c) { ipc_pool().release(p.c->r); p.c->r.reset(); }       // a borrow of the pool's memory: back to the pool, never freed
         if (p.side) { hipStreamSynchronize(p.side); hipStreamDestroy(p.side); }
         for (void* q : {(void*)p.send_cols, (void*)p.push_ticket, (void*)p.pll[0], (void*)p.pll[1], (void*)p.dst_self[0], (void*)p.dst_self[1], (void*)p.dst_all[0], (void*)p.dst_all[1],
                         (void*)p.flag_all[0], (void*)p.flag_all[1]}) if (q) hipFree(q);
@@ -491,7 +491,8 @@ int team_finish_setup(mi355cg_team_s* t) {
         p.pack.g = c->g; p.unpack.g = c->g; p.unpack.scatter = 1;
         for (size_t i = 0; i < p.sends.size(); ++i) if (p.sends[i].kind == 1) { if (p.pack.ns >= kMaxColSegs) return fail(MI355CG_ERR_INVALID, "too many column messages"); p.pack.s[p.pack.ns++] = ColSeg{p.sends[i].x0, p.sends[i].y0, (int)seg_count(p.sends[i]), 0, p.send_off[i]}; }
         for (size_t i = 0; i < p.recvs.size(); ++i) if (p.recvs[i].kind == 1) { if (p.unpack.ns >= kMaxColSegs) return fail(MI355CG_ERR_INVALID, "too many column messages"); p.unpack.s[p.unpack.ns++] = ColSeg{p.recvs[i].x0, p.recvs[i].y0, (int)seg_count(p.recvs[i]), 0, p.recv_off[i]}; }
-        if (int rc = alloc_vec(&p.send_cols, std::max<long long>(L.send_len, 1))) return rc;
+        HIPCK(hipMalloc((void**)&p.send_cols, sizeof(double) * std::max<long long>(L.send_len, 1)));
+        HIPCK(hipMemset(p.send_cols, 0, sizeof(double) * std::max<long long>(L.send_len, 1)));
         p.pack.buf = p.send_cols; p.unpack.buf = p.recv_cols;
         p.peer_mbox.assign(t->world, nullptr); p.peer_cols.assign(t->world, nullptr); p.peer_r.assign(t->world, nullptr);
         p.peer_mbox[p.rank] = p.mbox; p.peer_cols[p.rank] = p.recv_cols; p.peer_r[p.rank] = c->r;
@@ -1361,7 +1362,7 @@ int mi355cg_team_set_dtype(mi355cg_team t, int dtype) {
         for (auto& p : t->parts) {
             HIPCK(hipSetDevice(p.c->device));
             if (int rc = ensure_f32_vectors(p.c)) return rc;
-            p.c->rf = (float*)p.c->r;                    // the fp32 residual lives in the fp64 residual's memory: see seg_bytes
+            p.c->rf.borrow((float*)p.c->r.get());        // the fp32 residual lives in the fp64 residual's memory: see seg_bytes
         }
     }
     t->dtype = dtype;
@@ -1483,8 +1484,8 @@ struct BootRec { hipIpcMemHandle_t slab, r; char bus[32]; int ok, pad; unsigned 
 // all-gather of `bytes` per rank through the team's communicator (host buffers; staged through device memory)
 int boot_all_gather(mi355cg_team_s* t, const void* mine, void* all, size_t bytes) {
     TeamPart& p = t->parts[0];
-    unsigned char* d = nullptr;
-    HIPCK(hipMalloc((void**)&d, bytes * t->world));
+    Buf<unsigned char> d;
+    if (int rc = Buf<unsigned char>::device(d, (long long)(bytes * t->world))) return rc;
     int rc = MI355CG_OK;
     if (hipMemcpy(d + bytes * p.rank, mine, bytes, hipMemcpyHostToDevice) != hipSuccess) rc = fail(MI355CG_ERR_HIP, "boot upload failed");
     if (!rc) {
@@ -1492,7 +1493,6 @@ int boot_all_gather(mi355cg_team_s* t, const void* mine, void* all, size_t bytes
         if (r != ncclSuccess) rc = fail(MI355CG_ERR_HIP, "ncclAllGather (team bootstrap) failed: %s", rccl_api()->GetErrorString(r));
     }
     if (!rc && (hipStreamSynchronize(p.comm) != hipSuccess || hipMemcpy(all, d, bytes * t->world, hipMemcpyDeviceToHost) != hipSuccess)) rc = fail(MI355CG_ERR_HIP, "boot download failed");
-    hipFree(d);
     return rc;
 }
 // Map every other rank's mailbox / residual / column buffer (IPC).  Collective.  Leaves t->ipc_ok = false (and nothing mapped)
@@ -1588,8 +1588,7 @@ int mi355cg_team_create_rccl(int n, int m, double a, double b, double c_, double
         // the residual vector is what the neighbours' push launches write into: it has to come from the pool (see IpcPool)
         void* pooled = nullptr;
         if ((rc = ipc_pool().acquire(device, sizeof(double) * p.c->storage_len, false, &pooled))) { mi355cg_destroy(p.c); team_free(t); return rc; }
-        hipFree(p.c->r);
-        p.c->r = (double*)pooled; p.r_pooled = true;
+        p.c->r.borrow((double*)pooled); p.r_pooled = true;       // frees the part's own vector
     }
     t->parts.push_back(p);
     stage("residual vector pooled");
