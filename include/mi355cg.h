@@ -39,6 +39,8 @@
  *   mi355cg_eigs_release           free the workspace the eigen solves keep on the handle
  *   mi355cg_block_gram / _combine  the block kernels of that iteration on host vectors
  *   mi355cg_rayleigh_ritz          its Rayleigh-Ritz step (pure host arithmetic, no GPU needed)
+ *   mi355cg_set_solve_mode / _get_solve_mode   opt-in: chunks of a plain fp64 solve as one launch of one workgroup, grids up to N = 128
+ *   mi355cg_onchip_plan            the layout of that mode for a grid (pure host arithmetic, no GPU needed)
  *
  * Plain pointers and sizes only; no C++/torch types.  All host vectors are in the reference's
  * PACKED unknown order (bottom-right block row-major, then the upper block row-major;
@@ -406,6 +408,31 @@ int  mi355cg_get_layout(mi355cg_handle h, long long *padded_len, int *pitch_bott
  * an explicit MI355CG_XSTEPS turns it off.  depth: the depth in use, 0 = fused update.  extra_buffers: vectors the ring holds
  * beyond the handle's own, 0 until the first solve that folds (a failed allocation there sets depth to 0 for good).            */
 int  mi355cg_get_xfold(mi355cg_handle h, int *depth, int *extra_buffers);
+
+/* ---- on-chip solve mode: small grids in one workgroup (opt-in) --------------
+ * The default solve runs two launches per iteration, whose cost is launch-bound and barely falls below N = 256.  For plain fp64
+ * grid handles up to N = 128 the direction fits in the LDS of one CU and x, r in the registers of one workgroup: in mode
+ * MI355CG_SOLVE_ONCHIP every chunk of iterations (sync_every, the callback schedule and the iteration cap cut them as before) is
+ * ONE launch of ONE workgroup, ordered by workgroup barriers alone.  It takes bit-identical steps to the two-launch path: the
+ * same x, residual, iteration count, stop reason, norms and callbacks; warm starts, shifts, mi355cg_time_steps and stop requests
+ * work unchanged, and a solve may continue in the other mode through mi355cg_use_solution_as_initial_guess.
+ *   mi355cg_set_solve_mode   MI355CG_ERR_INVALID (message names the limit) for N above 128, for CSR, F32_MIXED and slab/part
+ *                            handles and for handles that have a preconditioner; mi355cg_set_preconditioner* on an on-chip handle
+ *                            is refused the same way (MI355CG_PRECOND_NONE is always accepted): go back to
+ *                            MI355CG_SOLVE_LAUNCHES first.  Changing the mode drops the cached chunk graphs.
+ *   mi355cg_get_solve_mode   the mode, and how many on-chip chunk launches the last mi355cg_solve issued.  A diagnostics solve
+ *                            (REL_2NORM with the per-iteration true residual) keeps the two-launch path in either mode and reports 0.
+ *                            With mi355cg_set_profiling on, on-chip solves are not per-kernel timed: mi355cg_get_kernel_time
+ *                            reports no launches for them.
+ *   mi355cg_onchip_plan      pure host arithmetic, no GPU needed: the workgroup size, the LDS bytes in use and the unknowns per
+ *                            thread for grid n; MI355CG_ERR_INVALID for odd n, n < 6 and n above the cap.
+ * Environment: MI355CG_ONCHIP=1, read by mi355cg_create, selects the mode on eligible handles and is ignored on the others, so
+ * an unmodified host of the reference's C++ interface can opt in.                                                              */
+#define MI355CG_SOLVE_LAUNCHES 0
+#define MI355CG_SOLVE_ONCHIP   1
+int  mi355cg_set_solve_mode(mi355cg_handle h, int mode);
+int  mi355cg_get_solve_mode(mi355cg_handle h, int *mode, long long *onchip_launches_last_solve);
+int  mi355cg_onchip_plan(int n, int *threads, int *lds_bytes, int *elems_per_thread);
 
 /* ---- multi-GPU: one context per rank, one contiguous slab of grid rows per context --------------
  * The reference is single-process (no collectives exist in it); this is the scaling

@@ -37,10 +37,12 @@ EXPORTS = [
     "mi355cg_eigs", "mi355cg_eigs_device", "mi355cg_eigs_release", "mi355cg_block_gram", "mi355cg_block_gram_indexed",
     "mi355cg_block_combine", "mi355cg_rayleigh_ritz",
     "mi355cg_set_smoother", "mi355cg_get_smoother",
+    "mi355cg_set_solve_mode", "mi355cg_get_solve_mode", "mi355cg_onchip_plan",
 ]
 DECOMP_ROWS, DECOMP_2D = 0, 1
 PRECOND_NONE, PRECOND_MG, PRECOND_MG_ANY = 0, 1, 2
 CYCLE_F64, CYCLE_F32 = 0, 1
+SOLVE_LAUNCHES, SOLVE_ONCHIP = 0, 1
 SMOOTHER_JACOBI, SMOOTHER_LINE_X, SMOOTHER_LINE_Y, SMOOTHER_LINE_AUTO = 0, 1, 2, 3
 BATCH_MAX = 64          # MI355CG_BATCH_MAX
 EIG_BLOCK_MAX = 16      # MI355CG_EIG_BLOCK_MAX
@@ -209,6 +211,10 @@ def load():
     if hasattr(L, "mi355cg_set_smoother"):       # absent from an older build loaded through MI355CG_LIB
         L.mi355cg_set_smoother.argtypes = [H, C.c_int]
         L.mi355cg_get_smoother.argtypes = [H, IP, IP]
+    if hasattr(L, "mi355cg_set_solve_mode"):    # absent from an older build loaded through MI355CG_LIB
+        L.mi355cg_set_solve_mode.argtypes = [H, C.c_int]
+        L.mi355cg_get_solve_mode.argtypes = [H, IP, LLP]
+        L.mi355cg_onchip_plan.argtypes = [C.c_int, IP, IP, IP]
     if hasattr(L, "mi355cg_get_xfold"):         # absent from an older build loaded through MI355CG_LIB
         L.mi355cg_get_xfold.argtypes = [H, IP, IP]
     _lib = L

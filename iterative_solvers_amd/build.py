@@ -13,7 +13,7 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.path.join(PKG_DIR, "libmi355cg.so")
 SOURCES = ["mi355cg.hip", "grid_setup.cpp"]
-HEADERS = ["solve_loop.h", "item_table.h", "device_buffer.h","cg_kernels.h", "csr_kernels.h", "mg_kernels.h", "mg_kernels_f32.h", "mg_batch_kernels.h", "mg_line_kernels.h", "eig_kernels.h", "step_kernels.h", "team.h", "grid_setup.h", os.path.join("..", "..", "include", "mi355cg.h")]
+HEADERS = ["solve_loop.h", "item_table.h", "device_buffer.h","cg_kernels.h", "csr_kernels.h", "mg_kernels.h", "mg_kernels_f32.h", "mg_batch_kernels.h", "mg_line_kernels.h", "eig_kernels.h", "step_kernels.h", "onchip_plan.h", "onchip_kernels.h", "team.h", "grid_setup.h", os.path.join("..", "..", "include", "mi355cg.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17",
          "-Wno-unused-value", "-Wno-unused-result", "-pthread",
          # a one-lane atomic stays a one-lane atomic: the optimizer's wave-aggregated form reads its result back at once, which drains

@@ -433,6 +433,10 @@ public:
     // returns to plain CG.  std::invalid_argument for PRECOND_MG on a grid without a nested hierarchy.
     // cycle: MI355CG_CYCLE_F32 runs the V-cycle in fp32 inside the fp64 PCG (mi355cg_set_preconditioner_ex).
     void setPreconditioner(int kind, int cycle = MI355CG_CYCLE_F64) { mi355cg_compat::check(mi355cg_set_preconditioner_ex(ctx_->h, kind, cycle)); }
+    // Extension: MI355CG_SOLVE_ONCHIP runs the chunks of every plain fp64 solve on this system as one launch of one workgroup (grids
+    // up to N = 128, the same bits as the default), MI355CG_SOLVE_LAUNCHES goes back (mi355cg_set_solve_mode).  std::invalid_argument
+    // when the system is not eligible: a larger grid, a preconditioner that is set.
+    void setSolveMode(int mode) { mi355cg_compat::check(mi355cg_set_solve_mode(ctx_->h, mode)); }
     // Extension: the smoother of the fp64 V-cycle (mi355cg_set_smoother): MI355CG_SMOOTHER_JACOBI (the default), or line Jacobi
     // MI355CG_SMOOTHER_LINE_X / _LINE_Y / _LINE_AUTO for a stretched domain.  Before or after setPreconditioner.
     void setSmoother(int smoother) { mi355cg_compat::check(mi355cg_set_smoother(ctx_->h, smoother)); }
@@ -685,6 +689,14 @@ public:
         grid = std::make_unique<GridSystem>(m_internal, n_internal, a_bound, b_bound, c_bound, d_bound);
         if (!devices_.empty()) grid->distribute(devices_, decomp_);
         if (precond_ != MI355CG_PRECOND_NONE) mi355cg_compat::check(mi355cg_set_preconditioner_ex(grid->context()->h, precond_, cycle_));
+        if (solve_mode_ != MI355CG_SOLVE_LAUNCHES) mi355cg_compat::check(mi355cg_set_solve_mode(grid->context()->h, solve_mode_));
+    }
+    // Extension: the solve mode of this facade's solves (MatrixFreeSystem::setSolveMode), single-GPU only.  Kept across
+    // setGridParameters, where a grid above the mode's limit then throws std::invalid_argument.
+    void setSolveMode(int mode) {
+        if (mode != MI355CG_SOLVE_LAUNCHES && !devices_.empty()) throw std::invalid_argument("the on-chip solve mode is single-GPU only");
+        if (grid) mi355cg_compat::check(mi355cg_set_solve_mode(grid->context()->h, mode));
+        solve_mode_ = mode;
     }
     // Extension (the reference has no preconditioner): MI355CG_PRECOND_MG_ANY or MI355CG_PRECOND_MG = multigrid-preconditioned CG
     // for the solves of this facade, single-GPU only (not together with setDevices).  The kind is kept across setGridParameters;
@@ -722,6 +734,7 @@ public:
     // Extension: solve on several GPUs of this process (see GridSystem::distribute).  Kept across setGridParameters.
     void setDevices(const std::vector<int>& devices, int decomp = MI355CG_DECOMP_ROWS) {
         if (!devices.empty() && precond_ != MI355CG_PRECOND_NONE) throw std::invalid_argument("the multigrid preconditioner is single-GPU only");
+        if (!devices.empty() && solve_mode_ != MI355CG_SOLVE_LAUNCHES) throw std::invalid_argument("the on-chip solve mode is single-GPU only");
         devices_ = devices; decomp_ = decomp;
         if (grid) grid->distribute(devices_, decomp_);
     }
@@ -793,6 +806,7 @@ private:
     int decomp_ = MI355CG_DECOMP_ROWS;
     int precond_ = MI355CG_PRECOND_NONE;
     int cycle_ = MI355CG_CYCLE_F64;
+    int solve_mode_ = MI355CG_SOLVE_LAUNCHES;
     KokkosVector guess_;
     bool has_guess_ = false, continue_ = false;
 };

@@ -251,8 +251,10 @@ __device__ inline Decision decide_after_update(const StateLite& s, const RulePar
 }
 
 // One thread of the grid: the full state object travels through this thread only.
+// INLINE_COPY (k_onchip only): the copy in line.  A call inside that kernel's iteration loop would spill the x and r it keeps in registers.
+template <bool INLINE_COPY = false>
 __device__ inline void write_state_after_decision(CgState* out, HistEntry* hist, const CgState* in, const StateLite& s, const Decision& d) {
-    copy_state(out, in);
+    if (INLINE_COPY) *out = *in; else copy_state(out, in);
     CgState* o = out;
     o->rr_prev = s.rr; o->rr = d.rr; o->rnorm2 = d.rnorm2; o->r0norm = d.r0norm; o->beta = d.beta;
     o->rmax = d.rmax; o->dmax = d.dmax; o->emax = d.emax; o->d2 = d.d2; o->e2 = d.e2;

@@ -13,6 +13,7 @@
 #include "mg_line_kernels.h"
 #include "mg_kernels_f32.h"
 #include "step_kernels.h"
+#include "onchip_kernels.h"
 
 #include <algorithm>
 #include <cfloat>
@@ -237,6 +238,10 @@ struct mi355cg_ctx {
     mi355cg_params graph_prm{};          // parameters the cached graphs were captured with
     bool graph_stop = false;            // ... and whether those solves sampled the stop word
     int use_graph = -1;                 // env MI355CG_GRAPH: -1 auto (small grids), 0 off, 1 on
+    // On-chip solve mode (mi355cg_set_solve_mode, env MI355CG_ONCHIP): plain fp64 solves without diagnostics run their
+    // chunks as one launch of one workgroup (k_onchip) instead of two launches per iteration.
+    int solve_mode = MI355CG_SOLVE_LAUNCHES;
+    long long onchip_launches = 0;      // on-chip chunk launches of the last mi355cg_solve
 
     hipEvent_t ev_loop[2] = {nullptr, nullptr};   // brackets the iterations of the last solve (mi355cg_results::loop_seconds)
     std::unique_ptr<MgHier> mg;         // opt-in preconditioner (mi355cg_set_preconditioner): mi355cg_solve runs solve_mg while set
@@ -1935,6 +1940,20 @@ extern "C" {
 const char* mi355cg_last_error(void) { return g_err.c_str(); }
 const char* mi355cg_version(void) { return "mi355cg 0.2 (gfx950)"; }
 
+// What the on-chip mode refuses (nullptr: the handle is eligible): every handle whose iteration is not the plain fp64 grid CG, and
+// grids whose direction does not fit in one CU's LDS.
+static const char* onchip_refusal(const mi355cg_ctx* c) {
+    static char buf[160];
+    if (c->is_csr) return "the on-chip solve keeps the grid's direction in LDS: a CSR handle has no grid";
+    if (c->is_slab) return "the on-chip solve is one workgroup on one GPU: this handle owns one part of a decomposed grid";
+    if (c->dtype != MI355CG_F64) return "the on-chip solve is fp64 only: this handle was created with MI355CG_F32_MIXED";
+    if (c->mg) return "the on-chip solve runs plain CG: this handle has a preconditioner (mi355cg_set_preconditioner(h, MI355CG_PRECOND_NONE) first)";
+    if (!onchip_supported(c->gp.n)) {
+        snprintf(buf, sizeof buf, "the on-chip solve takes grids up to N = %d (the direction must fit in one CU's LDS): this handle has N = %d", kOnchipMaxN, c->gp.n);
+        return buf;
+    }
+    return nullptr;
+}
 // What every handle keeps, grid or CSR: the partials of the two phases and of the flat reductions, the device-side CG state with
 // its history, and their pinned copies.  The zero-fills run on the NULL stream and are asynchronous to the host; the context's own
 // stream is non-blocking and does not order with them.  Without the callers' device-wide wait after it a delayed memset can land
@@ -2029,6 +2048,7 @@ static int create_impl(int n, int m, double a, double b, double c_, double d, in
         grid_fill_box(gp, c->g.y_lo, c->g.y_hi, s_lo * kStripCols, s_hi == ns_all ? gp.n : s_hi * kStripCols, c->rhs_h.data(), c->u_h.data(), nullptr, nullptr);
         if ((rc = upload_packed<double>(c, c->rhs_h.data(), c->b))) return cleanup();
     }
+    if (env_int("MI355CG_ONCHIP", 0) == 1 && !onchip_refusal(c)) c->solve_mode = MI355CG_SOLVE_ONCHIP;      // ignored on handles the mode refuses
     *out = c;
     return MI355CG_OK;
 }
@@ -2241,6 +2261,34 @@ static void launch_init_fresh(mi355cg_ctx* c, bool has_u) {
     else hipLaunchKernelGGL((k_init_fresh<double, 2, false>), dim3(c->whole.grid), dim3(kBlock), 0, c->stream, f);
 }
 
+// One chunk of m iterations in one launch of one workgroup, from and to the iteration-boundary state of the two-launch path.
+static void launch_onchip_chunk(mi355cg_ctx* c, const IterCfg& cfg, const mi355cg_params* prm, int m) {
+    OnchipArgs a{};
+    a.g = c->g; a.pl = onchip_plan(c->gp.n);
+    a.x = c->x; a.r = c->r; a.u = c->u;
+    for (int k = 0; k < c->xsteps; ++k) a.p[k] = c->p[k];
+    a.xsteps = c->xsteps;
+    a.partB = c->partB; a.nB = c->nB_own; a.strideB = c->strideB;
+    a.s = c->sB; a.hist = c->hist; a.rp = cfg.rp;
+    a.has_u = cfg.has_u ? 1 : 0; a.u_always = cfg.rp.eps_exact_error > 0 ? 1 : 0; a.every = prm->callback_every;       // need_u of mi355cg_solve
+    a.m = m; a.stop_req = c->stop_dev;
+    const dim3 grid(1), block(a.pl.threads);
+    const bool msg = cfg.rp.rule == MI355CG_RULE_MSG_MAXNORM;
+#define MI355CG_OC(E) do { if (msg) hipLaunchKernelGGL((k_onchip<E, true>), grid, block, 0, c->stream, a); \
+                           else hipLaunchKernelGGL((k_onchip<E, false>), grid, block, 0, c->stream, a); } while (0)
+    switch (a.pl.elems) {
+        case 1: MI355CG_OC(1); break;
+        case 2: MI355CG_OC(2); break;
+        case 4: MI355CG_OC(4); break;
+        case 8: MI355CG_OC(8); break;
+        case 16: MI355CG_OC(16); break;
+        default: MI355CG_OC(kOnchipMaxElems); break;
+    }
+#undef MI355CG_OC
+    c->nB_own = 1;                               // the chunk leaves its update partials in one slot
+    ++c->onchip_launches;
+}
+
 int mi355cg_solve(mi355cg_handle c, const mi355cg_params* prm, mi355cg_iter_cb cb, void* user,
                   const volatile int* stop_flag, mi355cg_results* out) {
     if (!c || !prm) return fail(MI355CG_ERR_INVALID, "null argument");
@@ -2249,11 +2297,16 @@ int mi355cg_solve(mi355cg_handle c, const mi355cg_params* prm, mi355cg_iter_cb c
     HIPCK(hipSetDevice(c->device));
     const bool warm = c->guess_pending;          // one-shot: this solve consumes the guess, whatever it returns
     c->guess_pending = false;                    // x_is_guess stays until a solve has completed: a solve that fails before it leaves no solution behind
+    c->onchip_launches = 0;
     if (c->is_csr) return solve_csr(c, prm, cb, user, stop_flag, out);
     if (c->dtype == MI355CG_F32_MIXED) return solve_mixed(c, prm, cb, user, stop_flag, out);
     if (c->mg) return solve_mg(c, prm, cb, user, stop_flag, out, warm);               // opt-in preconditioner (fp64 grid handles only)
     const bool msg = prm->rule == MI355CG_RULE_MSG_MAXNORM;
     IterCfg cfg0 = make_cfg(prm);
+    // On-chip mode: the chunks below are single launches of k_onchip, which steps x every iteration (nothing folded, nothing to flush).
+    // A diagnostics solve needs a true residual per iteration and keeps the two-launch path in either mode.
+    const bool onchip = c->solve_mode == MI355CG_SOLVE_ONCHIP && cfg0.want_diag == 0;
+    if (onchip) cfg0.x2 = false;
     cfg0.fold = cfg0.x2 && ensure_fold_ring(c);
     const IterCfg cfg = cfg0;
     const bool diag = cfg.want_diag != 0, fold = cfg.fold;
@@ -2358,7 +2411,9 @@ int mi355cg_solve(mi355cg_handle c, const mi355cg_params* prm, mi355cg_iter_cb c
             }
             return MI355CG_OK;
         };
-        if (graph_ok && m >= 8) {
+        if (onchip) {
+            launch_onchip_chunk(c, cfg, prm, m);
+        } else if (graph_ok && m >= 8) {
             // Launch-bound grids: replay the chunk as one hipGraph.  The chunk's kernel arguments depend only on
             // (m, direction-buffer parity, which iterations read u), so equal shapes share an instantiated graph.
             std::vector<char> flags(m);
@@ -2650,6 +2705,35 @@ int mi355cg_get_xfold(mi355cg_handle c, int* depth, int* extra_buffers) {
     return MI355CG_OK;
 }
 
+// ---- on-chip solve mode -----------------------------------------------------------------------------
+int mi355cg_set_solve_mode(mi355cg_handle c, int mode) {
+    if (!c) return fail(MI355CG_ERR_INVALID, "null handle");
+    if (mode != MI355CG_SOLVE_LAUNCHES && mode != MI355CG_SOLVE_ONCHIP)
+        return fail(MI355CG_ERR_INVALID, "unknown solve mode %d (MI355CG_SOLVE_LAUNCHES = 0, MI355CG_SOLVE_ONCHIP = 1)", mode);
+    if (mode == MI355CG_SOLVE_ONCHIP) if (const char* why = onchip_refusal(c)) return fail(MI355CG_ERR_INVALID, "%s", why);
+    if (mode == c->solve_mode) return MI355CG_OK;
+    HIPCK(hipSetDevice(c->device));
+    HIPCK(hipStreamSynchronize(c->stream));
+    clear_graphs(c);                                               // chunks of the other mode
+    c->solve_mode = mode;
+    return MI355CG_OK;
+}
+int mi355cg_get_solve_mode(mi355cg_handle c, int* mode, long long* onchip_launches_last_solve) {
+    if (!c) return fail(MI355CG_ERR_INVALID, "null handle");
+    if (mode) *mode = c->solve_mode;
+    if (onchip_launches_last_solve) *onchip_launches_last_solve = c->onchip_launches;
+    return MI355CG_OK;
+}
+int mi355cg_onchip_plan(int n, int* threads, int* lds_bytes, int* elems_per_thread) {
+    if (!onchip_supported(n))
+        return fail(MI355CG_ERR_INVALID, "grid %d rejected: the on-chip solve takes even n from 6 to %d", n, kOnchipMaxN);
+    const OnchipPlan pl = onchip_plan(n);
+    if (threads) *threads = pl.threads;
+    if (lds_bytes) *lds_bytes = pl.lds_bytes;
+    if (elems_per_thread) *elems_per_thread = pl.elems;
+    return MI355CG_OK;
+}
+
 // ---- geometric multigrid preconditioner (opt-in) ----------------------------------------------------------------------
 int mi355cg_mg_levels(int n, int* levels, int* coarsest_n) {
     std::vector<int> ns;
@@ -2685,6 +2769,8 @@ int mi355cg_set_preconditioner_ex(mi355cg_handle c, int kind, int cycle) {
     if (c->is_csr) return fail(MI355CG_ERR_INVALID, "the multigrid preconditioner needs the grid operator: a CSR handle has no grid");
     if (c->is_slab) return fail(MI355CG_ERR_INVALID, "the multigrid preconditioner is single-GPU only: this handle owns one part of a decomposed grid");
     if (c->dtype != MI355CG_F64) return fail(MI355CG_ERR_INVALID, "the multigrid preconditioner is fp64 only: this handle was created with MI355CG_F32_MIXED");
+    if (c->solve_mode == MI355CG_SOLVE_ONCHIP)
+        return fail(MI355CG_ERR_INVALID, "this handle is in the on-chip solve mode, which runs plain CG: mi355cg_set_solve_mode(h, MI355CG_SOLVE_LAUNCHES) first");
     std::vector<int> ns;
     if (int rc = mg_shape(kind, c->gp.n, &ns)) return rc;          // refused: the handle keeps what it had
     if (cycle != MI355CG_CYCLE_F64 && cycle != MI355CG_CYCLE_F32)

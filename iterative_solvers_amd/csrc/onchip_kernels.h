@@ -1,0 +1,263 @@
+// onchip_kernels.h -- a chunk of CG iterations inside ONE workgroup: plain fp64 grid handles up to N = kOnchipMaxN.
+//
+// One launch of one workgroup runs up to `m` iterations.  The direction lives in LDS as an (N+1) x (N+1) image with zeros where the
+// grid has boundary nodes or no nodes (onchip_plan.h); every thread keeps x, r (and u when the error norm is read) of its unknowns in
+// registers.  Nothing but __syncthreads() orders the threads: three barriers per iteration --
+//   1  after the new direction z = r + beta*z is in the image (the stencil reads neighbours),
+//   2  after the waves' partials of (Az, z) [and (r, z)] are in LDS,
+//   3  after the waves' partials of (r, r), |r|, |dx|, |x - u| and the sampled stop word are in LDS
+// -- each reduction combining all its fields behind its one barrier.  The three partial areas and the image are distinct, and between
+// two uses of any of them lie two other barriers, so no barrier is needed to "protect the previous use".
+//
+// Entry and exit are the iteration-boundary state of the two-launch path (cg_kernels.h): x, r and the direction of iteration `it` in
+// the handle's storage layout (the direction in ring slot it % xsteps), the CgState the update launch leaves in sB, the update
+// partials in partB (any number of slots at entry, ONE slot at exit).  Every element-wise expression is that path's, in its order,
+// decisions come from decide_after_update and the state is written by write_state_after_decision; the inner products are double-double
+// pairs, whose rounded value does not depend on the order of summation.  Hence the same bits as k_stencil + k_update_st, step by step.
+#pragma once
+#include "cg_kernels.h"
+#include "onchip_plan.h"
+
+namespace mi355cg {
+
+struct OnchipArgs {
+    Geom g;
+    OnchipPlan pl;
+    double* x; double* r;
+    double* p[kRing]; int xsteps;        // the direction ring: the direction of iteration k is in p[k % xsteps]
+    const double* u;
+    double* partB; int nB, strideB;      // update partials: nB slots at entry, one at exit
+    CgState* s;                          // the state at the iteration boundary (the handle's sB)
+    HistEntry* hist;
+    RuleParams rp;
+    int has_u;                           // the solve reads u at all ...
+    int u_always, every;                 // ... on every iteration / on iteration 1 and every `every`-th (mi355cg_solve: need_u)
+    int m;                               // iterations of this chunk
+    const int* stop_req;                 // pinned host word, sampled once per iteration by one lane; may be null
+};
+
+constexpr int kOcWaves = kOnchipMaxThreads / kWave;
+constexpr int kOcFieldsA = 4, kOcFieldsB = 10;
+static_assert(kOcWaves * (kOcFieldsA + kOcFieldsB) * 8 + (int)sizeof(CgState) <= kOnchipSideBytes, "onchip_plan.h: the side data");
+
+struct OcSumsA { dd pap, rz; };
+struct OcSumsB { dd rr, d2, e2; double rmax, dmax, emax, stop; };
+
+// All threads get the workgroup totals: lane tree inside a wave, the waves' partials through LDS behind one barrier, waves in order.
+template <bool MSG>
+__device__ inline OcSumsA oc_reduce_a(OcSumsA v, double* scr, int nwaves) {
+    v.pap = wave_sum_dd(v.pap);
+    if (MSG) v.rz = wave_sum_dd(v.rz);
+    const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x / kWave;
+    if (lane == 0) { double* o = scr + w * kOcFieldsA; o[0] = v.pap.hi; o[1] = v.pap.lo; o[2] = v.rz.hi; o[3] = v.rz.lo; }
+    __syncthreads();
+    OcSumsA t{dd{scr[0], scr[1]}, dd{scr[2], scr[3]}};
+#pragma unroll 1
+    for (int k = 1; k < nwaves; ++k) {
+        const double* o = scr + k * kOcFieldsA;
+        t.pap = dd_add(t.pap, dd{o[0], o[1]});
+        if (MSG) t.rz = dd_add(t.rz, dd{o[2], o[3]});
+    }
+    return t;
+}
+// FULL: all fields (the MSG rule's update, the partials found at entry); otherwise (r, r) and |r| only -- the others are zero.
+// In two halves, so that the totals need not stay in registers: the exit combines the last partials once more.
+template <bool FULL>
+__device__ inline OcSumsB oc_combine_b(const double* scr, int nwaves) {
+    OcSumsB t{dd{scr[0], scr[1]}, dd_zero(), dd_zero(), scr[2], 0.0, 0.0, scr[3]};
+    if (FULL) { t.d2 = dd{scr[4], scr[5]}; t.e2 = dd{scr[6], scr[7]}; t.dmax = scr[8]; t.emax = scr[9]; }
+#pragma unroll 1
+    for (int k = 1; k < nwaves; ++k) {
+        const double* o = scr + k * kOcFieldsB;
+        t.rr = dd_add(t.rr, dd{o[0], o[1]}); t.rmax = fmax(t.rmax, o[2]);
+        if (FULL) {
+            t.d2 = dd_add(t.d2, dd{o[4], o[5]}); t.e2 = dd_add(t.e2, dd{o[6], o[7]});
+            t.dmax = fmax(t.dmax, o[8]); t.emax = fmax(t.emax, o[9]);
+        }
+    }
+    return t;
+}
+template <bool FULL>
+__device__ inline void oc_publish_b(OcSumsB v, double* scr) {
+    v.rr = wave_sum_dd(v.rr); v.rmax = wave_max(v.rmax);
+    if (FULL) { v.d2 = wave_sum_dd(v.d2); v.e2 = wave_sum_dd(v.e2); v.dmax = wave_max(v.dmax); v.emax = wave_max(v.emax); }
+    const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x / kWave;
+    if (lane == 0) {
+        double* o = scr + w * kOcFieldsB;
+        o[0] = v.rr.hi; o[1] = v.rr.lo; o[2] = v.rmax; o[3] = v.stop;             // stop: thread 0's sample, 0 elsewhere
+        if (FULL) { o[4] = v.d2.hi; o[5] = v.d2.lo; o[6] = v.e2.hi; o[7] = v.e2.lo; o[8] = v.dmax; o[9] = v.emax; }
+    }
+    __syncthreads();
+}
+
+// E: slots per thread (OnchipPlan::elems).  MSG: the max-norm rule -- x and its norms every iteration, (r, z) reduced, u in registers.
+template <int E, bool MSG>
+__global__ __launch_bounds__(kOnchipMaxThreads) void k_onchip(const OnchipArgs a) {
+    __shared__ double img[kOnchipMaxCells];
+    __shared__ double scrA[kOcWaves * kOcFieldsA], scrB[kOcWaves * kOcFieldsB];
+    // The CG state, in LDS while the chunk runs.  ONE object: write_state_after_decision is handed it as source and destination, so
+    // its copy is a copy onto itself and only the fields it sets are stored (two objects cost 46 registers per copy, in mid-loop).
+    __shared__ CgState st;
+    static_assert(sizeof(CgState) % sizeof(double) == 0, "the state travels as doubles");
+    constexpr int kStateWords = (int)(sizeof(CgState) / sizeof(double));
+    const Geom& g = a.g;
+    const OnchipPlan& pl = a.pl;
+    const int t = threadIdx.x, T = blockDim.x, nwaves = T / kWave;
+    StateLite s = load_state_lite(a.s);
+    if (s.done) return;                                // the state already says done: x, r, the state and the partials stay
+    const bool use_u = MSG && a.has_u;
+
+    for (int i = t; i < pl.cells; i += T) img[i] = 0.0;
+    if (t < kStateWords) reinterpret_cast<double*>(&st)[t] = reinterpret_cast<const double*>(a.s)[t];      // (thread 0 reads it behind two barriers)
+    // the partials the launch before left (the init pass: one slot per workgroup of it; an on-chip chunk: one slot)
+    OcSumsB v0{dd_zero(), dd_zero(), dd_zero(), 0.0, 0.0, 0.0, 0.0};
+    for (int i = t; i < a.nB; i += T) {
+        const double* q = a.partB + i;
+        const int sb = a.strideB;
+        v0.rr = dd_add(v0.rr, dd{q[FB_RR * sb], q[(FB_RR + FB_LO) * sb]});
+        v0.d2 = dd_add(v0.d2, dd{q[FB_D2 * sb], q[(FB_D2 + FB_LO) * sb]});
+        v0.e2 = dd_add(v0.e2, dd{q[FB_E2 * sb], q[(FB_E2 + FB_LO) * sb]});
+        v0.rmax = fmax(v0.rmax, q[FB_RMAX * sb]); v0.dmax = fmax(v0.dmax, q[FB_DMAX * sb]); v0.emax = fmax(v0.emax, q[FB_EMAX * sb]);
+    }
+    __syncthreads();                                   // the image is zero everywhere before the owners fill their cells
+
+    // this thread's unknowns: image cell, x, r [, u] from the storage layout into registers, the direction into the image
+    auto storage_off = [&](int i) { int xx, yy; onchip_node(pl, i, &xx, &yy); return (long long)(row_off(g, yy) + xx - g.base0); };
+    unsigned cell2[(E + 1) / 2] = {};                   // image cells, two 16-bit indices per register (kOnchipMaxCells < 65536)
+    static_assert(kOnchipMaxCells <= 0x10000, "a cell index fits in 16 bits");
+    double x[E], r[E], u[MSG ? E : 1];
+    int cnt = 0;                                       // valid slots: a prefix
+    const double* pin = a.p[s.it % a.xsteps];
+#pragma unroll
+    for (int k = 0; k < E; ++k) {
+        const int i = onchip_owned(pl, t, k);
+        x[k] = 0.0; r[k] = 0.0;
+        if (MSG) u[k] = 0.0;
+        if (i >= 0) {
+            int xx, yy;
+            onchip_node(pl, i, &xx, &yy);
+            const int c = onchip_cell(pl, xx, yy);
+            cell2[k / 2] |= (unsigned)c << (16 * (k & 1));
+            const long long off = row_off(g, yy) + xx - g.base0;
+            x[k] = a.x[off]; r[k] = a.r[off]; img[c] = pin[off];
+            if (use_u) u[k] = a.u[off];
+            cnt = k + 1;
+        }
+    }
+    oc_publish_b<true>(v0, scrB);
+    // what the next decision needs of the totals: (r, r), and under MSG the three max-norms
+    double rr, rmax = 0, dmax = 0, emax = 0;
+    { const OcSumsB tot = oc_combine_b<MSG>(scrB, nwaves); rr = dd_value(tot.rr); if (MSG) { rmax = tot.rmax; dmax = tot.dmax; if (a.rp.use_u) emax = tot.emax; } }
+
+    const double cA = g.A, cxk = g.xk, cyk = g.yk;
+    const int pitch = pl.pitch;
+    // A z at an owned cell: the stencil launch's formula, verbatim (every owned node is interior: nothing to mask)
+    auto apply_at = [&](int c, double cc) {
+        double v = cA * cc;
+        v = v + cxk * img[c - 1];
+        v = v + cxk * img[c + 1];
+        v = v + cyk * img[c + pitch];                  // row y+1
+        v = v + cyk * img[c - pitch];                  // row y-1
+        return v;
+    };
+
+    // What a slot's loop body starts from: the cell index, opaque to the optimizer.  Otherwise it keeps the five LDS addresses of
+    // every slot (and the storage offsets the exit needs) in registers across the whole iteration loop, and spills them.
+    auto own_cell = [&](int k) { unsigned c2 = cell2[k / 2]; asm volatile("" : "+v"(c2)); return (int)((c2 >> (16 * (k & 1))) & 0xffffu); };
+    int ran = 0;
+    for (int it_k = 0; it_k < a.m; ++it_k) {
+        // the stop request (a pinned HOST word): one lane asks now and hands the answer to the update reduction
+        double stop_word = 0.0;
+        if (t == 0 && a.stop_req) stop_word = __hip_atomic_load(a.stop_req, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0 ? 1.0 : 0.0;
+
+        // ---- the stencil launch's prologue: decide from the update partials (reduce_and_decide without diagnostics)
+        const Decision d = decide_after_update(s, a.rp, rr, rmax, dmax, emax, 0.0, 0.0);
+        if (t == 0) write_state_after_decision<true>(&st, a.hist, &st, s, d);
+        if (d.done) break;
+        const double beta = d.beta;
+
+        // ---- phase A': z = r + beta*z, (Az, z) [and (r, z)]
+#pragma unroll
+        for (int k = 0; k < E; ++k) if (k < cnt) { const int c = own_cell(k); img[c] = r[k] + beta * img[c]; }        // z = r + beta*z
+        __syncthreads();                                                                              // barrier 1
+        OcSumsA va{dd_zero(), dd_zero()};
+#pragma unroll
+        for (int k = 0; k < E; ++k) if (k < cnt) {
+            const int c = own_cell(k);
+            const double cc = img[c];
+            const double ap = apply_at(c, cc);
+            dd_acc_prod(va.pap, cc, ap);
+            if (MSG) dd_acc_prod(va.rz, r[k], cc);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        const OcSumsA ta = oc_reduce_a<MSG>(va, scrA, nwaves);                                        // barrier 2
+        const double pap = dd_value(ta.pap);
+        double rz = 0.0, alpha_d;
+        if (MSG) { rz = dd_value(ta.rz); alpha_d = rz / pap; }                                        // msg_solver.cpp:102
+        else alpha_d = d.rr / pap;                                                                    // matrix_free_system.cpp:419
+        const double alpha = alpha_d;
+
+        // ---- phase B: r -= alpha*Az (A z rebuilt from the image: same operands, same order), x += alpha*z, the norms
+        const int it_new = s.it + 1;
+        const bool u_now = use_u && (a.u_always || it_new == 1 || (a.every > 0 && it_new % a.every == 0));
+        OcSumsB vb{dd_zero(), dd_zero(), dd_zero(), 0.0, 0.0, 0.0, stop_word};
+#pragma unroll
+        for (int k = 0; k < E; ++k) if (k < cnt) {
+            const int c = own_cell(k);
+            const double cc = img[c];
+            const double apj = apply_at(c, cc);
+            const double rn = r[k] - alpha * apj;                  // r = r - alpha*A_z      msg_solver.cpp:110-112
+            dd_acc_prod(vb.rr, rn, rn);
+            vb.rmax = fmax(vb.rmax, fabs(rn));
+            const double xn = x[k] + alpha * cc;                   // x = x + alpha*z        msg_solver.cpp:105-107
+            if (MSG) {
+                const double dx = xn - x[k];                       // diff = x - x_prev      msg_solver.cpp:124-127
+                vb.dmax = fmax(vb.dmax, fabs(dx));
+                dd_acc_prod(vb.d2, dx, dx);
+                if (u_now) {
+                    const double ee = xn - u[k];                   // error = x - u          msg_solver.cpp:132-136
+                    vb.emax = fmax(vb.emax, fabs(ee));
+                    dd_acc_prod(vb.e2, ee, ee);
+                }
+            }
+            r[k] = rn; x[k] = xn;
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        oc_publish_b<MSG>(vb, scrB);                                                                  // barrier 3
+        int stop;
+        { const OcSumsB tot = oc_combine_b<MSG>(scrB, nwaves); rr = dd_value(tot.rr); stop = tot.stop != 0.0; if (MSG) { rmax = tot.rmax; dmax = tot.dmax; if (a.rp.use_u) emax = tot.emax; } }
+        if (t == 0) {                                              // what the update launch writes
+            CgState* o = &st;
+            o->it = it_new; o->first = 0; o->alpha = alpha_d; o->rz = rz; o->alpha_hist[it_new & (kRing - 1)] = alpha_d;
+            o->stop = stop;                                        // the reference tests its flag once per iteration (msg_solver.cpp:82-87)
+        }
+        s.rr_prev = s.rr; s.rr = d.rr; s.r0norm = d.r0norm;        // what the next decision reads back from that state
+        s.alpha = alpha_d; s.rz = rz; s.it = it_new; s.first = 0; s.stop = stop;
+        ++ran;
+    }
+
+    // ---- exit: the iteration-boundary state, for the host, the next chunk or the two-launch path
+    if (ran > 0) {
+        double* pout = a.p[s.it % a.xsteps];
+#pragma unroll
+        for (int k = 0; k < E; ++k) if (k < cnt) {
+            int i = k * T + t;
+            asm volatile("" : "+v"(i));                            // recomputed here, not carried through the loop
+            const long long off = storage_off(i);
+            a.x[off] = x[k]; a.r[off] = r[k]; pout[off] = img[own_cell(k)];
+        }
+    }
+    __syncthreads();                                               // thread 0's last state stores
+    if (t < kStateWords) reinterpret_cast<double*>(a.s)[t] = reinterpret_cast<const double*>(&st)[t];
+    if (t == 0) {
+        // the partials of the last update (no update ran: of the launch before), all fields, as one slot
+        const OcSumsB tot = (MSG || ran == 0) ? oc_combine_b<true>(scrB, nwaves) : oc_combine_b<false>(scrB, nwaves);
+        const int sb = a.strideB;
+        a.partB[FB_RR * sb] = tot.rr.hi; a.partB[(FB_RR + FB_LO) * sb] = tot.rr.lo;
+        a.partB[FB_D2 * sb] = tot.d2.hi; a.partB[(FB_D2 + FB_LO) * sb] = tot.d2.lo;
+        a.partB[FB_E2 * sb] = tot.e2.hi; a.partB[(FB_E2 + FB_LO) * sb] = tot.e2.lo;
+        a.partB[FB_RMAX * sb] = tot.rmax; a.partB[FB_DMAX * sb] = tot.dmax; a.partB[FB_EMAX * sb] = tot.emax;
+    }
+}
+
+}  // namespace mi355cg

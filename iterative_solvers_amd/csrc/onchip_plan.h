@@ -1,0 +1,76 @@
+// onchip_plan.h -- the layout of the single-workgroup on-chip CG solve: which thread owns which unknown, where a
+// node and its four neighbours sit in the LDS image of the direction, how much LDS that takes.
+//
+// Free of HIP includes, like item_table.h: the kernel (onchip_kernels.h), mi355cg_onchip_plan and tests/cpp/onchip_plan_driver.cpp
+// all read the layout from here.
+//
+//   * Unknowns are numbered row by row, x fastest: first the rows 1 .. N/2 of the bottom-right block (columns N/2+1 .. N-1), then the
+//     rows N/2+1 .. N-1 of the upper block (columns 1 .. N-1).
+//   * Thread t of T owns the unknowns t, t + T, t + 2T, ... (slot k = unknown k*T + t): the lanes of a wave touch neighbouring
+//     cells of the image in every slot.  Its valid slots are a prefix of its `elems` slots.
+//   * The image is the whole (N+1) x (N+1) bounding grid, cell(x, y) = y*(N+1) + x.  The neighbours of a cell are cell +- 1 and
+//     cell +- (N+1).  Boundary nodes and the cut-out quadrant are cells no thread owns: they are zeroed once and never written, so they
+//     are the Dirichlet zeros and the in_j masking of the streaming kernels in one.  Every neighbour of an interior node lies in the image.
+#pragma once
+#include "item_table.h"               // MI355CG_HD
+
+namespace mi355cg {
+
+constexpr int kOnchipMaxN = 128;                      // largest grid the on-chip path takes (DESIGN section 12 says why)
+constexpr int kOnchipMaxThreads = 512;                // one workgroup: 8 wave64, two per SIMD, so that a wave may use 256 VGPRs
+constexpr int kOnchipMaxElems = 24;                   // unknowns per thread at the cap
+constexpr int kOnchipLdsLimit = 160 * 1024;           // LDS of one CU (gfx950)
+constexpr int kOnchipMaxCells = (kOnchipMaxN + 1) * (kOnchipMaxN + 1);
+// beside the image: the per-wave partials of the two reductions (4 and 10 doubles per wave) and the CG state (256 B at most)
+constexpr int kOnchipSideBytes = (kOnchipMaxThreads / 64) * (4 + 10) * 8 + 256;
+
+struct OnchipPlan {
+    int n, half;
+    int unknowns;                     // (N/2 - 1)(3N/2 - 1)
+    int nbottom, wbottom, wupper;     // unknowns of the bottom block; interior columns of a bottom / an upper row
+    int threads, elems;               // workgroup size (a multiple of 64); slots per thread (the kernel's unroll class: 1, 2, 4, 8, 16 or 24)
+    int pitch, cells;                 // image: N + 1 cells per row, (N + 1)^2 cells
+    int lds_bytes;                    // image of this N + the side data
+};
+
+MI355CG_HD inline bool onchip_supported(int n) { return n >= 6 && n % 2 == 0 && n <= kOnchipMaxN; }
+
+// Small grids should not pay for 8 waves of reduction: the workgroup grows (64, 128, 256, 512 threads) only as far as it takes
+// to keep a thread at four unknowns or fewer; from there the slots per thread grow.
+MI355CG_HD inline OnchipPlan onchip_plan(int n) {
+    OnchipPlan p{};
+    if (!onchip_supported(n)) return p;
+    p.n = n; p.half = n / 2;
+    p.wbottom = p.half - 1; p.wupper = n - 1;
+    p.nbottom = p.half * p.wbottom;
+    p.unknowns = p.nbottom + (p.half - 1) * p.wupper;
+    int t = 64;
+    while (t < kOnchipMaxThreads && 4 * t < p.unknowns) t *= 2;
+    p.threads = t;
+    const int need = (p.unknowns + t - 1) / t;
+    p.elems = need <= 1 ? 1 : need <= 2 ? 2 : need <= 4 ? 4 : need <= 8 ? 8 : need <= 16 ? 16 : kOnchipMaxElems;
+    p.pitch = n + 1; p.cells = p.pitch * p.pitch;
+    p.lds_bytes = p.cells * 8 + kOnchipSideBytes;
+    return p;
+}
+
+// unknown i in [0, unknowns) -> its node
+MI355CG_HD inline void onchip_node(const OnchipPlan& p, int i, int* x, int* y) {
+    if (i < p.nbottom) { *y = 1 + i / p.wbottom; *x = p.half + 1 + i % p.wbottom; }
+    else { const int j = i - p.nbottom; *y = p.half + 1 + j / p.wupper; *x = 1 + j % p.wupper; }
+}
+// the unknown in slot `slot` of thread `thread`, -1: the slot is empty
+MI355CG_HD inline int onchip_owned(const OnchipPlan& p, int thread, int slot) {
+    const int i = slot * p.threads + thread;
+    return i < p.unknowns ? i : -1;
+}
+MI355CG_HD inline int onchip_cell(const OnchipPlan& p, int x, int y) { return y * p.pitch + x; }
+// left, right, upper (y + 1) and lower (y - 1) neighbour of a cell
+MI355CG_HD inline void onchip_neighbours(const OnchipPlan& p, int cell, int nb[4]) {
+    nb[0] = cell - 1; nb[1] = cell + 1; nb[2] = cell + p.pitch; nb[3] = cell - p.pitch;
+}
+
+static_assert(kOnchipMaxCells * 8 + kOnchipSideBytes <= kOnchipLdsLimit, "the image of the largest grid and the side data fit in one CU's LDS");
+static_assert(kOnchipMaxThreads * kOnchipMaxElems >= (kOnchipMaxN / 2 - 1) * (3 * kOnchipMaxN / 2 - 1), "every unknown of the largest grid has a slot");
+
+}  // namespace mi355cg

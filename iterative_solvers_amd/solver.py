@@ -219,6 +219,21 @@ class _Handle:
             raise ValueError(self._lib.mi355cg_last_error().decode())
         _capi.check(rc)
 
+    def set_solve_mode(self, mode: int):
+        """Extension (no reference twin): _capi.SOLVE_ONCHIP runs every chunk of a plain fp64 solve as one launch of one workgroup
+        (grids up to N = 128, bit-identical to the default), _capi.SOLVE_LAUNCHES goes back to two launches per iteration
+        (include/mi355cg.h, mi355cg_set_solve_mode).  ValueError if refused; the handle then keeps its mode."""
+        rc = self._lib.mi355cg_set_solve_mode(self._h, int(mode))
+        if rc == _capi.ERR_INVALID:
+            raise ValueError(self._lib.mi355cg_last_error().decode())
+        _capi.check(rc)
+
+    def solve_mode_info(self):
+        """(mode, on-chip chunk launches of the last solve)."""
+        mode, n = C.c_int(), C.c_longlong()
+        _capi.check(self._lib.mi355cg_get_solve_mode(self._h, C.byref(mode), C.byref(n)))
+        return mode.value, n.value
+
     def preconditioner_info(self):
         """(kind, cycle, levels) of the preconditioner that is set; (PRECOND_NONE, CYCLE_F64, 0) without one."""
         k, cy, lv = C.c_int(), C.c_int(), C.c_int()
@@ -451,6 +466,18 @@ def mg_hierarchy(n: int, kind: int = _capi.PRECOND_MG_ANY):
     return tuple(buf[:L.value])
 
 
+def onchip_plan(n: int):
+    """The layout of the on-chip solve mode for an n x n grid (host arithmetic, no GPU): a dict with the workgroup's `threads`, the
+    `lds_bytes` in use and the unknowns per thread `elems_per_thread`; ValueError if n is odd, < 6 or above the mode's cap."""
+    t, lds, e = C.c_int(), C.c_int(), C.c_int()
+    lib = _capi.load()
+    rc = lib.mi355cg_onchip_plan(int(n), C.byref(t), C.byref(lds), C.byref(e))
+    if rc == _capi.ERR_INVALID:
+        raise ValueError(lib.mi355cg_last_error().decode())
+    _capi.check(rc)
+    return {"threads": t.value, "lds_bytes": lds.value, "elems_per_thread": e.value}
+
+
 def rayleigh_ritz(g, h):
     """The Rayleigh-Ritz step of eigs on the host (mi355cg_rayleigh_ritz, no GPU): for the k x k pair G = S^T S, H = S^T K S
     (k <= 48) returns (theta[k] ascending, coef[k, k]) with coef.T @ G @ coef = I and coef.T @ H @ coef = diag(theta).
@@ -500,6 +527,21 @@ class MatrixFreeSystem:
     def preconditioner_info(self):
         """(kind, cycle, levels) of the preconditioner that is set; (PRECOND_NONE, CYCLE_F64, 0) without one."""
         return self._handle.preconditioner_info()
+
+    def set_solve_mode(self, mode: int):
+        """Extension (no reference twin): SOLVE_ONCHIP / SOLVE_LAUNCHES.  In the on-chip mode every plain fp64 solve built on this
+        system (MatrixFreeSolver without diagnostics, MSGSolver, time_steps) runs its chunks of iterations as one launch of one
+        workgroup: the same bits, a fraction of the launch cost, grids up to N = 128.  ValueError if the system is not eligible."""
+        self._handle.set_solve_mode(mode)
+
+    def solve_mode_info(self):
+        """{"mode", "onchip_launches" of the last solve, "plan": onchip_plan(n) or None above the cap}."""
+        mode, launches = self._handle.solve_mode_info()
+        try:
+            plan = onchip_plan(self.n)
+        except ValueError:
+            plan = None
+        return {"mode": mode, "onchip_launches": launches, "plan": plan}
 
     def set_smoother(self, smoother: int):
         """Extension (no reference twin): _capi.SMOOTHER_JACOBI (the default) or SMOOTHER_LINE_X / _LINE_Y / _LINE_AUTO, line
