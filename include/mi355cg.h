@@ -41,6 +41,8 @@
  *   mi355cg_rayleigh_ritz          its Rayleigh-Ritz step (pure host arithmetic, no GPU needed)
  *   mi355cg_set_solve_mode / _get_solve_mode   opt-in: chunks of a plain fp64 solve as one launch of one workgroup, grids up to N = 128
  *   mi355cg_onchip_plan            the layout of that mode for a grid (pure host arithmetic, no GPU needed)
+ *   mi355cg_solve_many / _from / _device / _device_from   many small systems (own b, guess and shift each), one workgroup per system
+ *   mi355cg_solve_many_info        LDS per workgroup, resident workgroups per CU and workspace bytes of such a batch
  *
  * Plain pointers and sizes only; no C++/torch types.  All host vectors are in the reference's
  * PACKED unknown order (bottom-right block row-major, then the upper block row-major;
@@ -433,6 +435,49 @@ int  mi355cg_get_xfold(mi355cg_handle h, int *depth, int *extra_buffers);
 int  mi355cg_set_solve_mode(mi355cg_handle h, int mode);
 int  mi355cg_get_solve_mode(mi355cg_handle h, int *mode, long long *onchip_launches_last_solve);
 int  mi355cg_onchip_plan(int n, int *threads, int *lds_bytes, int *elems_per_thread);
+
+/* Batched on-chip solves: nsys independent systems on the grid of one eligible handle (plain fp64, N <= 128, no preconditioner),
+ * ONE workgroup per system and one launch per chunk of iterations for all systems still iterating; a workgroup's LDS follows N,
+ * so small grids share a CU.  The systems differ in right-hand side, guess and diagonal shift.
+ * b, x: nsys vectors of mi355cg_size(h) doubles each, packed order, one after the other; out: nsys entries.
+ * sigma: nsys doubles, each finite and >= 0, or NULL = every system has the handle's current shift.  The diagonal of system s is
+ * A_diag - sigma_s, rounded once on the host, exactly as mi355cg_set_shift stores it.
+ * System s gets exactly the bits that mi355cg_set_shift(h, sigma_s); mi355cg_set_rhs(h, b_s); [_from: mi355cg_set_initial_guess(h,
+ * x0_s);] mi355cg_solve(h, params, NULL, NULL, stop_flag, &res); mi355cg_get_solution(h, x_s) gives on the same handle in either
+ * solve mode: all of x_s and iterations, converged, stop_reason, final_residual_norm, final_precision, r_norm2, initial_r_norm2.
+ * Every system follows the stop rule on its own numbers; one whose state says done costs an early-returning workgroup in later
+ * chunks.  Both rules and fixed_iterations work.  _from: x is in/out, a guess per system; a warm MSG_MAXNORM system has the
+ * start-state tests of mi355cg_solve applied and may end with 0 iterations, x = x0.  stop_flag is sampled by every workgroup once
+ * per iteration: when it is set, every system still iterating ends MI355CG_STOP_INTERRUPTED and the finished ones keep their
+ * results; a flag already set at the call interrupts all systems at 0 iterations.  final_error_norm is DBL_MAX; solve_seconds and
+ * loop_seconds are the whole batch's, the same in every entry.  The handle's own state is untouched: its b, x, r, shift, solve
+ * mode, pending guess and what the getters return; the call works whichever solve mode the handle is in.
+ * MI355CG_ERR_INVALID, before anything is allocated or written: a null pointer, nsys < 1 or > MI355CG_MANY_MAX, x overlapping b,
+ * an unknown rule, use_true_solution != 0 or diagnostics != 0 (note that mi355cg_default_params sets use_true_solution = 1), a
+ * sigma that is negative or not finite, and every handle mi355cg_set_solve_mode(h, MI355CG_SOLVE_ONCHIP) refuses for its kind or
+ * size (N > 128, CSR, F32_MIXED, slab / part handles), with that call's message.  MI355CG_ERR_STATE: the handle has a
+ * preconditioner (mi355cg_solve_batch is the preconditioned batch).
+ * _device: b_dev, x_dev and sigma_dev are in device memory of the handle's GPU.  The work runs on the handle's own stream: the
+ * caller makes them complete before the call, and the call returns after that stream is idle, x_dev written.
+ * Workspace: per system three packed vectors (x, r, one direction), two CG states, one slot of update partials, the diagonal and
+ * ||r0||_2 -- 24 mi355cg_size(h) + 456 bytes -- plus 8 bytes; the host entry points stage b and x on top (2 nsys packed
+ * vectors).  Allocated on first use, kept on the handle, grown when a larger nsys comes; freed by mi355cg_batch_release and
+ * mi355cg_destroy.  If it cannot be allocated: MI355CG_ERR_HIP, nothing leaked, the handle usable as before.
+ * mi355cg_solve_many_info (null out-pointers are skipped): the LDS bytes one workgroup of this grid takes; how many such
+ * workgroups the runtime's occupancy query lets reside on one CU (the REL_2NORM kernel); the device workspace bytes for nsys
+ * systems without the staging.  Refuses the handles the solves refuse.  Not a pure query when workgroups_per_cu is asked for: for
+ * images above 64 KB (N >= 90) it opts the kernel in to that much dynamic LDS (hipFuncSetAttribute), as the first solve would;
+ * the occupancy query needs it.                                                                                                 */
+#define MI355CG_MANY_MAX 65536
+int  mi355cg_solve_many(mi355cg_handle h, const mi355cg_params *params, int nsys, const double *b, double *x, const double *sigma,
+                        const volatile int *stop_flag, mi355cg_results *out);
+int  mi355cg_solve_many_from(mi355cg_handle h, const mi355cg_params *params, int nsys, const double *b, double *x, const double *sigma,
+                             const volatile int *stop_flag, mi355cg_results *out);
+int  mi355cg_solve_many_device(mi355cg_handle h, const mi355cg_params *params, int nsys, const double *b_dev, double *x_dev,
+                               const double *sigma_dev, const volatile int *stop_flag, mi355cg_results *out);
+int  mi355cg_solve_many_device_from(mi355cg_handle h, const mi355cg_params *params, int nsys, const double *b_dev, double *x_dev,
+                                    const double *sigma_dev, const volatile int *stop_flag, mi355cg_results *out);
+int  mi355cg_solve_many_info(mi355cg_handle h, int nsys, int *lds_bytes_per_workgroup, int *workgroups_per_cu, long long *workspace_bytes);
 
 /* ---- multi-GPU: one context per rank, one contiguous slab of grid rows per context --------------
  * The reference is single-process (no collectives exist in it); this is the scaling

@@ -461,6 +461,35 @@ public:
         if (results) *results = std::move(res);
         return x;
     }
+    // Extension: many independent small systems on this grid, one workgroup each and one launch per chunk of iterations for all of
+    // them (mi355cg_solve_many; plain CG, grids up to N = 128, no preconditioner).  System s solves (A - sigma[s] I) x = b[s] from
+    // x0[s]; an empty sigma means this system's own shift for all, an empty x0 cold starts.  x[s] and results[s] have the bits of
+    // mi355cg_set_shift; a single solve of b[s] (from x0[s]) on this system; the system's own state is left as it was.
+    // params.use_true_solution and params.diagnostics must be 0.  std::invalid_argument for an empty batch, more than
+    // MI355CG_MANY_MAX systems, a sigma or x0 of another length, a vector of the wrong size and what the library refuses as
+    // invalid; std::runtime_error on a system with a preconditioner.
+    std::vector<std::vector<double>> solveMany(const std::vector<std::vector<double>>& b, const mi355cg_params& params,
+                                               std::vector<mi355cg_results>* results = nullptr, const std::vector<double>& sigma = {},
+                                               const std::vector<std::vector<double>>& x0 = {}) {
+        if (b.empty() || b.size() > (size_t)MI355CG_MANY_MAX) throw std::invalid_argument("solveMany: a batch has 1 .. MI355CG_MANY_MAX systems");
+        const size_t n = rhs.size(), k = b.size();
+        if (!sigma.empty() && sigma.size() != k) throw std::invalid_argument("solveMany: sigma does not have one entry per system");
+        if (!x0.empty() && x0.size() != k) throw std::invalid_argument("solveMany: x0 does not have one vector per system");
+        std::vector<double> bp(n * k), xp(n * k);
+        for (size_t s = 0; s < k; ++s) {
+            if (b[s].size() != n || (!x0.empty() && x0[s].size() != n)) throw std::invalid_argument("solveMany: vector size does not match the system");
+            std::copy(b[s].begin(), b[s].end(), bp.begin() + (std::ptrdiff_t)(s * n));
+            if (!x0.empty()) std::copy(x0[s].begin(), x0[s].end(), xp.begin() + (std::ptrdiff_t)(s * n));
+        }
+        std::vector<mi355cg_results> res(k);
+        const double* sg = sigma.empty() ? nullptr : sigma.data();
+        mi355cg_compat::check(x0.empty() ? mi355cg_solve_many(ctx_->h, &params, (int)k, bp.data(), xp.data(), sg, nullptr, res.data())
+                                         : mi355cg_solve_many_from(ctx_->h, &params, (int)k, bp.data(), xp.data(), sg, nullptr, res.data()));
+        std::vector<std::vector<double>> x(k);
+        for (size_t s = 0; s < k; ++s) x[s].assign(xp.begin() + (std::ptrdiff_t)(s * n), xp.begin() + (std::ptrdiff_t)((s + 1) * n));
+        if (results) *results = std::move(res);
+        return x;
+    }
     void batchRelease() { mi355cg_compat::check(mi355cg_batch_release(ctx_->h)); }
     // Extension: the nev lowest eigenpairs of this system's operator by a block preconditioned iteration with one multigrid V-cycle
     // per vector and iteration (mi355cg_eigs; needs setPreconditioner with the fp64 cycle first).  lambda > 0 ascending with

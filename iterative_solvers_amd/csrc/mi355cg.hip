@@ -157,6 +157,21 @@ struct EigWs {
     Buf<double> stage;                  // packed vectors of the host entry point, cap x pk_len
 };
 
+// Workspace of the batched on-chip solves (mi355cg_solve_many*; kernels in onchip_kernels.h).  The device part
+// is what onchip_many_workspace_bytes (onchip_plan.h) counts: packed vectors system-major, the small per-system data, one counter.
+struct OnchipManyWs {
+    int cap = 0;                        // systems it holds
+    Buf<double> vec;                    // x of every system, then r, then the direction: 3 x cap x pk_len
+    Buf<double> small;                  // update partials (cap x FB_COUNT), diagonals (cap), ||r0||_2 (cap)
+    Buf<CgState> s, summary;            // cap each: the iteration-boundary states; what the host reads
+    Buf<int> done;                      // systems whose state says done (two words: the copies stay 8-byte)
+    Buf<CgState> summary_h;             // pinned copies
+    Buf<double> small_h;                // pinned: the layout of `small`
+    Buf<int> done_h;
+    Buf<double> stage;                  // packed vectors of the host entry points: b, then x
+    long long stage_cap = 0;            // systems it holds
+};
+
 }  // namespace
 
 struct mi355cg_ctx {
@@ -247,6 +262,7 @@ struct mi355cg_ctx {
     std::unique_ptr<MgHier> mg;         // opt-in preconditioner (mi355cg_set_preconditioner): mi355cg_solve runs solve_mg while set
     std::unique_ptr<MgBatchWs> batch;   // workspace of mi355cg_solve_batch*, nullptr until the first batch
     std::unique_ptr<EigWs> eig;         // workspace of mi355cg_eigs*, nullptr until the first eigen solve
+    std::unique_ptr<OnchipManyWs> many; // workspace of mi355cg_solve_many*, nullptr until the first such batch
     bool profiling = false;
     EventPool events;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pairs[2];
@@ -704,6 +720,19 @@ void prof_collect(mi355cg_ctx* c) {
 int fetch_state(mi355cg_ctx* c, hipStream_t st) {
     HIPCK(hipMemcpyAsync(c->summary_h, c->summary, sizeof(CgState), hipMemcpyDeviceToHost, st));
     HIPCK(hipMemcpyAsync(c->hist_h, c->hist, sizeof(HistEntry) * kHist, hipMemcpyDeviceToHost, st));
+    return MI355CG_OK;
+}
+// Wait for the context's stream.  With a stop flag the wait polls: the caller's flag lives in ordinary host memory, and while this
+// thread waits for a chunk it forwards the flag to the pinned word the kernels sample (mi355cg_solve and mi355cg_solve_many*).
+int wait_stream_forwarding_stop(mi355cg_ctx* c, const volatile int* stop_flag) {
+    if (!stop_flag) { HIPCK(hipStreamSynchronize(c->stream)); return MI355CG_OK; }
+    for (;;) {
+        if (*stop_flag) *c->stop_h = 1;
+        const hipError_t q = hipStreamQuery(c->stream);
+        if (q == hipSuccess) break;
+        if (q != hipErrorNotReady) HIPCK(q);
+        std::this_thread::yield();
+    }
     return MI355CG_OK;
 }
 // mi355cg_results::loop_seconds: two events around the iterations.  The caller waits (for the second event or for its stream)
@@ -1412,6 +1441,11 @@ void mg_batch_free(mi355cg_ctx* c) {
     if (!c->batch) return;
     if (c->stream) hipStreamSynchronize(c->stream);
     c->batch.reset();
+}
+void onchip_many_free(mi355cg_ctx* c) {                            // the workspace of mi355cg_solve_many*
+    if (!c->many) return;
+    if (c->stream) hipStreamSynchronize(c->stream);
+    c->many.reset();
 }
 
 // Vectors for nsys systems of the handle's hierarchy (and, stage_sys > 0, the host entry point's packed staging).  A workspace
@@ -2129,6 +2163,7 @@ void mi355cg_destroy(mi355cg_handle c) {
     if (c->stream) hipStreamSynchronize(c->stream);
     clear_graphs(c);
     mg_batch_free(c);
+    onchip_many_free(c);
     eig_free(c);
     c->events.destroy();
     for (hipEvent_t e : c->ev_loop) if (e) hipEventDestroy(e);
@@ -2331,17 +2366,7 @@ int mi355cg_solve(mi355cg_handle c, const mi355cg_params* prm, mi355cg_iter_cb c
     *c->stop_h = 0;
     c->stop_dev = nullptr;
     if (stop_flag) HIPCK(hipHostGetDevicePointer((void**)&c->stop_dev, c->stop_h, 0));
-    auto wait_stream = [&]() -> int {
-        if (!stop_flag) { HIPCK(hipStreamSynchronize(c->stream)); return MI355CG_OK; }
-        for (;;) {
-            if (*stop_flag) *c->stop_h = 1;
-            const hipError_t q = hipStreamQuery(c->stream);
-            if (q == hipSuccess) break;
-            if (q != hipErrorNotReady) HIPCK(q);
-            std::this_thread::yield();
-        }
-        return MI355CG_OK;
-    };
+    auto wait_stream = [&]() -> int { return wait_stream_forwarding_stop(c, stop_flag); };
     bool polled = false;
     auto poll = [&]() -> int {
         launch_check(c, cfg, c->stream, own_partB(c));
@@ -2892,9 +2917,222 @@ int mi355cg_solve_batch_from(mi355cg_handle c, const mi355cg_params* prm, int nr
 
 int mi355cg_batch_release(mi355cg_handle c) {
     if (!c) return fail(MI355CG_ERR_INVALID, "null handle");
-    if (!c->batch) return MI355CG_OK;
+    if (!c->batch && !c->many) return MI355CG_OK;
     HIPCK(hipSetDevice(c->device));
     mg_batch_free(c);
+    onchip_many_free(c);
+    return MI355CG_OK;
+}
+
+// ---- batched on-chip solves: many small systems, one workgroup each ---------------------------------------
+// what every entry point refuses before anything is allocated or written (sigma: checked by the caller, once it is in host memory)
+static int many_check(mi355cg_ctx* c, const mi355cg_params* prm, int nsys, const void* b, const void* x, const mi355cg_results* out) {
+    if (!c || !prm || !b || !x || !out) return fail(MI355CG_ERR_INVALID, "null argument");
+    if (nsys < 1 || nsys > MI355CG_MANY_MAX) return fail(MI355CG_ERR_INVALID, "a batch of on-chip solves has 1 .. %d systems, not %d", MI355CG_MANY_MAX, nsys);
+    if (prm->rule != MI355CG_RULE_MSG_MAXNORM && prm->rule != MI355CG_RULE_REL_2NORM) return fail(MI355CG_ERR_INVALID, "unknown rule %d", prm->rule);
+    if (prm->use_true_solution) return fail(MI355CG_ERR_INVALID, "a batch has no per-system exact solution: use_true_solution must be 0");
+    if (prm->diagnostics) return fail(MI355CG_ERR_INVALID, "a batch has no callbacks: diagnostics must be 0");
+    if (c->mg) return fail(MI355CG_ERR_STATE, "this handle has a preconditioner: mi355cg_solve_many is plain CG in one workgroup per system (mi355cg_solve_batch is the preconditioned batch)");
+    if (const char* why = onchip_refusal(c)) return fail(MI355CG_ERR_INVALID, "%s", why);
+    const size_t bytes = sizeof(double) * (size_t)c->gp.size * (size_t)nsys;
+    const uintptr_t bb = (uintptr_t)b, xb = (uintptr_t)x;
+    if (bb < xb + bytes && xb < bb + bytes) return fail(MI355CG_ERR_INVALID, "x overlaps b");
+    return MI355CG_OK;
+}
+static int many_check_sigma(const double* sigma, int nsys) {
+    for (int s = 0; sigma && s < nsys; ++s)
+        if (!std::isfinite(sigma[s]) || sigma[s] < 0.0)
+            return fail(MI355CG_ERR_INVALID, "shift %g of system %d rejected: sigma must be finite and >= 0 (A - sigma I stays negative definite)", sigma[s], s);
+    return MI355CG_OK;
+}
+
+// A workspace that is large enough is kept; a larger one replaces it only once it is complete, so a failure leaves the handle as it was.
+static int onchip_many_ensure(mi355cg_ctx* c, int nsys, bool stage) {
+    if (!c->many || c->many->cap < nsys) {
+        std::unique_ptr<OnchipManyWs> W(new OnchipManyWs());
+        auto failed = [&](const char* what) { return fail(MI355CG_ERR_HIP, "on-chip batch workspace for %d systems: %s allocation failed", nsys, what); };
+        constexpr int kSmall = FB_COUNT + 2;
+        static_assert(2 * sizeof(CgState) + kSmall * sizeof(double) == kOnchipManySysBytes && 2 * sizeof(int) == kOnchipManyFixedBytes, "onchip_plan.h: the workspace formula");
+        if (Buf<double>::device(W->vec, 3 * c->pk_len * nsys)) return failed("vector");
+        if (Buf<double>::device(W->small, (long long)kSmall * nsys)) return failed("partials");
+        if (Buf<CgState>::device(W->s, nsys) || Buf<CgState>::device(W->summary, nsys)) return failed("state");
+        if (Buf<int>::device(W->done, 2)) return failed("counter");
+        if (Buf<CgState>::pinned(W->summary_h, nsys) || Buf<double>::pinned(W->small_h, (long long)kSmall * nsys) || Buf<int>::pinned(W->done_h, 2)) return failed("pinned copy");
+        W->cap = nsys;
+        if (c->many) { W->stage = std::move(c->many->stage); W->stage_cap = c->many->stage_cap; }
+        onchip_many_free(c);
+        c->many = std::move(W);
+    }
+    OnchipManyWs* W = c->many.get();
+    if (stage && nsys > W->stage_cap) {
+        HIPCK(hipStreamSynchronize(c->stream));                    // nothing in flight reads the buffer that is replaced
+        if (Buf<double>::device(W->stage, 2 * c->pk_len * nsys))
+            return fail(MI355CG_ERR_HIP, "on-chip batch staging for %d packed vectors: allocation failed", 2 * nsys);
+        W->stage_cap = nsys;
+    }
+    return MI355CG_OK;
+}
+
+static const void* onchip_many_kernel(int elems, bool msg) {
+#define MI355CG_OCM(E) return msg ? (const void*)&k_onchip_many<E, true> : (const void*)&k_onchip_many<E, false>
+    switch (elems) {
+        case 1: MI355CG_OCM(1);
+        case 2: MI355CG_OCM(2);
+        case 4: MI355CG_OCM(4);
+        case 8: MI355CG_OCM(8);
+        case 16: MI355CG_OCM(16);
+        default: MI355CG_OCM(kOnchipMaxElems);
+    }
+#undef MI355CG_OCM
+}
+// Dynamic LDS above 64 KB is opt-in per kernel.
+static int onchip_many_allow_lds(const void* kernel, int lds) {
+    if (lds > 64 * 1024) HIPCK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    return MI355CG_OK;
+}
+
+// b_dev, x_dev: nsys packed vectors each in device memory (x_dev: the guesses when warm); sigma: host memory or NULL, checked.
+static int solve_many(mi355cg_ctx* c, const mi355cg_params* prm, int nsys, const double* b_dev, double* x_dev, const double* sigma,
+                      const volatile int* stop_flag, mi355cg_results* out, bool warm) {
+    const auto t0 = std::chrono::steady_clock::now();
+    OnchipManyWs* W = c->many.get();
+    const OnchipPlan pl = onchip_plan(c->gp.n);
+    const bool msg = prm->rule == MI355CG_RULE_MSG_MAXNORM;
+    const IterCfg cfg = make_cfg(prm);
+    if (c->pk_len != pl.unknowns) return fail(MI355CG_ERR_STATE, "on-chip batch: the handle packs %lld unknowns, the plan of N = %d has %d", c->pk_len, pl.n, pl.unknowns);
+    const long long U = pl.unknowns, count = U * nsys;       // ONE stride for the caller's packed vectors and the workspace's
+    const int lds = onchip_many_lds_bytes(pl.n);
+    double* partB = W->small; double* diag = partB + (long long)FB_COUNT * nsys; double* norm0 = diag + nsys;
+    double* diag_h = W->small_h + (long long)FB_COUNT * nsys; const double* norm0_h = diag_h + nsys;
+
+    for (int s = 0; s < nsys; ++s) diag_h[s] = sigma ? c->gp.A - sigma[s] : c->g.A;          // mi355cg_set_shift's rounding
+    HIPCK(hipMemcpyAsync(diag, diag_h, sizeof(double) * nsys, hipMemcpyHostToDevice, c->stream));
+    HIPCK(hipMemsetAsync(W->done, 0, sizeof(int) * 2, c->stream));
+    W->done_h[0] = 0;
+
+    OnchipManyInitArgs ia{};
+    ia.pl = pl; ia.xk = c->g.xk; ia.yk = c->g.yk; ia.diag = diag; ia.b = b_dev; ia.x0 = warm ? x_dev : nullptr;
+    ia.x = W->vec; ia.r = W->vec + count; ia.p = W->vec + 2 * count; ia.stride = U;
+    ia.partB = partB; ia.s = W->s; ia.summary = W->summary; ia.norm0 = norm0; ia.done_count = W->done; ia.rp = cfg.rp;
+    const void* k_init = warm ? (const void*)&k_onchip_many_init<true> : (const void*)&k_onchip_many_init<false>;
+    if (int rc = onchip_many_allow_lds(k_init, lds)) return rc;
+    { void* args[] = {&ia}; HIPCK(hipLaunchKernel(k_init, dim3(nsys), dim3(pl.threads), args, lds, c->stream)); }
+
+    // the stop request: sampled by every workgroup once per iteration, forwarded by this thread while it waits (as in mi355cg_solve)
+    *c->stop_h = 0;
+    int* stop_dev = nullptr;
+    if (stop_flag) HIPCK(hipHostGetDevicePointer((void**)&stop_dev, c->stop_h, 0));
+    auto wait_stream = [&]() -> int { return wait_stream_forwarding_stop(c, stop_flag); };
+    bool polled = false;
+    auto poll = [&]() -> int {                                     // one word per chunk: how many systems are done
+        HIPCK(hipMemcpyAsync(W->done_h, W->done, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        polled = true;
+        return wait_stream();
+    };
+    if (msg && warm) if (int rc = poll()) return rc;               // the start states were tested (k_onchip_many_init)
+    if (int rc = loop_timer_begin(c, c->stream)) return rc;
+
+    OnchipManyArgs a{};
+    a.pl = pl; a.xk = c->g.xk; a.yk = c->g.yk; a.diag = diag;
+    a.x = ia.x; a.r = ia.r; a.p = ia.p; a.stride = U;
+    a.partB = partB; a.s = W->s; a.summary = W->summary; a.done_count = W->done; a.rp = cfg.rp; a.stop_req = stop_dev;
+    const void* k_chunk = onchip_many_kernel(pl.elems, msg);
+    if (int rc = onchip_many_allow_lds(k_chunk, lds)) return rc;
+    const int sync_every = default_sync_every(prm, msg);
+    int it_done = 0;
+    bool interrupted = false;
+    while (W->done_h[0] < nsys) {
+        if (stop_flag && *stop_flag) { interrupted = true; break; }
+        if (it_done > prm->max_iterations) return fail(MI355CG_ERR_HIP, "on-chip batch: %d of %d systems still iterate past the iteration cap", nsys - W->done_h[0], nsys);
+        a.m = chunk_len(prm, msg, sync_every, it_done, false);
+        { void* args[] = {&a}; HIPCK(hipLaunchKernel(k_chunk, dim3(nsys), dim3(pl.threads), args, lds, c->stream)); }
+        if (int rc = poll()) return rc;
+        it_done += a.m;
+    }
+    if (int rc = loop_timer_end(c, c->stream)) return rc;
+    // a batch stopped before anything was polled reports the empty state, as a single solve does
+    if (polled) {
+        HIPCK(hipMemcpyAsync(W->summary_h, W->summary, sizeof(CgState) * nsys, hipMemcpyDeviceToHost, c->stream));
+        if (warm) HIPCK(hipMemcpyAsync(W->small_h + (long long)(FB_COUNT + 1) * nsys, norm0, sizeof(double) * nsys, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCK(hipMemcpyAsync(x_dev, ia.x, sizeof(double) * count, hipMemcpyDeviceToDevice, c->stream));
+    HIPCK(hipStreamSynchronize(c->stream));
+    HIPCK(hipEventSynchronize(c->ev_loop[1]));
+    const double loop_seconds = loop_timer_seconds(c);
+    for (int s = 0; s < nsys; ++s) {
+        const CgState fin = polled ? W->summary_h[s] : CgState{};
+        const bool intr = (interrupted && !fin.done) || (fin.done && fin.reason == MI355CG_STOP_INTERRUPTED);
+        out[s] = make_results(fin, intr, false, warm && polled ? norm0_h[s] : fin.r0norm);
+        out[s].loop_seconds = loop_seconds;
+    }
+    const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    for (int s = 0; s < nsys; ++s) out[s].solve_seconds = secs;
+    return MI355CG_OK;
+}
+
+static int solve_many_device(mi355cg_ctx* c, const mi355cg_params* prm, int nsys, const double* b_dev, double* x_dev, const double* sigma_dev,
+                             const volatile int* stop_flag, mi355cg_results* out, bool warm) {
+    if (int rc = many_check(c, prm, nsys, b_dev, x_dev, out)) return rc;
+    HIPCK(hipSetDevice(c->device));
+    std::vector<double> sigma;
+    if (sigma_dev) {
+        sigma.resize(nsys);
+        HIPCK(hipMemcpy(sigma.data(), sigma_dev, sizeof(double) * nsys, hipMemcpyDeviceToHost));
+        if (int rc = many_check_sigma(sigma.data(), nsys)) return rc;
+    }
+    if (int rc = onchip_many_ensure(c, nsys, false)) return rc;
+    return solve_many(c, prm, nsys, b_dev, x_dev, sigma_dev ? sigma.data() : nullptr, stop_flag, out, warm);
+}
+static int solve_many_host(mi355cg_ctx* c, const mi355cg_params* prm, int nsys, const double* b, double* x, const double* sigma,
+                           const volatile int* stop_flag, mi355cg_results* out, bool warm) {
+    if (int rc = many_check(c, prm, nsys, b, x, out)) return rc;
+    if (int rc = many_check_sigma(sigma, nsys)) return rc;
+    HIPCK(hipSetDevice(c->device));
+    if (int rc = onchip_many_ensure(c, nsys, true)) return rc;
+    const size_t count = (size_t)c->pk_len * (size_t)nsys, bytes = sizeof(double) * count;
+    double* stage = c->many->stage;                                // b in the first half, the guesses / the solutions in the second
+    HIPCK(hipMemcpyAsync(stage, b, bytes, hipMemcpyHostToDevice, c->stream));
+    if (warm) HIPCK(hipMemcpyAsync(stage + count, x, bytes, hipMemcpyHostToDevice, c->stream));
+    if (int rc = solve_many(c, prm, nsys, stage, stage + count, sigma, stop_flag, out, warm)) return rc;
+    HIPCK(hipMemcpyAsync(x, stage + count, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(hipStreamSynchronize(c->stream));
+    return MI355CG_OK;
+}
+
+int mi355cg_solve_many(mi355cg_handle c, const mi355cg_params* prm, int nsys, const double* b, double* x, const double* sigma,
+                       const volatile int* stop_flag, mi355cg_results* out) {
+    return solve_many_host(c, prm, nsys, b, x, sigma, stop_flag, out, false);
+}
+int mi355cg_solve_many_from(mi355cg_handle c, const mi355cg_params* prm, int nsys, const double* b, double* x, const double* sigma,
+                            const volatile int* stop_flag, mi355cg_results* out) {
+    return solve_many_host(c, prm, nsys, b, x, sigma, stop_flag, out, true);
+}
+int mi355cg_solve_many_device(mi355cg_handle c, const mi355cg_params* prm, int nsys, const double* b_dev, double* x_dev, const double* sigma_dev,
+                              const volatile int* stop_flag, mi355cg_results* out) {
+    return solve_many_device(c, prm, nsys, b_dev, x_dev, sigma_dev, stop_flag, out, false);
+}
+int mi355cg_solve_many_device_from(mi355cg_handle c, const mi355cg_params* prm, int nsys, const double* b_dev, double* x_dev, const double* sigma_dev,
+                                   const volatile int* stop_flag, mi355cg_results* out) {
+    return solve_many_device(c, prm, nsys, b_dev, x_dev, sigma_dev, stop_flag, out, true);
+}
+
+int mi355cg_solve_many_info(mi355cg_handle c, int nsys, int* lds_bytes_per_workgroup, int* workgroups_per_cu, long long* workspace_bytes) {
+    if (!c) return fail(MI355CG_ERR_INVALID, "null handle");
+    if (nsys < 1 || nsys > MI355CG_MANY_MAX) return fail(MI355CG_ERR_INVALID, "a batch of on-chip solves has 1 .. %d systems, not %d", MI355CG_MANY_MAX, nsys);
+    if (c->mg) return fail(MI355CG_ERR_STATE, "this handle has a preconditioner: mi355cg_solve_many is plain CG in one workgroup per system (mi355cg_solve_batch is the preconditioned batch)");
+    if (const char* why = onchip_refusal(c)) return fail(MI355CG_ERR_INVALID, "%s", why);
+    const OnchipPlan pl = onchip_plan(c->gp.n);
+    const int lds = onchip_many_lds_bytes(pl.n);
+    if (lds_bytes_per_workgroup) *lds_bytes_per_workgroup = lds;
+    if (workspace_bytes) *workspace_bytes = onchip_many_workspace_bytes(pl.n, nsys);
+    if (workgroups_per_cu) {
+        HIPCK(hipSetDevice(c->device));
+        const void* k = onchip_many_kernel(pl.elems, false);
+        if (int rc = onchip_many_allow_lds(k, lds)) return rc;
+        int nb = 0;
+        HIPCK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, pl.threads, (size_t)lds));
+        *workgroups_per_cu = nb;
+    }
     return MI355CG_OK;
 }
 

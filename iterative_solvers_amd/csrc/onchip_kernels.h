@@ -14,6 +14,10 @@
 // partials in partB (any number of slots at entry, ONE slot at exit).  Every element-wise expression is that path's, in its order,
 // decisions come from decide_after_update and the state is written by write_state_after_decision; the inner products are double-double
 // pairs, whose rounded value does not depend on the order of summation.  Hence the same bits as k_stencil + k_update_st, step by step.
+//
+// The iteration is written once, in oc_chunk.  k_onchip runs it on the handle's own vectors; k_onchip_many on
+// system blockIdx.x of a batch of independent systems of one grid -- own right-hand side, guess and diagonal each --, with an LDS
+// allocation that follows N, so that small grids share a CU; k_onchip_many_init starts all systems of a batch on the device.
 #pragma once
 #include "cg_kernels.h"
 #include "onchip_plan.h"
@@ -90,30 +94,120 @@ __device__ inline void oc_publish_b(OcSumsB v, double* scr) {
     __syncthreads();
 }
 
+// ---- what the chunk body reads of the system it iterates on ---------------------------------------------------------------------
+// k_onchip: the handle's vectors in storage layout, its direction ring, its history ring, the diagonal of its Geom.
+struct OcLds { double* img; double* scrA; double* scrB; CgState* st; };
+struct OcOne {
+    static constexpr bool kMany = false;
+    // the image of the largest grid, statically: one workgroup per CU whatever N is
+    __device__ static __forceinline__ OcLds lds(int /*cells*/) {
+        __shared__ double img[kOnchipMaxCells];
+        __shared__ double scrA[kOcWaves * kOcFieldsA], scrB[kOcWaves * kOcFieldsB];
+        __shared__ CgState st;
+        return OcLds{img, scrA, scrB, &st};
+    }
+    typedef OnchipArgs Args;
+    // (accessors over the arguments, not a copy of them in a struct of its own: that cost k_onchip<24, false> five words of scratch)
+    __device__ static double* x(const Args& a) { return a.x; }
+    __device__ static double* r(const Args& a) { return a.r; }
+    __device__ static const double* u(const Args& a) { return a.u; }
+    __device__ static double* partB(const Args& a) { return a.partB; }
+    __device__ static int nB(const Args& a) { return a.nB; }
+    __device__ static int strideB(const Args& a) { return a.strideB; }
+    __device__ static CgState* s(const Args& a) { return a.s; }
+    __device__ static HistEntry* hist(const Args& a) { return a.hist; }
+    __device__ static double cA(const Args& a) { return a.g.A; }
+    __device__ static double cxk(const Args& a) { return a.g.xk; }
+    __device__ static double cyk(const Args& a) { return a.g.yk; }
+    __device__ static int has_u(const OnchipArgs& a) { return a.has_u; }
+    __device__ static int u_always(const OnchipArgs& a) { return a.u_always; }
+    __device__ static int every(const OnchipArgs& a) { return a.every; }
+    __device__ static double* dir(const OnchipArgs& a, int it) { return a.p[it % a.xsteps]; }
+    __device__ static long long off(const OnchipArgs& a, int /*i*/, int xx, int yy) { return (long long)(row_off(a.g, yy) + xx - a.g.base0); }
+    __device__ static void finished(const Args&) {}
+};
+// k_onchip_many: system blockIdx.x of a batch.  Vectors in PACKED order (unknown i of onchip_plan.h at i: the
+// order of the host interface), one direction buffer, one slot of partials, no history ring, the diagonal from a device array.
+struct OnchipManyArgs {
+    OnchipPlan pl;
+    double xk, yk;
+    const double* diag;                  // nsys: A_diag - sigma_s, rounded on the host
+    double* x; double* r; double* p;     // nsys vectors of `stride` doubles each
+    long long stride;
+    double* partB;                       // nsys x FB_COUNT (field-major with stride 1)
+    CgState* s;                          // nsys: the states at the iteration boundary
+    CgState* summary;                    // nsys: what the end-of-chunk check of a single solve leaves for the host
+    int* done_count;                     // systems whose state says done
+    RuleParams rp;
+    int m;
+    const int* stop_req;
+};
+struct OcMany {
+    static constexpr bool kMany = true;
+    typedef OnchipManyArgs Args;
+    // All LDS is the dynamic region of onchip_many_lds_bytes(n) bytes, so that small grids share a CU: the side data at fixed
+    // offsets, then the image of THIS grid.
+    __device__ static __forceinline__ OcLds lds(int /*cells*/) {
+        extern __shared__ __attribute__((aligned(16))) char oc_dyn_lds[];
+        double* side = reinterpret_cast<double*>(oc_dyn_lds);
+        return OcLds{reinterpret_cast<double*>(oc_dyn_lds + kOnchipSideBytes), side, side + kOcWaves * kOcFieldsA,
+                     reinterpret_cast<CgState*>(side + kOcWaves * (kOcFieldsA + kOcFieldsB))};
+    }
+    __device__ static long long sys() { return blockIdx.x; }
+    __device__ static double* x(const Args& a) { return a.x + sys() * a.stride; }
+    __device__ static double* r(const Args& a) { return a.r + sys() * a.stride; }
+    __device__ static const double* u(const Args&) { return nullptr; }
+    __device__ static double* partB(const Args& a) { return a.partB + sys() * FB_COUNT; }
+    __device__ static int nB(const Args&) { return 1; }
+    __device__ static int strideB(const Args&) { return 1; }
+    __device__ static CgState* s(const Args& a) { return a.s + sys(); }
+    __device__ static CgState* summary(const Args& a) { return a.summary + sys(); }
+    __device__ static HistEntry* hist(const Args&) { return nullptr; }
+    __device__ static double cA(const Args& a) { return a.diag[sys()]; }
+    __device__ static double cxk(const Args& a) { return a.xk; }
+    __device__ static double cyk(const Args& a) { return a.yk; }
+    __device__ static int has_u(const OnchipManyArgs&) { return 0; }
+    __device__ static int u_always(const OnchipManyArgs&) { return 0; }
+    __device__ static int every(const OnchipManyArgs&) { return 0; }
+    __device__ static double* dir(const OnchipManyArgs& a, int) { return a.p + sys() * a.stride; }
+    __device__ static long long off(const OnchipManyArgs&, int i, int, int) { return i; }
+    __device__ static void finished(const Args& a) { atomicAdd(a.done_count, 1); }       // thread 0, once per system: the launch in which its state turns done
+};
+
+// The iteration body, written once.  Its LDS is the system type's (Sys::lds): img, pl.cells doubles; scrA, scrB, kOcWaves x
+// kOcFieldsA / kOcFieldsB doubles; st, the CG state, in LDS while the chunk runs.  ONE object: write_state_after_decision is handed
+// it as source and destination, so its copy is a copy onto itself and only the fields it sets are stored (two objects cost 46
+// registers per copy, in mid-loop).
 // E: slots per thread (OnchipPlan::elems).  MSG: the max-norm rule -- x and its norms every iteration, (r, z) reduced, u in registers.
-template <int E, bool MSG>
-__global__ __launch_bounds__(kOnchipMaxThreads) void k_onchip(const OnchipArgs a) {
-    __shared__ double img[kOnchipMaxCells];
-    __shared__ double scrA[kOcWaves * kOcFieldsA], scrB[kOcWaves * kOcFieldsB];
-    // The CG state, in LDS while the chunk runs.  ONE object: write_state_after_decision is handed it as source and destination, so
-    // its copy is a copy onto itself and only the fields it sets are stored (two objects cost 46 registers per copy, in mid-loop).
-    __shared__ CgState st;
+// Sys::kMany: the chunk also takes the closing decision a single solve leaves to k_check, per system: the state after the last update
+// goes to y.s as it is, the decided state to y.summary, and to y.s as well if it says done (what the next chunk's first decision
+// would write: the same numbers decided again).
+template <int E, bool MSG, class Sys>
+__device__ __forceinline__ void oc_chunk(const typename Sys::Args a) {
+    // (The kernel's arguments by value and as a whole, untouched by the kernel itself: the body is optimized before it is inlined.
+    // Behind a reference every load of an argument is a load that any store may have changed -- 60 more registers at E = 16, and
+    // scratch; and a kernel that reads single fields has its copy cut up, after which the body's copy stays in scratch.)
+    const int has_u = Sys::has_u(a), u_always = Sys::u_always(a), every = Sys::every(a);
+    const OnchipPlan& pl = a.pl;
+    const RuleParams& rp = a.rp;
+    const int m = a.m;
+    const int* const stop_req = a.stop_req;
+    const OcLds lds = Sys::lds(pl.cells);
+    double* const img = lds.img; double* const scrA = lds.scrA; double* const scrB = lds.scrB; CgState* const st = lds.st;
     static_assert(sizeof(CgState) % sizeof(double) == 0, "the state travels as doubles");
     constexpr int kStateWords = (int)(sizeof(CgState) / sizeof(double));
-    const Geom& g = a.g;
-    const OnchipPlan& pl = a.pl;
     const int t = threadIdx.x, T = blockDim.x, nwaves = T / kWave;
-    StateLite s = load_state_lite(a.s);
+    StateLite s = load_state_lite(Sys::s(a));
     if (s.done) return;                                // the state already says done: x, r, the state and the partials stay
-    const bool use_u = MSG && a.has_u;
+    const bool use_u = MSG && has_u;
 
     for (int i = t; i < pl.cells; i += T) img[i] = 0.0;
-    if (t < kStateWords) reinterpret_cast<double*>(&st)[t] = reinterpret_cast<const double*>(a.s)[t];      // (thread 0 reads it behind two barriers)
+    if (t < kStateWords) reinterpret_cast<double*>(st)[t] = reinterpret_cast<const double*>(Sys::s(a))[t];      // (thread 0 reads it behind two barriers)
     // the partials the launch before left (the init pass: one slot per workgroup of it; an on-chip chunk: one slot)
     OcSumsB v0{dd_zero(), dd_zero(), dd_zero(), 0.0, 0.0, 0.0, 0.0};
-    for (int i = t; i < a.nB; i += T) {
-        const double* q = a.partB + i;
-        const int sb = a.strideB;
+    for (int i = t; i < Sys::nB(a); i += T) {
+        const double* q = Sys::partB(a) + i;
+        const int sb = Sys::strideB(a);
         v0.rr = dd_add(v0.rr, dd{q[FB_RR * sb], q[(FB_RR + FB_LO) * sb]});
         v0.d2 = dd_add(v0.d2, dd{q[FB_D2 * sb], q[(FB_D2 + FB_LO) * sb]});
         v0.e2 = dd_add(v0.e2, dd{q[FB_E2 * sb], q[(FB_E2 + FB_LO) * sb]});
@@ -121,13 +215,13 @@ __global__ __launch_bounds__(kOnchipMaxThreads) void k_onchip(const OnchipArgs a
     }
     __syncthreads();                                   // the image is zero everywhere before the owners fill their cells
 
-    // this thread's unknowns: image cell, x, r [, u] from the storage layout into registers, the direction into the image
-    auto storage_off = [&](int i) { int xx, yy; onchip_node(pl, i, &xx, &yy); return (long long)(row_off(g, yy) + xx - g.base0); };
+    // this thread's unknowns: image cell, x, r [, u] from the system's vectors into registers, the direction into the image
+    auto storage_off = [&](int i) { int xx, yy; onchip_node(pl, i, &xx, &yy); return Sys::off(a, i, xx, yy); };
     unsigned cell2[(E + 1) / 2] = {};                   // image cells, two 16-bit indices per register (kOnchipMaxCells < 65536)
     static_assert(kOnchipMaxCells <= 0x10000, "a cell index fits in 16 bits");
     double x[E], r[E], u[MSG ? E : 1];
     int cnt = 0;                                       // valid slots: a prefix
-    const double* pin = a.p[s.it % a.xsteps];
+    const double* pin = Sys::dir(a, s.it);
 #pragma unroll
     for (int k = 0; k < E; ++k) {
         const int i = onchip_owned(pl, t, k);
@@ -138,18 +232,18 @@ __global__ __launch_bounds__(kOnchipMaxThreads) void k_onchip(const OnchipArgs a
             onchip_node(pl, i, &xx, &yy);
             const int c = onchip_cell(pl, xx, yy);
             cell2[k / 2] |= (unsigned)c << (16 * (k & 1));
-            const long long off = row_off(g, yy) + xx - g.base0;
-            x[k] = a.x[off]; r[k] = a.r[off]; img[c] = pin[off];
-            if (use_u) u[k] = a.u[off];
+            const long long off = Sys::off(a, i, xx, yy);
+            x[k] = Sys::x(a)[off]; r[k] = Sys::r(a)[off]; img[c] = pin[off];
+            if (use_u) u[k] = Sys::u(a)[off];
             cnt = k + 1;
         }
     }
     oc_publish_b<true>(v0, scrB);
     // what the next decision needs of the totals: (r, r), and under MSG the three max-norms
     double rr, rmax = 0, dmax = 0, emax = 0;
-    { const OcSumsB tot = oc_combine_b<MSG>(scrB, nwaves); rr = dd_value(tot.rr); if (MSG) { rmax = tot.rmax; dmax = tot.dmax; if (a.rp.use_u) emax = tot.emax; } }
+    { const OcSumsB tot = oc_combine_b<MSG>(scrB, nwaves); rr = dd_value(tot.rr); if (MSG) { rmax = tot.rmax; dmax = tot.dmax; if (rp.use_u) emax = tot.emax; } }
 
-    const double cA = g.A, cxk = g.xk, cyk = g.yk;
+    const double cA = Sys::cA(a), cxk = Sys::cxk(a), cyk = Sys::cyk(a);
     const int pitch = pl.pitch;
     // A z at an owned cell: the stencil launch's formula, verbatim (every owned node is interior: nothing to mask)
     auto apply_at = [&](int c, double cc) {
@@ -165,15 +259,16 @@ __global__ __launch_bounds__(kOnchipMaxThreads) void k_onchip(const OnchipArgs a
     // every slot (and the storage offsets the exit needs) in registers across the whole iteration loop, and spills them.
     auto own_cell = [&](int k) { unsigned c2 = cell2[k / 2]; asm volatile("" : "+v"(c2)); return (int)((c2 >> (16 * (k & 1))) & 0xffffu); };
     int ran = 0;
-    for (int it_k = 0; it_k < a.m; ++it_k) {
+    bool decided = false;                              // the loop ended on a decision that says done
+    for (int it_k = 0; it_k < m; ++it_k) {
         // the stop request (a pinned HOST word): one lane asks now and hands the answer to the update reduction
         double stop_word = 0.0;
-        if (t == 0 && a.stop_req) stop_word = __hip_atomic_load(a.stop_req, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0 ? 1.0 : 0.0;
+        if (t == 0 && stop_req) stop_word = __hip_atomic_load(stop_req, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0 ? 1.0 : 0.0;
 
         // ---- the stencil launch's prologue: decide from the update partials (reduce_and_decide without diagnostics)
-        const Decision d = decide_after_update(s, a.rp, rr, rmax, dmax, emax, 0.0, 0.0);
-        if (t == 0) write_state_after_decision<true>(&st, a.hist, &st, s, d);
-        if (d.done) break;
+        const Decision d = decide_after_update(s, rp, rr, rmax, dmax, emax, 0.0, 0.0);
+        if (t == 0) write_state_after_decision<true>(st, Sys::hist(a), st, s, d);
+        if (d.done) { if constexpr (Sys::kMany) decided = true; break; }
         const double beta = d.beta;
 
         // ---- phase A': z = r + beta*z, (Az, z) [and (r, z)]
@@ -199,7 +294,7 @@ __global__ __launch_bounds__(kOnchipMaxThreads) void k_onchip(const OnchipArgs a
 
         // ---- phase B: r -= alpha*Az (A z rebuilt from the image: same operands, same order), x += alpha*z, the norms
         const int it_new = s.it + 1;
-        const bool u_now = use_u && (a.u_always || it_new == 1 || (a.every > 0 && it_new % a.every == 0));
+        const bool u_now = use_u && (u_always || it_new == 1 || (every > 0 && it_new % every == 0));
         OcSumsB vb{dd_zero(), dd_zero(), dd_zero(), 0.0, 0.0, 0.0, stop_word};
 #pragma unroll
         for (int k = 0; k < E; ++k) if (k < cnt) {
@@ -225,9 +320,9 @@ __global__ __launch_bounds__(kOnchipMaxThreads) void k_onchip(const OnchipArgs a
         }
         oc_publish_b<MSG>(vb, scrB);                                                                  // barrier 3
         int stop;
-        { const OcSumsB tot = oc_combine_b<MSG>(scrB, nwaves); rr = dd_value(tot.rr); stop = tot.stop != 0.0; if (MSG) { rmax = tot.rmax; dmax = tot.dmax; if (a.rp.use_u) emax = tot.emax; } }
+        { const OcSumsB tot = oc_combine_b<MSG>(scrB, nwaves); rr = dd_value(tot.rr); stop = tot.stop != 0.0; if (MSG) { rmax = tot.rmax; dmax = tot.dmax; if (rp.use_u) emax = tot.emax; } }
         if (t == 0) {                                              // what the update launch writes
-            CgState* o = &st;
+            CgState* o = st;
             o->it = it_new; o->first = 0; o->alpha = alpha_d; o->rz = rz; o->alpha_hist[it_new & (kRing - 1)] = alpha_d;
             o->stop = stop;                                        // the reference tests its flag once per iteration (msg_solver.cpp:82-87)
         }
@@ -238,25 +333,137 @@ __global__ __launch_bounds__(kOnchipMaxThreads) void k_onchip(const OnchipArgs a
 
     // ---- exit: the iteration-boundary state, for the host, the next chunk or the two-launch path
     if (ran > 0) {
-        double* pout = a.p[s.it % a.xsteps];
+        double* pout = Sys::dir(a, s.it);
 #pragma unroll
         for (int k = 0; k < E; ++k) if (k < cnt) {
             int i = k * T + t;
             asm volatile("" : "+v"(i));                            // recomputed here, not carried through the loop
             const long long off = storage_off(i);
-            a.x[off] = x[k]; a.r[off] = r[k]; pout[off] = img[own_cell(k)];
+            Sys::x(a)[off] = x[k]; Sys::r(a)[off] = r[k]; pout[off] = img[own_cell(k)];
         }
     }
     __syncthreads();                                               // thread 0's last state stores
-    if (t < kStateWords) reinterpret_cast<double*>(a.s)[t] = reinterpret_cast<const double*>(&st)[t];
+    if (t < kStateWords) reinterpret_cast<double*>(Sys::s(a))[t] = reinterpret_cast<const double*>(st)[t];
     if (t == 0) {
         // the partials of the last update (no update ran: of the launch before), all fields, as one slot
         const OcSumsB tot = (MSG || ran == 0) ? oc_combine_b<true>(scrB, nwaves) : oc_combine_b<false>(scrB, nwaves);
-        const int sb = a.strideB;
-        a.partB[FB_RR * sb] = tot.rr.hi; a.partB[(FB_RR + FB_LO) * sb] = tot.rr.lo;
-        a.partB[FB_D2 * sb] = tot.d2.hi; a.partB[(FB_D2 + FB_LO) * sb] = tot.d2.lo;
-        a.partB[FB_E2 * sb] = tot.e2.hi; a.partB[(FB_E2 + FB_LO) * sb] = tot.e2.lo;
-        a.partB[FB_RMAX * sb] = tot.rmax; a.partB[FB_DMAX * sb] = tot.dmax; a.partB[FB_EMAX * sb] = tot.emax;
+        const int sb = Sys::strideB(a);
+        Sys::partB(a)[FB_RR * sb] = tot.rr.hi; Sys::partB(a)[(FB_RR + FB_LO) * sb] = tot.rr.lo;
+        Sys::partB(a)[FB_D2 * sb] = tot.d2.hi; Sys::partB(a)[(FB_D2 + FB_LO) * sb] = tot.d2.lo;
+        Sys::partB(a)[FB_E2 * sb] = tot.e2.hi; Sys::partB(a)[(FB_E2 + FB_LO) * sb] = tot.e2.lo;
+        Sys::partB(a)[FB_RMAX * sb] = tot.rmax; Sys::partB(a)[FB_DMAX * sb] = tot.dmax; Sys::partB(a)[FB_EMAX * sb] = tot.emax;
+    }
+    if constexpr (Sys::kMany) {
+        // ---- the closing decision (k_check's: the same numbers the next chunk's first decision would see, without advancing)
+        bool done_now = decided;
+        if (!decided) {
+            // k_check reduces the max-norms and (dx, dx) of the last update's partials under either rule (REL_2NORM: |r| is there, the
+            // x norms are zeros); scrB still holds them: m >= 1 iterations ran
+            const OcSumsB tot = oc_combine_b<MSG>(scrB, nwaves);
+            const Decision d = decide_after_update(s, rp, dd_value(tot.rr), tot.rmax, tot.dmax, 0.0, dd_value(tot.d2), 0.0);
+            __syncthreads();                                       // the copy of the undecided state above has read st
+            if (t == 0) write_state_after_decision<true>(st, nullptr, st, s, d);
+            __syncthreads();
+            done_now = d.done != 0;
+        }
+        if (t < kStateWords) {
+            const double w = reinterpret_cast<const double*>(st)[t];
+            reinterpret_cast<double*>(Sys::summary(a))[t] = w;
+            if (done_now) reinterpret_cast<double*>(Sys::s(a))[t] = w;   // the same lanes that stored the undecided words: in program order
+        }
+        if (t == 0 && done_now) Sys::finished(a);
+    }
+}
+
+template <int E, bool MSG>
+__global__ __launch_bounds__(kOnchipMaxThreads) void k_onchip(const OnchipArgs a) {
+    oc_chunk<E, MSG, OcOne>(a);
+}
+
+// ---- many systems, one workgroup each ---------------------------------------------------------------------
+static_assert(sizeof(CgState) <= 256 && 2 * (int)sizeof(CgState) + (FB_COUNT + 2) * 8 == kOnchipManySysBytes, "onchip_plan.h: a system's share of the batch workspace");
+template <int E, bool MSG>
+__global__ __launch_bounds__(kOnchipMaxThreads) void k_onchip_many(const OnchipManyArgs a) {
+    oc_chunk<E, MSG, OcMany>(a);
+}
+
+// The start of a batch, one workgroup (of the plan's size) per system: what k_init_fresh, or launch_apply + k_init_guess +
+// k_guess_state, leave for a single solve.  Cold: x = 0, r = b, z = 0.  WARM: x = x0, r = b - A x0 in one rounding with A x0 by the
+// stencil formula from an image of x0, (b, b) beside (r, r), first = 2 with the reference norm ||b||_2, norm0 = ||r0||_2.  The sums
+// are double-double pairs, so their rounded values are those of the flat passes although the elements are dealt differently.
+// A warm MSG system gets the poll of mi355cg_solve too: the decision on the start state goes to its summary, with the start-state
+// tests (msg_stop_reason without a precision) applied; one that is done never iterates.
+struct OnchipManyInitArgs {
+    OnchipPlan pl;
+    double xk, yk;
+    const double* diag;
+    const double* b; const double* x0;   // nsys packed vectors of `stride` doubles each, like x, r, p (x0: WARM only)
+    double* x; double* r; double* p;
+    long long stride;
+    double* partB; CgState* s; CgState* summary; double* norm0; int* done_count;
+    RuleParams rp;
+};
+template <bool WARM>
+__global__ __launch_bounds__(kOnchipMaxThreads) void k_onchip_many_init(const OnchipManyInitArgs a) {
+    const OnchipPlan& pl = a.pl;
+    const OcLds l = OcMany::lds(pl.cells);
+    const int t = threadIdx.x, T = blockDim.x, nwaves = T / kWave;
+    const long long sys = blockIdx.x, base = sys * a.stride;
+    const double* b = a.b + base;
+    if (WARM) {
+        const double* x0 = a.x0 + base;
+        for (int i = t; i < pl.cells; i += T) l.img[i] = 0.0;
+        __syncthreads();
+        for (int i = t; i < pl.unknowns; i += T) { int xx, yy; onchip_node(pl, i, &xx, &yy); l.img[onchip_cell(pl, xx, yy)] = x0[i]; }
+        __syncthreads();
+    }
+    const double cA = WARM ? a.diag[sys] : 0.0, cxk = a.xk, cyk = a.yk;
+    const int pitch = pl.pitch;
+    OcSumsB v{dd_zero(), dd_zero(), dd_zero(), 0.0, 0.0, 0.0, 0.0};       // d2 carries (b, b)
+    for (int i = t; i < pl.unknowns; i += T) {
+        const double bv = b[i];
+        double rv = bv, xv = 0.0;
+        if (WARM) {
+            int xx, yy;
+            onchip_node(pl, i, &xx, &yy);
+            const int c = onchip_cell(pl, xx, yy);
+            xv = l.img[c];
+            double ax = cA * xv;                                   // apply_at of the chunk body: k_stencil's formula
+            ax = ax + cxk * l.img[c - 1];
+            ax = ax + cxk * l.img[c + 1];
+            ax = ax + cyk * l.img[c + pitch];
+            ax = ax + cyk * l.img[c - pitch];
+            rv = bv - ax;                                          // r = b - A*x       matrix_free_system.cpp:389-392
+            dd_acc_prod(v.d2, bv, bv);
+        }
+        dd_acc_prod(v.rr, rv, rv);
+        v.rmax = fmax(v.rmax, fabs(rv));
+        a.x[base + i] = xv; a.r[base + i] = rv; a.p[base + i] = 0.0;
+    }
+    oc_publish_b<true>(v, l.scrB);
+    if (t != 0) return;
+    const OcSumsB tot = oc_combine_b<true>(l.scrB, nwaves);
+    double* q = a.partB + sys * FB_COUNT;
+    q[FB_RR] = tot.rr.hi; q[FB_RR + FB_LO] = tot.rr.lo;
+    q[FB_D2] = 0.0; q[FB_D2 + FB_LO] = 0.0; q[FB_E2] = 0.0; q[FB_E2 + FB_LO] = 0.0;
+    q[FB_RMAX] = tot.rmax; q[FB_DMAX] = 0.0; q[FB_EMAX] = 0.0;
+    const double rr = dd_value(tot.rr);
+    CgState* sp = a.s + sys;
+    *sp = CgState{};
+    sp->first = 1;
+    a.norm0[sys] = sqrt(rr);
+    if (WARM) {
+        sp->r0norm = sqrt(dd_value(tot.d2)); sp->first = 2;
+        if (a.rp.rule == 0 /*MSG_MAXNORM*/) {
+            StateLite s{};
+            s.r0norm = sp->r0norm; s.first = 2;
+            const Decision d = decide_after_update(s, a.rp, rr, tot.rmax, 0.0, 0.0, 0.0, 0.0);
+            const bool met = !a.rp.fixed_iterations && a.rp.eps_residual > 0 && tot.rmax < a.rp.eps_residual;      // msg_stop_reason(prm, false, ..)
+            CgState* sm = a.summary + sys;
+            write_state_after_decision<true>(sm, nullptr, sp, s, d);
+            if (met) { sm->done = 1; sm->converged = 1; sm->reason = 2 /*RESIDUAL*/; }
+            if (d.done || met) { *sp = *sm; atomicAdd(a.done_count, 1); }
+        }
     }
 }
 

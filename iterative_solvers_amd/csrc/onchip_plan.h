@@ -70,7 +70,24 @@ MI355CG_HD inline void onchip_neighbours(const OnchipPlan& p, int cell, int nb[4
     nb[0] = cell - 1; nb[1] = cell + 1; nb[2] = cell + p.pitch; nb[3] = cell - p.pitch;
 }
 
+// ---- many systems, one workgroup each (k_onchip_many) ---------------------------------------------------------
+// A workgroup's LDS is dynamic and follows N: the side data, then the image of its grid, the total rounded up to 16 bytes.  So small
+// grids share a CU: floor(160 KiB / bytes) workgroups, as far as waves and registers allow.
+MI355CG_HD inline int onchip_many_image_bytes(int cells) { return (cells * 8 + 15) / 16 * 16; }
+MI355CG_HD inline int onchip_many_lds_bytes(int n) { return onchip_supported(n) ? onchip_many_image_bytes((n + 1) * (n + 1)) + kOnchipSideBytes : 0; }
+// Device workspace of a batch of nsys systems: per system three packed vectors (x, r, one direction) and kOnchipManySysBytes of
+// small data -- two CG states (the iteration boundary's and the host's summary) of 184 bytes, one slot of nine update partials, the
+// system's diagonal and ||r0||_2 -- plus one counter of finished systems.  (The host entry points stage b and x on top: 2 nsys
+// packed vectors; pinned host mirrors are not counted.)
+constexpr int kOnchipManySysBytes = 2 * 184 + (9 + 2) * 8;
+constexpr int kOnchipManyFixedBytes = 8;
+MI355CG_HD inline long long onchip_many_workspace_bytes(int n, int nsys) {
+    if (!onchip_supported(n) || nsys < 1) return 0;
+    return (long long)nsys * (3LL * 8 * onchip_plan(n).unknowns + kOnchipManySysBytes) + kOnchipManyFixedBytes;
+}
+
 static_assert(kOnchipMaxCells * 8 + kOnchipSideBytes <= kOnchipLdsLimit, "the image of the largest grid and the side data fit in one CU's LDS");
+static_assert((kOnchipMaxCells * 8 + 15) / 16 * 16 + kOnchipSideBytes <= kOnchipLdsLimit, "... with the image rounded up to 16 bytes too");
 static_assert(kOnchipMaxThreads * kOnchipMaxElems >= (kOnchipMaxN / 2 - 1) * (3 * kOnchipMaxN / 2 - 1), "every unknown of the largest grid has a slot");
 
 }  // namespace mi355cg

@@ -265,9 +265,9 @@ class _Handle:
         return z
 
     @staticmethod
-    def _check_batch(b, size):
-        """(nrhs, on_device) of a batch of right-hand sides: a NumPy array or a CUDA torch tensor, [nrhs, size] float64.
-        ValueError for anything else; the library has not been called when it is raised."""
+    def _check_batch(b, size, most=_capi.BATCH_MAX):
+        """(nrhs, on_device) of a batch of right-hand sides: a NumPy array or a CUDA torch tensor, [nrhs, size] float64, at most
+        `most` rows.  ValueError for anything else; the library has not been called when it is raised."""
         on_device = not isinstance(b, np.ndarray)
         if on_device:
             if not (type(b).__module__.split(".")[0] == "torch" and hasattr(b, "data_ptr")):
@@ -284,8 +284,8 @@ class _Handle:
         shape = tuple(b.shape)
         if len(shape) != 2 or shape[1] != size:
             raise ValueError(f"batch has shape {shape}, expected (nrhs, {size})")
-        if not 1 <= shape[0] <= _capi.BATCH_MAX:
-            raise ValueError(f"a batch has 1 .. {_capi.BATCH_MAX} right-hand sides, not {shape[0]}")
+        if not 1 <= shape[0] <= most:
+            raise ValueError(f"a batch has 1 .. {most} right-hand sides, not {shape[0]}")
         return shape[0], on_device
 
     def solve_batch(self, params: _capi.Params, b, stop_flag: Optional[C.c_int] = None, x0=None):
@@ -324,8 +324,61 @@ class _Handle:
         return x, list(res)
 
     def batch_release(self):
-        """Free the workspace solve_batch keeps on the handle (nothing to free is fine)."""
+        """Free the workspaces solve_batch and solve_many keep on the handle (nothing to free is fine)."""
         _capi.check(self._lib.mi355cg_batch_release(self._h))
+
+    def solve_many(self, params: _capi.Params, b, stop_flag: Optional[C.c_int] = None, x0=None, sigma=None):
+        """Extension (no reference twin): many small systems on this grid, one workgroup each (mi355cg_solve_many; plain fp64 grid
+        handles up to the on-chip cap, no preconditioner).  Returns (x, [Results per system]); system s gets the bits
+        set_shift(sigma[s]); set_rhs(b[s]); [set_initial_guess(x0[s]);] solve(params); solution() gives, and the handle itself is
+        left as it was.  b: NumPy [nsys, size] float64 -> NumPy x; or a contiguous CUDA torch.Tensor of that shape on the handle's
+        device -> a new tensor there (torch's current stream is synchronised first).  x0: a guess per system, of b's kind and
+        shape; not modified.  sigma: a shift per system, [nsys] float64 of b's kind (a sequence is fine beside a NumPy b); None =
+        the handle's current shift for all.  params.use_true_solution and params.diagnostics must be 0."""
+        nsys, on_device = self._check_batch(b, self.size, _capi.MANY_MAX)
+        if x0 is not None:
+            if self._check_batch(x0, self.size, _capi.MANY_MAX) != (nsys, on_device):
+                raise ValueError(f"x0 has shape {tuple(x0.shape)}: the guesses are of the kind (NumPy / CUDA tensor) and shape of b, "
+                                 f"{tuple(b.shape)}")
+        res = (_capi.Results * nsys)()
+        sp = C.cast(C.pointer(stop_flag), C.c_void_p) if stop_flag is not None else None
+        if on_device:
+            import torch
+            if b.device.index != self._device:
+                raise ValueError(f"batch is on {b.device}, the handle on device {self._device}")
+            if x0 is not None and x0.device != b.device:
+                raise ValueError(f"x0 is on {x0.device}, b on {b.device}")
+            if sigma is not None:
+                if not (hasattr(sigma, "data_ptr") and sigma.is_cuda and sigma.device == b.device and sigma.dtype == torch.float64
+                        and tuple(sigma.shape) == (nsys,) and sigma.is_contiguous()):
+                    raise ValueError(f"sigma beside a CUDA batch is a contiguous float64 tensor of shape ({nsys},) on {b.device}")
+            x = torch.empty_like(b) if x0 is None else x0.clone()
+            torch.cuda.current_stream(b.device).synchronize()
+            fn = self._lib.mi355cg_solve_many_device if x0 is None else self._lib.mi355cg_solve_many_device_from
+            rc = fn(self._h, C.byref(params), nsys, b.data_ptr(), x.data_ptr(), sigma.data_ptr() if sigma is not None else None, sp, res)
+        else:
+            b = np.ascontiguousarray(b)
+            if sigma is not None:
+                sigma = np.ascontiguousarray(sigma, dtype=np.float64)
+                if sigma.shape != (nsys,):
+                    raise ValueError(f"sigma has shape {sigma.shape}, expected ({nsys},)")
+            x = np.empty_like(b) if x0 is None else np.array(x0, dtype=np.float64, order="C", copy=True)
+            fn = self._lib.mi355cg_solve_many if x0 is None else self._lib.mi355cg_solve_many_from
+            rc = fn(self._h, C.byref(params), nsys, b.ctypes.data, x.ctypes.data, sigma.ctypes.data if sigma is not None else None, sp, res)
+        if rc == _capi.ERR_INVALID:
+            raise ValueError(self._lib.mi355cg_last_error().decode())
+        _capi.check(rc)
+        return x, list(res)
+
+    def solve_many_info(self, nsys: int):
+        """{"lds_bytes_per_workgroup", "workgroups_per_cu", "workspace_bytes"} of a solve_many batch of nsys systems on this grid
+        (mi355cg_solve_many_info); ValueError for handles solve_many refuses."""
+        lds, wg, ws = C.c_int(), C.c_int(), C.c_longlong()
+        rc = self._lib.mi355cg_solve_many_info(self._h, int(nsys), C.byref(lds), C.byref(wg), C.byref(ws))
+        if rc == _capi.ERR_INVALID:
+            raise ValueError(self._lib.mi355cg_last_error().decode())
+        _capi.check(rc)
+        return {"lds_bytes_per_workgroup": lds.value, "workgroups_per_cu": wg.value, "workspace_bytes": ws.value}
 
     @staticmethod
     def _check_block(v, size, most, what):
@@ -607,8 +660,29 @@ class MatrixFreeSystem:
         return self._handle.solve_batch(params, b, x0=x0)
 
     def batch_release(self):
-        """Free the device workspace solve_batch keeps on this system."""
+        """Free the device workspaces solve_batch and solve_many keep on this system."""
         self._handle.batch_release()
+
+    def solve_many(self, b, eps: float = 1e-6, max_iterations: int = 10000, rule: int = _capi.RULE_REL_2NORM, params=None, x0=None,
+                   sigma=None):
+        """Extension (no reference twin): many independent small systems on this grid -- an ensemble, a parameter sweep, a time
+        step per member -- by plain CG with ONE workgroup per system and one launch per chunk of iterations for all of them
+        (grids up to the on-chip cap, N = 128; no preconditioner).  b: [nsys, size()] float64, NumPy or a CUDA torch tensor;
+        x0: a starting vector per system; sigma: a shift per system (system s solves (A - sigma[s] I) x = b[s]), None = this
+        system's own shift.  Returns (x of b's kind, one _capi.Results per system), every system with the bits a
+        set_shift / MatrixFreeSolver or MSGSolver solve of it on this system gives; this system's own state stays as it was.
+        eps, max_iterations, rule as in solve_batch; params, if given, is used as it is."""
+        if params is None:
+            params = default_params(rule)
+            params.max_iterations = max_iterations
+            params.eps_rel = params.eps_precision = params.eps_residual = eps
+            params.use_true_solution = 0
+        return self._handle.solve_many(params, b, x0=x0, sigma=sigma)
+
+    def solve_many_info(self, nsys: int):
+        """What a solve_many batch of nsys systems costs on this grid: the LDS bytes of one workgroup, how many workgroups the
+        runtime lets reside on one CU, and the device workspace bytes."""
+        return self._handle.solve_many_info(nsys)
 
     def eigs(self, nev: int, block: Optional[int] = None, tol: float = 1e-8, max_iterations: int = 200, x0=None, seed: int = 0,
              stop_flag: Optional[C.c_int] = None):
