@@ -43,6 +43,8 @@
  *   mi355cg_onchip_plan            the layout of that mode for a grid (pure host arithmetic, no GPU needed)
  *   mi355cg_solve_many / _from / _device / _device_from   many small systems (own b, guess and shift each), one workgroup per system
  *   mi355cg_solve_many_info        LDS per workgroup, resident workgroups per CU and workspace bytes of such a batch
+ *   mi355cg_time_steps_many / _device   an ensemble of small time steppers (own state, forcing and tau each), the step loop inside the launch
+ *   mi355cg_time_steps_many_workspace   the device workspace bytes of such an ensemble (pure host arithmetic, no GPU needed)
  *
  * Plain pointers and sizes only; no C++/torch types.  All host vectors are in the reference's
  * PACKED unknown order (bottom-right block row-major, then the upper block row-major;
@@ -478,6 +480,51 @@ int  mi355cg_solve_many_device(mi355cg_handle h, const mi355cg_params *params, i
 int  mi355cg_solve_many_device_from(mi355cg_handle h, const mi355cg_params *params, int nsys, const double *b_dev, double *x_dev,
                                     const double *sigma_dev, const volatile int *stop_flag, mi355cg_results *out);
 int  mi355cg_solve_many_info(mi355cg_handle h, int nsys, int *lds_bytes_per_workgroup, int *workgroups_per_cu, long long *workspace_bytes);
+
+/* Ensemble time stepping on chip: nsys members on the grid of one eligible handle (exactly the handles mi355cg_solve_many takes),
+ * each integrated over nsteps steps of the theta scheme for u_t = A u - g (mi355cg_time_steps), ONE workgroup per member from its
+ * first step to its last: the step loop runs inside the launch and the host sees chunks only.  The members
+ * differ in state u_s (in/out), forcing g_s and time step tau_s; theta and nsteps are shared.
+ * tau: nsys doubles in HOST memory (both entry points).  g: nsys packed vectors, or NULL = the handle's right-hand side for every
+ * member.  u: nsys packed vectors of mi355cg_size(h) doubles, the start states in, the states after steps_done[s] steps out (after
+ * a step that did not converge: that step's last iterate).  out: nsys entries, the LAST STEP ATTEMPTED of each member.
+ * steps_done: nsys ints, the converged steps.  step_iterations: NULL, or nsys x nsteps ints, member-major: the iterations of every
+ * step attempted, -1 for steps not taken.
+ * Member s gets exactly the bits that mi355cg_set_rhs(h, g_s); mi355cg_set_initial_guess(h, u0_s); mi355cg_time_steps(h, params,
+ * tau_s, theta, nsteps, ..) give on a handle of the same grid in either solve mode: all of u_s, steps_done, the iteration count of
+ * every step and, for the last step attempted, iterations, converged, stop_reason, r_norm2, initial_r_norm2, final_precision and
+ * final_residual_norm.  The shift of member s is sigma_s = 1 / (theta tau_s), its diagonal A_diag - sigma_s rounded once on the
+ * host as mi355cg_set_shift stores it; every step starts as a warm solve does (r = b_step - (A - sigma_s) u, reference norm
+ * ||b_step||_2; under MSG_MAXNORM the start-state tests apply, so a step may take 0 iterations); max_iterations counts per step.  A
+ * member ends after nsteps steps or after its first step that does not converge (the iteration cap or a stop request).
+ * A launch gives every member sync_every units (default 200, MSG_MAXNORM 100): a CG iteration costs one, the transition from one
+ * step to the next costs one; between two launches the host reads one word.  stop_flag is sampled by every workgroup once per
+ * iteration: members still stepping end MI355CG_STOP_INTERRUPTED, finished members keep their results, a flag already set at the
+ * call leaves every member at 0 steps with u = u0; a member the host stops between two steps reports the empty state of a step not
+ * begun.  final_error_norm is DBL_MAX; solve_seconds and loop_seconds are the whole call's, the same in every entry.  The handle's
+ * own state is untouched -- its b, x, r, shift, solve mode, pending guess and what the getters return; unlike mi355cg_time_steps,
+ * which leaves the shift set.
+ * MI355CG_ERR_INVALID, before anything is allocated or written: a null pointer (stop_flag, g and step_iterations may be null), nsys
+ * < 1 or > MI355CG_MANY_MAX, nsteps < 0 or > MI355CG_STEPS_MANY_MAX_STEPS, nsys * nsteps > 2^26 with step_iterations given, theta
+ * outside (0, 1], a tau_s that is not finite or <= 0 or whose 1 / (theta tau_s) is not finite, u overlapping g, an unknown rule,
+ * use_true_solution != 0 or diagnostics != 0, and every handle mi355cg_solve_many refuses for its kind or size, with its message.
+ * MI355CG_ERR_STATE: the handle has a preconditioner.  nsteps = 0 is MI355CG_OK and writes only steps_done = 0.  MI355CG_ERR_HIP
+ * if a member still steps after ceil(nsteps (max_iterations + 1) / sync_every) + 1 launches (a guard: it cannot happen).
+ * _device: g_dev and u_dev are in device memory of the handle's GPU, everything else in host memory; the work runs on the handle's
+ * stream and the call returns after that stream is idle.
+ * Workspace: that of mi355cg_solve_many for nsys systems, 16 bytes per member (its shift, its step index and ended flag), one
+ * packed vector (the handle's right-hand side) and, with step_iterations, 4 nsys nsteps bytes; the host entry point stages g and u
+ * on top (2 nsys packed vectors).  It grows on demand, shares the batch workspace of the handle and is freed by
+ * mi355cg_batch_release and mi355cg_destroy.  mi355cg_time_steps_many_workspace: that many bytes for grid n, pure host arithmetic,
+ * no GPU needed; MI355CG_ERR_INVALID for a grid, an nsys, an nsteps or a number of counts the calls above refuse.                */
+#define MI355CG_STEPS_MANY_MAX_STEPS 65536
+int  mi355cg_time_steps_many(mi355cg_handle h, const mi355cg_params *params, int nsys, int nsteps, double theta, const double *tau,
+                             const double *g, double *u, const volatile int *stop_flag, mi355cg_results *out, int *steps_done,
+                             int *step_iterations);
+int  mi355cg_time_steps_many_device(mi355cg_handle h, const mi355cg_params *params, int nsys, int nsteps, double theta, const double *tau,
+                                    const double *g_dev, double *u_dev, const volatile int *stop_flag, mi355cg_results *out,
+                                    int *steps_done, int *step_iterations);
+int  mi355cg_time_steps_many_workspace(int n, int nsys, int nsteps, int with_step_iterations, long long *bytes);
 
 /* ---- multi-GPU: one context per rank, one contiguous slab of grid rows per context --------------
  * The reference is single-process (no collectives exist in it); this is the scaling

@@ -39,6 +39,7 @@ EXPORTS = [
     "mi355cg_set_smoother", "mi355cg_get_smoother",
     "mi355cg_set_solve_mode", "mi355cg_get_solve_mode", "mi355cg_onchip_plan",
     "mi355cg_solve_many", "mi355cg_solve_many_from", "mi355cg_solve_many_device", "mi355cg_solve_many_device_from", "mi355cg_solve_many_info",
+    "mi355cg_time_steps_many", "mi355cg_time_steps_many_device", "mi355cg_time_steps_many_workspace",
 ]
 DECOMP_ROWS, DECOMP_2D = 0, 1
 PRECOND_NONE, PRECOND_MG, PRECOND_MG_ANY = 0, 1, 2
@@ -47,6 +48,7 @@ SOLVE_LAUNCHES, SOLVE_ONCHIP = 0, 1
 SMOOTHER_JACOBI, SMOOTHER_LINE_X, SMOOTHER_LINE_Y, SMOOTHER_LINE_AUTO = 0, 1, 2, 3
 BATCH_MAX = 64          # MI355CG_BATCH_MAX
 MANY_MAX = 65536        # MI355CG_MANY_MAX
+STEPS_MANY_MAX_STEPS = 65536   # MI355CG_STEPS_MANY_MAX_STEPS
 EIG_BLOCK_MAX = 16      # MI355CG_EIG_BLOCK_MAX
 EIG_BASIS_MAX = 48      # vectors of a Rayleigh-Ritz basis, and of a group of block_gram
 EIG_CONVERGED, EIG_ITERATIONS, EIG_INTERRUPTED, EIG_BREAKDOWN = range(4)
@@ -222,6 +224,12 @@ def load():
         for fn in (L.mi355cg_solve_many, L.mi355cg_solve_many_from, L.mi355cg_solve_many_device, L.mi355cg_solve_many_device_from):
             fn.argtypes = [H, C.POINTER(Params), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Results)]
         L.mi355cg_solve_many_info.argtypes = [H, C.c_int, IP, IP, LLP]
+    if hasattr(L, "mi355cg_time_steps_many"):   # absent from an older build loaded through MI355CG_LIB
+        # tau (host), g and u (host arrays / device memory for _device), the stop flag, steps_done and step_iterations as plain addresses
+        for fn in (L.mi355cg_time_steps_many, L.mi355cg_time_steps_many_device):
+            fn.argtypes = [H, C.POINTER(Params), C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                           C.POINTER(Results), C.c_void_p, C.c_void_p]
+        L.mi355cg_time_steps_many_workspace.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, LLP]
     if hasattr(L, "mi355cg_get_xfold"):         # absent from an older build loaded through MI355CG_LIB
         L.mi355cg_get_xfold.argtypes = [H, IP, IP]
     _lib = L

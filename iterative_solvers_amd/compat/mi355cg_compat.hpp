@@ -490,6 +490,43 @@ public:
         if (results) *results = std::move(res);
         return x;
     }
+    // Extension: an ensemble of time steppers on this grid, one workgroup per member from its first step to its last, the step loop
+    // inside the launch (mi355cg_time_steps_many; plain CG, grids up to N = 128, no preconditioner).  Member s takes nsteps steps
+    // of the theta scheme for u_t = A u - g[s] from u0[s] with the time step tau[s]; an empty g means this system's right-hand
+    // side for every member.  u[s], results[s] (the last step attempted), steps_done[s] and step_iterations[s] (one count per
+    // step, -1 = not taken) have the bits of mi355cg_set_rhs, mi355cg_set_initial_guess and mi355cg_time_steps on this system;
+    // the system's own state, the shift included, is left as it was.  params.use_true_solution and params.diagnostics must be 0.
+    // std::invalid_argument for an empty ensemble, more than MI355CG_MANY_MAX members, a tau or g of another length, a vector of
+    // the wrong size and what the library refuses as invalid; std::runtime_error on a system with a preconditioner.
+    std::vector<std::vector<double>> timeStepsMany(const std::vector<std::vector<double>>& u0, const std::vector<double>& tau, double theta,
+                                                   int nsteps, const mi355cg_params& params, std::vector<mi355cg_results>* results = nullptr,
+                                                   std::vector<int>* steps_done = nullptr, std::vector<std::vector<int>>* step_iterations = nullptr,
+                                                   const std::vector<std::vector<double>>& g = {}) {
+        if (u0.empty() || u0.size() > (size_t)MI355CG_MANY_MAX) throw std::invalid_argument("timeStepsMany: an ensemble has 1 .. MI355CG_MANY_MAX members");
+        const size_t n = rhs.size(), k = u0.size();
+        if (tau.size() != k) throw std::invalid_argument("timeStepsMany: tau does not have one entry per member");
+        if (!g.empty() && g.size() != k) throw std::invalid_argument("timeStepsMany: g does not have one vector per member");
+        if (nsteps < 0 || nsteps > MI355CG_STEPS_MANY_MAX_STEPS) throw std::invalid_argument("timeStepsMany: nsteps is 0 .. MI355CG_STEPS_MANY_MAX_STEPS");
+        std::vector<double> gp(g.empty() ? 0 : n * k), up(n * k);
+        for (size_t s = 0; s < k; ++s) {
+            if (u0[s].size() != n || (!g.empty() && g[s].size() != n)) throw std::invalid_argument("timeStepsMany: vector size does not match the system");
+            std::copy(u0[s].begin(), u0[s].end(), up.begin() + (std::ptrdiff_t)(s * n));
+            if (!g.empty()) std::copy(g[s].begin(), g[s].end(), gp.begin() + (std::ptrdiff_t)(s * n));
+        }
+        std::vector<mi355cg_results> res(k);
+        std::vector<int> done(k, 0), its(step_iterations ? k * (size_t)nsteps : 0, -1);
+        mi355cg_compat::check(mi355cg_time_steps_many(ctx_->h, &params, (int)k, nsteps, theta, tau.data(), g.empty() ? nullptr : gp.data(), up.data(),
+                                                      nullptr, res.data(), done.data(), step_iterations && nsteps > 0 ? its.data() : nullptr));
+        std::vector<std::vector<double>> u(k);
+        for (size_t s = 0; s < k; ++s) u[s].assign(up.begin() + (std::ptrdiff_t)(s * n), up.begin() + (std::ptrdiff_t)((s + 1) * n));
+        if (step_iterations) {
+            step_iterations->assign(k, std::vector<int>());
+            for (size_t s = 0; s < k; ++s) (*step_iterations)[s].assign(its.begin() + (std::ptrdiff_t)(s * (size_t)nsteps), its.begin() + (std::ptrdiff_t)((s + 1) * (size_t)nsteps));
+        }
+        if (results) *results = std::move(res);
+        if (steps_done) *steps_done = std::move(done);
+        return u;
+    }
     void batchRelease() { mi355cg_compat::check(mi355cg_batch_release(ctx_->h)); }
     // Extension: the nev lowest eigenpairs of this system's operator by a block preconditioned iteration with one multigrid V-cycle
     // per vector and iteration (mi355cg_eigs; needs setPreconditioner with the fp64 cycle first).  lambda > 0 ascending with

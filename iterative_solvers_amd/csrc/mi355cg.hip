@@ -170,6 +170,16 @@ struct OnchipManyWs {
     Buf<int> done_h;
     Buf<double> stage;                  // packed vectors of the host entry points: b, then x
     long long stage_cap = 0;            // systems it holds
+    // mi355cg_time_steps_many* on top (onchip_steps_workspace_bytes), allocated by the first such call
+    int steps_cap = 0;                  // members the next five hold
+    Buf<double> step_sigma;             // 1 / (theta tau_s)
+    Buf<OcStepBook> book;               // step index and ended flag of every member
+    Buf<double> g_one;                  // the handle's right-hand side, packed: the forcing of every member when g = NULL
+    Buf<double> step_sigma_h;           // pinned copies; s_h: the iteration-boundary states, read after an interrupted call only
+    Buf<OcStepBook> book_h;
+    Buf<CgState> s_h;
+    Buf<int> step_it;                   // iteration counts, member-major, -1 = step not taken: only when the caller asks for them
+    long long step_it_cap = 0;          // counts it holds
 };
 
 }  // namespace
@@ -3133,6 +3143,223 @@ int mi355cg_solve_many_info(mi355cg_handle c, int nsys, int* lds_bytes_per_workg
         HIPCK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, pl.threads, (size_t)lds));
         *workgroups_per_cu = nb;
     }
+    return MI355CG_OK;
+}
+
+// ---- ensemble time stepping on chip: the step loop inside the launch -----------------------------------------
+static_assert(MI355CG_MANY_MAX == kOnchipStepsMaxSys && MI355CG_STEPS_MANY_MAX_STEPS == kOnchipStepsMaxSteps, "onchip_plan.h: the limits of an ensemble");
+// what both entry points refuse before anything is allocated or written (tau is in host memory for both)
+static int steps_many_check(mi355cg_ctx* c, const mi355cg_params* prm, int nsys, int nsteps, double theta, const double* tau, const void* g,
+                            const void* u, const mi355cg_results* out, const int* steps_done, const int* step_iterations) {
+    if (!c || !prm || !tau || !u || !out || !steps_done) return fail(MI355CG_ERR_INVALID, "null argument");
+    if (nsys < 1 || nsys > MI355CG_MANY_MAX) return fail(MI355CG_ERR_INVALID, "an ensemble of on-chip steppers has 1 .. %d members, not %d", MI355CG_MANY_MAX, nsys);
+    if (nsteps < 0 || nsteps > MI355CG_STEPS_MANY_MAX_STEPS) return fail(MI355CG_ERR_INVALID, "nsteps %d rejected: it must be 0 .. %d", nsteps, MI355CG_STEPS_MANY_MAX_STEPS);
+    if (step_iterations && (long long)nsys * nsteps > kOnchipStepsMaxCounts)
+        return fail(MI355CG_ERR_INVALID, "step_iterations for %d members x %d steps rejected: at most %lld counts", nsys, nsteps, kOnchipStepsMaxCounts);
+    if (!(theta > 0.0 && theta <= 1.0)) return fail(MI355CG_ERR_INVALID, "theta %g rejected: the scheme needs 0 < theta <= 1", theta);
+    if (prm->rule != MI355CG_RULE_MSG_MAXNORM && prm->rule != MI355CG_RULE_REL_2NORM) return fail(MI355CG_ERR_INVALID, "unknown rule %d", prm->rule);
+    if (prm->use_true_solution) return fail(MI355CG_ERR_INVALID, "a step has no exact solution: use_true_solution must be 0");
+    if (prm->diagnostics) return fail(MI355CG_ERR_INVALID, "the stepper has no callbacks: diagnostics must be 0");
+    if (c->mg) return fail(MI355CG_ERR_STATE, "this handle has a preconditioner: mi355cg_time_steps_many is plain CG in one workgroup per member");
+    if (const char* why = onchip_refusal(c)) return fail(MI355CG_ERR_INVALID, "%s", why);
+    for (int s = 0; s < nsys; ++s) {
+        if (!std::isfinite(tau[s]) || !(tau[s] > 0.0)) return fail(MI355CG_ERR_INVALID, "time step %g of member %d rejected: tau must be finite and > 0", tau[s], s);
+        if (!std::isfinite(1.0 / (theta * tau[s]))) return fail(MI355CG_ERR_INVALID, "time step %g of member %d rejected: 1 / (theta tau) is not finite", tau[s], s);
+    }
+    if (g) {
+        const size_t bytes = sizeof(double) * (size_t)c->gp.size * (size_t)nsys;
+        const uintptr_t gb = (uintptr_t)g, ub = (uintptr_t)u;
+        if (gb < ub + bytes && ub < gb + bytes) return fail(MI355CG_ERR_INVALID, "u overlaps g");
+    }
+    return MI355CG_OK;
+}
+
+// The batch workspace for nsys members, then the stepping parts on top: built complete before they replace what is there.
+static int onchip_steps_ensure(mi355cg_ctx* c, int nsys, long long counts, bool stage) {
+    if (int rc = onchip_many_ensure(c, nsys, stage)) return rc;
+    OnchipManyWs* W = c->many.get();
+    auto failed = [&](const char* what) { return fail(MI355CG_ERR_HIP, "on-chip stepping workspace for %d members: %s allocation failed", nsys, what); };
+    if (W->steps_cap < nsys) {
+        Buf<double> sigma, sigma_h, g_one; Buf<OcStepBook> book, book_h; Buf<CgState> s_h;
+        if (Buf<double>::device(sigma, nsys) || Buf<OcStepBook>::device(book, nsys)) return failed("bookkeeping");
+        if (Buf<double>::device(g_one, c->pk_len)) return failed("vector");
+        if (Buf<double>::pinned(sigma_h, nsys) || Buf<OcStepBook>::pinned(book_h, nsys) || Buf<CgState>::pinned(s_h, nsys)) return failed("pinned copy");
+        HIPCK(hipStreamSynchronize(c->stream));
+        W->step_sigma = std::move(sigma); W->book = std::move(book); W->g_one = std::move(g_one);
+        W->step_sigma_h = std::move(sigma_h); W->book_h = std::move(book_h); W->s_h = std::move(s_h);
+        W->steps_cap = nsys;
+    }
+    if (counts > W->step_it_cap) {
+        HIPCK(hipStreamSynchronize(c->stream));
+        if (Buf<int>::device(W->step_it, counts)) return failed("iteration count");
+        W->step_it_cap = counts;
+    }
+    return MI355CG_OK;
+}
+
+static const void* onchip_steps_kernel(int elems, bool msg) {
+#define MI355CG_OCS(E) return msg ? (const void*)&k_onchip_steps<E, true> : (const void*)&k_onchip_steps<E, false>
+    switch (elems) {
+        case 1: MI355CG_OCS(1);
+        case 2: MI355CG_OCS(2);
+        case 4: MI355CG_OCS(4);
+        case 8: MI355CG_OCS(8);
+        case 16: MI355CG_OCS(16);
+        default: MI355CG_OCS(kOnchipMaxElems);
+    }
+#undef MI355CG_OCS
+}
+
+// REL_2NORM reports the max-norm of the residual only where k_check decided, i.e. when the solve ended on a poll of mi355cg_solve's
+// chunk schedule; a decision inside a chunk carries 0 (the rule does not reduce that norm).  A member's chunks are cut by its budget,
+// not by that schedule, so the host says which of the two a single solve of `it` iterations reports.
+static bool rel_solve_ends_on_a_poll(const mi355cg_params* prm, int sync_every, int it, bool watched) {
+    if (it <= 0) return false;                                     // decided by the first launch, before any poll
+    int done = 0;
+    for (bool first = watched; done < it; first = false) done += chunk_len(prm, false, sync_every, done, first);
+    return done == it;
+}
+
+// g_dev (or NULL), u_dev: nsys packed vectors each in device memory; tau: host memory, checked; nsteps >= 1.
+static int steps_many(mi355cg_ctx* c, const mi355cg_params* prm, int nsys, int nsteps, double theta, const double* tau, const double* g_dev,
+                      double* u_dev, const volatile int* stop_flag, mi355cg_results* out, int* steps_done, int* step_iterations) {
+    const auto t0 = std::chrono::steady_clock::now();
+    OnchipManyWs* W = c->many.get();
+    const OnchipPlan pl = onchip_plan(c->gp.n);
+    const bool msg = prm->rule == MI355CG_RULE_MSG_MAXNORM;
+    const IterCfg cfg = make_cfg(prm);
+    if (c->pk_len != pl.unknowns) return fail(MI355CG_ERR_STATE, "on-chip stepping: the handle packs %lld unknowns, the plan of N = %d has %d", c->pk_len, pl.n, pl.unknowns);
+    const long long U = pl.unknowns, count = U * nsys, counts = step_iterations ? (long long)nsys * nsteps : 0;
+    const int lds = onchip_many_lds_bytes(pl.n);
+    double* partB = W->small; double* diag = partB + (long long)FB_COUNT * nsys; double* norm0 = diag + nsys;
+    double* diag_h = W->small_h + (long long)FB_COUNT * nsys; const double* norm0_h = diag_h + nsys;
+
+    for (int s = 0; s < nsys; ++s) {
+        W->step_sigma_h[s] = 1.0 / (theta * tau[s]);                 // mi355cg_time_steps's shift, in that form ...
+        diag_h[s] = c->gp.A - W->step_sigma_h[s];                    // ... and mi355cg_set_shift's rounding
+    }
+    HIPCK(hipMemcpyAsync(diag, diag_h, sizeof(double) * nsys, hipMemcpyHostToDevice, c->stream));
+    HIPCK(hipMemcpyAsync(W->step_sigma, W->step_sigma_h, sizeof(double) * nsys, hipMemcpyHostToDevice, c->stream));
+    HIPCK(hipMemsetAsync(W->done, 0, sizeof(int) * 2, c->stream));
+    HIPCK(hipMemsetAsync(W->book, 0, sizeof(OcStepBook) * nsys, c->stream));
+    if (counts) HIPCK(hipMemsetAsync(W->step_it, 0xff, sizeof(int) * counts, c->stream));              // -1: not taken
+    W->done_h[0] = 0;
+    if (!g_dev) {                                                  // the handle's right-hand side for every member
+        hipLaunchKernelGGL((k_pack<double>), dim3(flat_grid(c->pk_len)), dim3(kBlock), 0, c->stream, c->pg, (const double*)c->b, W->g_one.get());
+        HIPCK(hipGetLastError());
+    }
+
+    OnchipStepsArgs e{};
+    e.pl = pl; e.xk = c->g.xk; e.yk = c->g.yk; e.diag = diag; e.sigma = W->step_sigma;
+    e.g = g_dev ? g_dev : W->g_one.get(); e.g_stride = g_dev ? U : 0; e.u0 = u_dev;
+    e.x = W->vec; e.r = W->vec + count; e.p = W->vec + 2 * count; e.stride = U;
+    e.partB = partB; e.s = W->s; e.summary = W->summary; e.norm0 = norm0; e.done_count = W->done;
+    e.book = W->book; e.step_it = counts ? W->step_it.get() : nullptr; e.nsteps = nsteps;
+    e.k = OnchipStepCoef{c->gp.A, c->gp.x_k, c->gp.y_k, theta, (1.0 - theta) / theta, theta < 1.0 ? 1 : 0};       // launch_step_rhs's
+    e.rp = cfg.rp;
+    const void* k_init = (const void*)&k_onchip_steps_init;
+    if (int rc = onchip_many_allow_lds(k_init, lds)) return rc;
+    { void* args[] = {&e}; HIPCK(hipLaunchKernel(k_init, dim3(nsys), dim3(pl.threads), args, lds, c->stream)); }
+
+    // the stop request: sampled by every workgroup once per iteration, forwarded by this thread while it waits (as in mi355cg_solve_many)
+    *c->stop_h = 0;
+    int* stop_dev = nullptr;
+    if (stop_flag) HIPCK(hipHostGetDevicePointer((void**)&stop_dev, c->stop_h, 0));
+    bool polled = false;
+    auto poll = [&]() -> int {                                     // one word per chunk: how many members have ended
+        HIPCK(hipMemcpyAsync(W->done_h, W->done, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        polled = true;
+        return wait_stream_forwarding_stop(c, stop_flag);
+    };
+    if (msg) if (int rc = poll()) return rc;                       // the start states were tested, as mi355cg_solve polls a warm MSG start
+    if (int rc = loop_timer_begin(c, c->stream)) return rc;
+
+    OnchipManyArgs a{};
+    a.pl = pl; a.xk = c->g.xk; a.yk = c->g.yk; a.diag = diag;
+    a.x = e.x; a.r = e.r; a.p = e.p; a.stride = U;
+    a.partB = partB; a.s = W->s; a.summary = W->summary; a.done_count = W->done; a.rp = cfg.rp; a.stop_req = stop_dev;
+    const void* k_chunk = onchip_steps_kernel(pl.elems, msg);
+    if (int rc = onchip_many_allow_lds(k_chunk, lds)) return rc;
+    e.m = default_sync_every(prm, msg);                            // units per member and launch: an iteration or a transition each
+    const long long per_member = (long long)nsteps * ((long long)std::max(prm->max_iterations, 0) + 1);
+    const long long max_launches = (per_member + e.m - 1) / e.m + 1;
+    long long launches = 0;
+    bool interrupted = false;
+    while (W->done_h[0] < nsys) {
+        if (stop_flag && *stop_flag) { interrupted = true; break; }
+        if (launches >= max_launches) return fail(MI355CG_ERR_HIP, "on-chip stepping: %d of %d members still step after %lld launches", nsys - W->done_h[0], nsys, launches);
+        { void* args[] = {&a, &e}; HIPCK(hipLaunchKernel(k_chunk, dim3(nsys), dim3(pl.threads), args, lds, c->stream)); }
+        if (int rc = poll()) return rc;
+        ++launches;
+    }
+    if (int rc = loop_timer_end(c, c->stream)) return rc;
+    if (polled) {
+        HIPCK(hipMemcpyAsync(W->summary_h, W->summary, sizeof(CgState) * nsys, hipMemcpyDeviceToHost, c->stream));
+        HIPCK(hipMemcpyAsync(W->small_h + (long long)(FB_COUNT + 1) * nsys, norm0, sizeof(double) * nsys, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCK(hipMemcpyAsync(W->book_h, W->book, sizeof(OcStepBook) * nsys, hipMemcpyDeviceToHost, c->stream));
+    if (!msg) HIPCK(hipMemcpyAsync(W->small_h, partB, sizeof(double) * FB_COUNT * nsys, hipMemcpyDeviceToHost, c->stream));     // |r| of the last update
+    if (interrupted) HIPCK(hipMemcpyAsync(W->s_h, W->s, sizeof(CgState) * nsys, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(hipMemcpyAsync(u_dev, e.x, sizeof(double) * count, hipMemcpyDeviceToDevice, c->stream));
+    HIPCK(hipStreamSynchronize(c->stream));
+    if (counts) HIPCK(hipMemcpy(step_iterations, W->step_it, sizeof(int) * counts, hipMemcpyDeviceToHost));
+    HIPCK(hipEventSynchronize(c->ev_loop[1]));
+    const double loop_seconds = loop_timer_seconds(c);
+    for (int s = 0; s < nsys; ++s) {
+        const OcStepBook bk = W->book_h[s];
+        const CgState fin = polled ? W->summary_h[s] : CgState{};
+        if (bk.ended) {                                            // after its last step, or a step that did not converge
+            steps_done[s] = bk.step;
+            out[s] = make_results(fin, fin.done && fin.reason == MI355CG_STOP_INTERRUPTED, false, norm0_h[s]);
+            if (!msg) out[s].final_residual_norm = rel_solve_ends_on_a_poll(prm, e.m, fin.it, stop_flag != nullptr) ? W->small_h[(long long)s * FB_COUNT + FB_RMAX] : 0.0;
+        } else if (W->s_h[s].done) {                               // stopped by the host between two steps: the next one was not begun
+            steps_done[s] = bk.step + 1;
+            if (counts) step_iterations[(long long)s * nsteps + bk.step] = W->s_h[s].it;
+            out[s] = make_results(CgState{}, true, false, 0.0);
+        } else {                                                   // stopped by the host inside a step (REL_2NORM: no state is read before its first chunk)
+            const bool begun = polled && (msg || W->s_h[s].it > 0);
+            steps_done[s] = bk.step;
+            out[s] = make_results(begun ? fin : CgState{}, true, false, begun ? norm0_h[s] : 0.0);
+            if (counts) step_iterations[(long long)s * nsteps + bk.step] = out[s].iterations;              // attempted: its count so far
+        }
+        out[s].loop_seconds = loop_seconds;
+    }
+    const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    for (int s = 0; s < nsys; ++s) out[s].solve_seconds = secs;
+    return MI355CG_OK;
+}
+
+int mi355cg_time_steps_many_device(mi355cg_handle c, const mi355cg_params* prm, int nsys, int nsteps, double theta, const double* tau,
+                                   const double* g_dev, double* u_dev, const volatile int* stop_flag, mi355cg_results* out, int* steps_done,
+                                   int* step_iterations) {
+    if (int rc = steps_many_check(c, prm, nsys, nsteps, theta, tau, g_dev, u_dev, out, steps_done, step_iterations)) return rc;
+    if (nsteps == 0) { for (int s = 0; s < nsys; ++s) steps_done[s] = 0; return MI355CG_OK; }
+    HIPCK(hipSetDevice(c->device));
+    if (int rc = onchip_steps_ensure(c, nsys, step_iterations ? (long long)nsys * nsteps : 0, false)) return rc;
+    return steps_many(c, prm, nsys, nsteps, theta, tau, g_dev, u_dev, stop_flag, out, steps_done, step_iterations);
+}
+int mi355cg_time_steps_many(mi355cg_handle c, const mi355cg_params* prm, int nsys, int nsteps, double theta, const double* tau, const double* g,
+                            double* u, const volatile int* stop_flag, mi355cg_results* out, int* steps_done, int* step_iterations) {
+    if (int rc = steps_many_check(c, prm, nsys, nsteps, theta, tau, g, u, out, steps_done, step_iterations)) return rc;
+    if (nsteps == 0) { for (int s = 0; s < nsys; ++s) steps_done[s] = 0; return MI355CG_OK; }
+    HIPCK(hipSetDevice(c->device));
+    if (int rc = onchip_steps_ensure(c, nsys, step_iterations ? (long long)nsys * nsteps : 0, true)) return rc;
+    const size_t count = (size_t)c->pk_len * (size_t)nsys, bytes = sizeof(double) * count;
+    double* stage = c->many->stage;                                // g in the first half, the states in the second
+    if (g) HIPCK(hipMemcpyAsync(stage, g, bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCK(hipMemcpyAsync(stage + count, u, bytes, hipMemcpyHostToDevice, c->stream));
+    if (int rc = steps_many(c, prm, nsys, nsteps, theta, tau, g ? stage : nullptr, stage + count, stop_flag, out, steps_done, step_iterations)) return rc;
+    HIPCK(hipMemcpyAsync(u, stage + count, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(hipStreamSynchronize(c->stream));
+    return MI355CG_OK;
+}
+int mi355cg_time_steps_many_workspace(int n, int nsys, int nsteps, int with_step_iterations, long long* bytes) {
+    if (!bytes) return fail(MI355CG_ERR_INVALID, "null argument");
+    const long long v = onchip_steps_workspace_bytes(n, nsys, nsteps, with_step_iterations);
+    if (v == 0)
+        return fail(MI355CG_ERR_INVALID, "ensemble rejected: even n from 6 to %d, 1 .. %d members, 0 .. %d steps, at most %lld iteration counts",
+                    kOnchipMaxN, kOnchipStepsMaxSys, kOnchipStepsMaxSteps, kOnchipStepsMaxCounts);
+    *bytes = v;
     return MI355CG_OK;
 }
 

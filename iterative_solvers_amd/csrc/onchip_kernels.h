@@ -17,7 +17,9 @@
 //
 // The iteration is written once, in oc_chunk.  k_onchip runs it on the handle's own vectors; k_onchip_many on
 // system blockIdx.x of a batch of independent systems of one grid -- own right-hand side, guess and diagonal each --, with an LDS
-// allocation that follows N, so that small grids share a CU; k_onchip_many_init starts all systems of a batch on the device.
+// allocation that follows N, so that small grids share a CU; k_onchip_many_init starts all systems of a batch on the device;
+// k_onchip_steps alternates it with the start of the next time step of member blockIdx.x of an ensemble, so
+// that a workgroup takes its member through all its steps inside the launches.
 #pragma once
 #include "cg_kernels.h"
 #include "onchip_plan.h"
@@ -125,6 +127,9 @@ struct OcOne {
     __device__ static double* dir(const OnchipArgs& a, int it) { return a.p[it % a.xsteps]; }
     __device__ static long long off(const OnchipArgs& a, int /*i*/, int xx, int yy) { return (long long)(row_off(a.g, yy) + xx - a.g.base0); }
     __device__ static void finished(const Args&) {}
+    __device__ static int budget(const Args& a) { return a.m; }                            // iterations of this chunk
+    __device__ static int tid() { return threadIdx.x; }
+    __device__ static StateLite state(const Args& a) { return load_state_lite(a.s); }
 };
 // k_onchip_many: system blockIdx.x of a batch.  Vectors in PACKED order (unknown i of onchip_plan.h at i: the
 // order of the host interface), one direction buffer, one slot of partials, no history ring, the diagonal from a device array.
@@ -172,6 +177,9 @@ struct OcMany {
     __device__ static double* dir(const OnchipManyArgs& a, int) { return a.p + sys() * a.stride; }
     __device__ static long long off(const OnchipManyArgs&, int i, int, int) { return i; }
     __device__ static void finished(const Args& a) { atomicAdd(a.done_count, 1); }       // thread 0, once per system: the launch in which its state turns done
+    __device__ static int budget(const Args& a) { return a.m; }
+    __device__ static int tid() { return threadIdx.x; }
+    __device__ static StateLite state(const Args& a) { return load_state_lite(s(a)); }
 };
 
 // The iteration body, written once.  Its LDS is the system type's (Sys::lds): img, pl.cells doubles; scrA, scrB, kOcWaves x
@@ -190,14 +198,14 @@ __device__ __forceinline__ void oc_chunk(const typename Sys::Args a) {
     const int has_u = Sys::has_u(a), u_always = Sys::u_always(a), every = Sys::every(a);
     const OnchipPlan& pl = a.pl;
     const RuleParams& rp = a.rp;
-    const int m = a.m;
+    const int m = Sys::budget(a);
     const int* const stop_req = a.stop_req;
     const OcLds lds = Sys::lds(pl.cells);
     double* const img = lds.img; double* const scrA = lds.scrA; double* const scrB = lds.scrB; CgState* const st = lds.st;
     static_assert(sizeof(CgState) % sizeof(double) == 0, "the state travels as doubles");
     constexpr int kStateWords = (int)(sizeof(CgState) / sizeof(double));
-    const int t = threadIdx.x, T = blockDim.x, nwaves = T / kWave;
-    StateLite s = load_state_lite(Sys::s(a));
+    const int t = Sys::tid(), T = blockDim.x, nwaves = T / kWave;
+    StateLite s = Sys::state(a);
     if (s.done) return;                                // the state already says done: x, r, the state and the partials stay
     const bool use_u = MSG && has_u;
 
@@ -403,30 +411,41 @@ struct OnchipManyInitArgs {
     double* partB; CgState* s; CgState* summary; double* norm0; int* done_count;
     RuleParams rp;
 };
-template <bool WARM>
-__global__ __launch_bounds__(kOnchipMaxThreads) void k_onchip_many_init(const OnchipManyInitArgs a) {
-    const OnchipPlan& pl = a.pl;
-    const OcLds l = OcMany::lds(pl.cells);
-    const int t = threadIdx.x, T = blockDim.x, nwaves = T / kWave;
-    const long long sys = blockIdx.x, base = sys * a.stride;
-    const double* b = a.b + base;
+// Where the start takes b from.  OcBVector: a packed vector.  OcBStep: the right-hand side of a theta-scheme step, formed in
+// registers from the image of the state (which the warm start holds anyway) and the forcing g -- it is never stored, CG needs only
+// r and ||b||_2.  The step's expression is onchip_step_rhs (onchip_plan.h), k_step_rhs's: the neighbours in that order.
+struct OcBVector {
+    const double* b;
+    __device__ double at(int i, int, const double*, int) const { return b[i]; }
+};
+struct OcBStep {
+    const double* g; OnchipStepCoef k; double sigma;
+    __device__ double at(int i, int c, const double* img, int pitch) const {
+        return onchip_step_rhs(k, sigma, g[i], img[c], img[c - 1], img[c + 1], img[c - pitch], img[c + pitch]);
+    }
+};
+// One system's share of the workspace, as the start writes it.  COUNT: a system whose start state says done is counted in
+// *done_count (a batch: it is finished; a stepping member is not: its next step follows).
+struct OcStartOut { double* x; double* r; double* p; double* partB; CgState* s; CgState* summary; double* norm0; int* done_count; };
+template <bool WARM, bool COUNT, class B>
+__device__ __forceinline__ void oc_start(const OnchipPlan& pl, const OcLds& l, const RuleParams& rp, double diag, double cxk, double cyk,
+                                         const double* x0, const OcStartOut& o, const B& bsrc, int t) {
+    const int T = blockDim.x, nwaves = T / kWave;
     if (WARM) {
-        const double* x0 = a.x0 + base;
         for (int i = t; i < pl.cells; i += T) l.img[i] = 0.0;
         __syncthreads();
         for (int i = t; i < pl.unknowns; i += T) { int xx, yy; onchip_node(pl, i, &xx, &yy); l.img[onchip_cell(pl, xx, yy)] = x0[i]; }
         __syncthreads();
     }
-    const double cA = WARM ? a.diag[sys] : 0.0, cxk = a.xk, cyk = a.yk;
+    const double cA = WARM ? diag : 0.0;
     const int pitch = pl.pitch;
     OcSumsB v{dd_zero(), dd_zero(), dd_zero(), 0.0, 0.0, 0.0, 0.0};       // d2 carries (b, b)
     for (int i = t; i < pl.unknowns; i += T) {
-        const double bv = b[i];
+        int c = 0;
+        if (WARM) { int xx, yy; onchip_node(pl, i, &xx, &yy); c = onchip_cell(pl, xx, yy); }
+        const double bv = bsrc.at(i, c, l.img, pitch);
         double rv = bv, xv = 0.0;
         if (WARM) {
-            int xx, yy;
-            onchip_node(pl, i, &xx, &yy);
-            const int c = onchip_cell(pl, xx, yy);
             xv = l.img[c];
             double ax = cA * xv;                                   // apply_at of the chunk body: k_stencil's formula
             ax = ax + cxk * l.img[c - 1];
@@ -438,32 +457,137 @@ __global__ __launch_bounds__(kOnchipMaxThreads) void k_onchip_many_init(const On
         }
         dd_acc_prod(v.rr, rv, rv);
         v.rmax = fmax(v.rmax, fabs(rv));
-        a.x[base + i] = xv; a.r[base + i] = rv; a.p[base + i] = 0.0;
+        o.x[i] = xv; o.r[i] = rv; o.p[i] = 0.0;
     }
     oc_publish_b<true>(v, l.scrB);
     if (t != 0) return;
     const OcSumsB tot = oc_combine_b<true>(l.scrB, nwaves);
-    double* q = a.partB + sys * FB_COUNT;
+    double* q = o.partB;
     q[FB_RR] = tot.rr.hi; q[FB_RR + FB_LO] = tot.rr.lo;
     q[FB_D2] = 0.0; q[FB_D2 + FB_LO] = 0.0; q[FB_E2] = 0.0; q[FB_E2 + FB_LO] = 0.0;
     q[FB_RMAX] = tot.rmax; q[FB_DMAX] = 0.0; q[FB_EMAX] = 0.0;
     const double rr = dd_value(tot.rr);
-    CgState* sp = a.s + sys;
+    CgState* sp = o.s;
     *sp = CgState{};
     sp->first = 1;
-    a.norm0[sys] = sqrt(rr);
+    *o.norm0 = sqrt(rr);
     if (WARM) {
         sp->r0norm = sqrt(dd_value(tot.d2)); sp->first = 2;
-        if (a.rp.rule == 0 /*MSG_MAXNORM*/) {
+        if (rp.rule == 0 /*MSG_MAXNORM*/) {
             StateLite s{};
             s.r0norm = sp->r0norm; s.first = 2;
-            const Decision d = decide_after_update(s, a.rp, rr, tot.rmax, 0.0, 0.0, 0.0, 0.0);
-            const bool met = !a.rp.fixed_iterations && a.rp.eps_residual > 0 && tot.rmax < a.rp.eps_residual;      // msg_stop_reason(prm, false, ..)
-            CgState* sm = a.summary + sys;
+            const Decision d = decide_after_update(s, rp, rr, tot.rmax, 0.0, 0.0, 0.0, 0.0);
+            const bool met = !rp.fixed_iterations && rp.eps_residual > 0 && tot.rmax < rp.eps_residual;      // msg_stop_reason(prm, false, ..)
+            CgState* sm = o.summary;
             write_state_after_decision<true>(sm, nullptr, sp, s, d);
             if (met) { sm->done = 1; sm->converged = 1; sm->reason = 2 /*RESIDUAL*/; }
-            if (d.done || met) { *sp = *sm; atomicAdd(a.done_count, 1); }
+            if (d.done || met) { *sp = *sm; if (COUNT) atomicAdd(o.done_count, 1); }
         }
+    }
+}
+template <bool WARM>
+__global__ __launch_bounds__(kOnchipMaxThreads) void k_onchip_many_init(const OnchipManyInitArgs a) {
+    const long long sys = blockIdx.x, base = sys * a.stride;
+    const OcStartOut o{a.x + base, a.r + base, a.p + base, a.partB + sys * FB_COUNT, a.s + sys, a.summary + sys, a.norm0 + sys, a.done_count};
+    oc_start<WARM, true>(a.pl, OcMany::lds(a.pl.cells), a.rp, WARM ? a.diag[sys] : 0.0, a.xk, a.yk, WARM ? a.x0 + base : nullptr, o,
+                         OcBVector{a.b + base}, threadIdx.x);
+}
+
+// ---- ensemble time stepping: the step loop inside the launch ----------------------------------------------
+// Member blockIdx.x of an ensemble on one grid is integrated over nsteps theta-scheme steps of u_t = A u - g_s with its own step
+// tau_s: every step is the warm-started solve of (A - sigma_s I) u' = b_step(u), sigma_s = 1 / (theta tau_s), that
+// mi355cg_time_steps runs on a handle, and ONE workgroup takes the member from its first step to its last.  A launch gives each
+// member `m` units: a CG iteration costs one, the transition from a converged step to the next costs one, so a launch is bounded by
+// m whatever happens (runs of 0-iteration steps included).  The kernel alternates oc_chunk on the member's workspace (x, r, the
+// direction, the state: what a batch keeps per system) with the transition: record the step, the new state u = x from the
+// workspace into the image, b_step in registers, the warm start of k_onchip_many_init on it (oc_start).  A member ends after its
+// last step or after the first step that does not converge (iteration cap, stop request) and is then counted in *done_count, once.
+struct OcStepBook { int step, ended; };       // converged steps so far (the index of the step being solved); the member has ended
+static_assert(sizeof(double) + sizeof(OcStepBook) == kOnchipStepsSysBytes, "onchip_plan.h: a member's share of the stepping workspace");
+struct OnchipStepsArgs {                 // (its own copies of what it shares with OnchipManyArgs: the chunk's arguments stay whole)
+    OnchipPlan pl;
+    double xk, yk;
+    const double* diag; const double* sigma;         // nsys each: A_diag - sigma_s as mi355cg_set_shift rounds it; sigma_s
+    const double* g; long long g_stride;             // forcing: member s reads g + s * g_stride (0: one vector for all)
+    const double* u0;                                // k_onchip_steps_init: nsys packed start states of `stride` doubles
+    double* x; double* r; double* p;
+    long long stride;
+    double* partB; CgState* s; CgState* summary; double* norm0; int* done_count;
+    OcStepBook* book;                                // nsys
+    int* step_it; int nsteps;                        // nsys x nsteps iteration counts, or null
+    OnchipStepCoef k;
+    RuleParams rp;
+    int m;                                           // units of this launch
+};
+__device__ inline int oc_wg_load(const int* p) {     // what a thread of this workgroup stored before the last barrier; uniform
+    return __builtin_amdgcn_readfirstlane(__hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+}
+// The system type of a stepping member: a batch's system, whose chunk length is what is left of the launch's budget (a word of the
+// LDS side data, written before the barrier in front of the chunk) and whose state is re-read after stores of this very launch --
+// with vector loads: the scalar cache is only invalidated at kernel start.  The step kernel counts finished members itself.
+struct OcSteps : OcMany {
+    __device__ static int budget(const Args&) {
+        extern __shared__ __attribute__((aligned(16))) char oc_dyn_lds[];
+        return __builtin_amdgcn_readfirstlane(*reinterpret_cast<const int*>(oc_dyn_lds + kOnchipBudgetOffset));
+    }
+    __device__ static StateLite state(const Args& a) {
+        const CgState* p = s(a);
+        auto ld = [](const double* q) { return __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); };
+        StateLite L;
+        L.alpha = ld(&p->alpha); L.rr = ld(&p->rr); L.rr_prev = ld(&p->rr_prev); L.rz = ld(&p->rz); L.r0norm = ld(&p->r0norm);
+        L.it = oc_wg_load(&p->it); L.done = oc_wg_load(&p->done); L.first = oc_wg_load(&p->first); L.stop = oc_wg_load(&p->stop);
+        return L;
+    }
+    __device__ static void finished(const Args&) {}
+    // The thread index, opaque to the optimizer, taken anew by every pass of the step loop: what a pass derives from it (the nodes,
+    // cells and offsets of its slots) would otherwise be computed once in front of the loop and kept in registers across all of it.
+    __device__ static int tid() { int t = threadIdx.x; asm volatile("" : "+v"(t)); return t; }
+};
+__device__ __forceinline__ void oc_step_start(const OnchipStepsArgs& e, const OcLds& l, const double* x0, int t) {
+    const long long sys = blockIdx.x, base = sys * e.stride;
+    const OcStartOut o{e.x + base, e.r + base, e.p + base, e.partB + sys * FB_COUNT, e.s + sys, e.summary + sys, e.norm0 + sys, nullptr};
+    oc_start<true, false>(e.pl, l, e.rp, e.diag[sys], e.xk, e.yk, x0, o, OcBStep{e.g + sys * e.g_stride, e.k, e.sigma[sys]}, t);
+}
+// the first step's start, from the caller's states (the book is zeroed by the host)
+__global__ __launch_bounds__(kOnchipMaxThreads) void k_onchip_steps_init(const OnchipStepsArgs e) {
+    oc_step_start(e, OcMany::lds(e.pl.cells), e.u0 + blockIdx.x * e.stride, threadIdx.x);
+}
+template <int E, bool MSG>
+__global__ __launch_bounds__(kOnchipMaxThreads) void k_onchip_steps(const OnchipManyArgs a, const OnchipStepsArgs e) {
+    extern __shared__ __attribute__((aligned(16))) char oc_dyn_lds[];
+    int* const budget_w = reinterpret_cast<int*>(oc_dyn_lds + kOnchipBudgetOffset);
+    const int t = threadIdx.x;
+    const long long sys = blockIdx.x;
+    OcStepBook* const bk = e.book + sys;
+    const CgState* const sp = e.s + sys;
+    if (oc_wg_load(&bk->ended)) return;
+    int step = oc_wg_load(&bk->step), budget = e.m;
+    for (;;) {                                                     // every pass but the last costs a unit or more
+        int done = oc_wg_load(&sp->done);
+        if (!done) {
+            if (budget < 1) break;
+            const int it0 = oc_wg_load(&sp->it);
+            if (t == 0) *budget_w = budget;
+            __syncthreads();
+            oc_chunk<E, MSG, OcSteps>(a);
+            __syncthreads();                                       // the state the chunk left, for every thread
+            budget -= oc_wg_load(&sp->it) - it0;
+            done = oc_wg_load(&sp->done);
+            if (!done) break;                                      // the budget ran out inside the step
+        }
+        // the step is over: the member's end, or the transition to its next step
+        const int conv = oc_wg_load(&sp->converged);
+        const bool last = !conv || step + 1 >= e.nsteps;
+        if (!last && budget < 1) break;                            // the transition waits for the next launch
+        if (t == 0) {
+            if (e.step_it) e.step_it[sys * e.nsteps + step] = oc_wg_load(&sp->it);
+            bk->step = step + (conv ? 1 : 0);
+            if (last) { bk->ended = 1; atomicAdd(e.done_count, 1); }
+        }
+        if (last) break;
+        budget -= 1; ++step;
+        oc_step_start(e, OcMany::lds(e.pl.cells), e.x + sys * e.stride, OcSteps::tid());      // u: the x the chunk (or the start before it) left
+        __syncthreads();                                           // thread 0's state, partials and norm
     }
 }
 

@@ -86,6 +86,38 @@ MI355CG_HD inline long long onchip_many_workspace_bytes(int n, int nsys) {
     return (long long)nsys * (3LL * 8 * onchip_plan(n).unknowns + kOnchipManySysBytes) + kOnchipManyFixedBytes;
 }
 
+// ---- ensemble time stepping: the step loop inside the launch (k_onchip_steps) --------------------------------
+// The right-hand side of one theta-scheme step of u_t = A u - g at ONE node: k_step_rhs's expression (step_kernels.h) in its order,
+//   b = (stencil ? g / theta : g) - sigma u;   stencil (theta < 1):  b = b - c1 (A0 u + xk (left + right) + yk (down + up)),
+// with the UNSHIFTED diagonal A0 and c1 = (1 - theta) / theta.  Not the summation order of the CG stencil (apply_at).  Plain fp64,
+// no contraction: every translation unit that calls it is compiled with -ffp-contract=off.
+struct OnchipStepCoef { double A0, xk, yk, theta, c1; int stencil; };
+MI355CG_HD inline double onchip_step_rhs(const OnchipStepCoef& k, double sigma, double g, double uc, double left, double right, double down, double up) {
+    double b = (k.stencil ? g / k.theta : g) - sigma * uc;
+    if (k.stencil) {
+        const double au = k.A0 * uc + k.xk * (left + right) + k.yk * (down + up);
+        b = b - k.c1 * au;
+    }
+    return b;
+}
+// The launch's budget of units (one CG iteration or one step transition each) travels to the chunk body through one word of the
+// side data, behind the CG state (184 bytes of the 256 reserved for it).
+constexpr int kOnchipBudgetOffset = kOnchipSideBytes - 64;
+// Device workspace of nsys members: that of a batch of nsys systems, per member its shift 1 / (theta tau_s) and the step
+// bookkeeping (step index, ended flag), one packed vector (the handle's right-hand side, for g = NULL), and the iteration counts
+// of nsys x nsteps steps (ints) when the caller asks for them.  (The host entry point stages u and g on top: 2 nsys packed vectors.)
+// 0: refused -- a size the plan refuses or an ensemble beyond the limits of mi355cg_time_steps_many.
+constexpr int kOnchipStepsMaxSys = 65536, kOnchipStepsMaxSteps = 65536;
+constexpr long long kOnchipStepsMaxCounts = 1LL << 26;
+constexpr int kOnchipStepsSysBytes = 8 + 2 * 4;
+MI355CG_HD inline long long onchip_steps_workspace_bytes(int n, int nsys, int nsteps, int with_step_iterations) {
+    if (!onchip_supported(n) || nsys < 1 || nsys > kOnchipStepsMaxSys || nsteps < 0 || nsteps > kOnchipStepsMaxSteps) return 0;
+    const long long counts = with_step_iterations ? (long long)nsys * nsteps : 0;
+    if (counts > kOnchipStepsMaxCounts) return 0;
+    return onchip_many_workspace_bytes(n, nsys) + (long long)nsys * kOnchipStepsSysBytes + 8LL * onchip_plan(n).unknowns + 4 * counts;
+}
+
+static_assert(kOnchipSideBytes - 256 + 184 <= kOnchipBudgetOffset && kOnchipBudgetOffset % 8 == 0, "the budget word lies behind the CG state");
 static_assert(kOnchipMaxCells * 8 + kOnchipSideBytes <= kOnchipLdsLimit, "the image of the largest grid and the side data fit in one CU's LDS");
 static_assert((kOnchipMaxCells * 8 + 15) / 16 * 16 + kOnchipSideBytes <= kOnchipLdsLimit, "... with the image rounded up to 16 bytes too");
 static_assert(kOnchipMaxThreads * kOnchipMaxElems >= (kOnchipMaxN / 2 - 1) * (3 * kOnchipMaxN / 2 - 1), "every unknown of the largest grid has a slot");

@@ -370,6 +370,58 @@ class _Handle:
         _capi.check(rc)
         return x, list(res)
 
+    def time_steps_many(self, params: _capi.Params, u0, tau, theta: float, nsteps: int, g=None, stop_flag: Optional[C.c_int] = None):
+        """Extension (no reference twin): an ensemble of time steppers on this grid, one workgroup per member with the step loop
+        inside the launch (mi355cg_time_steps_many; the handles solve_many takes).  Member s is integrated over nsteps steps of the
+        theta scheme for u_t = A u - g[s] from u0[s] with its own time step tau[s] and gets the bits set_rhs(g[s]);
+        set_initial_guess(u0[s]); time_steps(params, tau[s], theta, nsteps) give; the handle itself is left as it was.  Returns
+        (u, [Results of the last step attempted per member], steps_done int32 [nsys], step_iterations int32 [nsys, nsteps], -1 =
+        step not taken).  u0: NumPy [nsys, size] float64 -> NumPy u; or a contiguous CUDA torch.Tensor of that shape on the
+        handle's device -> a new tensor there (torch's current stream is synchronised first); not modified.  g: of u0's kind and
+        shape, None = the handle's right-hand side for every member.  tau: a scalar or [nsys] (host values).
+        params.use_true_solution and params.diagnostics must be 0."""
+        nsys, on_device = self._check_batch(u0, self.size, _capi.MANY_MAX)
+        if g is not None:
+            if self._check_batch(g, self.size, _capi.MANY_MAX) != (nsys, on_device):
+                raise ValueError(f"g has shape {tuple(g.shape)}: the forcings are of the kind (NumPy / CUDA tensor) and shape of u0, "
+                                 f"{tuple(u0.shape)}")
+        if hasattr(tau, "data_ptr"):
+            tau = tau.detach().cpu().numpy()
+        tau = np.ascontiguousarray(np.broadcast_to(np.asarray(tau, dtype=np.float64), (nsys,)) if np.ndim(tau) == 0 else tau, dtype=np.float64)
+        if tau.shape != (nsys,):
+            raise ValueError(f"tau has shape {tau.shape}, expected a scalar or ({nsys},)")
+        nsteps = int(nsteps)
+        if not 0 <= nsteps <= _capi.STEPS_MANY_MAX_STEPS:
+            raise ValueError(f"nsteps {nsteps} rejected: it must be 0 .. {_capi.STEPS_MANY_MAX_STEPS}")
+        if nsys * nsteps > 1 << 26:
+            raise ValueError(f"{nsys} members x {nsteps} steps: more than 2^26 iteration counts")
+        res = (_capi.Results * nsys)()
+        steps_done = np.zeros(nsys, dtype=np.int32)
+        step_it = np.full((nsys, nsteps), -1, dtype=np.int32)
+        sp = C.cast(C.pointer(stop_flag), C.c_void_p) if stop_flag is not None else None
+        if on_device:
+            import torch
+            if u0.device.index != self._device:
+                raise ValueError(f"ensemble is on {u0.device}, the handle on device {self._device}")
+            if g is not None and g.device != u0.device:
+                raise ValueError(f"g is on {g.device}, u0 on {u0.device}")
+            u = u0.clone()
+            torch.cuda.current_stream(u0.device).synchronize()
+            rc = self._lib.mi355cg_time_steps_many_device(self._h, C.byref(params), nsys, nsteps, float(theta), tau.ctypes.data,
+                                                          g.data_ptr() if g is not None else None, u.data_ptr(), sp, res,
+                                                          steps_done.ctypes.data, step_it.ctypes.data)
+        else:
+            u = np.array(u0, dtype=np.float64, order="C", copy=True)
+            if g is not None:
+                g = np.ascontiguousarray(g)
+            rc = self._lib.mi355cg_time_steps_many(self._h, C.byref(params), nsys, nsteps, float(theta), tau.ctypes.data,
+                                                   g.ctypes.data if g is not None else None, u.ctypes.data, sp, res,
+                                                   steps_done.ctypes.data, step_it.ctypes.data)
+        if rc == _capi.ERR_INVALID:
+            raise ValueError(self._lib.mi355cg_last_error().decode())
+        _capi.check(rc)
+        return u, list(res), steps_done, step_it
+
     def solve_many_info(self, nsys: int):
         """{"lds_bytes_per_workgroup", "workgroups_per_cu", "workspace_bytes"} of a solve_many batch of nsys systems on this grid
         (mi355cg_solve_many_info); ValueError for handles solve_many refuses."""
@@ -531,6 +583,19 @@ def onchip_plan(n: int):
     return {"threads": t.value, "lds_bytes": lds.value, "elems_per_thread": e.value}
 
 
+def time_steps_many_workspace(n: int, nsys: int, nsteps: int, with_step_iterations: bool = True) -> int:
+    """The device workspace bytes of MatrixFreeSystem.time_steps_many for nsys members and nsteps steps on an n x n grid (host
+    arithmetic, no GPU; mi355cg_time_steps_many_workspace).  The Python interface always asks for the per-step iteration counts.
+    ValueError for a grid or an ensemble the call refuses."""
+    out = C.c_longlong()
+    lib = _capi.load()
+    rc = lib.mi355cg_time_steps_many_workspace(int(n), int(nsys), int(nsteps), 1 if with_step_iterations else 0, C.byref(out))
+    if rc == _capi.ERR_INVALID:
+        raise ValueError(lib.mi355cg_last_error().decode())
+    _capi.check(rc)
+    return out.value
+
+
 def rayleigh_ritz(g, h):
     """The Rayleigh-Ritz step of eigs on the host (mi355cg_rayleigh_ritz, no GPU): for the k x k pair G = S^T S, H = S^T K S
     (k <= 48) returns (theta[k] ascending, coef[k, k]) with coef.T @ G @ coef = I and coef.T @ H @ coef = diag(theta).
@@ -678,6 +743,24 @@ class MatrixFreeSystem:
             params.eps_rel = params.eps_precision = params.eps_residual = eps
             params.use_true_solution = 0
         return self._handle.solve_many(params, b, x0=x0, sigma=sigma)
+
+    def time_steps_many(self, u0, tau, theta: float = 1.0, nsteps: int = 1, g=None, eps: float = 1e-8, max_iterations: int = 10000,
+                        rule: int = _capi.RULE_REL_2NORM, params=None):
+        """Extension (no reference twin): an ensemble of time steppers on this grid -- time_steps for many members at once, ONE
+        workgroup per member from its first step to its last, the step loop inside the launch (grids up to the on-chip cap,
+        N = 128; no preconditioner).  u0: [nsys, size()] float64, NumPy or a CUDA torch tensor, the start states; tau: a time
+        step per member ([nsys]) or one for all; g: a forcing per member, of u0's kind and shape, None = this system's right-hand
+        side for all; theta and nsteps are shared.  Returns (u of u0's kind, one _capi.Results per member for its last step
+        attempted, steps_done [nsys], step_iterations [nsys, nsteps] with -1 for steps not taken), every member with the bits
+        set_rhs(g[s]) and time_steps(u0[s], tau[s], theta, nsteps) give on this system.  A member ends after its first step that
+        does not converge.  Unlike time_steps the call leaves this system as it was, the shift included.  eps, max_iterations
+        (per step), rule as in time_steps; params, if given, is used as it is."""
+        if params is None:
+            params = default_params(rule)
+            params.max_iterations = max_iterations
+            params.eps_rel = params.eps_precision = params.eps_residual = eps
+            params.use_true_solution = 0
+        return self._handle.time_steps_many(params, u0, tau, theta, nsteps, g=g)
 
     def solve_many_info(self, nsys: int):
         """What a solve_many batch of nsys systems costs on this grid: the LDS bytes of one workgroup, how many workgroups the
