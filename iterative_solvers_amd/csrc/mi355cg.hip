@@ -27,6 +27,7 @@
 #include <memory>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 using namespace mi355cg;
@@ -181,6 +182,12 @@ struct OnchipManyWs {
     Buf<int> step_it;                   // iteration counts, member-major, -1 = step not taken: only when the caller asks for them
     long long step_it_cap = 0;          // counts it holds
 };
+
+// `small` and its pinned mirror in a call of nsys <= cap systems: nsys x FB_COUNT update partials, then nsys diagonals, then nsys ||r0||_2
+struct OnchipSmallView { double* partB; double* diag; double* norm0; };
+inline OnchipSmallView onchip_small_view(double* base, int nsys) {
+    return OnchipSmallView{base, base + (long long)FB_COUNT * nsys, base + (long long)(FB_COUNT + 1) * nsys};
+}
 
 }  // namespace
 
@@ -1617,19 +1624,92 @@ int solve_mg_batch(mi355cg_ctx* c, const mi355cg_params* prm, int nrhs, const do
     return MI355CG_OK;
 }
 
+// What the on-chip mode refuses (nullptr: the handle is eligible): every handle whose iteration is not the plain fp64 grid CG, and
+// grids whose direction does not fit in one CU's LDS.
+const char* onchip_refusal(const mi355cg_ctx* c) {
+    static char buf[160];
+    if (c->is_csr) return "the on-chip solve keeps the grid's direction in LDS: a CSR handle has no grid";
+    if (c->is_slab) return "the on-chip solve is one workgroup on one GPU: this handle owns one part of a decomposed grid";
+    if (c->dtype != MI355CG_F64) return "the on-chip solve is fp64 only: this handle was created with MI355CG_F32_MIXED";
+    if (c->mg) return "the on-chip solve runs plain CG: this handle has a preconditioner (mi355cg_set_preconditioner(h, MI355CG_PRECOND_NONE) first)";
+    if (!onchip_supported(c->gp.n)) {
+        snprintf(buf, sizeof buf, "the on-chip solve takes grids up to N = %d (the direction must fit in one CU's LDS): this handle has N = %d", kOnchipMaxN, c->gp.n);
+        return buf;
+    }
+    return nullptr;
+}
+
+// The refusals the batched entry points share, each written once; what differs is what a kind of batch calls its parts.  Every
+// entry point runs the ones it has in its own order (batch_check, many_check, steps_many_check, mi355cg_solve_many_info).
+struct BatchKind {
+    int most; const char* count_text;                              // "... 1 .. %d <things>, not %d"
+    const char* no_exact; const char* no_callbacks;
+    const char* plain_cg;                                          // on-chip kinds: what the entry point is, to a handle with a preconditioner
+    int count(int n) const { return n < 1 || n > most ? fail(MI355CG_ERR_INVALID, count_text, most, n) : MI355CG_OK; }
+    int params(const mi355cg_params* prm) const {
+        if (prm->rule != MI355CG_RULE_MSG_MAXNORM && prm->rule != MI355CG_RULE_REL_2NORM) return fail(MI355CG_ERR_INVALID, "unknown rule %d", prm->rule);
+        if (prm->use_true_solution) return fail(MI355CG_ERR_INVALID, "%s: use_true_solution must be 0", no_exact);
+        if (prm->diagnostics) return fail(MI355CG_ERR_INVALID, "%s has no callbacks: diagnostics must be 0", no_callbacks);
+        return MI355CG_OK;
+    }
+    int onchip(const mi355cg_ctx* c) const {
+        if (c->mg) return fail(MI355CG_ERR_STATE, "this handle has a preconditioner: %s", plain_cg);
+        if (const char* why = onchip_refusal(c)) return fail(MI355CG_ERR_INVALID, "%s", why);
+        return MI355CG_OK;
+    }
+    // two groups of n full vectors each, `first` the one that is written
+    static int apart(const mi355cg_ctx* c, int n, const void* first, const void* second, const char* text) {
+        const size_t bytes = sizeof(double) * (size_t)c->gp.size * (size_t)n;
+        const uintptr_t fb = (uintptr_t)first, sb = (uintptr_t)second;
+        return sb < fb + bytes && fb < sb + bytes ? fail(MI355CG_ERR_INVALID, "%s", text) : MI355CG_OK;
+    }
+};
+const char* const kBatchNoExact = "a batch has no per-system exact solution";
+const BatchKind kMgBatch{MI355CG_BATCH_MAX, "a batch has 1 .. %d right-hand sides, not %d", kBatchNoExact, "a batch", nullptr};
+const BatchKind kOnchipBatch{MI355CG_MANY_MAX, "a batch of on-chip solves has 1 .. %d systems, not %d", kBatchNoExact, "a batch",
+                             "mi355cg_solve_many is plain CG in one workgroup per system (mi355cg_solve_batch is the preconditioned batch)"};
+const BatchKind kEnsemble{MI355CG_MANY_MAX, "an ensemble of on-chip steppers has 1 .. %d members, not %d", "a step has no exact solution", "the stepper",
+                          "mi355cg_time_steps_many is plain CG in one workgroup per member"};
+
 // what both entry points refuse before anything is allocated or written
 int batch_check(mi355cg_ctx* c, const mi355cg_params* prm, int nrhs, const void* b, const void* x, const mi355cg_results* out) {
     if (!c || !prm || !b || !x || !out) return fail(MI355CG_ERR_INVALID, "null argument");
-    if (nrhs < 1 || nrhs > MI355CG_BATCH_MAX) return fail(MI355CG_ERR_INVALID, "a batch has 1 .. %d right-hand sides, not %d", MI355CG_BATCH_MAX, nrhs);
-    if (prm->rule != MI355CG_RULE_MSG_MAXNORM && prm->rule != MI355CG_RULE_REL_2NORM) return fail(MI355CG_ERR_INVALID, "unknown rule %d", prm->rule);
-    if (prm->use_true_solution) return fail(MI355CG_ERR_INVALID, "a batch has no per-system exact solution: use_true_solution must be 0");
-    if (prm->diagnostics) return fail(MI355CG_ERR_INVALID, "a batch has no callbacks: diagnostics must be 0");
-    const size_t bytes = sizeof(double) * (size_t)c->gp.size * (size_t)nrhs;
-    const uintptr_t bb = (uintptr_t)b, xb = (uintptr_t)x;
-    if (bb < xb + bytes && xb < bb + bytes) return fail(MI355CG_ERR_INVALID, "x overlaps b");
+    if (int rc = kMgBatch.count(nrhs)) return rc;
+    if (int rc = kMgBatch.params(prm)) return rc;
+    if (int rc = BatchKind::apart(c, nrhs, x, b, "x overlaps b")) return rc;
     if (!c->mg) return fail(MI355CG_ERR_STATE, "no preconditioner is set on this handle (mi355cg_set_preconditioner): a batch is multigrid-preconditioned CG");
     if (c->mg->cycle != MI355CG_CYCLE_F64) return fail(MI355CG_ERR_INVALID, "a batch runs the fp64 V-cycle: this handle's preconditioner was set with MI355CG_CYCLE_F32");
     return MI355CG_OK;
+}
+
+// A host entry point of a batched solve: the packed vectors go up into the staging buffer, `body(first, second)` runs on them in
+// device memory, `second` comes down.  second_at: where the second group starts (count: b or g in the first half, x or u in the
+// second; 0: one group that goes up and comes down).  A null source is not copied.  The caller has ensured the buffer before.
+template <class Body>
+int run_staged(mi355cg_ctx* c, double* stage, size_t count, size_t second_at, const double* up_first, const double* up_second, double* down, Body body) {
+    const size_t bytes = sizeof(double) * count;
+    double* const second = stage + second_at;
+    if (up_first) HIPCK(hipMemcpyAsync(stage, up_first, bytes, hipMemcpyHostToDevice, c->stream));
+    if (up_second) HIPCK(hipMemcpyAsync(second, up_second, bytes, hipMemcpyHostToDevice, c->stream));
+    if (int rc = body((const double*)stage, second)) return rc;
+    HIPCK(hipMemcpyAsync(down, second, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(hipStreamSynchronize(c->stream));
+    return MI355CG_OK;
+}
+
+// The unroll classes of onchip_plan (OnchipPlan::elems) and the rule as template arguments, for every on-chip kernel:
+// f(std::integral_constant<int, E>, std::bool_constant<MSG>), e.g. to name an instantiation k<decltype(e)::value, decltype(m)::value>.
+template <class F>
+auto onchip_dispatch(int elems, bool msg, F f) {
+    auto with_rule = [&](auto e) { return msg ? f(e, std::true_type{}) : f(e, std::false_type{}); };
+    switch (elems) {
+        case 1: return with_rule(std::integral_constant<int, 1>{});
+        case 2: return with_rule(std::integral_constant<int, 2>{});
+        case 4: return with_rule(std::integral_constant<int, 4>{});
+        case 8: return with_rule(std::integral_constant<int, 8>{});
+        case 16: return with_rule(std::integral_constant<int, 16>{});
+        default: return with_rule(std::integral_constant<int, kOnchipMaxElems>{});
+    }
 }
 
 
@@ -1984,20 +2064,6 @@ extern "C" {
 const char* mi355cg_last_error(void) { return g_err.c_str(); }
 const char* mi355cg_version(void) { return "mi355cg 0.2 (gfx950)"; }
 
-// What the on-chip mode refuses (nullptr: the handle is eligible): every handle whose iteration is not the plain fp64 grid CG, and
-// grids whose direction does not fit in one CU's LDS.
-static const char* onchip_refusal(const mi355cg_ctx* c) {
-    static char buf[160];
-    if (c->is_csr) return "the on-chip solve keeps the grid's direction in LDS: a CSR handle has no grid";
-    if (c->is_slab) return "the on-chip solve is one workgroup on one GPU: this handle owns one part of a decomposed grid";
-    if (c->dtype != MI355CG_F64) return "the on-chip solve is fp64 only: this handle was created with MI355CG_F32_MIXED";
-    if (c->mg) return "the on-chip solve runs plain CG: this handle has a preconditioner (mi355cg_set_preconditioner(h, MI355CG_PRECOND_NONE) first)";
-    if (!onchip_supported(c->gp.n)) {
-        snprintf(buf, sizeof buf, "the on-chip solve takes grids up to N = %d (the direction must fit in one CU's LDS): this handle has N = %d", kOnchipMaxN, c->gp.n);
-        return buf;
-    }
-    return nullptr;
-}
 // What every handle keeps, grid or CSR: the partials of the two phases and of the flat reductions, the device-side CG state with
 // its history, and their pinned copies.  The zero-fills run on the NULL stream and are asynchronous to the host; the context's own
 // stream is non-blocking and does not order with them.  Without the callers' device-wide wait after it a delayed memset can land
@@ -2317,19 +2383,10 @@ static void launch_onchip_chunk(mi355cg_ctx* c, const IterCfg& cfg, const mi355c
     a.s = c->sB; a.hist = c->hist; a.rp = cfg.rp;
     a.has_u = cfg.has_u ? 1 : 0; a.u_always = cfg.rp.eps_exact_error > 0 ? 1 : 0; a.every = prm->callback_every;       // need_u of mi355cg_solve
     a.m = m; a.stop_req = c->stop_dev;
-    const dim3 grid(1), block(a.pl.threads);
-    const bool msg = cfg.rp.rule == MI355CG_RULE_MSG_MAXNORM;
-#define MI355CG_OC(E) do { if (msg) hipLaunchKernelGGL((k_onchip<E, true>), grid, block, 0, c->stream, a); \
-                           else hipLaunchKernelGGL((k_onchip<E, false>), grid, block, 0, c->stream, a); } while (0)
-    switch (a.pl.elems) {
-        case 1: MI355CG_OC(1); break;
-        case 2: MI355CG_OC(2); break;
-        case 4: MI355CG_OC(4); break;
-        case 8: MI355CG_OC(8); break;
-        case 16: MI355CG_OC(16); break;
-        default: MI355CG_OC(kOnchipMaxElems); break;
-    }
-#undef MI355CG_OC
+    const void* k = onchip_dispatch(a.pl.elems, cfg.rp.rule == MI355CG_RULE_MSG_MAXNORM,
+                                    [](auto e, auto m) { return (const void*)&k_onchip<decltype(e)::value, decltype(m)::value>; });
+    void* args[] = {&a};
+    hipLaunchKernel(k, dim3(1), dim3(a.pl.threads), args, 0, c->stream);
     c->nB_own = 1;                               // the chunk leaves its update partials in one slot
     ++c->onchip_launches;
 }
@@ -2879,50 +2936,41 @@ int mi355cg_apply_preconditioner(mi355cg_handle c, const double* r, double* z) {
 }
 
 // ---- batched solves: nrhs right-hand sides by one multigrid-PCG loop ----------------------------------------
+// warm (the _from entry points): a guess per system, x is in/out; system s gets the bits of set_rhs(b_s); set_initial_guess(x0_s); solve; get_solution.
+static int solve_batch_device(mi355cg_ctx* c, const mi355cg_params* prm, int nrhs, const double* b_dev, double* x_dev,
+                              const volatile int* stop_flag, mi355cg_results* out, bool warm) {
+    if (int rc = batch_check(c, prm, nrhs, b_dev, x_dev, out)) return rc;
+    HIPCK(hipSetDevice(c->device));
+    if (int rc = mg_batch_ensure(c, nrhs, 0)) return rc;
+    return solve_mg_batch(c, prm, nrhs, b_dev, x_dev, stop_flag, out, warm);
+}
+static int solve_batch_host(mi355cg_ctx* c, const mi355cg_params* prm, int nrhs, const double* b, double* x,
+                            const volatile int* stop_flag, mi355cg_results* out, bool warm) {
+    if (int rc = batch_check(c, prm, nrhs, b, x, out)) return rc;
+    HIPCK(hipSetDevice(c->device));
+    if (int rc = mg_batch_ensure(c, nrhs, warm ? 2 * nrhs : nrhs)) return rc;
+    // cold: b goes up and x comes down through the same buffer; warm: b in the first half, the guesses (then the solutions) in the second
+    const size_t count = (size_t)c->pk_len * (size_t)nrhs;
+    return run_staged(c, c->batch->stage, count, warm ? count : 0, b, warm ? x : nullptr, x, [&](const double* b_dev, double* x_dev) {
+        return solve_mg_batch(c, prm, nrhs, b_dev, x_dev, stop_flag, out, warm);
+    });
+}
+
 int mi355cg_solve_batch_device(mi355cg_handle c, const mi355cg_params* prm, int nrhs, const double* b_dev, double* x_dev,
                                const volatile int* stop_flag, mi355cg_results* out) {
-    if (int rc = batch_check(c, prm, nrhs, b_dev, x_dev, out)) return rc;
-    HIPCK(hipSetDevice(c->device));
-    if (int rc = mg_batch_ensure(c, nrhs, 0)) return rc;
-    return solve_mg_batch(c, prm, nrhs, b_dev, x_dev, stop_flag, out);
+    return solve_batch_device(c, prm, nrhs, b_dev, x_dev, stop_flag, out, false);
 }
-
 int mi355cg_solve_batch(mi355cg_handle c, const mi355cg_params* prm, int nrhs, const double* b, double* x,
                         const volatile int* stop_flag, mi355cg_results* out) {
-    if (int rc = batch_check(c, prm, nrhs, b, x, out)) return rc;
-    HIPCK(hipSetDevice(c->device));
-    if (int rc = mg_batch_ensure(c, nrhs, nrhs)) return rc;
-    double* stage = c->batch->stage;                               // b goes up and x comes down through the same buffer
-    const size_t bytes = sizeof(double) * (size_t)c->pk_len * (size_t)nrhs;
-    HIPCK(hipMemcpyAsync(stage, b, bytes, hipMemcpyHostToDevice, c->stream));
-    if (int rc = solve_mg_batch(c, prm, nrhs, stage, stage, stop_flag, out)) return rc;
-    HIPCK(hipMemcpyAsync(x, stage, bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCK(hipStreamSynchronize(c->stream));
-    return MI355CG_OK;
+    return solve_batch_host(c, prm, nrhs, b, x, stop_flag, out, false);
 }
-
-// The same with a guess per system: x is in/out.  System s gets the bits of set_rhs(b_s); set_initial_guess(x0_s); solve; get_solution.
 int mi355cg_solve_batch_device_from(mi355cg_handle c, const mi355cg_params* prm, int nrhs, const double* b_dev, double* x_dev,
                                     const volatile int* stop_flag, mi355cg_results* out) {
-    if (int rc = batch_check(c, prm, nrhs, b_dev, x_dev, out)) return rc;
-    HIPCK(hipSetDevice(c->device));
-    if (int rc = mg_batch_ensure(c, nrhs, 0)) return rc;
-    return solve_mg_batch(c, prm, nrhs, b_dev, x_dev, stop_flag, out, true);
+    return solve_batch_device(c, prm, nrhs, b_dev, x_dev, stop_flag, out, true);
 }
-
 int mi355cg_solve_batch_from(mi355cg_handle c, const mi355cg_params* prm, int nrhs, const double* b, double* x,
                              const volatile int* stop_flag, mi355cg_results* out) {
-    if (int rc = batch_check(c, prm, nrhs, b, x, out)) return rc;
-    HIPCK(hipSetDevice(c->device));
-    if (int rc = mg_batch_ensure(c, nrhs, 2 * nrhs)) return rc;
-    double* stage = c->batch->stage;                               // b in the first half, the guesses (then the solutions) in the second
-    const size_t count = (size_t)c->pk_len * (size_t)nrhs, bytes = sizeof(double) * count;
-    HIPCK(hipMemcpyAsync(stage, b, bytes, hipMemcpyHostToDevice, c->stream));
-    HIPCK(hipMemcpyAsync(stage + count, x, bytes, hipMemcpyHostToDevice, c->stream));
-    if (int rc = solve_mg_batch(c, prm, nrhs, stage, stage + count, stop_flag, out, true)) return rc;
-    HIPCK(hipMemcpyAsync(x, stage + count, bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCK(hipStreamSynchronize(c->stream));
-    return MI355CG_OK;
+    return solve_batch_host(c, prm, nrhs, b, x, stop_flag, out, true);
 }
 
 int mi355cg_batch_release(mi355cg_handle c) {
@@ -2938,16 +2986,10 @@ int mi355cg_batch_release(mi355cg_handle c) {
 // what every entry point refuses before anything is allocated or written (sigma: checked by the caller, once it is in host memory)
 static int many_check(mi355cg_ctx* c, const mi355cg_params* prm, int nsys, const void* b, const void* x, const mi355cg_results* out) {
     if (!c || !prm || !b || !x || !out) return fail(MI355CG_ERR_INVALID, "null argument");
-    if (nsys < 1 || nsys > MI355CG_MANY_MAX) return fail(MI355CG_ERR_INVALID, "a batch of on-chip solves has 1 .. %d systems, not %d", MI355CG_MANY_MAX, nsys);
-    if (prm->rule != MI355CG_RULE_MSG_MAXNORM && prm->rule != MI355CG_RULE_REL_2NORM) return fail(MI355CG_ERR_INVALID, "unknown rule %d", prm->rule);
-    if (prm->use_true_solution) return fail(MI355CG_ERR_INVALID, "a batch has no per-system exact solution: use_true_solution must be 0");
-    if (prm->diagnostics) return fail(MI355CG_ERR_INVALID, "a batch has no callbacks: diagnostics must be 0");
-    if (c->mg) return fail(MI355CG_ERR_STATE, "this handle has a preconditioner: mi355cg_solve_many is plain CG in one workgroup per system (mi355cg_solve_batch is the preconditioned batch)");
-    if (const char* why = onchip_refusal(c)) return fail(MI355CG_ERR_INVALID, "%s", why);
-    const size_t bytes = sizeof(double) * (size_t)c->gp.size * (size_t)nsys;
-    const uintptr_t bb = (uintptr_t)b, xb = (uintptr_t)x;
-    if (bb < xb + bytes && xb < bb + bytes) return fail(MI355CG_ERR_INVALID, "x overlaps b");
-    return MI355CG_OK;
+    if (int rc = kOnchipBatch.count(nsys)) return rc;
+    if (int rc = kOnchipBatch.params(prm)) return rc;
+    if (int rc = kOnchipBatch.onchip(c)) return rc;
+    return BatchKind::apart(c, nsys, x, b, "x overlaps b");
 }
 static int many_check_sigma(const double* sigma, int nsys) {
     for (int s = 0; sigma && s < nsys; ++s)
@@ -2984,16 +3026,7 @@ static int onchip_many_ensure(mi355cg_ctx* c, int nsys, bool stage) {
 }
 
 static const void* onchip_many_kernel(int elems, bool msg) {
-#define MI355CG_OCM(E) return msg ? (const void*)&k_onchip_many<E, true> : (const void*)&k_onchip_many<E, false>
-    switch (elems) {
-        case 1: MI355CG_OCM(1);
-        case 2: MI355CG_OCM(2);
-        case 4: MI355CG_OCM(4);
-        case 8: MI355CG_OCM(8);
-        case 16: MI355CG_OCM(16);
-        default: MI355CG_OCM(kOnchipMaxElems);
-    }
-#undef MI355CG_OCM
+    return onchip_dispatch(elems, msg, [](auto e, auto m) { return (const void*)&k_onchip_many<decltype(e)::value, decltype(m)::value>; });
 }
 // Dynamic LDS above 64 KB is opt-in per kernel.
 static int onchip_many_allow_lds(const void* kernel, int lds) {
@@ -3001,83 +3034,123 @@ static int onchip_many_allow_lds(const void* kernel, int lds) {
     return MI355CG_OK;
 }
 
+// One call of mi355cg_solve_many* or mi355cg_time_steps_many* on the handle's OnchipManyWs: everything the two have in common.  A
+// caller supplies the diagonals, its start kernel, how long a launch is and what a finished member reports, in this order:
+//   open;  host.diag[s] = ...;  upload_diag;  reset_done;  [its own resets];  start(its start kernel);  begin_loop;
+//   while (more()) { its cap test;  a.m or its own budget;  launch_and_poll(its chunk kernel) }
+//   end_loop;  [its own read-backs];  finish;  out[s] from fin(s) and the mirrors;  stamp_times.
+namespace {
+struct OnchipManyRun {
+    mi355cg_ctx* c; OnchipManyWs* W; const volatile int* stop_flag;
+    std::chrono::steady_clock::time_point t0;
+    OnchipPlan pl; RuleParams rp; bool msg;
+    int nsys, lds;
+    long long U, count;                          // ONE stride for the caller's packed vectors and the workspace's; doubles of nsys vectors
+    OnchipSmallView dev, host;                   // W->small and its pinned mirror
+    double* x; double* r; double* p;             // W->vec
+    OnchipManyArgs a;                            // the chunk's arguments, complete but for m (begin_loop)
+    bool polled, interrupted;                    // a poll has brought the counter back; the host's stop flag ended the loop
+
+    int open(mi355cg_ctx* c_, const mi355cg_params* prm, int nsys_, const volatile int* stop_flag_, const char* what) {
+        t0 = std::chrono::steady_clock::now();
+        c = c_; W = c->many.get(); stop_flag = stop_flag_; nsys = nsys_;
+        pl = onchip_plan(c->gp.n); rp = make_cfg(prm).rp; msg = prm->rule == MI355CG_RULE_MSG_MAXNORM;
+        if (c->pk_len != pl.unknowns) return fail(MI355CG_ERR_STATE, "on-chip %s: the handle packs %lld unknowns, the plan of N = %d has %d", what, c->pk_len, pl.n, pl.unknowns);
+        U = pl.unknowns; count = U * nsys; lds = onchip_many_lds_bytes(pl.n);
+        dev = onchip_small_view(W->small, nsys); host = onchip_small_view(W->small_h, nsys);
+        x = W->vec; r = x + count; p = x + 2 * count;
+        polled = interrupted = false;
+        return MI355CG_OK;
+    }
+    int upload_diag() { HIPCK(hipMemcpyAsync(dev.diag, host.diag, sizeof(double) * nsys, hipMemcpyHostToDevice, c->stream)); return MI355CG_OK; }
+    int reset_done() { HIPCK(hipMemsetAsync(W->done, 0, sizeof(int) * 2, c->stream)); W->done_h[0] = 0; return MI355CG_OK; }
+    int allow_lds(const void* kernel) const { return onchip_many_allow_lds(kernel, lds); }
+    int launch(const void* kernel, void** args) { HIPCK(hipLaunchKernel(kernel, dim3(nsys), dim3(pl.threads), args, lds, c->stream)); return MI355CG_OK; }
+    int start(const void* kernel, void** args) { if (int rc = allow_lds(kernel)) return rc; return launch(kernel, args); }
+    int poll() {                                                   // one word per chunk: how many systems are done
+        HIPCK(hipMemcpyAsync(W->done_h, W->done, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        polled = true;
+        return wait_stream_forwarding_stop(c, stop_flag);
+    }
+    // After the start kernel.  The stop request: sampled by every workgroup once per iteration, forwarded by this thread while it
+    // waits (as in mi355cg_solve).  start_tested: the start kernel has tested the start states, so they are polled before the loop.
+    int begin_loop(bool start_tested) {
+        *c->stop_h = 0;
+        int* stop_dev = nullptr;
+        if (stop_flag) HIPCK(hipHostGetDevicePointer((void**)&stop_dev, c->stop_h, 0));
+        a = OnchipManyArgs{};
+        a.pl = pl; a.xk = c->g.xk; a.yk = c->g.yk; a.diag = dev.diag;
+        a.x = x; a.r = r; a.p = p; a.stride = U;
+        a.partB = dev.partB; a.s = W->s; a.summary = W->summary; a.done_count = W->done; a.rp = rp; a.stop_req = stop_dev;
+        if (start_tested) if (int rc = poll()) return rc;
+        return loop_timer_begin(c, c->stream);
+    }
+    bool more() {                                                  // false: every system is done, or the host asks to stop
+        if (W->done_h[0] >= nsys) return false;
+        if (stop_flag && *stop_flag) { interrupted = true; return false; }
+        return true;
+    }
+    int unfinished() const { return nsys - W->done_h[0]; }
+    int launch_and_poll(const void* kernel, void** args) { if (int rc = launch(kernel, args)) return rc; return poll(); }
+    // a call stopped before anything was polled reports the empty state, as a single solve does; with_norm0: ||r0||_2 is not the state's r0norm
+    int end_loop(bool with_norm0) {
+        if (int rc = loop_timer_end(c, c->stream)) return rc;
+        if (polled) {
+            HIPCK(hipMemcpyAsync(W->summary_h, W->summary, sizeof(CgState) * nsys, hipMemcpyDeviceToHost, c->stream));
+            if (with_norm0) HIPCK(hipMemcpyAsync(host.norm0, dev.norm0, sizeof(double) * nsys, hipMemcpyDeviceToHost, c->stream));
+        }
+        return MI355CG_OK;
+    }
+    int finish(double* x_out) {                                    // the solutions to the caller; every read-back has landed on return
+        HIPCK(hipMemcpyAsync(x_out, x, sizeof(double) * count, hipMemcpyDeviceToDevice, c->stream));
+        HIPCK(hipStreamSynchronize(c->stream));
+        return MI355CG_OK;
+    }
+    CgState fin(int s) const { return polled ? W->summary_h[s] : CgState{}; }
+    int stamp_times(mi355cg_results* out) {
+        HIPCK(hipEventSynchronize(c->ev_loop[1]));
+        const double loop_seconds = loop_timer_seconds(c);
+        const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        for (int s = 0; s < nsys; ++s) { out[s].loop_seconds = loop_seconds; out[s].solve_seconds = secs; }
+        return MI355CG_OK;
+    }
+};
+}  // namespace
+
 // b_dev, x_dev: nsys packed vectors each in device memory (x_dev: the guesses when warm); sigma: host memory or NULL, checked.
 static int solve_many(mi355cg_ctx* c, const mi355cg_params* prm, int nsys, const double* b_dev, double* x_dev, const double* sigma,
                       const volatile int* stop_flag, mi355cg_results* out, bool warm) {
-    const auto t0 = std::chrono::steady_clock::now();
-    OnchipManyWs* W = c->many.get();
-    const OnchipPlan pl = onchip_plan(c->gp.n);
-    const bool msg = prm->rule == MI355CG_RULE_MSG_MAXNORM;
-    const IterCfg cfg = make_cfg(prm);
-    if (c->pk_len != pl.unknowns) return fail(MI355CG_ERR_STATE, "on-chip batch: the handle packs %lld unknowns, the plan of N = %d has %d", c->pk_len, pl.n, pl.unknowns);
-    const long long U = pl.unknowns, count = U * nsys;       // ONE stride for the caller's packed vectors and the workspace's
-    const int lds = onchip_many_lds_bytes(pl.n);
-    double* partB = W->small; double* diag = partB + (long long)FB_COUNT * nsys; double* norm0 = diag + nsys;
-    double* diag_h = W->small_h + (long long)FB_COUNT * nsys; const double* norm0_h = diag_h + nsys;
-
-    for (int s = 0; s < nsys; ++s) diag_h[s] = sigma ? c->gp.A - sigma[s] : c->g.A;          // mi355cg_set_shift's rounding
-    HIPCK(hipMemcpyAsync(diag, diag_h, sizeof(double) * nsys, hipMemcpyHostToDevice, c->stream));
-    HIPCK(hipMemsetAsync(W->done, 0, sizeof(int) * 2, c->stream));
-    W->done_h[0] = 0;
+    OnchipManyRun R;
+    if (int rc = R.open(c, prm, nsys, stop_flag, "batch")) return rc;
+    const OnchipManyWs* W = R.W;
+    for (int s = 0; s < nsys; ++s) R.host.diag[s] = sigma ? c->gp.A - sigma[s] : c->g.A;          // mi355cg_set_shift's rounding
+    if (int rc = R.upload_diag()) return rc;
+    if (int rc = R.reset_done()) return rc;
 
     OnchipManyInitArgs ia{};
-    ia.pl = pl; ia.xk = c->g.xk; ia.yk = c->g.yk; ia.diag = diag; ia.b = b_dev; ia.x0 = warm ? x_dev : nullptr;
-    ia.x = W->vec; ia.r = W->vec + count; ia.p = W->vec + 2 * count; ia.stride = U;
-    ia.partB = partB; ia.s = W->s; ia.summary = W->summary; ia.norm0 = norm0; ia.done_count = W->done; ia.rp = cfg.rp;
-    const void* k_init = warm ? (const void*)&k_onchip_many_init<true> : (const void*)&k_onchip_many_init<false>;
-    if (int rc = onchip_many_allow_lds(k_init, lds)) return rc;
-    { void* args[] = {&ia}; HIPCK(hipLaunchKernel(k_init, dim3(nsys), dim3(pl.threads), args, lds, c->stream)); }
+    ia.pl = R.pl; ia.xk = c->g.xk; ia.yk = c->g.yk; ia.diag = R.dev.diag; ia.b = b_dev; ia.x0 = warm ? x_dev : nullptr;
+    ia.x = R.x; ia.r = R.r; ia.p = R.p; ia.stride = R.U;
+    ia.partB = R.dev.partB; ia.s = W->s; ia.summary = W->summary; ia.norm0 = R.dev.norm0; ia.done_count = W->done; ia.rp = R.rp;
+    { void* args[] = {&ia}; if (int rc = R.start(warm ? (const void*)&k_onchip_many_init<true> : (const void*)&k_onchip_many_init<false>, args)) return rc; }
+    if (int rc = R.begin_loop(R.msg && warm)) return rc;           // the start states of a warm MSG batch were tested (k_onchip_many_init)
 
-    // the stop request: sampled by every workgroup once per iteration, forwarded by this thread while it waits (as in mi355cg_solve)
-    *c->stop_h = 0;
-    int* stop_dev = nullptr;
-    if (stop_flag) HIPCK(hipHostGetDevicePointer((void**)&stop_dev, c->stop_h, 0));
-    auto wait_stream = [&]() -> int { return wait_stream_forwarding_stop(c, stop_flag); };
-    bool polled = false;
-    auto poll = [&]() -> int {                                     // one word per chunk: how many systems are done
-        HIPCK(hipMemcpyAsync(W->done_h, W->done, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        polled = true;
-        return wait_stream();
-    };
-    if (msg && warm) if (int rc = poll()) return rc;               // the start states were tested (k_onchip_many_init)
-    if (int rc = loop_timer_begin(c, c->stream)) return rc;
-
-    OnchipManyArgs a{};
-    a.pl = pl; a.xk = c->g.xk; a.yk = c->g.yk; a.diag = diag;
-    a.x = ia.x; a.r = ia.r; a.p = ia.p; a.stride = U;
-    a.partB = partB; a.s = W->s; a.summary = W->summary; a.done_count = W->done; a.rp = cfg.rp; a.stop_req = stop_dev;
-    const void* k_chunk = onchip_many_kernel(pl.elems, msg);
-    if (int rc = onchip_many_allow_lds(k_chunk, lds)) return rc;
-    const int sync_every = default_sync_every(prm, msg);
-    int it_done = 0;
-    bool interrupted = false;
-    while (W->done_h[0] < nsys) {
-        if (stop_flag && *stop_flag) { interrupted = true; break; }
-        if (it_done > prm->max_iterations) return fail(MI355CG_ERR_HIP, "on-chip batch: %d of %d systems still iterate past the iteration cap", nsys - W->done_h[0], nsys);
-        a.m = chunk_len(prm, msg, sync_every, it_done, false);
-        { void* args[] = {&a}; HIPCK(hipLaunchKernel(k_chunk, dim3(nsys), dim3(pl.threads), args, lds, c->stream)); }
-        if (int rc = poll()) return rc;
-        it_done += a.m;
+    const void* k_chunk = onchip_many_kernel(R.pl.elems, R.msg);
+    if (int rc = R.allow_lds(k_chunk)) return rc;
+    const int sync_every = default_sync_every(prm, R.msg);
+    void* args[] = {&R.a};
+    for (int it_done = 0; R.more(); it_done += R.a.m) {
+        if (it_done > prm->max_iterations) return fail(MI355CG_ERR_HIP, "on-chip batch: %d of %d systems still iterate past the iteration cap", R.unfinished(), nsys);
+        R.a.m = chunk_len(prm, R.msg, sync_every, it_done, false);
+        if (int rc = R.launch_and_poll(k_chunk, args)) return rc;
     }
-    if (int rc = loop_timer_end(c, c->stream)) return rc;
-    // a batch stopped before anything was polled reports the empty state, as a single solve does
-    if (polled) {
-        HIPCK(hipMemcpyAsync(W->summary_h, W->summary, sizeof(CgState) * nsys, hipMemcpyDeviceToHost, c->stream));
-        if (warm) HIPCK(hipMemcpyAsync(W->small_h + (long long)(FB_COUNT + 1) * nsys, norm0, sizeof(double) * nsys, hipMemcpyDeviceToHost, c->stream));
-    }
-    HIPCK(hipMemcpyAsync(x_dev, ia.x, sizeof(double) * count, hipMemcpyDeviceToDevice, c->stream));
-    HIPCK(hipStreamSynchronize(c->stream));
-    HIPCK(hipEventSynchronize(c->ev_loop[1]));
-    const double loop_seconds = loop_timer_seconds(c);
+    if (int rc = R.end_loop(warm)) return rc;
+    if (int rc = R.finish(x_dev)) return rc;
     for (int s = 0; s < nsys; ++s) {
-        const CgState fin = polled ? W->summary_h[s] : CgState{};
-        const bool intr = (interrupted && !fin.done) || (fin.done && fin.reason == MI355CG_STOP_INTERRUPTED);
-        out[s] = make_results(fin, intr, false, warm && polled ? norm0_h[s] : fin.r0norm);
-        out[s].loop_seconds = loop_seconds;
+        const CgState fin = R.fin(s);
+        const bool intr = (R.interrupted && !fin.done) || (fin.done && fin.reason == MI355CG_STOP_INTERRUPTED);
+        out[s] = make_results(fin, intr, false, warm && R.polled ? R.host.norm0[s] : fin.r0norm);
     }
-    const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    for (int s = 0; s < nsys; ++s) out[s].solve_seconds = secs;
-    return MI355CG_OK;
+    return R.stamp_times(out);
 }
 
 static int solve_many_device(mi355cg_ctx* c, const mi355cg_params* prm, int nsys, const double* b_dev, double* x_dev, const double* sigma_dev,
@@ -3099,14 +3172,10 @@ static int solve_many_host(mi355cg_ctx* c, const mi355cg_params* prm, int nsys, 
     if (int rc = many_check_sigma(sigma, nsys)) return rc;
     HIPCK(hipSetDevice(c->device));
     if (int rc = onchip_many_ensure(c, nsys, true)) return rc;
-    const size_t count = (size_t)c->pk_len * (size_t)nsys, bytes = sizeof(double) * count;
-    double* stage = c->many->stage;                                // b in the first half, the guesses / the solutions in the second
-    HIPCK(hipMemcpyAsync(stage, b, bytes, hipMemcpyHostToDevice, c->stream));
-    if (warm) HIPCK(hipMemcpyAsync(stage + count, x, bytes, hipMemcpyHostToDevice, c->stream));
-    if (int rc = solve_many(c, prm, nsys, stage, stage + count, sigma, stop_flag, out, warm)) return rc;
-    HIPCK(hipMemcpyAsync(x, stage + count, bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCK(hipStreamSynchronize(c->stream));
-    return MI355CG_OK;
+    const size_t count = (size_t)c->pk_len * (size_t)nsys;         // b in the first half, the guesses / the solutions in the second
+    return run_staged(c, c->many->stage, count, count, b, warm ? x : nullptr, x, [&](const double* b_dev, double* x_dev) {
+        return solve_many(c, prm, nsys, b_dev, x_dev, sigma, stop_flag, out, warm);
+    });
 }
 
 int mi355cg_solve_many(mi355cg_handle c, const mi355cg_params* prm, int nsys, const double* b, double* x, const double* sigma,
@@ -3128,9 +3197,8 @@ int mi355cg_solve_many_device_from(mi355cg_handle c, const mi355cg_params* prm, 
 
 int mi355cg_solve_many_info(mi355cg_handle c, int nsys, int* lds_bytes_per_workgroup, int* workgroups_per_cu, long long* workspace_bytes) {
     if (!c) return fail(MI355CG_ERR_INVALID, "null handle");
-    if (nsys < 1 || nsys > MI355CG_MANY_MAX) return fail(MI355CG_ERR_INVALID, "a batch of on-chip solves has 1 .. %d systems, not %d", MI355CG_MANY_MAX, nsys);
-    if (c->mg) return fail(MI355CG_ERR_STATE, "this handle has a preconditioner: mi355cg_solve_many is plain CG in one workgroup per system (mi355cg_solve_batch is the preconditioned batch)");
-    if (const char* why = onchip_refusal(c)) return fail(MI355CG_ERR_INVALID, "%s", why);
+    if (int rc = kOnchipBatch.count(nsys)) return rc;
+    if (int rc = kOnchipBatch.onchip(c)) return rc;
     const OnchipPlan pl = onchip_plan(c->gp.n);
     const int lds = onchip_many_lds_bytes(pl.n);
     if (lds_bytes_per_workgroup) *lds_bytes_per_workgroup = lds;
@@ -3152,26 +3220,18 @@ static_assert(MI355CG_MANY_MAX == kOnchipStepsMaxSys && MI355CG_STEPS_MANY_MAX_S
 static int steps_many_check(mi355cg_ctx* c, const mi355cg_params* prm, int nsys, int nsteps, double theta, const double* tau, const void* g,
                             const void* u, const mi355cg_results* out, const int* steps_done, const int* step_iterations) {
     if (!c || !prm || !tau || !u || !out || !steps_done) return fail(MI355CG_ERR_INVALID, "null argument");
-    if (nsys < 1 || nsys > MI355CG_MANY_MAX) return fail(MI355CG_ERR_INVALID, "an ensemble of on-chip steppers has 1 .. %d members, not %d", MI355CG_MANY_MAX, nsys);
+    if (int rc = kEnsemble.count(nsys)) return rc;
     if (nsteps < 0 || nsteps > MI355CG_STEPS_MANY_MAX_STEPS) return fail(MI355CG_ERR_INVALID, "nsteps %d rejected: it must be 0 .. %d", nsteps, MI355CG_STEPS_MANY_MAX_STEPS);
     if (step_iterations && (long long)nsys * nsteps > kOnchipStepsMaxCounts)
         return fail(MI355CG_ERR_INVALID, "step_iterations for %d members x %d steps rejected: at most %lld counts", nsys, nsteps, kOnchipStepsMaxCounts);
     if (!(theta > 0.0 && theta <= 1.0)) return fail(MI355CG_ERR_INVALID, "theta %g rejected: the scheme needs 0 < theta <= 1", theta);
-    if (prm->rule != MI355CG_RULE_MSG_MAXNORM && prm->rule != MI355CG_RULE_REL_2NORM) return fail(MI355CG_ERR_INVALID, "unknown rule %d", prm->rule);
-    if (prm->use_true_solution) return fail(MI355CG_ERR_INVALID, "a step has no exact solution: use_true_solution must be 0");
-    if (prm->diagnostics) return fail(MI355CG_ERR_INVALID, "the stepper has no callbacks: diagnostics must be 0");
-    if (c->mg) return fail(MI355CG_ERR_STATE, "this handle has a preconditioner: mi355cg_time_steps_many is plain CG in one workgroup per member");
-    if (const char* why = onchip_refusal(c)) return fail(MI355CG_ERR_INVALID, "%s", why);
+    if (int rc = kEnsemble.params(prm)) return rc;
+    if (int rc = kEnsemble.onchip(c)) return rc;
     for (int s = 0; s < nsys; ++s) {
         if (!std::isfinite(tau[s]) || !(tau[s] > 0.0)) return fail(MI355CG_ERR_INVALID, "time step %g of member %d rejected: tau must be finite and > 0", tau[s], s);
         if (!std::isfinite(1.0 / (theta * tau[s]))) return fail(MI355CG_ERR_INVALID, "time step %g of member %d rejected: 1 / (theta tau) is not finite", tau[s], s);
     }
-    if (g) {
-        const size_t bytes = sizeof(double) * (size_t)c->gp.size * (size_t)nsys;
-        const uintptr_t gb = (uintptr_t)g, ub = (uintptr_t)u;
-        if (gb < ub + bytes && ub < gb + bytes) return fail(MI355CG_ERR_INVALID, "u overlaps g");
-    }
-    return MI355CG_OK;
+    return g ? BatchKind::apart(c, nsys, u, g, "u overlaps g") : MI355CG_OK;
 }
 
 // The batch workspace for nsys members, then the stepping parts on top: built complete before they replace what is there.
@@ -3197,136 +3257,62 @@ static int onchip_steps_ensure(mi355cg_ctx* c, int nsys, long long counts, bool 
     return MI355CG_OK;
 }
 
-static const void* onchip_steps_kernel(int elems, bool msg) {
-#define MI355CG_OCS(E) return msg ? (const void*)&k_onchip_steps<E, true> : (const void*)&k_onchip_steps<E, false>
-    switch (elems) {
-        case 1: MI355CG_OCS(1);
-        case 2: MI355CG_OCS(2);
-        case 4: MI355CG_OCS(4);
-        case 8: MI355CG_OCS(8);
-        case 16: MI355CG_OCS(16);
-        default: MI355CG_OCS(kOnchipMaxElems);
-    }
-#undef MI355CG_OCS
-}
-
-// REL_2NORM reports the max-norm of the residual only where k_check decided, i.e. when the solve ended on a poll of mi355cg_solve's
-// chunk schedule; a decision inside a chunk carries 0 (the rule does not reduce that norm).  A member's chunks are cut by its budget,
-// not by that schedule, so the host says which of the two a single solve of `it` iterations reports.
-static bool rel_solve_ends_on_a_poll(const mi355cg_params* prm, int sync_every, int it, bool watched) {
-    if (it <= 0) return false;                                     // decided by the first launch, before any poll
-    int done = 0;
-    for (bool first = watched; done < it; first = false) done += chunk_len(prm, false, sync_every, done, first);
-    return done == it;
-}
-
 // g_dev (or NULL), u_dev: nsys packed vectors each in device memory; tau: host memory, checked; nsteps >= 1.
 static int steps_many(mi355cg_ctx* c, const mi355cg_params* prm, int nsys, int nsteps, double theta, const double* tau, const double* g_dev,
                       double* u_dev, const volatile int* stop_flag, mi355cg_results* out, int* steps_done, int* step_iterations) {
-    const auto t0 = std::chrono::steady_clock::now();
-    OnchipManyWs* W = c->many.get();
-    const OnchipPlan pl = onchip_plan(c->gp.n);
-    const bool msg = prm->rule == MI355CG_RULE_MSG_MAXNORM;
-    const IterCfg cfg = make_cfg(prm);
-    if (c->pk_len != pl.unknowns) return fail(MI355CG_ERR_STATE, "on-chip stepping: the handle packs %lld unknowns, the plan of N = %d has %d", c->pk_len, pl.n, pl.unknowns);
-    const long long U = pl.unknowns, count = U * nsys, counts = step_iterations ? (long long)nsys * nsteps : 0;
-    const int lds = onchip_many_lds_bytes(pl.n);
-    double* partB = W->small; double* diag = partB + (long long)FB_COUNT * nsys; double* norm0 = diag + nsys;
-    double* diag_h = W->small_h + (long long)FB_COUNT * nsys; const double* norm0_h = diag_h + nsys;
-
+    OnchipManyRun R;
+    if (int rc = R.open(c, prm, nsys, stop_flag, "stepping")) return rc;
+    OnchipManyWs* W = R.W;
+    const bool msg = R.msg;
+    const long long counts = step_iterations ? (long long)nsys * nsteps : 0;
     for (int s = 0; s < nsys; ++s) {
         W->step_sigma_h[s] = 1.0 / (theta * tau[s]);                 // mi355cg_time_steps's shift, in that form ...
-        diag_h[s] = c->gp.A - W->step_sigma_h[s];                    // ... and mi355cg_set_shift's rounding
+        R.host.diag[s] = c->gp.A - W->step_sigma_h[s];               // ... and mi355cg_set_shift's rounding
     }
-    HIPCK(hipMemcpyAsync(diag, diag_h, sizeof(double) * nsys, hipMemcpyHostToDevice, c->stream));
+    if (int rc = R.upload_diag()) return rc;
     HIPCK(hipMemcpyAsync(W->step_sigma, W->step_sigma_h, sizeof(double) * nsys, hipMemcpyHostToDevice, c->stream));
-    HIPCK(hipMemsetAsync(W->done, 0, sizeof(int) * 2, c->stream));
+    if (int rc = R.reset_done()) return rc;
     HIPCK(hipMemsetAsync(W->book, 0, sizeof(OcStepBook) * nsys, c->stream));
     if (counts) HIPCK(hipMemsetAsync(W->step_it, 0xff, sizeof(int) * counts, c->stream));              // -1: not taken
-    W->done_h[0] = 0;
     if (!g_dev) {                                                  // the handle's right-hand side for every member
         hipLaunchKernelGGL((k_pack<double>), dim3(flat_grid(c->pk_len)), dim3(kBlock), 0, c->stream, c->pg, (const double*)c->b, W->g_one.get());
         HIPCK(hipGetLastError());
     }
 
     OnchipStepsArgs e{};
-    e.pl = pl; e.xk = c->g.xk; e.yk = c->g.yk; e.diag = diag; e.sigma = W->step_sigma;
-    e.g = g_dev ? g_dev : W->g_one.get(); e.g_stride = g_dev ? U : 0; e.u0 = u_dev;
-    e.x = W->vec; e.r = W->vec + count; e.p = W->vec + 2 * count; e.stride = U;
-    e.partB = partB; e.s = W->s; e.summary = W->summary; e.norm0 = norm0; e.done_count = W->done;
+    e.pl = R.pl; e.xk = c->g.xk; e.yk = c->g.yk; e.diag = R.dev.diag; e.sigma = W->step_sigma;
+    e.g = g_dev ? g_dev : W->g_one.get(); e.g_stride = g_dev ? R.U : 0; e.u0 = u_dev;
+    e.x = R.x; e.r = R.r; e.p = R.p; e.stride = R.U;
+    e.partB = R.dev.partB; e.s = W->s; e.summary = W->summary; e.norm0 = R.dev.norm0; e.done_count = W->done;
     e.book = W->book; e.step_it = counts ? W->step_it.get() : nullptr; e.nsteps = nsteps;
     e.k = OnchipStepCoef{c->gp.A, c->gp.x_k, c->gp.y_k, theta, (1.0 - theta) / theta, theta < 1.0 ? 1 : 0};       // launch_step_rhs's
-    e.rp = cfg.rp;
-    const void* k_init = (const void*)&k_onchip_steps_init;
-    if (int rc = onchip_many_allow_lds(k_init, lds)) return rc;
-    { void* args[] = {&e}; HIPCK(hipLaunchKernel(k_init, dim3(nsys), dim3(pl.threads), args, lds, c->stream)); }
+    e.rp = R.rp;
+    { void* args[] = {&e}; if (int rc = R.start((const void*)&k_onchip_steps_init, args)) return rc; }
+    if (int rc = R.begin_loop(msg)) return rc;                     // the start states were tested, as mi355cg_solve polls a warm MSG start
 
-    // the stop request: sampled by every workgroup once per iteration, forwarded by this thread while it waits (as in mi355cg_solve_many)
-    *c->stop_h = 0;
-    int* stop_dev = nullptr;
-    if (stop_flag) HIPCK(hipHostGetDevicePointer((void**)&stop_dev, c->stop_h, 0));
-    bool polled = false;
-    auto poll = [&]() -> int {                                     // one word per chunk: how many members have ended
-        HIPCK(hipMemcpyAsync(W->done_h, W->done, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        polled = true;
-        return wait_stream_forwarding_stop(c, stop_flag);
-    };
-    if (msg) if (int rc = poll()) return rc;                       // the start states were tested, as mi355cg_solve polls a warm MSG start
-    if (int rc = loop_timer_begin(c, c->stream)) return rc;
-
-    OnchipManyArgs a{};
-    a.pl = pl; a.xk = c->g.xk; a.yk = c->g.yk; a.diag = diag;
-    a.x = e.x; a.r = e.r; a.p = e.p; a.stride = U;
-    a.partB = partB; a.s = W->s; a.summary = W->summary; a.done_count = W->done; a.rp = cfg.rp; a.stop_req = stop_dev;
-    const void* k_chunk = onchip_steps_kernel(pl.elems, msg);
-    if (int rc = onchip_many_allow_lds(k_chunk, lds)) return rc;
+    const void* k_chunk = onchip_dispatch(R.pl.elems, msg, [](auto el, auto m) { return (const void*)&k_onchip_steps<decltype(el)::value, decltype(m)::value>; });
+    if (int rc = R.allow_lds(k_chunk)) return rc;
     e.m = default_sync_every(prm, msg);                            // units per member and launch: an iteration or a transition each
-    const long long per_member = (long long)nsteps * ((long long)std::max(prm->max_iterations, 0) + 1);
-    const long long max_launches = (per_member + e.m - 1) / e.m + 1;
-    long long launches = 0;
-    bool interrupted = false;
-    while (W->done_h[0] < nsys) {
-        if (stop_flag && *stop_flag) { interrupted = true; break; }
-        if (launches >= max_launches) return fail(MI355CG_ERR_HIP, "on-chip stepping: %d of %d members still step after %lld launches", nsys - W->done_h[0], nsys, launches);
-        { void* args[] = {&a, &e}; HIPCK(hipLaunchKernel(k_chunk, dim3(nsys), dim3(pl.threads), args, lds, c->stream)); }
-        if (int rc = poll()) return rc;
-        ++launches;
+    const long long max_launches = onchip_steps_launch_cap(nsteps, prm->max_iterations, e.m);
+    void* args[] = {&R.a, &e};
+    for (long long launches = 0; R.more(); ++launches) {
+        if (launches >= max_launches) return fail(MI355CG_ERR_HIP, "on-chip stepping: %d of %d members still step after %lld launches", R.unfinished(), nsys, launches);
+        if (int rc = R.launch_and_poll(k_chunk, args)) return rc;
     }
-    if (int rc = loop_timer_end(c, c->stream)) return rc;
-    if (polled) {
-        HIPCK(hipMemcpyAsync(W->summary_h, W->summary, sizeof(CgState) * nsys, hipMemcpyDeviceToHost, c->stream));
-        HIPCK(hipMemcpyAsync(W->small_h + (long long)(FB_COUNT + 1) * nsys, norm0, sizeof(double) * nsys, hipMemcpyDeviceToHost, c->stream));
-    }
+    if (int rc = R.end_loop(true)) return rc;
     HIPCK(hipMemcpyAsync(W->book_h, W->book, sizeof(OcStepBook) * nsys, hipMemcpyDeviceToHost, c->stream));
-    if (!msg) HIPCK(hipMemcpyAsync(W->small_h, partB, sizeof(double) * FB_COUNT * nsys, hipMemcpyDeviceToHost, c->stream));     // |r| of the last update
-    if (interrupted) HIPCK(hipMemcpyAsync(W->s_h, W->s, sizeof(CgState) * nsys, hipMemcpyDeviceToHost, c->stream));
-    HIPCK(hipMemcpyAsync(u_dev, e.x, sizeof(double) * count, hipMemcpyDeviceToDevice, c->stream));
-    HIPCK(hipStreamSynchronize(c->stream));
+    if (!msg) HIPCK(hipMemcpyAsync(R.host.partB, R.dev.partB, sizeof(double) * FB_COUNT * nsys, hipMemcpyDeviceToHost, c->stream));     // |r| of the last update
+    if (R.interrupted) HIPCK(hipMemcpyAsync(W->s_h, W->s, sizeof(CgState) * nsys, hipMemcpyDeviceToHost, c->stream));
+    if (int rc = R.finish(u_dev)) return rc;
     if (counts) HIPCK(hipMemcpy(step_iterations, W->step_it, sizeof(int) * counts, hipMemcpyDeviceToHost));
-    HIPCK(hipEventSynchronize(c->ev_loop[1]));
-    const double loop_seconds = loop_timer_seconds(c);
-    for (int s = 0; s < nsys; ++s) {
-        const OcStepBook bk = W->book_h[s];
-        const CgState fin = polled ? W->summary_h[s] : CgState{};
-        if (bk.ended) {                                            // after its last step, or a step that did not converge
-            steps_done[s] = bk.step;
-            out[s] = make_results(fin, fin.done && fin.reason == MI355CG_STOP_INTERRUPTED, false, norm0_h[s]);
-            if (!msg) out[s].final_residual_norm = rel_solve_ends_on_a_poll(prm, e.m, fin.it, stop_flag != nullptr) ? W->small_h[(long long)s * FB_COUNT + FB_RMAX] : 0.0;
-        } else if (W->s_h[s].done) {                               // stopped by the host between two steps: the next one was not begun
-            steps_done[s] = bk.step + 1;
-            if (counts) step_iterations[(long long)s * nsteps + bk.step] = W->s_h[s].it;
-            out[s] = make_results(CgState{}, true, false, 0.0);
-        } else {                                                   // stopped by the host inside a step (REL_2NORM: no state is read before its first chunk)
-            const bool begun = polled && (msg || W->s_h[s].it > 0);
-            steps_done[s] = bk.step;
-            out[s] = make_results(begun ? fin : CgState{}, true, false, begun ? norm0_h[s] : 0.0);
-            if (counts) step_iterations[(long long)s * nsteps + bk.step] = out[s].iterations;              // attempted: its count so far
-        }
-        out[s].loop_seconds = loop_seconds;
+    for (int s = 0; s < nsys; ++s) {                               // onchip_plan.h: what a member reports
+        const OcStepReport rep = onchip_step_report(prm, msg, R.polled, R.interrupted, W->book_h[s], W->summary_h[s], W->s_h[s], R.host.norm0[s],
+                                                    R.host.partB[(long long)s * FB_COUNT + FB_RMAX], e.m, stop_flag != nullptr);
+        steps_done[s] = rep.steps_done;
+        out[s] = rep.res;
+        if (counts && rep.patch_step >= 0) step_iterations[(long long)s * nsteps + rep.patch_step] = rep.patch_iterations;
     }
-    const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    for (int s = 0; s < nsys; ++s) out[s].solve_seconds = secs;
-    return MI355CG_OK;
+    return R.stamp_times(out);
 }
 
 int mi355cg_time_steps_many_device(mi355cg_handle c, const mi355cg_params* prm, int nsys, int nsteps, double theta, const double* tau,
@@ -3344,14 +3330,10 @@ int mi355cg_time_steps_many(mi355cg_handle c, const mi355cg_params* prm, int nsy
     if (nsteps == 0) { for (int s = 0; s < nsys; ++s) steps_done[s] = 0; return MI355CG_OK; }
     HIPCK(hipSetDevice(c->device));
     if (int rc = onchip_steps_ensure(c, nsys, step_iterations ? (long long)nsys * nsteps : 0, true)) return rc;
-    const size_t count = (size_t)c->pk_len * (size_t)nsys, bytes = sizeof(double) * count;
-    double* stage = c->many->stage;                                // g in the first half, the states in the second
-    if (g) HIPCK(hipMemcpyAsync(stage, g, bytes, hipMemcpyHostToDevice, c->stream));
-    HIPCK(hipMemcpyAsync(stage + count, u, bytes, hipMemcpyHostToDevice, c->stream));
-    if (int rc = steps_many(c, prm, nsys, nsteps, theta, tau, g ? stage : nullptr, stage + count, stop_flag, out, steps_done, step_iterations)) return rc;
-    HIPCK(hipMemcpyAsync(u, stage + count, bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCK(hipStreamSynchronize(c->stream));
-    return MI355CG_OK;
+    const size_t count = (size_t)c->pk_len * (size_t)nsys;         // g in the first half, the states in the second
+    return run_staged(c, c->many->stage, count, count, g, u, u, [&](const double* g_dev, double* u_dev) {
+        return steps_many(c, prm, nsys, nsteps, theta, tau, g ? g_dev : nullptr, u_dev, stop_flag, out, steps_done, step_iterations);
+    });
 }
 int mi355cg_time_steps_many_workspace(int n, int nsys, int nsteps, int with_step_iterations, long long* bytes) {
     if (!bytes) return fail(MI355CG_ERR_INVALID, "null argument");
@@ -3377,13 +3359,10 @@ int mi355cg_eigs(mi355cg_handle c, int nev, int block, double tol, int max_itera
     if (int rc = eig_check(c, nev, block, tol, max_iterations, x, lambda, resid, out)) return rc;
     HIPCK(hipSetDevice(c->device));
     if (int rc = eig_ensure(c, block, true)) return rc;
-    double* stage = c->eig->stage;                                 // the start block goes up and the Ritz vectors come down through it
-    const size_t bytes = sizeof(double) * (size_t)c->pk_len * (size_t)block;
-    HIPCK(hipMemcpyAsync(stage, x, bytes, hipMemcpyHostToDevice, c->stream));
-    if (int rc = solve_eigs(c, nev, block, tol, max_iterations, stage, lambda, resid, stop_flag, out)) return rc;
-    HIPCK(hipMemcpyAsync(x, stage, bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCK(hipStreamSynchronize(c->stream));
-    return MI355CG_OK;
+    // the start block goes up and the Ritz vectors come down through one buffer
+    return run_staged(c, c->eig->stage, (size_t)c->pk_len * (size_t)block, 0, x, nullptr, x, [&](const double*, double* x_dev) {
+        return solve_eigs(c, nev, block, tol, max_iterations, x_dev, lambda, resid, stop_flag, out);
+    });
 }
 
 int mi355cg_eigs_release(mi355cg_handle c) {

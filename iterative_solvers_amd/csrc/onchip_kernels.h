@@ -502,8 +502,6 @@ __global__ __launch_bounds__(kOnchipMaxThreads) void k_onchip_many_init(const On
 // direction, the state: what a batch keeps per system) with the transition: record the step, the new state u = x from the
 // workspace into the image, b_step in registers, the warm start of k_onchip_many_init on it (oc_start).  A member ends after its
 // last step or after the first step that does not converge (iteration cap, stop request) and is then counted in *done_count, once.
-struct OcStepBook { int step, ended; };       // converged steps so far (the index of the step being solved); the member has ended
-static_assert(sizeof(double) + sizeof(OcStepBook) == kOnchipStepsSysBytes, "onchip_plan.h: a member's share of the stepping workspace");
 struct OnchipStepsArgs {                 // (its own copies of what it shares with OnchipManyArgs: the chunk's arguments stay whole)
     OnchipPlan pl;
     double xk, yk;

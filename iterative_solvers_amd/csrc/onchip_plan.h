@@ -2,7 +2,8 @@
 // node and its four neighbours sit in the LDS image of the direction, how much LDS that takes.
 //
 // Free of HIP includes, like item_table.h: the kernel (onchip_kernels.h), mi355cg_onchip_plan and tests/cpp/onchip_plan_driver.cpp
-// all read the layout from here.
+// all read the layout from here.  So do the decisions the host takes about an ensemble of steppers (section 12.2, at the end):
+// tests/cpp/onchip_report_driver.cpp prints them without a GPU.
 //
 //   * Unknowns are numbered row by row, x fastest: first the rows 1 .. N/2 of the bottom-right block (columns N/2+1 .. N-1), then the
 //     rows N/2+1 .. N-1 of the upper block (columns 1 .. N-1).
@@ -13,6 +14,7 @@
 //     are the Dirichlet zeros and the in_j masking of the streaming kernels in one.  Every neighbour of an interior node lies in the image.
 #pragma once
 #include "item_table.h"               // MI355CG_HD
+#include "solve_loop.h"               // CgState, chunk_len, make_results: what the report of an ensemble member is made of
 
 namespace mi355cg {
 
@@ -115,6 +117,55 @@ MI355CG_HD inline long long onchip_steps_workspace_bytes(int n, int nsys, int ns
     const long long counts = with_step_iterations ? (long long)nsys * nsteps : 0;
     if (counts > kOnchipStepsMaxCounts) return 0;
     return onchip_many_workspace_bytes(n, nsys) + (long long)nsys * kOnchipStepsSysBytes + 8LL * onchip_plan(n).unknowns + 4 * counts;
+}
+struct OcStepBook { int step, ended; };       // converged steps so far (the index of the step being solved); the member has ended
+static_assert(sizeof(double) + sizeof(OcStepBook) == kOnchipStepsSysBytes, "a member's share of the stepping workspace");
+
+// -- what the host decides about an ensemble (mi355cg_time_steps_many*), free of HIP ------------------------------------------------
+// Launches that take every member to its end when each gives a member m units: an iteration costs one, a transition costs one, so
+// a member needs at most nsteps * (max_iterations + 1) units; one launch more notices the end.  More than that is an error.
+inline long long onchip_steps_launch_cap(int nsteps, int max_iterations, int m) {
+    const long long per_member = (long long)nsteps * ((long long)std::max(max_iterations, 0) + 1);
+    return (per_member + m - 1) / m + 1;
+}
+// REL_2NORM reports the max-norm of the residual only where k_check decided, i.e. when the solve ended on a poll of mi355cg_solve's
+// chunk schedule; a decision inside a chunk carries 0 (the rule does not reduce that norm).  A member's chunks are cut by its budget,
+// not by that schedule, so the host says which of the two a single solve of `it` iterations reports.
+inline bool rel_solve_ends_on_a_poll(const mi355cg_params* prm, int sync_every, int it, bool watched) {
+    if (it <= 0) return false;                                     // decided by the first launch, before any poll
+    int done = 0;
+    for (bool first = watched; done < it; first = false) done += chunk_len(prm, false, sync_every, done, first);
+    return done == it;
+}
+// What one member reports after the last launch.  polled: a summary was read at all (otherwise the empty state stands for it);
+// interrupted: the host's stop flag ended the call, and only then is `boundary`, the iteration-boundary state, read.  summary: the
+// member's state as the host polls it; norm0: ||r0||_2 of its last step; last_rmax: |r| of its last update (REL_2NORM); budget: the
+// units of a launch (the sync_every of the single solve); watched: the caller passed a stop flag.
+//   ended (after its last step, or a step that did not converge): the steps it converged, the state of the last one;
+//   stopped between two steps: the step it finished counts, its iteration count is patched in, the next was not begun: empty state;
+//   stopped inside a step: that step does not count and reports its state so far (REL_2NORM: no state is read before its first chunk).
+// patch_step >= 0: step_iterations[patch_step] of this member becomes patch_iterations (when the caller asked for the counts).
+struct OcStepReport { int steps_done; mi355cg_results res; int patch_step, patch_iterations; };
+static inline OcStepReport onchip_step_report(const mi355cg_params* prm, bool msg, bool polled, bool interrupted, const OcStepBook& bk,
+                                       const CgState& summary, const CgState& boundary, double norm0, double last_rmax, int budget, bool watched) {
+    const CgState fin = polled ? summary : CgState{};
+    OcStepReport rep{};
+    rep.patch_step = -1;
+    if (bk.ended || !interrupted) {
+        rep.steps_done = bk.step;
+        rep.res = make_results(fin, fin.done && fin.reason == MI355CG_STOP_INTERRUPTED, false, norm0);
+        if (!msg) rep.res.final_residual_norm = rel_solve_ends_on_a_poll(prm, budget, fin.it, watched) ? last_rmax : 0.0;
+    } else if (boundary.done) {
+        rep.steps_done = bk.step + 1;
+        rep.patch_step = bk.step; rep.patch_iterations = boundary.it;
+        rep.res = make_results(CgState{}, true, false, 0.0);
+    } else {
+        const bool begun = polled && (msg || boundary.it > 0);
+        rep.steps_done = bk.step;
+        rep.res = make_results(begun ? fin : CgState{}, true, false, begun ? norm0 : 0.0);
+        rep.patch_step = bk.step; rep.patch_iterations = rep.res.iterations;        // attempted: its count so far
+    }
+    return rep;
 }
 
 static_assert(kOnchipSideBytes - 256 + 184 <= kOnchipBudgetOffset && kOnchipBudgetOffset % 8 == 0, "the budget word lies behind the CG state");

@@ -50,9 +50,7 @@ class _Handle:
         self._h = C.c_void_p()
         rc = self._lib.mi355cg_create(int(n), int(m), float(a), float(b), float(c), float(d),
                                       int(dtype), int(device), C.byref(self._h))
-        if rc == _capi.ERR_INVALID:
-            raise ValueError(self._lib.mi355cg_last_error().decode())   # std::invalid_argument
-        _capi.check(rc)
+        self._check_rc(rc)
         self.size = int(self._lib.mi355cg_size(self._h))
         self._device = int(device)
 
@@ -66,9 +64,7 @@ class _Handle:
         entries = np.ascontiguousarray(entries, dtype=np.int32)
         values = np.ascontiguousarray(values, dtype=np.float64)
         rc = self._lib.mi355cg_create_csr(len(row_map) - 1, row_map, entries, values, int(device), C.byref(self._h))
-        if rc == _capi.ERR_INVALID:
-            raise ValueError(self._lib.mi355cg_last_error().decode())
-        _capi.check(rc)
+        self._check_rc(rc)
         self.size = int(self._lib.mi355cg_size(self._h))
         self._device = int(device)
         return self
@@ -142,9 +138,9 @@ class _Handle:
             raise ValueError(f"initial guess has shape {tuple(x0.shape)}, expected ({size},)")
         return on_device
 
-    def _guess_rc(self, rc):
+    def _check_rc(self, rc):
         if rc == _capi.ERR_INVALID:
-            raise ValueError(self._lib.mi355cg_last_error().decode())
+            raise ValueError(self._lib.mi355cg_last_error().decode())     # std::invalid_argument
         _capi.check(rc)
 
     def set_initial_guess(self, x0):
@@ -153,26 +149,26 @@ class _Handle:
         torch.Tensor on the handle's device, which is read in place (mi355cg_set_initial_guess_device); None withdraws a
         pending guess.  Until the next solve solution() and the residuals raise.  ValueError on CSR and F32_MIXED handles."""
         if x0 is None:
-            return self._guess_rc(self._lib.mi355cg_set_initial_guess(self._h, None))
+            return self._check_rc(self._lib.mi355cg_set_initial_guess(self._h, None))
         if self._check_guess(x0, self.size):
             import torch
             if x0.device.index != self._device:
                 raise ValueError(f"initial guess is on {x0.device}, the handle on device {self._device}")
             torch.cuda.current_stream(x0.device).synchronize()       # the library works on its own stream
-            return self._guess_rc(self._lib.mi355cg_set_initial_guess_device(self._h, x0.data_ptr()))
+            return self._check_rc(self._lib.mi355cg_set_initial_guess_device(self._h, x0.data_ptr()))
         x0 = np.ascontiguousarray(x0)
-        self._guess_rc(self._lib.mi355cg_set_initial_guess(self._h, x0.ctypes.data))
+        self._check_rc(self._lib.mi355cg_set_initial_guess(self._h, x0.ctypes.data))
 
     def use_solution_as_initial_guess(self):
         """The x of the last solve is the next solve's starting point, without a copy: after a solve that was interrupted or hit
         its iteration cap this continues it (mi355cg_use_solution_as_initial_guess)."""
-        self._guess_rc(self._lib.mi355cg_use_solution_as_initial_guess(self._h))
+        self._check_rc(self._lib.mi355cg_use_solution_as_initial_guess(self._h))
 
     def set_shift(self, sigma: float):
         """Extension (no reference twin): the handle's operator becomes A - sigma I, for apply(), every solve, the preconditioner
         and the batched solves (mi355cg_set_shift).  sigma is finite and >= 0; 0 restores the Laplacian bit for bit.  ValueError
         if refused (a bad sigma; CSR, slab and F32_MIXED handles); the handle then keeps what it had."""
-        self._guess_rc(self._lib.mi355cg_set_shift(self._h, float(sigma)))
+        self._check_rc(self._lib.mi355cg_set_shift(self._h, float(sigma)))
 
     def get_shift(self) -> float:
         s = C.c_double()
@@ -193,9 +189,7 @@ class _Handle:
         done = C.c_int(0)
         sp = C.cast(C.pointer(stop_flag), C.c_void_p) if stop_flag is not None else None
         rc = self._lib.mi355cg_time_steps(self._h, C.byref(params), float(tau), float(theta), n, sp, res, C.byref(done))
-        if rc == _capi.ERR_INVALID:
-            raise ValueError(self._lib.mi355cg_last_error().decode())
-        _capi.check(rc)
+        self._check_rc(rc)
         return list(res[:min(n, done.value + 1)]), done.value
 
     def solve(self, params: _capi.Params, callback=None, stop_flag: Optional[C.c_int] = None) -> _capi.Results:
@@ -203,9 +197,7 @@ class _Handle:
         cb = _capi.ITER_CB(lambda user, it, p, r, e: callback(it, p, r, e)) if callback else _capi.ITER_CB()
         sp = C.cast(C.pointer(stop_flag), C.c_void_p) if stop_flag is not None else None
         rc = self._lib.mi355cg_solve(self._h, C.byref(params), cb, None, sp, C.byref(res))
-        if rc == _capi.ERR_INVALID:
-            raise ValueError(self._lib.mi355cg_last_error().decode())     # std::invalid_argument
-        _capi.check(rc)
+        self._check_rc(rc)
         return res
 
     def set_preconditioner(self, kind: int, cycle: int = _capi.CYCLE_F64):
@@ -215,18 +207,14 @@ class _Handle:
         for the V-cycle in fp32 inside the fp64 PCG (mi355cg_set_preconditioner_ex).  ValueError if refused; the handle then
         keeps what it had."""
         rc = self._lib.mi355cg_set_preconditioner_ex(self._h, int(kind), int(cycle))
-        if rc == _capi.ERR_INVALID:
-            raise ValueError(self._lib.mi355cg_last_error().decode())
-        _capi.check(rc)
+        self._check_rc(rc)
 
     def set_solve_mode(self, mode: int):
         """Extension (no reference twin): _capi.SOLVE_ONCHIP runs every chunk of a plain fp64 solve as one launch of one workgroup
         (grids up to N = 128, bit-identical to the default), _capi.SOLVE_LAUNCHES goes back to two launches per iteration
         (include/mi355cg.h, mi355cg_set_solve_mode).  ValueError if refused; the handle then keeps its mode."""
         rc = self._lib.mi355cg_set_solve_mode(self._h, int(mode))
-        if rc == _capi.ERR_INVALID:
-            raise ValueError(self._lib.mi355cg_last_error().decode())
-        _capi.check(rc)
+        self._check_rc(rc)
 
     def solve_mode_info(self):
         """(mode, on-chip chunk launches of the last solve)."""
@@ -245,9 +233,7 @@ class _Handle:
         _capi.SMOOTHER_LINE_X / _LINE_Y / _LINE_AUTO for stretched domains (include/mi355cg.h, mi355cg_set_smoother).  Before or
         after set_preconditioner.  ValueError if refused; the handle then keeps what it had."""
         rc = self._lib.mi355cg_set_smoother(self._h, int(smoother))
-        if rc == _capi.ERR_INVALID:
-            raise ValueError(self._lib.mi355cg_last_error().decode())
-        _capi.check(rc)
+        self._check_rc(rc)
 
     def smoother_info(self):
         """(smoother, direction): the smoother as set, and the line direction it means on this grid (0 none, 1 x, 2 y)."""
@@ -288,6 +274,22 @@ class _Handle:
             raise ValueError(f"a batch has 1 .. {most} right-hand sides, not {shape[0]}")
         return shape[0], on_device
 
+    def _batched(self, main, other, names, most, stop_flag):
+        """What solve_batch, solve_many and time_steps_many check before they call the library: (count, on_device, stop pointer).
+        main: the batch; other: its optional companion of the same kind and shape; names: what the messages call main, other, the
+        others and the whole, e.g. ("b", "x0", "guesses", "batch").  The return code then goes through _check_rc."""
+        n, on_device = self._check_batch(main, self.size, most)
+        m_name, o_name, o_plural, whole = names
+        if other is not None and self._check_batch(other, self.size, most) != (n, on_device):
+            raise ValueError(f"{o_name} has shape {tuple(other.shape)}: the {o_plural} are of the kind (NumPy / CUDA tensor) and shape of {m_name}, "
+                             f"{tuple(main.shape)}")
+        if on_device:
+            if main.device.index != self._device:
+                raise ValueError(f"{whole} is on {main.device}, the handle on device {self._device}")
+            if other is not None and other.device != main.device:
+                raise ValueError(f"{o_name} is on {other.device}, {m_name} on {main.device}")
+        return n, on_device, C.cast(C.pointer(stop_flag), C.c_void_p) if stop_flag is not None else None
+
     def solve_batch(self, params: _capi.Params, b, stop_flag: Optional[C.c_int] = None, x0=None):
         """Extension (no reference twin): solve b[s] for every row s of b by one multigrid-preconditioned CG loop
         (mi355cg_solve_batch; needs set_preconditioner first).  Returns (x, [Results per system]); system s gets the bits
@@ -296,19 +298,10 @@ class _Handle:
         current stream is synchronised first, since the library works on its own stream).  params.use_true_solution and
         params.diagnostics must be 0.  x0: a guess per system, of b's kind and shape (mi355cg_solve_batch_from): system s then
         gets the bits of set_rhs(b[s]); set_initial_guess(x0[s]); solve(params); solution().  x0 is not modified."""
-        nrhs, on_device = self._check_batch(b, self.size)
-        if x0 is not None:
-            if self._check_batch(x0, self.size) != (nrhs, on_device):
-                raise ValueError(f"x0 has shape {tuple(x0.shape)}: the guesses are of the kind (NumPy / CUDA tensor) and shape of b, "
-                                 f"{tuple(b.shape)}")
+        nrhs, on_device, sp = self._batched(b, x0, ("b", "x0", "guesses", "batch"), _capi.BATCH_MAX, stop_flag)
         res = (_capi.Results * nrhs)()
-        sp = C.cast(C.pointer(stop_flag), C.c_void_p) if stop_flag is not None else None
         if on_device:
             import torch
-            if b.device.index != self._device:
-                raise ValueError(f"batch is on {b.device}, the handle on device {self._device}")
-            if x0 is not None and x0.device != b.device:
-                raise ValueError(f"x0 is on {x0.device}, b on {b.device}")
             x = torch.empty_like(b) if x0 is None else x0.clone()
             torch.cuda.current_stream(b.device).synchronize()
             fn = self._lib.mi355cg_solve_batch_device if x0 is None else self._lib.mi355cg_solve_batch_device_from
@@ -318,9 +311,7 @@ class _Handle:
             x = np.empty_like(b) if x0 is None else np.array(x0, dtype=np.float64, order="C", copy=True)
             fn = self._lib.mi355cg_solve_batch if x0 is None else self._lib.mi355cg_solve_batch_from
             rc = fn(self._h, C.byref(params), nrhs, b.ctypes.data, x.ctypes.data, sp, res)
-        if rc == _capi.ERR_INVALID:
-            raise ValueError(self._lib.mi355cg_last_error().decode())
-        _capi.check(rc)
+        self._check_rc(rc)
         return x, list(res)
 
     def batch_release(self):
@@ -335,19 +326,10 @@ class _Handle:
         device -> a new tensor there (torch's current stream is synchronised first).  x0: a guess per system, of b's kind and
         shape; not modified.  sigma: a shift per system, [nsys] float64 of b's kind (a sequence is fine beside a NumPy b); None =
         the handle's current shift for all.  params.use_true_solution and params.diagnostics must be 0."""
-        nsys, on_device = self._check_batch(b, self.size, _capi.MANY_MAX)
-        if x0 is not None:
-            if self._check_batch(x0, self.size, _capi.MANY_MAX) != (nsys, on_device):
-                raise ValueError(f"x0 has shape {tuple(x0.shape)}: the guesses are of the kind (NumPy / CUDA tensor) and shape of b, "
-                                 f"{tuple(b.shape)}")
+        nsys, on_device, sp = self._batched(b, x0, ("b", "x0", "guesses", "batch"), _capi.MANY_MAX, stop_flag)
         res = (_capi.Results * nsys)()
-        sp = C.cast(C.pointer(stop_flag), C.c_void_p) if stop_flag is not None else None
         if on_device:
             import torch
-            if b.device.index != self._device:
-                raise ValueError(f"batch is on {b.device}, the handle on device {self._device}")
-            if x0 is not None and x0.device != b.device:
-                raise ValueError(f"x0 is on {x0.device}, b on {b.device}")
             if sigma is not None:
                 if not (hasattr(sigma, "data_ptr") and sigma.is_cuda and sigma.device == b.device and sigma.dtype == torch.float64
                         and tuple(sigma.shape) == (nsys,) and sigma.is_contiguous()):
@@ -365,9 +347,7 @@ class _Handle:
             x = np.empty_like(b) if x0 is None else np.array(x0, dtype=np.float64, order="C", copy=True)
             fn = self._lib.mi355cg_solve_many if x0 is None else self._lib.mi355cg_solve_many_from
             rc = fn(self._h, C.byref(params), nsys, b.ctypes.data, x.ctypes.data, sigma.ctypes.data if sigma is not None else None, sp, res)
-        if rc == _capi.ERR_INVALID:
-            raise ValueError(self._lib.mi355cg_last_error().decode())
-        _capi.check(rc)
+        self._check_rc(rc)
         return x, list(res)
 
     def time_steps_many(self, params: _capi.Params, u0, tau, theta: float, nsteps: int, g=None, stop_flag: Optional[C.c_int] = None):
@@ -380,11 +360,7 @@ class _Handle:
         handle's device -> a new tensor there (torch's current stream is synchronised first); not modified.  g: of u0's kind and
         shape, None = the handle's right-hand side for every member.  tau: a scalar or [nsys] (host values).
         params.use_true_solution and params.diagnostics must be 0."""
-        nsys, on_device = self._check_batch(u0, self.size, _capi.MANY_MAX)
-        if g is not None:
-            if self._check_batch(g, self.size, _capi.MANY_MAX) != (nsys, on_device):
-                raise ValueError(f"g has shape {tuple(g.shape)}: the forcings are of the kind (NumPy / CUDA tensor) and shape of u0, "
-                                 f"{tuple(u0.shape)}")
+        nsys, on_device, sp = self._batched(u0, g, ("u0", "g", "forcings", "ensemble"), _capi.MANY_MAX, stop_flag)
         if hasattr(tau, "data_ptr"):
             tau = tau.detach().cpu().numpy()
         tau = np.ascontiguousarray(np.broadcast_to(np.asarray(tau, dtype=np.float64), (nsys,)) if np.ndim(tau) == 0 else tau, dtype=np.float64)
@@ -398,13 +374,8 @@ class _Handle:
         res = (_capi.Results * nsys)()
         steps_done = np.zeros(nsys, dtype=np.int32)
         step_it = np.full((nsys, nsteps), -1, dtype=np.int32)
-        sp = C.cast(C.pointer(stop_flag), C.c_void_p) if stop_flag is not None else None
         if on_device:
             import torch
-            if u0.device.index != self._device:
-                raise ValueError(f"ensemble is on {u0.device}, the handle on device {self._device}")
-            if g is not None and g.device != u0.device:
-                raise ValueError(f"g is on {g.device}, u0 on {u0.device}")
             u = u0.clone()
             torch.cuda.current_stream(u0.device).synchronize()
             rc = self._lib.mi355cg_time_steps_many_device(self._h, C.byref(params), nsys, nsteps, float(theta), tau.ctypes.data,
@@ -417,9 +388,7 @@ class _Handle:
             rc = self._lib.mi355cg_time_steps_many(self._h, C.byref(params), nsys, nsteps, float(theta), tau.ctypes.data,
                                                    g.ctypes.data if g is not None else None, u.ctypes.data, sp, res,
                                                    steps_done.ctypes.data, step_it.ctypes.data)
-        if rc == _capi.ERR_INVALID:
-            raise ValueError(self._lib.mi355cg_last_error().decode())
-        _capi.check(rc)
+        self._check_rc(rc)
         return u, list(res), steps_done, step_it
 
     def solve_many_info(self, nsys: int):
@@ -427,9 +396,7 @@ class _Handle:
         (mi355cg_solve_many_info); ValueError for handles solve_many refuses."""
         lds, wg, ws = C.c_int(), C.c_int(), C.c_longlong()
         rc = self._lib.mi355cg_solve_many_info(self._h, int(nsys), C.byref(lds), C.byref(wg), C.byref(ws))
-        if rc == _capi.ERR_INVALID:
-            raise ValueError(self._lib.mi355cg_last_error().decode())
-        _capi.check(rc)
+        self._check_rc(rc)
         return {"lds_bytes_per_workgroup": lds.value, "workgroups_per_cu": wg.value, "workspace_bytes": ws.value}
 
     @staticmethod
@@ -478,9 +445,7 @@ class _Handle:
             v = np.array(x, dtype=np.float64, order="C", copy=True)
             rc = self._lib.mi355cg_eigs(self._h, nev, block, float(tol), int(max_iterations), v.ctypes.data, lam.ctypes.data,
                                         res.ctypes.data, sp, C.byref(out))
-        if rc == _capi.ERR_INVALID:
-            raise ValueError(self._lib.mi355cg_last_error().decode())
-        _capi.check(rc)
+        self._check_rc(rc)
         return lam[:block], v, res[:block], out
 
     def eigs_release(self):
@@ -498,9 +463,7 @@ class _Handle:
         rc = self._lib.mi355cg_block_gram_indexed(self._h, a.shape[0], a.ctypes.data, 0 if ia is None else ia.size,
                                                   None if ia is None else ia.ctypes.data, b.shape[0], b.ctypes.data,
                                                   0 if ib is None else ib.size, None if ib is None else ib.ctypes.data, out.ctypes.data)
-        if rc == _capi.ERR_INVALID:
-            raise ValueError(self._lib.mi355cg_last_error().decode())
-        _capi.check(rc)
+        self._check_rc(rc)
         return out
 
     def block_combine(self, s, coef):
@@ -511,9 +474,7 @@ class _Handle:
             raise ValueError(f"coef has shape {tuple(coef.shape)}, expected ({s.shape[0]}, 1 .. {_capi.EIG_BLOCK_MAX})")
         y = np.empty((coef.shape[1], self.size))
         rc = self._lib.mi355cg_block_combine(self._h, s.shape[0], s.ctypes.data, coef.shape[1], coef.ctypes.data, y.ctypes.data)
-        if rc == _capi.ERR_INVALID:
-            raise ValueError(self._lib.mi355cg_last_error().decode())
-        _capi.check(rc)
+        self._check_rc(rc)
         return y
 
     def setup_on_device(self):
