@@ -45,6 +45,8 @@
  *   mi355cg_solve_many_info        LDS per workgroup, resident workgroups per CU and workspace bytes of such a batch
  *   mi355cg_time_steps_many / _device   an ensemble of small time steppers (own state, forcing and tau each), the step loop inside the launch
  *   mi355cg_time_steps_many_workspace   the device workspace bytes of such an ensemble (pure host arithmetic, no GPU needed)
+ *   mi355cg_wave_steps_many / _device   an ensemble of small wave-equation steppers u_tt = A u - g: velocity Verlet or Newmark
+ *   mi355cg_wave_steps_many_workspace / mi355cg_wave_cfl   its workspace bytes; the explicit scheme's bound on tau (host arithmetic)
  *
  * Plain pointers and sizes only; no C++/torch types.  All host vectors are in the reference's
  * PACKED unknown order (bottom-right block row-major, then the upper block row-major;
@@ -525,6 +527,55 @@ int  mi355cg_time_steps_many_device(mi355cg_handle h, const mi355cg_params *para
                                     const double *g_dev, double *u_dev, const volatile int *stop_flag, mi355cg_results *out,
                                     int *steps_done, int *step_iterations);
 int  mi355cg_time_steps_many_workspace(int n, int nsys, int nsteps, int with_step_iterations, long long *bytes);
+
+/* Ensemble wave-equation steps on chip: nsys members on the grid of one eligible handle (exactly the handles mi355cg_solve_many
+ * takes), each integrated over nsteps steps of u_tt = A u - g_s with its own time step tau_s, ONE workgroup per member (DESIGN
+ * section 12.3).  A is the UNSHIFTED operator of the handle.  The state of member s is the pair (u_s, v_s), v = u_t, both in and
+ * out; nsteps and the scheme are shared.  One call of k steps gives the bits of k calls of one step: that is how a caller takes
+ * snapshots.
+ * tau: nsys doubles in HOST memory (both entry points).  g: nsys packed vectors, or NULL = the handle's right-hand side for every
+ * member.  u, v: nsys packed vectors of mi355cg_size(h) doubles each.  out: nsys entries.  steps_done: nsys ints.
+ * MI355CG_WAVE_VERLET, explicit: with h = 0.5 tau and au(u) = A0 u + xk (left + right) + yk (down + up), one rounding per
+ * operation in this order,   a = au(u) - g;  vh = v + h a;  u = u + tau vh;  a = au(u) - g;  v = vh + h a.
+ * The step loop runs inside the launch: one stencil pass and two axpys per step, no inner product and no decision; params is not
+ * read and may be NULL, step_iterations must be NULL or is left untouched.  All members take the same number of steps; out[s]
+ * reports iterations 0, converged 1.  tau_s must not exceed the bound of mi355cg_wave_cfl, beyond which the scheme diverges.
+ * steps_per_launch (0: the default, 512; 1024 steps were measured at 15.3 ms per launch for 1024 members
+ * of N = 128, the profile has the default's own times) cuts the run into ceil(nsteps / steps_per_launch)
+ * launches; before each the host waits for the one before and tests stop_flag: when it is set, steps_done is what has run, every
+ * member reports MI355CG_STOP_INTERRUPTED and (u, v) are the state at that step.
+ * MI355CG_WAVE_NEWMARK, implicit (beta = 1/4, gamma = 1/2, unconditionally stable): with sigma = 4 / tau^2 and hv = 2 / tau,
+ *    w = u + tau v;  b = (g + g) - sigma w;  b = b - au(u);  solve (A - sigma I) x = b from x0 = u;  v = hv (x - u) - v;  u = x,
+ * every step the warm-started solve mi355cg_time_steps_many runs, under params as there (both rules, fixed_iterations,
+ * max_iterations per step, sync_every units per launch; steps_per_launch is not read), the diagonal A_diag - sigma rounded once
+ * as mi355cg_set_shift stores it: member s gets the bits of that solve on a handle of the same grid.  A member ends after its
+ * first step that does not converge (the iteration cap or a stop request); its (u, v) are then the state after its last converged
+ * step, out[s] and step_iterations report the step attempted, as mi355cg_time_steps_many does.
+ * The handle's own state is untouched: its b, x, r, shift, solve mode, pending guess and what the getters return.
+ * MI355CG_ERR_INVALID, before anything is allocated or written: a null h, tau, u, v, out or steps_done (Newmark: params), an
+ * unknown scheme, any overlap among u, v and g, nsys < 1 or > MI355CG_MANY_MAX, nsteps < 0 or > MI355CG_STEPS_MANY_MAX_STEPS,
+ * steps_per_launch < 0, a tau_s that is not finite or <= 0, Verlet: a tau_s above mi355cg_wave_cfl (the message names the bound
+ * and the member), Newmark: a tau_s whose 4 / tau_s^2 is not finite, nsys * nsteps > 2^26 with step_iterations given, an unknown
+ * rule, use_true_solution != 0 or diagnostics != 0, and every handle mi355cg_solve_many refuses, with its message.
+ * MI355CG_ERR_STATE: the handle has a preconditioner.  nsteps = 0 is MI355CG_OK and writes only steps_done = 0.
+ * _device: g_dev, u_dev and v_dev are in device memory of the handle's GPU, everything else in host memory; the work runs on the
+ * handle's stream and the call returns after that stream is idle.
+ * Workspace: Verlet, that of mi355cg_solve_many for nsys systems, 16 bytes per member (tau and 2 / tau) and one packed vector
+ * (the handle's right-hand side); Newmark, that of mi355cg_time_steps_many and 16 bytes per member.  The host entry point stages
+ * g, u and v on top (3 nsys packed vectors).  It shares the batch workspace of the handle, grows on demand and is freed by
+ * mi355cg_batch_release and mi355cg_destroy.  mi355cg_wave_steps_many_workspace: that many bytes, pure host arithmetic.
+ * mi355cg_wave_cfl: tau_max = 2 / sqrt(2 |A_diag|) of the UNSHIFTED operator, Gershgorin's bound on the spectrum: sufficient for
+ * stability, not sharp; host arithmetic on the handle's geometry, for grid handles of any size.                               */
+#define MI355CG_WAVE_VERLET  0     /* explicit: velocity Verlet (= leapfrog), tau limited by the CFL bound */
+#define MI355CG_WAVE_NEWMARK 1     /* implicit: Newmark beta = 1/4, gamma = 1/2 (trapezoidal), unconditionally stable */
+int  mi355cg_wave_steps_many(mi355cg_handle h, const mi355cg_params *params, int nsys, int nsteps, int scheme, const double *tau,
+                             const double *g, double *u, double *v, int steps_per_launch, const volatile int *stop_flag,
+                             mi355cg_results *out, int *steps_done, int *step_iterations);
+int  mi355cg_wave_steps_many_device(mi355cg_handle h, const mi355cg_params *params, int nsys, int nsteps, int scheme, const double *tau,
+                                    const double *g_dev, double *u_dev, double *v_dev, int steps_per_launch,
+                                    const volatile int *stop_flag, mi355cg_results *out, int *steps_done, int *step_iterations);
+int  mi355cg_wave_steps_many_workspace(int n, int nsys, int nsteps, int scheme, int with_step_iterations, long long *bytes);
+int  mi355cg_wave_cfl(mi355cg_handle h, double *tau_max);
 
 /* ---- multi-GPU: one context per rank, one contiguous slab of grid rows per context --------------
  * The reference is single-process (no collectives exist in it); this is the scaling

@@ -40,7 +40,9 @@ EXPORTS = [
     "mi355cg_set_solve_mode", "mi355cg_get_solve_mode", "mi355cg_onchip_plan",
     "mi355cg_solve_many", "mi355cg_solve_many_from", "mi355cg_solve_many_device", "mi355cg_solve_many_device_from", "mi355cg_solve_many_info",
     "mi355cg_time_steps_many", "mi355cg_time_steps_many_device", "mi355cg_time_steps_many_workspace",
+    "mi355cg_wave_steps_many", "mi355cg_wave_steps_many_device", "mi355cg_wave_steps_many_workspace", "mi355cg_wave_cfl",
 ]
+WAVE_VERLET, WAVE_NEWMARK = 0, 1    # MI355CG_WAVE_VERLET, MI355CG_WAVE_NEWMARK
 DECOMP_ROWS, DECOMP_2D = 0, 1
 PRECOND_NONE, PRECOND_MG, PRECOND_MG_ANY = 0, 1, 2
 CYCLE_F64, CYCLE_F32 = 0, 1
@@ -230,6 +232,13 @@ def load():
             fn.argtypes = [H, C.POINTER(Params), C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                            C.POINTER(Results), C.c_void_p, C.c_void_p]
         L.mi355cg_time_steps_many_workspace.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, LLP]
+    if hasattr(L, "mi355cg_wave_steps_many"):   # absent from an older build loaded through MI355CG_LIB
+        # tau (host), g, u and v (host arrays / device memory for _device), the stop flag, steps_done and step_iterations as plain addresses
+        for fn in (L.mi355cg_wave_steps_many, L.mi355cg_wave_steps_many_device):
+            fn.argtypes = [H, C.POINTER(Params), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                           C.c_void_p, C.POINTER(Results), C.c_void_p, C.c_void_p]
+        L.mi355cg_wave_steps_many_workspace.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, LLP]
+        L.mi355cg_wave_cfl.argtypes = [H, DBP]
     if hasattr(L, "mi355cg_get_xfold"):         # absent from an older build loaded through MI355CG_LIB
         L.mi355cg_get_xfold.argtypes = [H, IP, IP]
     _lib = L

@@ -527,6 +527,51 @@ public:
         if (steps_done) *steps_done = std::move(done);
         return u;
     }
+    // Extension: an ensemble of wave-equation steppers u_tt = A u - g[s] on this grid, one workgroup per member
+    // (mi355cg_wave_steps_many; grids up to N = 128, no preconditioner).  Member s takes nsteps steps of velocity Verlet
+    // (MI355CG_WAVE_VERLET: every tau at most waveCfl(), params not read) or of average-acceleration Newmark (MI355CG_WAVE_NEWMARK:
+    // every step a warm-started solve under params) from the state (u[s], v[s]), both updated in place, with the time step tau[s];
+    // an empty g means this system's right-hand side for every member.  One call of k steps gives the bits of k calls of one
+    // step.  results[s]: Verlet, 0 iterations and converged; Newmark, the last step attempted, with steps_done[s] converged steps
+    // and step_iterations[s] as timeStepsMany reports them.  The system's own state, the shift included, is left as it was.
+    // std::invalid_argument for an empty ensemble, more than MI355CG_MANY_MAX members, a v, tau or g of another length, a vector
+    // of the wrong size and what the library refuses as invalid (a Verlet tau above waveCfl() among it); std::runtime_error on a
+    // system with a preconditioner.
+    void waveStepsMany(std::vector<std::vector<double>>& u, std::vector<std::vector<double>>& v, const std::vector<double>& tau, int nsteps,
+                       int scheme, const mi355cg_params& params, std::vector<mi355cg_results>* results = nullptr,
+                       std::vector<int>* steps_done = nullptr, std::vector<std::vector<int>>* step_iterations = nullptr,
+                       const std::vector<std::vector<double>>& g = {}, int steps_per_launch = 0) {
+        if (u.empty() || u.size() > (size_t)MI355CG_MANY_MAX) throw std::invalid_argument("waveStepsMany: an ensemble has 1 .. MI355CG_MANY_MAX members");
+        const size_t n = rhs.size(), k = u.size();
+        if (v.size() != k) throw std::invalid_argument("waveStepsMany: v does not have one vector per member");
+        if (tau.size() != k) throw std::invalid_argument("waveStepsMany: tau does not have one entry per member");
+        if (!g.empty() && g.size() != k) throw std::invalid_argument("waveStepsMany: g does not have one vector per member");
+        if (nsteps < 0 || nsteps > MI355CG_STEPS_MANY_MAX_STEPS) throw std::invalid_argument("waveStepsMany: nsteps is 0 .. MI355CG_STEPS_MANY_MAX_STEPS");
+        std::vector<double> gp(g.empty() ? 0 : n * k), up(n * k), vp(n * k);
+        for (size_t s = 0; s < k; ++s) {
+            if (u[s].size() != n || v[s].size() != n || (!g.empty() && g[s].size() != n)) throw std::invalid_argument("waveStepsMany: vector size does not match the system");
+            std::copy(u[s].begin(), u[s].end(), up.begin() + (std::ptrdiff_t)(s * n));
+            std::copy(v[s].begin(), v[s].end(), vp.begin() + (std::ptrdiff_t)(s * n));
+            if (!g.empty()) std::copy(g[s].begin(), g[s].end(), gp.begin() + (std::ptrdiff_t)(s * n));
+        }
+        std::vector<mi355cg_results> res(k);
+        const bool counts = step_iterations && nsteps > 0 && scheme == MI355CG_WAVE_NEWMARK;
+        std::vector<int> done(k, 0), its(step_iterations ? k * (size_t)nsteps : 0, -1);
+        mi355cg_compat::check(mi355cg_wave_steps_many(ctx_->h, &params, (int)k, nsteps, scheme, tau.data(), g.empty() ? nullptr : gp.data(), up.data(),
+                                                      vp.data(), steps_per_launch, nullptr, res.data(), done.data(), counts ? its.data() : nullptr));
+        for (size_t s = 0; s < k; ++s) {
+            u[s].assign(up.begin() + (std::ptrdiff_t)(s * n), up.begin() + (std::ptrdiff_t)((s + 1) * n));
+            v[s].assign(vp.begin() + (std::ptrdiff_t)(s * n), vp.begin() + (std::ptrdiff_t)((s + 1) * n));
+        }
+        if (step_iterations) {
+            step_iterations->assign(k, std::vector<int>());
+            for (size_t s = 0; s < k; ++s) (*step_iterations)[s].assign(its.begin() + (std::ptrdiff_t)(s * (size_t)nsteps), its.begin() + (std::ptrdiff_t)((s + 1) * (size_t)nsteps));
+        }
+        if (results) *results = std::move(res);
+        if (steps_done) *steps_done = std::move(done);
+    }
+    // the largest time step MI355CG_WAVE_VERLET takes on this grid (mi355cg_wave_cfl)
+    double waveCfl() const { double t = 0.0; mi355cg_compat::check(mi355cg_wave_cfl(ctx_->h, &t)); return t; }
     void batchRelease() { mi355cg_compat::check(mi355cg_batch_release(ctx_->h)); }
     // Extension: the nev lowest eigenpairs of this system's operator by a block preconditioned iteration with one multigrid V-cycle
     // per vector and iteration (mi355cg_eigs; needs setPreconditioner with the fp64 cycle first).  lambda > 0 ascending with

@@ -169,8 +169,8 @@ struct OnchipManyWs {
     Buf<CgState> summary_h;             // pinned copies
     Buf<double> small_h;                // pinned: the layout of `small`
     Buf<int> done_h;
-    Buf<double> stage;                  // packed vectors of the host entry points: b, then x
-    long long stage_cap = 0;            // systems it holds
+    Buf<double> stage;                  // packed vectors of the host entry points: b, then x (the wave steppers: g, u, v)
+    long long stage_cap = 0;            // packed vectors it holds
     // mi355cg_time_steps_many* on top (onchip_steps_workspace_bytes), allocated by the first such call
     int steps_cap = 0;                  // members the next five hold
     Buf<double> step_sigma;             // 1 / (theta tau_s)
@@ -181,6 +181,10 @@ struct OnchipManyWs {
     Buf<CgState> s_h;
     Buf<int> step_it;                   // iteration counts, member-major, -1 = step not taken: only when the caller asks for them
     long long step_it_cap = 0;          // counts it holds
+    // mi355cg_wave_steps_many* on top (onchip_wave_workspace_bytes): g_one above is shared with the steppers
+    int wave_cap = 0;                   // members the next two hold
+    Buf<double> wave_tau;               // tau_s of every member, then 2 / tau_s
+    Buf<double> wave_tau_h;             // pinned copy
 };
 
 // `small` and its pinned mirror in a call of nsys <= cap systems: nsys x FB_COUNT update partials, then nsys diagonals, then nsys ||r0||_2
@@ -1670,6 +1674,8 @@ const BatchKind kOnchipBatch{MI355CG_MANY_MAX, "a batch of on-chip solves has 1 
                              "mi355cg_solve_many is plain CG in one workgroup per system (mi355cg_solve_batch is the preconditioned batch)"};
 const BatchKind kEnsemble{MI355CG_MANY_MAX, "an ensemble of on-chip steppers has 1 .. %d members, not %d", "a step has no exact solution", "the stepper",
                           "mi355cg_time_steps_many is plain CG in one workgroup per member"};
+const BatchKind kWaveEnsemble{MI355CG_MANY_MAX, "an ensemble of on-chip wave steppers has 1 .. %d members, not %d", "a step has no exact solution", "the stepper",
+                              "mi355cg_wave_steps_many is one workgroup per member on the plain operator"};
 
 // what both entry points refuse before anything is allocated or written
 int batch_check(mi355cg_ctx* c, const mi355cg_params* prm, int nrhs, const void* b, const void* x, const mi355cg_results* out) {
@@ -1682,19 +1688,26 @@ int batch_check(mi355cg_ctx* c, const mi355cg_params* prm, int nrhs, const void*
     return MI355CG_OK;
 }
 
-// A host entry point of a batched solve: the packed vectors go up into the staging buffer, `body(first, second)` runs on them in
-// device memory, `second` comes down.  second_at: where the second group starts (count: b or g in the first half, x or u in the
-// second; 0: one group that goes up and comes down).  A null source is not copied.  The caller has ensured the buffer before.
-template <class Body>
-int run_staged(mi355cg_ctx* c, double* stage, size_t count, size_t second_at, const double* up_first, const double* up_second, double* down, Body body) {
+// A host entry point of a batched solve: the packed vectors go up into the staging buffer, the body runs on them in device memory,
+// what it wrote comes down.  A group is `count` doubles at stage + at; a null source is not copied up, a null destination not
+// copied down.  The caller has ensured the buffer before.
+struct StagedGroup { size_t at; const double* up; double* down; };
+template <size_t G, class Body>
+int run_staged_groups(mi355cg_ctx* c, double* stage, size_t count, const StagedGroup (&groups)[G], Body body) {
     const size_t bytes = sizeof(double) * count;
-    double* const second = stage + second_at;
-    if (up_first) HIPCK(hipMemcpyAsync(stage, up_first, bytes, hipMemcpyHostToDevice, c->stream));
-    if (up_second) HIPCK(hipMemcpyAsync(second, up_second, bytes, hipMemcpyHostToDevice, c->stream));
-    if (int rc = body((const double*)stage, second)) return rc;
-    HIPCK(hipMemcpyAsync(down, second, bytes, hipMemcpyDeviceToHost, c->stream));
+    for (const StagedGroup& g : groups) if (g.up) HIPCK(hipMemcpyAsync(stage + g.at, g.up, bytes, hipMemcpyHostToDevice, c->stream));
+    if (int rc = body()) return rc;
+    for (const StagedGroup& g : groups) if (g.down) HIPCK(hipMemcpyAsync(g.down, stage + g.at, bytes, hipMemcpyDeviceToHost, c->stream));
     HIPCK(hipStreamSynchronize(c->stream));
     return MI355CG_OK;
+}
+// Two groups, `body(first, second)`, `second` comes down.  second_at: where the second group starts (count: b or g in the first
+// half, x or u in the second; 0: one group that goes up and comes down).
+template <class Body>
+int run_staged(mi355cg_ctx* c, double* stage, size_t count, size_t second_at, const double* up_first, const double* up_second, double* down, Body body) {
+    double* const second = stage + second_at;
+    const StagedGroup groups[2] = {{0, up_first, nullptr}, {second_at, up_second, down}};
+    return run_staged_groups(c, stage, count, groups, [&]() { return body((const double*)stage, second); });
 }
 
 // The unroll classes of onchip_plan (OnchipPlan::elems) and the rule as template arguments, for every on-chip kernel:
@@ -2999,7 +3012,8 @@ static int many_check_sigma(const double* sigma, int nsys) {
 }
 
 // A workspace that is large enough is kept; a larger one replaces it only once it is complete, so a failure leaves the handle as it was.
-static int onchip_many_ensure(mi355cg_ctx* c, int nsys, bool stage) {
+// stage_vecs: packed vectors per system the host entry point stages (0: a device entry point).
+static int onchip_many_ensure(mi355cg_ctx* c, int nsys, int stage_vecs) {
     if (!c->many || c->many->cap < nsys) {
         std::unique_ptr<OnchipManyWs> W(new OnchipManyWs());
         auto failed = [&](const char* what) { return fail(MI355CG_ERR_HIP, "on-chip batch workspace for %d systems: %s allocation failed", nsys, what); };
@@ -3016,11 +3030,11 @@ static int onchip_many_ensure(mi355cg_ctx* c, int nsys, bool stage) {
         c->many = std::move(W);
     }
     OnchipManyWs* W = c->many.get();
-    if (stage && nsys > W->stage_cap) {
+    if ((long long)stage_vecs * nsys > W->stage_cap) {
         HIPCK(hipStreamSynchronize(c->stream));                    // nothing in flight reads the buffer that is replaced
-        if (Buf<double>::device(W->stage, 2 * c->pk_len * nsys))
-            return fail(MI355CG_ERR_HIP, "on-chip batch staging for %d packed vectors: allocation failed", 2 * nsys);
-        W->stage_cap = nsys;
+        if (Buf<double>::device(W->stage, stage_vecs * c->pk_len * nsys))
+            return fail(MI355CG_ERR_HIP, "on-chip batch staging for %d packed vectors: allocation failed", stage_vecs * nsys);
+        W->stage_cap = (long long)stage_vecs * nsys;
     }
     return MI355CG_OK;
 }
@@ -3163,7 +3177,7 @@ static int solve_many_device(mi355cg_ctx* c, const mi355cg_params* prm, int nsys
         HIPCK(hipMemcpy(sigma.data(), sigma_dev, sizeof(double) * nsys, hipMemcpyDeviceToHost));
         if (int rc = many_check_sigma(sigma.data(), nsys)) return rc;
     }
-    if (int rc = onchip_many_ensure(c, nsys, false)) return rc;
+    if (int rc = onchip_many_ensure(c, nsys, 0)) return rc;
     return solve_many(c, prm, nsys, b_dev, x_dev, sigma_dev ? sigma.data() : nullptr, stop_flag, out, warm);
 }
 static int solve_many_host(mi355cg_ctx* c, const mi355cg_params* prm, int nsys, const double* b, double* x, const double* sigma,
@@ -3171,7 +3185,7 @@ static int solve_many_host(mi355cg_ctx* c, const mi355cg_params* prm, int nsys, 
     if (int rc = many_check(c, prm, nsys, b, x, out)) return rc;
     if (int rc = many_check_sigma(sigma, nsys)) return rc;
     HIPCK(hipSetDevice(c->device));
-    if (int rc = onchip_many_ensure(c, nsys, true)) return rc;
+    if (int rc = onchip_many_ensure(c, nsys, 2)) return rc;
     const size_t count = (size_t)c->pk_len * (size_t)nsys;         // b in the first half, the guesses / the solutions in the second
     return run_staged(c, c->many->stage, count, count, b, warm ? x : nullptr, x, [&](const double* b_dev, double* x_dev) {
         return solve_many(c, prm, nsys, b_dev, x_dev, sigma, stop_flag, out, warm);
@@ -3235,8 +3249,8 @@ static int steps_many_check(mi355cg_ctx* c, const mi355cg_params* prm, int nsys,
 }
 
 // The batch workspace for nsys members, then the stepping parts on top: built complete before they replace what is there.
-static int onchip_steps_ensure(mi355cg_ctx* c, int nsys, long long counts, bool stage) {
-    if (int rc = onchip_many_ensure(c, nsys, stage)) return rc;
+static int onchip_steps_ensure(mi355cg_ctx* c, int nsys, long long counts, int stage_vecs) {
+    if (int rc = onchip_many_ensure(c, nsys, stage_vecs)) return rc;
     OnchipManyWs* W = c->many.get();
     auto failed = [&](const char* what) { return fail(MI355CG_ERR_HIP, "on-chip stepping workspace for %d members: %s allocation failed", nsys, what); };
     if (W->steps_cap < nsys) {
@@ -3321,7 +3335,7 @@ int mi355cg_time_steps_many_device(mi355cg_handle c, const mi355cg_params* prm, 
     if (int rc = steps_many_check(c, prm, nsys, nsteps, theta, tau, g_dev, u_dev, out, steps_done, step_iterations)) return rc;
     if (nsteps == 0) { for (int s = 0; s < nsys; ++s) steps_done[s] = 0; return MI355CG_OK; }
     HIPCK(hipSetDevice(c->device));
-    if (int rc = onchip_steps_ensure(c, nsys, step_iterations ? (long long)nsys * nsteps : 0, false)) return rc;
+    if (int rc = onchip_steps_ensure(c, nsys, step_iterations ? (long long)nsys * nsteps : 0, 0)) return rc;
     return steps_many(c, prm, nsys, nsteps, theta, tau, g_dev, u_dev, stop_flag, out, steps_done, step_iterations);
 }
 int mi355cg_time_steps_many(mi355cg_handle c, const mi355cg_params* prm, int nsys, int nsteps, double theta, const double* tau, const double* g,
@@ -3329,7 +3343,7 @@ int mi355cg_time_steps_many(mi355cg_handle c, const mi355cg_params* prm, int nsy
     if (int rc = steps_many_check(c, prm, nsys, nsteps, theta, tau, g, u, out, steps_done, step_iterations)) return rc;
     if (nsteps == 0) { for (int s = 0; s < nsys; ++s) steps_done[s] = 0; return MI355CG_OK; }
     HIPCK(hipSetDevice(c->device));
-    if (int rc = onchip_steps_ensure(c, nsys, step_iterations ? (long long)nsys * nsteps : 0, true)) return rc;
+    if (int rc = onchip_steps_ensure(c, nsys, step_iterations ? (long long)nsys * nsteps : 0, 2)) return rc;
     const size_t count = (size_t)c->pk_len * (size_t)nsys;         // g in the first half, the states in the second
     return run_staged(c, c->many->stage, count, count, g, u, u, [&](const double* g_dev, double* u_dev) {
         return steps_many(c, prm, nsys, nsteps, theta, tau, g ? g_dev : nullptr, u_dev, stop_flag, out, steps_done, step_iterations);
@@ -3342,6 +3356,204 @@ int mi355cg_time_steps_many_workspace(int n, int nsys, int nsteps, int with_step
         return fail(MI355CG_ERR_INVALID, "ensemble rejected: even n from 6 to %d, 1 .. %d members, 0 .. %d steps, at most %lld iteration counts",
                     kOnchipMaxN, kOnchipStepsMaxSys, kOnchipStepsMaxSteps, kOnchipStepsMaxCounts);
     *bytes = v;
+    return MI355CG_OK;
+}
+
+// ---- ensemble wave-equation steps on chip: velocity Verlet and Newmark ---------------------------------------
+static_assert(MI355CG_WAVE_VERLET == kWaveVerlet && MI355CG_WAVE_NEWMARK == kWaveNewmark, "onchip_plan.h: the schemes");
+// what both entry points refuse before anything is allocated or written (tau is in host memory for both)
+static int wave_check(mi355cg_ctx* c, const mi355cg_params* prm, int nsys, int nsteps, int scheme, const double* tau, const void* g, const void* u,
+                      const void* v, int steps_per_launch, const mi355cg_results* out, const int* steps_done, const int* step_iterations) {
+    if (!c || !tau || !u || !v || !out || !steps_done) return fail(MI355CG_ERR_INVALID, "null argument");
+    if (scheme != MI355CG_WAVE_VERLET && scheme != MI355CG_WAVE_NEWMARK) return fail(MI355CG_ERR_INVALID, "unknown wave scheme %d", scheme);
+    const bool newmark = scheme == MI355CG_WAVE_NEWMARK;
+    if (newmark && !prm) return fail(MI355CG_ERR_INVALID, "null argument: the Newmark scheme reads params");
+    if (int rc = kWaveEnsemble.count(nsys)) return rc;
+    if (nsteps < 0 || nsteps > MI355CG_STEPS_MANY_MAX_STEPS) return fail(MI355CG_ERR_INVALID, "nsteps %d rejected: it must be 0 .. %d", nsteps, MI355CG_STEPS_MANY_MAX_STEPS);
+    if (steps_per_launch < 0) return fail(MI355CG_ERR_INVALID, "steps_per_launch %d rejected: 0 (the default) or a positive number of steps", steps_per_launch);
+    if (newmark && step_iterations && (long long)nsys * nsteps > kOnchipStepsMaxCounts)
+        return fail(MI355CG_ERR_INVALID, "step_iterations for %d members x %d steps rejected: at most %lld counts", nsys, nsteps, kOnchipStepsMaxCounts);
+    if (newmark) if (int rc = kWaveEnsemble.params(prm)) return rc;
+    if (int rc = kWaveEnsemble.onchip(c)) return rc;
+    const double bound = onchip_wave_cfl(c->gp.A);
+    for (int s = 0; s < nsys; ++s) {
+        if (!std::isfinite(tau[s]) || !(tau[s] > 0.0)) return fail(MI355CG_ERR_INVALID, "time step %g of member %d rejected: tau must be finite and > 0", tau[s], s);
+        if (newmark && !std::isfinite(4.0 / (tau[s] * tau[s]))) return fail(MI355CG_ERR_INVALID, "time step %g of member %d rejected: 4 / tau^2 is not finite", tau[s], s);
+        if (!newmark && tau[s] > bound)
+            return fail(MI355CG_ERR_INVALID, "time step %.17g of member %d rejected: velocity Verlet needs tau <= %.17g on this grid (mi355cg_wave_cfl); MI355CG_WAVE_NEWMARK has no bound",
+                        tau[s], s, bound);
+    }
+    if (int rc = BatchKind::apart(c, nsys, u, v, "u overlaps v")) return rc;
+    if (g) if (int rc = BatchKind::apart(c, nsys, u, g, "u overlaps g")) return rc;
+    return g ? BatchKind::apart(c, nsys, v, g, "v overlaps g") : MI355CG_OK;
+}
+
+// The workspace of the scheme's driver, then the wave parts on top: built complete before they replace what is there.
+static int onchip_wave_ensure(mi355cg_ctx* c, int nsys, int scheme, long long counts, int stage_vecs) {
+    if (int rc = scheme == MI355CG_WAVE_NEWMARK ? onchip_steps_ensure(c, nsys, counts, stage_vecs) : onchip_many_ensure(c, nsys, stage_vecs)) return rc;
+    OnchipManyWs* W = c->many.get();
+    auto failed = [&](const char* what) { return fail(MI355CG_ERR_HIP, "on-chip wave stepping workspace for %d members: %s allocation failed", nsys, what); };
+    if (W->wave_cap < nsys) {
+        Buf<double> tau, tau_h;
+        if (Buf<double>::device(tau, 2LL * nsys)) return failed("time step");
+        if (Buf<double>::pinned(tau_h, 2LL * nsys)) return failed("pinned copy");
+        HIPCK(hipStreamSynchronize(c->stream));
+        W->wave_tau = std::move(tau); W->wave_tau_h = std::move(tau_h);
+        W->wave_cap = nsys;
+    }
+    if (!W->g_one && Buf<double>::device(W->g_one, c->pk_len)) return failed("vector");
+    return MI355CG_OK;
+}
+
+// tau_s and 2 / tau_s of every member to the device; the handle's right-hand side, packed, when no forcing is given
+static int wave_upload(mi355cg_ctx* c, OnchipManyWs* W, int nsys, const double* tau, const double* g_dev) {
+    for (int s = 0; s < nsys; ++s) { W->wave_tau_h[s] = tau[s]; W->wave_tau_h[nsys + s] = 2.0 / tau[s]; }
+    HIPCK(hipMemcpyAsync(W->wave_tau, W->wave_tau_h, sizeof(double) * 2 * nsys, hipMemcpyHostToDevice, c->stream));
+    if (!g_dev) {
+        hipLaunchKernelGGL((k_pack<double>), dim3(flat_grid(c->pk_len)), dim3(kBlock), 0, c->stream, c->pg, (const double*)c->b, W->g_one.get());
+        HIPCK(hipGetLastError());
+    }
+    return MI355CG_OK;
+}
+
+// Explicit: ceil(nsteps / m) launches of m steps; before each the host waits for the one before it and tests the caller's flag.
+static int wave_verlet(mi355cg_ctx* c, int nsys, int nsteps, const double* tau, const double* g_dev, double* u_dev, double* v_dev,
+                       int steps_per_launch, const volatile int* stop_flag, mi355cg_results* out, int* steps_done) {
+    mi355cg_params none;                                           // the driver reads a rule; the scheme decides nothing
+    mi355cg_default_params(&none, MI355CG_RULE_REL_2NORM);
+    OnchipManyRun R;
+    if (int rc = R.open(c, &none, nsys, stop_flag, "wave stepping")) return rc;
+    OnchipManyWs* W = R.W;
+    if (int rc = wave_upload(c, W, nsys, tau, g_dev)) return rc;
+    OnchipWaveArgs a{};
+    a.pl = R.pl; a.k = OnchipWaveCoef{c->gp.A, c->gp.x_k, c->gp.y_k};
+    a.tau = W->wave_tau; a.g = g_dev ? g_dev : W->g_one.get(); a.g_stride = g_dev ? R.U : 0;
+    a.u = u_dev; a.v = v_dev; a.stride = R.U;
+    const void* k_steps = onchip_dispatch(R.pl.elems, false, [](auto el, auto) { return (const void*)&k_onchip_wave_verlet<decltype(el)::value>; });
+    if (int rc = R.allow_lds(k_steps)) return rc;
+    if (int rc = loop_timer_begin(c, c->stream)) return rc;
+    const int m = steps_per_launch > 0 ? steps_per_launch : kOnchipWaveDefaultSteps;
+    void* args[] = {&a};
+    int done = 0;
+    while (done < nsteps) {
+        if (done > 0) HIPCK(hipStreamSynchronize(c->stream));
+        if (stop_flag && *stop_flag) { R.interrupted = true; break; }
+        a.m = std::min(m, nsteps - done);
+        if (int rc = R.launch(k_steps, args)) return rc;
+        done += a.m;
+    }
+    if (int rc = R.end_loop(false)) return rc;
+    HIPCK(hipStreamSynchronize(c->stream));
+    CgState fin{};
+    fin.done = 1; fin.converged = 1;
+    for (int s = 0; s < nsys; ++s) { steps_done[s] = done; out[s] = make_results(fin, R.interrupted, false, 0.0); }
+    return R.stamp_times(out);
+}
+
+// Implicit: the loop, cap and poll of steps_many on k_onchip_wave_newmark.  The state moves in u_dev, v_dev themselves.
+static int wave_newmark(mi355cg_ctx* c, const mi355cg_params* prm, int nsys, int nsteps, const double* tau, const double* g_dev, double* u_dev,
+                        double* v_dev, const volatile int* stop_flag, mi355cg_results* out, int* steps_done, int* step_iterations) {
+    OnchipManyRun R;
+    if (int rc = R.open(c, prm, nsys, stop_flag, "wave stepping")) return rc;
+    OnchipManyWs* W = R.W;
+    const bool msg = R.msg;
+    const long long counts = step_iterations ? (long long)nsys * nsteps : 0;
+    for (int s = 0; s < nsys; ++s) {
+        W->step_sigma_h[s] = 4.0 / (tau[s] * tau[s]);
+        R.host.diag[s] = c->gp.A - W->step_sigma_h[s];               // mi355cg_set_shift's rounding
+    }
+    if (int rc = R.upload_diag()) return rc;
+    HIPCK(hipMemcpyAsync(W->step_sigma, W->step_sigma_h, sizeof(double) * nsys, hipMemcpyHostToDevice, c->stream));
+    if (int rc = wave_upload(c, W, nsys, tau, g_dev)) return rc;
+    if (int rc = R.reset_done()) return rc;
+    HIPCK(hipMemsetAsync(W->book, 0, sizeof(OcStepBook) * nsys, c->stream));
+    if (counts) HIPCK(hipMemsetAsync(W->step_it, 0xff, sizeof(int) * counts, c->stream));              // -1: not taken
+
+    OnchipNewmarkArgs e{};
+    e.pl = R.pl; e.xk = c->g.xk; e.yk = c->g.yk; e.diag = R.dev.diag; e.sigma = W->step_sigma; e.tau = W->wave_tau;
+    e.g = g_dev ? g_dev : W->g_one.get(); e.g_stride = g_dev ? R.U : 0; e.u = u_dev; e.v = v_dev;
+    e.x = R.x; e.r = R.r; e.p = R.p; e.stride = R.U;
+    e.partB = R.dev.partB; e.s = W->s; e.summary = W->summary; e.norm0 = R.dev.norm0; e.done_count = W->done;
+    e.book = W->book; e.step_it = counts ? W->step_it.get() : nullptr; e.nsteps = nsteps; e.nsys = nsys;
+    e.k = OnchipWaveCoef{c->gp.A, c->gp.x_k, c->gp.y_k};
+    e.rp = R.rp;
+    { void* args[] = {&e}; if (int rc = R.start((const void*)&k_onchip_wave_newmark_init, args)) return rc; }
+    if (int rc = R.begin_loop(msg)) return rc;
+
+    const void* k_chunk = onchip_dispatch(R.pl.elems, msg, [](auto el, auto m) { return (const void*)&k_onchip_wave_newmark<decltype(el)::value, decltype(m)::value>; });
+    if (int rc = R.allow_lds(k_chunk)) return rc;
+    e.m = default_sync_every(prm, msg);
+    const long long max_launches = onchip_steps_launch_cap(nsteps, prm->max_iterations, e.m);
+    void* args[] = {&R.a, &e};
+    for (long long launches = 0; R.more(); ++launches) {
+        if (launches >= max_launches) return fail(MI355CG_ERR_HIP, "on-chip wave stepping: %d of %d members still step after %lld launches", R.unfinished(), nsys, launches);
+        if (int rc = R.launch_and_poll(k_chunk, args)) return rc;
+    }
+    if (int rc = R.end_loop(true)) return rc;
+    HIPCK(hipMemcpyAsync(W->book_h, W->book, sizeof(OcStepBook) * nsys, hipMemcpyDeviceToHost, c->stream));
+    if (!msg) HIPCK(hipMemcpyAsync(R.host.partB, R.dev.partB, sizeof(double) * FB_COUNT * nsys, hipMemcpyDeviceToHost, c->stream));
+    if (R.interrupted) {
+        // A member stopped between two steps has a converged step whose transition waited for a launch that never came.  The report
+        // counts that step (onchip_step_report), so its state moves on now: the transition's velocity and state update alone.
+        HIPCK(hipMemcpyAsync(W->s_h, W->s, sizeof(CgState) * nsys, hipMemcpyDeviceToHost, c->stream));
+        void* fargs[] = {&e};
+        if (int rc = R.start((const void*)&k_onchip_wave_newmark_finish, fargs)) return rc;
+    }
+    HIPCK(hipStreamSynchronize(c->stream));
+    if (counts) HIPCK(hipMemcpy(step_iterations, W->step_it, sizeof(int) * counts, hipMemcpyDeviceToHost));
+    for (int s = 0; s < nsys; ++s) {                               // onchip_plan.h: what a member reports
+        const OcStepReport rep = onchip_step_report(prm, msg, R.polled, R.interrupted, W->book_h[s], W->summary_h[s], W->s_h[s], R.host.norm0[s],
+                                                    R.host.partB[(long long)s * FB_COUNT + FB_RMAX], e.m, stop_flag != nullptr);
+        steps_done[s] = rep.steps_done;
+        out[s] = rep.res;
+        if (counts && rep.patch_step >= 0) step_iterations[(long long)s * nsteps + rep.patch_step] = rep.patch_iterations;
+    }
+    return R.stamp_times(out);
+}
+
+static int wave_steps_many(mi355cg_ctx* c, const mi355cg_params* prm, int nsys, int nsteps, int scheme, const double* tau, const double* g_dev,
+                           double* u_dev, double* v_dev, int steps_per_launch, const volatile int* stop_flag, mi355cg_results* out,
+                           int* steps_done, int* step_iterations) {
+    if (scheme == MI355CG_WAVE_NEWMARK) return wave_newmark(c, prm, nsys, nsteps, tau, g_dev, u_dev, v_dev, stop_flag, out, steps_done, step_iterations);
+    return wave_verlet(c, nsys, nsteps, tau, g_dev, u_dev, v_dev, steps_per_launch, stop_flag, out, steps_done);
+}
+
+int mi355cg_wave_steps_many_device(mi355cg_handle c, const mi355cg_params* prm, int nsys, int nsteps, int scheme, const double* tau,
+                                   const double* g_dev, double* u_dev, double* v_dev, int steps_per_launch, const volatile int* stop_flag,
+                                   mi355cg_results* out, int* steps_done, int* step_iterations) {
+    if (int rc = wave_check(c, prm, nsys, nsteps, scheme, tau, g_dev, u_dev, v_dev, steps_per_launch, out, steps_done, step_iterations)) return rc;
+    if (nsteps == 0) { for (int s = 0; s < nsys; ++s) steps_done[s] = 0; return MI355CG_OK; }
+    HIPCK(hipSetDevice(c->device));
+    if (int rc = onchip_wave_ensure(c, nsys, scheme, step_iterations ? (long long)nsys * nsteps : 0, 0)) return rc;
+    return wave_steps_many(c, prm, nsys, nsteps, scheme, tau, g_dev, u_dev, v_dev, steps_per_launch, stop_flag, out, steps_done, step_iterations);
+}
+int mi355cg_wave_steps_many(mi355cg_handle c, const mi355cg_params* prm, int nsys, int nsteps, int scheme, const double* tau, const double* g,
+                            double* u, double* v, int steps_per_launch, const volatile int* stop_flag, mi355cg_results* out, int* steps_done,
+                            int* step_iterations) {
+    if (int rc = wave_check(c, prm, nsys, nsteps, scheme, tau, g, u, v, steps_per_launch, out, steps_done, step_iterations)) return rc;
+    if (nsteps == 0) { for (int s = 0; s < nsys; ++s) steps_done[s] = 0; return MI355CG_OK; }
+    HIPCK(hipSetDevice(c->device));
+    if (int rc = onchip_wave_ensure(c, nsys, scheme, step_iterations ? (long long)nsys * nsteps : 0, 3)) return rc;
+    const size_t count = (size_t)c->pk_len * (size_t)nsys;         // g, then u, then v; the state comes down
+    double* const g_dev = c->many->stage; double* const u_dev = g_dev + count; double* const v_dev = u_dev + count;
+    const StagedGroup groups[3] = {{0, g, nullptr}, {count, u, u}, {2 * count, v, v}};
+    return run_staged_groups(c, g_dev, count, groups, [&]() {
+        return wave_steps_many(c, prm, nsys, nsteps, scheme, tau, g ? g_dev : nullptr, u_dev, v_dev, steps_per_launch, stop_flag, out, steps_done, step_iterations);
+    });
+}
+int mi355cg_wave_steps_many_workspace(int n, int nsys, int nsteps, int scheme, int with_step_iterations, long long* bytes) {
+    if (!bytes) return fail(MI355CG_ERR_INVALID, "null argument");
+    const long long v = onchip_wave_workspace_bytes(n, nsys, nsteps, scheme, with_step_iterations);
+    if (v == 0)
+        return fail(MI355CG_ERR_INVALID, "wave ensemble rejected: even n from 6 to %d, 1 .. %d members, 0 .. %d steps, scheme 0 or 1, at most %lld iteration counts",
+                    kOnchipMaxN, kOnchipStepsMaxSys, kOnchipStepsMaxSteps, kOnchipStepsMaxCounts);
+    *bytes = v;
+    return MI355CG_OK;
+}
+int mi355cg_wave_cfl(mi355cg_handle c, double* tau_max) {
+    if (!c || !tau_max) return fail(MI355CG_ERR_INVALID, "null argument");
+    if (c->is_csr) return fail(MI355CG_ERR_INVALID, "a CSR handle has no grid: the bound is the grid operator's");
+    *tau_max = onchip_wave_cfl(c->gp.A);
     return MI355CG_OK;
 }
 

@@ -589,4 +589,172 @@ __global__ __launch_bounds__(kOnchipMaxThreads) void k_onchip_steps(const Onchip
     }
 }
 
+// ---- ensemble wave-equation steps: u_tt = A u - g ---------------------------------------------------------
+// Explicit: velocity Verlet.  Member blockIdx.x takes `m` steps with its own tau inside ONE launch: u lives in the image (a thread
+// reads its own cells back from it), v, the acceleration a = A u - g and g of its slots in registers.  A step is one stencil pass
+// and two axpys between two barriers -- the first before the owned cells are overwritten (every neighbour has read them), the
+// second after (every neighbour reads the new ones).  No reduction, no polling, nothing between workgroups.  a is carried from
+// one step to the next; at the entry of a launch it is formed anew from (u, g): the same expression, hence the same bits, so k
+// launches of one step give what one launch of k steps gives.  The expressions are onchip_plan.h's.
+struct OnchipWaveArgs {
+    OnchipPlan pl;
+    OnchipWaveCoef k;
+    const double* tau;                               // nsys
+    const double* g; long long g_stride;             // forcing: member s reads g + s * g_stride (0: one vector for all)
+    double* u; double* v;                            // nsys packed states of `stride` doubles each, in and out
+    long long stride;
+    int m;                                           // steps of this launch
+};
+template <int E>
+__global__ __launch_bounds__(kOnchipMaxThreads) void k_onchip_wave_verlet(const OnchipWaveArgs a) {
+    const OnchipPlan& pl = a.pl;
+    double* const img = OcMany::lds(pl.cells).img;
+    const int t = threadIdx.x, T = blockDim.x, pitch = pl.pitch;
+    const long long sys = blockIdx.x;
+    const double tau = a.tau[sys], h = 0.5 * tau;
+    const double* const gin = a.g + sys * a.g_stride;
+    double* const uio = a.u + sys * a.stride; double* const vio = a.v + sys * a.stride;
+
+    for (int i = t; i < pl.cells; i += T) img[i] = 0.0;
+    __syncthreads();                                               // the image is zero everywhere before the owners fill their cells
+    unsigned cell2[(E + 1) / 2] = {};                              // image cells, two 16-bit indices per register (as oc_chunk)
+    double v[E], acc[E], g[E];
+    int cnt = 0;                                                   // valid slots: a prefix
+#pragma unroll
+    for (int k = 0; k < E; ++k) {
+        const int i = onchip_owned(pl, t, k);
+        if (i >= 0) {                                              // (slots beyond cnt are never read: nothing to initialise)
+            int xx, yy;
+            onchip_node(pl, i, &xx, &yy);
+            const int c = onchip_cell(pl, xx, yy);
+            cell2[k / 2] |= (unsigned)c << (16 * (k & 1));
+            img[c] = uio[i]; v[k] = vio[i]; g[k] = gin[i];
+            cnt = k + 1;
+        }
+    }
+    __syncthreads();
+    auto own_cell = [&](int k) { unsigned c2 = cell2[k / 2]; asm volatile("" : "+v"(c2)); return (int)((c2 >> (16 * (k & 1))) & 0xffffu); };
+    auto accel_at = [&](int c, double gk) { return onchip_wave_accel(a.k, gk, img[c], img[c - 1], img[c + 1], img[c - pitch], img[c + pitch]); };
+#pragma unroll
+    for (int k = 0; k < E; ++k) if (k < cnt) { acc[k] = accel_at(own_cell(k), g[k]); __builtin_amdgcn_sched_barrier(0); }
+
+    for (int s = 0; s < a.m; ++s) {
+        __syncthreads();                                           // barrier 1: every neighbour has read the old cells
+#pragma unroll
+        for (int k = 0; k < E; ++k) if (k < cnt) {
+            const int c = own_cell(k);
+            v[k] = onchip_wave_kick(v[k], h, acc[k]);              // vh
+            img[c] = onchip_wave_drift(img[c], tau, v[k]);
+            __builtin_amdgcn_sched_barrier(0);                     // slot by slot: the loads of all slots at once would spill
+        }
+        __syncthreads();                                           // barrier 2: the new image is complete
+#pragma unroll
+        for (int k = 0; k < E; ++k) if (k < cnt) {
+            acc[k] = accel_at(own_cell(k), g[k]);
+            v[k] = onchip_wave_kick(v[k], h, acc[k]);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < E; ++k) if (k < cnt) {
+        int i = k * T + t;
+        asm volatile("" : "+v"(i));                                // recomputed here, not carried through the loop
+        uio[i] = img[own_cell(k)]; vio[i] = v[k];
+    }
+}
+
+// Implicit: average-acceleration Newmark.  k_onchip_steps with another right-hand side and a velocity: a step is the warm-started
+// solve of (A - sigma_s I) x = b_wave(u, v), sigma_s = 4 / tau_s^2, and the transition after a CONVERGED step updates the member's
+// state in the caller's vectors -- v = hv (x - u) - v, u = x, with u the state the step started from -- before the next step
+// starts from it.  After a step that did not converge (u, v) stay: the state after the last converged step.  Budget of units,
+// system type, book and report are k_onchip_steps's.
+struct OcBWave {
+    const double* g; const double* v; OnchipWaveCoef k; double sigma, tau;
+    __device__ double at(int i, int c, const double* img, int pitch) const {
+        return onchip_newmark_rhs(k, sigma, tau, g[i], v[i], img[c], img[c - 1], img[c + 1], img[c - pitch], img[c + pitch]);
+    }
+};
+struct OnchipNewmarkArgs {
+    OnchipPlan pl;
+    double xk, yk;
+    const double* diag; const double* sigma;         // nsys each: A_diag - sigma_s as mi355cg_set_shift rounds it; sigma_s
+    const double* tau;                               // nsys tau_s, then nsys 2 / tau_s
+    const double* g; long long g_stride;
+    double* u; double* v;                            // nsys packed states, in and out: the state after the last converged step
+    double* x; double* r; double* p;
+    long long stride;
+    double* partB; CgState* s; CgState* summary; double* norm0; int* done_count;
+    OcStepBook* book;
+    int* step_it; int nsteps, nsys;
+    OnchipWaveCoef k;
+    RuleParams rp;
+    int m;
+};
+__device__ __forceinline__ void oc_newmark_start(const OnchipNewmarkArgs& e, const OcLds& l, int t) {
+    const long long sys = blockIdx.x, base = sys * e.stride;
+    const OcStartOut o{e.x + base, e.r + base, e.p + base, e.partB + sys * FB_COUNT, e.s + sys, e.summary + sys, e.norm0 + sys, nullptr};
+    oc_start<true, false>(e.pl, l, e.rp, e.diag[sys], e.xk, e.yk, e.u + base, o,
+                          OcBWave{e.g + sys * e.g_stride, e.v + base, e.k, e.sigma[sys], e.tau[sys]}, t);
+}
+// the member's state moves on after a converged step: v first, it reads the u the step started from
+__device__ __forceinline__ void oc_newmark_advance(const OnchipNewmarkArgs& e, int t) {
+    const long long base = (long long)blockIdx.x * e.stride;
+    const double hv = e.tau[e.nsys + blockIdx.x];
+    for (int i = t; i < e.pl.unknowns; i += (int)blockDim.x) {
+        const double xv = e.x[base + i], uo = e.u[base + i];
+        e.v[base + i] = onchip_newmark_velocity(hv, xv, uo, e.v[base + i]);
+        e.u[base + i] = xv;
+    }
+}
+// After a call the host's stop flag ended: a member that has not ended but whose state says done has converged a step (one that
+// did not converge ends the member at once, without budget) and its transition waited for the next launch.  The host counts
+// that step, so this launch does the state's part of the transition; the book stays.
+__global__ __launch_bounds__(kOnchipMaxThreads) void k_onchip_wave_newmark_finish(const OnchipNewmarkArgs e) {
+    const CgState* const sp = e.s + blockIdx.x;
+    if (oc_wg_load(&e.book[blockIdx.x].ended) || !oc_wg_load(&sp->done) || !oc_wg_load(&sp->converged)) return;
+    oc_newmark_advance(e, threadIdx.x);
+}
+__global__ __launch_bounds__(kOnchipMaxThreads) void k_onchip_wave_newmark_init(const OnchipNewmarkArgs e) {
+    oc_newmark_start(e, OcMany::lds(e.pl.cells), threadIdx.x);
+}
+template <int E, bool MSG>
+__global__ __launch_bounds__(kOnchipMaxThreads) void k_onchip_wave_newmark(const OnchipManyArgs a, const OnchipNewmarkArgs e) {
+    extern __shared__ __attribute__((aligned(16))) char oc_dyn_lds[];
+    int* const budget_w = reinterpret_cast<int*>(oc_dyn_lds + kOnchipBudgetOffset);
+    const int t = threadIdx.x;
+    const long long sys = blockIdx.x;
+    OcStepBook* const bk = e.book + sys;
+    const CgState* const sp = e.s + sys;
+    if (oc_wg_load(&bk->ended)) return;
+    int step = oc_wg_load(&bk->step), budget = e.m;
+    for (;;) {                                                     // every pass but the last costs a unit or more
+        int done = oc_wg_load(&sp->done);
+        if (!done) {
+            if (budget < 1) break;
+            const int it0 = oc_wg_load(&sp->it);
+            if (t == 0) *budget_w = budget;
+            __syncthreads();
+            oc_chunk<E, MSG, OcSteps>(a);
+            __syncthreads();                                       // the state the chunk left, for every thread
+            budget -= oc_wg_load(&sp->it) - it0;
+            done = oc_wg_load(&sp->done);
+            if (!done) break;                                      // the budget ran out inside the step
+        }
+        // the step is over: the member's end, or the transition to its next step
+        const int conv = oc_wg_load(&sp->converged);
+        const bool last = !conv || step + 1 >= e.nsteps;
+        if (!last && budget < 1) break;                            // the transition waits for the next launch
+        if (t == 0) {
+            if (e.step_it) e.step_it[sys * e.nsteps + step] = oc_wg_load(&sp->it);
+            bk->step = step + (conv ? 1 : 0);
+            if (last) { bk->ended = 1; atomicAdd(e.done_count, 1); }
+        }
+        if (conv) { oc_newmark_advance(e, OcSteps::tid()); __syncthreads(); }
+        if (last) break;
+        budget -= 1; ++step;
+        oc_newmark_start(e, OcMany::lds(e.pl.cells), OcSteps::tid());
+        __syncthreads();                                           // thread 0's state, partials and norm
+    }
+}
+
 }  // namespace mi355cg

@@ -168,6 +168,51 @@ static inline OcStepReport onchip_step_report(const mi355cg_params* prm, bool ms
     return rep;
 }
 
+// ---- ensemble wave-equation steps: u_tt = A u - g (k_onchip_wave_verlet, k_onchip_wave_newmark) ---------------
+// The per-node expressions of both schemes, one rounding per operation, no contraction.  au is onchip_step_rhs's stencil: the
+// UNSHIFTED diagonal A0, the neighbours in that order.
+//   velocity Verlet, h = 0.5 * tau:   a = au(u) - g;   vh = v + h a;   u = u + tau vh;   a = au(u) - g;   v = vh + h a
+//   Newmark (beta = 1/4, gamma = 1/2), sigma = 4 / tau^2, hv = 2 / tau:
+//       w = u + tau v;   b = (g + g) - sigma w;   b = b - au(u);   (A - sigma I) x = b from x0 = u;   v = hv (x - u) - v;   u = x
+constexpr int kWaveVerlet = 0, kWaveNewmark = 1;      // MI355CG_WAVE_VERLET, MI355CG_WAVE_NEWMARK
+struct OnchipWaveCoef { double A0, xk, yk; };
+MI355CG_HD inline double onchip_wave_au(const OnchipWaveCoef& k, double uc, double left, double right, double down, double up) {
+    return k.A0 * uc + k.xk * (left + right) + k.yk * (down + up);
+}
+MI355CG_HD inline double onchip_wave_accel(const OnchipWaveCoef& k, double g, double uc, double left, double right, double down, double up) {
+    return onchip_wave_au(k, uc, left, right, down, up) - g;
+}
+MI355CG_HD inline double onchip_wave_kick(double v, double h, double a) { return v + h * a; }            // both half kicks
+MI355CG_HD inline double onchip_wave_drift(double u, double tau, double vh) { return u + tau * vh; }
+MI355CG_HD inline double onchip_newmark_rhs(const OnchipWaveCoef& k, double sigma, double tau, double g, double v, double uc, double left,
+                                            double right, double down, double up) {
+    const double w = uc + tau * v;
+    double b = (g + g) - sigma * w;
+    b = b - onchip_wave_au(k, uc, left, right, down, up);
+    return b;
+}
+MI355CG_HD inline double onchip_newmark_velocity(double hv, double x, double u, double v) { return hv * (x - u) - v; }
+// The Gershgorin bound of the explicit scheme: every eigenvalue of -A lies in [0, 2 |A0|], and velocity Verlet is stable for
+// tau^2 * lambda_max <= 4.  Sufficient, not sharp.
+inline double onchip_wave_cfl(double A0) { return 2.0 / std::sqrt(2.0 * std::fabs(A0)); }
+// Device workspace of nsys members.  Verlet: the batch workspace of nsys systems (the driver's), per member its tau and 2 / tau,
+// one packed vector (the handle's right-hand side, for g = NULL).  Newmark: the stepping workspace of nsys members and nsteps
+// steps (it has that vector), per member its tau and 2 / tau.  The state (u, v) lives in the caller's vectors.  (The host entry
+// point stages g, u and v on top: 3 nsys packed vectors.)  0: refused, as onchip_steps_workspace_bytes refuses.
+constexpr int kOnchipWaveSysBytes = 2 * 8;
+MI355CG_HD inline long long onchip_wave_workspace_bytes(int n, int nsys, int nsteps, int scheme, int with_step_iterations) {
+    if (scheme != kWaveVerlet && scheme != kWaveNewmark) return 0;
+    const long long steps = onchip_steps_workspace_bytes(n, nsys, nsteps, scheme == kWaveNewmark && with_step_iterations);
+    if (steps == 0) return 0;
+    if (scheme == kWaveNewmark) return steps + (long long)nsys * kOnchipWaveSysBytes;
+    return onchip_many_workspace_bytes(n, nsys) + (long long)nsys * kOnchipWaveSysBytes + 8LL * onchip_plan(n).unknowns;
+}
+// Steps of one explicit launch when the caller does not say: the host tests the stop flag between two launches, so the longest
+// launch is the latency of a stop request, to stay under 10 ms.  Measured on one MI355X at N = 128, a launch of 1024 steps: 3.7 ms
+// for one member, 4.0 ms for 256, 15.3 ms for 1024 members (one workgroup per CU at that size, so four in turn) -- hence half of
+// that, 512.  profiles/onchip_wave_time_to_solution.txt ends with the launch times of this default as the timing tool measures them.
+constexpr int kOnchipWaveDefaultSteps = 512;
+
 static_assert(kOnchipSideBytes - 256 + 184 <= kOnchipBudgetOffset && kOnchipBudgetOffset % 8 == 0, "the budget word lies behind the CG state");
 static_assert(kOnchipMaxCells * 8 + kOnchipSideBytes <= kOnchipLdsLimit, "the image of the largest grid and the side data fit in one CU's LDS");
 static_assert((kOnchipMaxCells * 8 + 15) / 16 * 16 + kOnchipSideBytes <= kOnchipLdsLimit, "... with the image rounded up to 16 bytes too");

@@ -391,6 +391,63 @@ class _Handle:
         self._check_rc(rc)
         return u, list(res), steps_done, step_it
 
+    def wave_steps_many(self, params: Optional[_capi.Params], u0, v0, tau, nsteps: int, scheme: int = _capi.WAVE_VERLET, g=None,
+                        steps_per_launch: int = 0, stop_flag: Optional[C.c_int] = None, step_iterations: bool = False):
+        """Extension (no reference twin): an ensemble of wave-equation steppers u_tt = A u - g[s] on this grid, one workgroup per
+        member (mi355cg_wave_steps_many; the handles solve_many takes).  Member s takes nsteps steps of velocity Verlet
+        (WAVE_VERLET; tau[s] at most wave_cfl()) or of average-acceleration Newmark (WAVE_NEWMARK; params as in time_steps_many)
+        from the state (u0[s], v0[s]) with its own time step tau[s]; the handle itself is left as it was.  Returns (u, v, [Results
+        per member], steps_done int32 [nsys]) and, with step_iterations, int32 [nsys, nsteps] (-1 = step not taken; Verlet takes no
+        iterations).  u0, v0: NumPy [nsys, size] float64 -> NumPy; or contiguous CUDA torch.Tensors of that shape on the handle's
+        device -> new tensors there (torch's current stream is synchronised first); not modified.  g: of u0's kind and shape,
+        None = the handle's right-hand side for every member.  tau: a scalar or [nsys] (host values).  params may be None for
+        Verlet."""
+        nsys, on_device, sp = self._batched(u0, g, ("u0", "g", "forcings", "ensemble"), _capi.MANY_MAX, stop_flag)
+        if self._check_batch(v0, self.size, _capi.MANY_MAX) != (nsys, on_device) or (on_device and v0.device != u0.device):
+            raise ValueError(f"v0 has shape {tuple(v0.shape)}: the velocities are of the kind (NumPy / CUDA tensor), shape and device of u0, {tuple(u0.shape)}")
+        if scheme not in (_capi.WAVE_VERLET, _capi.WAVE_NEWMARK):
+            raise ValueError(f"unknown wave scheme {scheme}")
+        if scheme == _capi.WAVE_NEWMARK and params is None:
+            raise ValueError("the Newmark scheme reads params")
+        if hasattr(tau, "data_ptr"):
+            tau = tau.detach().cpu().numpy()
+        tau = np.ascontiguousarray(np.broadcast_to(np.asarray(tau, dtype=np.float64), (nsys,)) if np.ndim(tau) == 0 else tau, dtype=np.float64)
+        if tau.shape != (nsys,):
+            raise ValueError(f"tau has shape {tau.shape}, expected a scalar or ({nsys},)")
+        nsteps = int(nsteps)
+        if not 0 <= nsteps <= _capi.STEPS_MANY_MAX_STEPS:
+            raise ValueError(f"nsteps {nsteps} rejected: it must be 0 .. {_capi.STEPS_MANY_MAX_STEPS}")
+        if step_iterations and nsys * nsteps > 1 << 26:
+            raise ValueError(f"{nsys} members x {nsteps} steps: more than 2^26 iteration counts")
+        res = (_capi.Results * nsys)()
+        steps_done = np.zeros(nsys, dtype=np.int32)
+        step_it = np.full((nsys, nsteps), -1, dtype=np.int32) if step_iterations else None
+        pp = C.byref(params) if params is not None else None
+        ip = step_it.ctypes.data if step_it is not None and scheme == _capi.WAVE_NEWMARK else None
+        if on_device:
+            import torch
+            u, v = u0.clone(), v0.clone()
+            torch.cuda.current_stream(u0.device).synchronize()
+            rc = self._lib.mi355cg_wave_steps_many_device(self._h, pp, nsys, nsteps, int(scheme), tau.ctypes.data,
+                                                          g.data_ptr() if g is not None else None, u.data_ptr(), v.data_ptr(),
+                                                          int(steps_per_launch), sp, res, steps_done.ctypes.data, ip)
+        else:
+            u = np.array(u0, dtype=np.float64, order="C", copy=True)
+            v = np.array(v0, dtype=np.float64, order="C", copy=True)
+            if g is not None:
+                g = np.ascontiguousarray(g)
+            rc = self._lib.mi355cg_wave_steps_many(self._h, pp, nsys, nsteps, int(scheme), tau.ctypes.data,
+                                                   g.ctypes.data if g is not None else None, u.ctypes.data, v.ctypes.data,
+                                                   int(steps_per_launch), sp, res, steps_done.ctypes.data, ip)
+        self._check_rc(rc)
+        return (u, v, list(res), steps_done) + ((step_it,) if step_iterations else ())
+
+    def wave_cfl(self) -> float:
+        """The largest time step velocity Verlet takes on this grid, 2 / sqrt(2 |A_diag|) of the unshifted operator (mi355cg_wave_cfl)."""
+        out = C.c_double()
+        self._check_rc(self._lib.mi355cg_wave_cfl(self._h, C.byref(out)))
+        return out.value
+
     def solve_many_info(self, nsys: int):
         """{"lds_bytes_per_workgroup", "workgroups_per_cu", "workspace_bytes"} of a solve_many batch of nsys systems on this grid
         (mi355cg_solve_many_info); ValueError for handles solve_many refuses."""
@@ -551,6 +608,18 @@ def time_steps_many_workspace(n: int, nsys: int, nsteps: int, with_step_iteratio
     out = C.c_longlong()
     lib = _capi.load()
     rc = lib.mi355cg_time_steps_many_workspace(int(n), int(nsys), int(nsteps), 1 if with_step_iterations else 0, C.byref(out))
+    if rc == _capi.ERR_INVALID:
+        raise ValueError(lib.mi355cg_last_error().decode())
+    _capi.check(rc)
+    return out.value
+
+
+def wave_steps_many_workspace(n: int, nsys: int, nsteps: int, scheme: int = _capi.WAVE_VERLET, with_step_iterations: bool = False) -> int:
+    """The device workspace bytes of MatrixFreeSystem.wave_steps_many for nsys members and nsteps steps on an n x n grid (host
+    arithmetic, no GPU; mi355cg_wave_steps_many_workspace).  ValueError for a grid, an ensemble or a scheme the call refuses."""
+    out = C.c_longlong()
+    lib = _capi.load()
+    rc = lib.mi355cg_wave_steps_many_workspace(int(n), int(nsys), int(nsteps), int(scheme), 1 if with_step_iterations else 0, C.byref(out))
     if rc == _capi.ERR_INVALID:
         raise ValueError(lib.mi355cg_last_error().decode())
     _capi.check(rc)
@@ -722,6 +791,33 @@ class MatrixFreeSystem:
             params.eps_rel = params.eps_precision = params.eps_residual = eps
             params.use_true_solution = 0
         return self._handle.time_steps_many(params, u0, tau, theta, nsteps, g=g)
+
+    def wave_steps_many(self, u0, v0, tau, nsteps: int = 1, scheme: int = _capi.WAVE_VERLET, g=None, eps: float = 1e-8,
+                        max_iterations: int = 10000, rule: int = _capi.RULE_REL_2NORM, params=None, steps_per_launch: int = 0,
+                        stop_flag: Optional[C.c_int] = None, step_iterations: bool = False):
+        """Extension (no reference twin): an ensemble of wave-equation steppers on this grid -- u_tt = A u - g[s] for many
+        members at once, ONE workgroup per member (grids up to the on-chip cap, N = 128; no preconditioner).  u0, v0: [nsys,
+        size()] float64, NumPy or CUDA torch tensors, the start states and velocities; tau: a time step per member ([nsys]) or one
+        for all; g: a forcing per member, None = this system's right-hand side for all; nsteps and the scheme are shared.
+        WAVE_VERLET (explicit velocity Verlet): the step loop runs inside the launch, one stencil pass and two axpys per step;
+        every tau is at most wave_cfl(), a larger one is a ValueError; steps_per_launch (0: the default) cuts the run into
+        launches between which stop_flag is tested.  WAVE_NEWMARK (implicit, beta = 1/4, gamma = 1/2, no bound on tau): every
+        step is the warm-started solve of time_steps_many with the shift 4 / tau^2, under eps, max_iterations (per step) and rule
+        or params; a member ends after its first step that does not converge, its state that after its last converged step.
+        Returns (u, v, one _capi.Results per member, steps_done [nsys]) and with step_iterations the iteration counts [nsys,
+        nsteps], -1 for steps not taken.  One call of k steps gives the bits of k calls of one step.  This system's own state,
+        right-hand side, shift and solve mode stay as they were."""
+        if params is None and scheme == _capi.WAVE_NEWMARK:
+            params = default_params(rule)
+            params.max_iterations = max_iterations
+            params.eps_rel = params.eps_precision = params.eps_residual = eps
+            params.use_true_solution = 0
+        return self._handle.wave_steps_many(params, u0, v0, tau, nsteps, scheme=scheme, g=g, steps_per_launch=steps_per_launch,
+                                            stop_flag=stop_flag, step_iterations=step_iterations)
+
+    def wave_cfl(self) -> float:
+        """The largest time step wave_steps_many takes with WAVE_VERLET on this grid: 2 / sqrt(2 |A_diag|), Gershgorin's bound."""
+        return self._handle.wave_cfl()
 
     def solve_many_info(self, nsys: int):
         """What a solve_many batch of nsys systems costs on this grid: the LDS bytes of one workgroup, how many workgroups the

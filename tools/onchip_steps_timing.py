@@ -57,13 +57,13 @@ def compile_report(path, csrc, title):
         elif cur is not None:
             cur[key.strip()] = val.strip()
     lines = [f"# {title}: the on-chip kernels as hipcc builds them for gfx950 (-Rpass-analysis=kernel-resource-usage, the library's flags).",
-             f"# {'kernel':<28} {'VGPRs':>5} {'AGPRs':>5} {'SGPRs':>5} {'scratch_B_per_lane':>18} {'waves_per_SIMD':>14}"]
+             f"# {'kernel':<34} {'VGPRs':>5} {'AGPRs':>5} {'SGPRs':>5} {'scratch_B_per_lane':>18} {'waves_per_SIMD':>14}"]
     for r in rows:
-        m = (re.search(r"(k_onchip(?:_many|_steps)?)ILi(\d+)ELb([01])E", r["name"]) or re.search(r"(k_onchip_many_init)()ILb([01])E", r["name"])
-             or re.search(r"(k_onchip_steps_init)()()", r["name"]))
+        m = (re.search(r"(k_onchip(?:_many|_steps|_wave_newmark)?)ILi(\d+)ELb([01])E", r["name"]) or re.search(r"(k_onchip_many_init)()ILb([01])E", r["name"])
+             or re.search(r"(k_onchip_wave_verlet)ILi(\d+)E()", r["name"]) or re.search(r"(k_onchip_steps_init|k_onchip_wave_newmark_init|k_onchip_wave_newmark_finish)()()", r["name"]))
         args = ", ".join(a for a in (m.group(2), {"1": "true", "0": "false"}.get(m.group(3), "")) if a) if m else ""
         name = (f"{m.group(1)}<{args}>" if args else m.group(1)) if m else r["name"]
-        lines.append(f"  {name:<28} {r.get('VGPRs', '?'):>5} {r.get('AGPRs', '?'):>5} {r.get('TotalSGPRs', '?'):>5} {r.get('ScratchSize [bytes/lane]', '?'):>18} "
+        lines.append(f"  {name:<34} {r.get('VGPRs', '?'):>5} {r.get('AGPRs', '?'):>5} {r.get('TotalSGPRs', '?'):>5} {r.get('ScratchSize [bytes/lane]', '?'):>18} "
                      f"{r.get('Occupancy [waves/SIMD]', '?'):>14}")
     with open(path, "w") as f:
         f.write("\n".join(lines) + "\n")
