@@ -3230,22 +3230,50 @@ int mi355cg_solve_many_info(mi355cg_handle c, int nsys, int* lds_bytes_per_workg
 
 // ---- ensemble time stepping on chip: the step loop inside the launch -----------------------------------------
 static_assert(MI355CG_MANY_MAX == kOnchipStepsMaxSys && MI355CG_STEPS_MANY_MAX_STEPS == kOnchipStepsMaxSteps, "onchip_plan.h: the limits of an ensemble");
+// The refusals the theta and the wave steppers share, each written once; a check runs them in its own order, among its own.
+struct StepChecks {
+    static int nsteps(int nsteps) {
+        return nsteps < 0 || nsteps > MI355CG_STEPS_MANY_MAX_STEPS ? fail(MI355CG_ERR_INVALID, "nsteps %d rejected: it must be 0 .. %d", nsteps, MI355CG_STEPS_MANY_MAX_STEPS) : MI355CG_OK;
+    }
+    static int counts(const int* step_iterations, int nsys, int nsteps) {
+        if (step_iterations && (long long)nsys * nsteps > kOnchipStepsMaxCounts)
+            return fail(MI355CG_ERR_INVALID, "step_iterations for %d members x %d steps rejected: at most %lld counts", nsys, nsteps, kOnchipStepsMaxCounts);
+        return MI355CG_OK;
+    }
+    static int tau(double tau, int s) {
+        return !std::isfinite(tau) || !(tau > 0.0) ? fail(MI355CG_ERR_INVALID, "time step %g of member %d rejected: tau must be finite and > 0", tau, s) : MI355CG_OK;
+    }
+    static int forcing_apart(const mi355cg_ctx* c, int nsys, const void* u, const void* g) { return g ? BatchKind::apart(c, nsys, u, g, "u overlaps g") : MI355CG_OK; }
+    // after the check: a call of no steps is over, nothing is selected, allocated or launched
+    static bool none(int nsys, int nsteps, int* steps_done) {
+        if (nsteps == 0) for (int s = 0; s < nsys; ++s) steps_done[s] = 0;
+        return nsteps == 0;
+    }
+};
 // what both entry points refuse before anything is allocated or written (tau is in host memory for both)
 static int steps_many_check(mi355cg_ctx* c, const mi355cg_params* prm, int nsys, int nsteps, double theta, const double* tau, const void* g,
                             const void* u, const mi355cg_results* out, const int* steps_done, const int* step_iterations) {
     if (!c || !prm || !tau || !u || !out || !steps_done) return fail(MI355CG_ERR_INVALID, "null argument");
     if (int rc = kEnsemble.count(nsys)) return rc;
-    if (nsteps < 0 || nsteps > MI355CG_STEPS_MANY_MAX_STEPS) return fail(MI355CG_ERR_INVALID, "nsteps %d rejected: it must be 0 .. %d", nsteps, MI355CG_STEPS_MANY_MAX_STEPS);
-    if (step_iterations && (long long)nsys * nsteps > kOnchipStepsMaxCounts)
-        return fail(MI355CG_ERR_INVALID, "step_iterations for %d members x %d steps rejected: at most %lld counts", nsys, nsteps, kOnchipStepsMaxCounts);
+    if (int rc = StepChecks::nsteps(nsteps)) return rc;
+    if (int rc = StepChecks::counts(step_iterations, nsys, nsteps)) return rc;
     if (!(theta > 0.0 && theta <= 1.0)) return fail(MI355CG_ERR_INVALID, "theta %g rejected: the scheme needs 0 < theta <= 1", theta);
     if (int rc = kEnsemble.params(prm)) return rc;
     if (int rc = kEnsemble.onchip(c)) return rc;
     for (int s = 0; s < nsys; ++s) {
-        if (!std::isfinite(tau[s]) || !(tau[s] > 0.0)) return fail(MI355CG_ERR_INVALID, "time step %g of member %d rejected: tau must be finite and > 0", tau[s], s);
+        if (int rc = StepChecks::tau(tau[s], s)) return rc;
         if (!std::isfinite(1.0 / (theta * tau[s]))) return fail(MI355CG_ERR_INVALID, "time step %g of member %d rejected: 1 / (theta tau) is not finite", tau[s], s);
     }
-    return g ? BatchKind::apart(c, nsys, u, g, "u overlaps g") : MI355CG_OK;
+    return StepChecks::forcing_apart(c, nsys, u, g);
+}
+
+// The handle's right-hand side, packed, as the forcing of every member when the caller gives none: where it is allocated (false:
+// it is there) and the launch that fills it.
+static bool g_one_alloc_failed(mi355cg_ctx* c) { return !c->many->g_one && Buf<double>::device(c->many->g_one, c->pk_len); }
+static int g_one_pack(mi355cg_ctx* c) {
+    hipLaunchKernelGGL((k_pack<double>), dim3(flat_grid(c->pk_len)), dim3(kBlock), 0, c->stream, c->pg, (const double*)c->b, c->many->g_one.get());
+    HIPCK(hipGetLastError());
+    return MI355CG_OK;
 }
 
 // The batch workspace for nsys members, then the stepping parts on top: built complete before they replace what is there.
@@ -3254,12 +3282,12 @@ static int onchip_steps_ensure(mi355cg_ctx* c, int nsys, long long counts, int s
     OnchipManyWs* W = c->many.get();
     auto failed = [&](const char* what) { return fail(MI355CG_ERR_HIP, "on-chip stepping workspace for %d members: %s allocation failed", nsys, what); };
     if (W->steps_cap < nsys) {
-        Buf<double> sigma, sigma_h, g_one; Buf<OcStepBook> book, book_h; Buf<CgState> s_h;
+        Buf<double> sigma, sigma_h; Buf<OcStepBook> book, book_h; Buf<CgState> s_h;
         if (Buf<double>::device(sigma, nsys) || Buf<OcStepBook>::device(book, nsys)) return failed("bookkeeping");
-        if (Buf<double>::device(g_one, c->pk_len)) return failed("vector");
+        if (g_one_alloc_failed(c)) return failed("vector");
         if (Buf<double>::pinned(sigma_h, nsys) || Buf<OcStepBook>::pinned(book_h, nsys) || Buf<CgState>::pinned(s_h, nsys)) return failed("pinned copy");
         HIPCK(hipStreamSynchronize(c->stream));
-        W->step_sigma = std::move(sigma); W->book = std::move(book); W->g_one = std::move(g_one);
+        W->step_sigma = std::move(sigma); W->book = std::move(book);
         W->step_sigma_h = std::move(sigma_h); W->book_h = std::move(book_h); W->s_h = std::move(s_h);
         W->steps_cap = nsys;
     }
@@ -3271,53 +3299,61 @@ static int onchip_steps_ensure(mi355cg_ctx* c, int nsys, long long counts, int s
     return MI355CG_OK;
 }
 
-// g_dev (or NULL), u_dev: nsys packed vectors each in device memory; tau: host memory, checked; nsteps >= 1.
-static int steps_many(mi355cg_ctx* c, const mi355cg_params* prm, int nsys, int nsteps, double theta, const double* tau, const double* g_dev,
-                      double* u_dev, const volatile int* stop_flag, mi355cg_results* out, int* steps_done, int* step_iterations) {
+// One call of an implicit stepper -- the theta scheme, or Newmark -- on the handle's OnchipManyWs: the step loop
+// inside the launches (oc_step_loop), written once on the host too.  g_dev (or NULL): nsys packed vectors in device memory;
+// nsteps >= 1.  Args is the scheme's argument struct; the fields every scheme has are filled here.  A scheme supplies
+//   label        what the failure texts call it;
+//   sigma(s)     member s's shift; its diagonal is A - sigma as mi355cg_set_shift rounds it;
+//   upload()     what else it sends ahead, behind the shifts and in front of the resets;
+//   prepare(e)    behind the resets: its own fields of e, and what it still has to put on the stream in front of the start;
+//   k_init, chunk_kernel(elems, msg)   its start kernel and its instantiation of the step loop;
+//   deliver(R, e)   behind the read-backs: the state to the caller; every read-back has landed on return.
+extern "C++" {                                                     // (a template among the C entry points)
+template <class Args, class Sigma, class Upload, class Prepare, class Deliver>
+static int implicit_steps(mi355cg_ctx* c, const mi355cg_params* prm, int nsys, int nsteps, const double* g_dev, const volatile int* stop_flag,
+                          mi355cg_results* out, int* steps_done, int* step_iterations, const char* label, Sigma sigma, Upload upload,
+                          Prepare prepare, const void* k_init, const void* (*chunk_kernel)(int, bool), Deliver deliver) {
     OnchipManyRun R;
-    if (int rc = R.open(c, prm, nsys, stop_flag, "stepping")) return rc;
+    if (int rc = R.open(c, prm, nsys, stop_flag, label)) return rc;
     OnchipManyWs* W = R.W;
     const bool msg = R.msg;
     const long long counts = step_iterations ? (long long)nsys * nsteps : 0;
     for (int s = 0; s < nsys; ++s) {
-        W->step_sigma_h[s] = 1.0 / (theta * tau[s]);                 // mi355cg_time_steps's shift, in that form ...
-        R.host.diag[s] = c->gp.A - W->step_sigma_h[s];               // ... and mi355cg_set_shift's rounding
+        W->step_sigma_h[s] = sigma(s);
+        R.host.diag[s] = c->gp.A - W->step_sigma_h[s];               // mi355cg_set_shift's rounding
     }
     if (int rc = R.upload_diag()) return rc;
     HIPCK(hipMemcpyAsync(W->step_sigma, W->step_sigma_h, sizeof(double) * nsys, hipMemcpyHostToDevice, c->stream));
+    if (int rc = upload()) return rc;
     if (int rc = R.reset_done()) return rc;
     HIPCK(hipMemsetAsync(W->book, 0, sizeof(OcStepBook) * nsys, c->stream));
     if (counts) HIPCK(hipMemsetAsync(W->step_it, 0xff, sizeof(int) * counts, c->stream));              // -1: not taken
-    if (!g_dev) {                                                  // the handle's right-hand side for every member
-        hipLaunchKernelGGL((k_pack<double>), dim3(flat_grid(c->pk_len)), dim3(kBlock), 0, c->stream, c->pg, (const double*)c->b, W->g_one.get());
-        HIPCK(hipGetLastError());
-    }
 
-    OnchipStepsArgs e{};
+    Args e{};
     e.pl = R.pl; e.xk = c->g.xk; e.yk = c->g.yk; e.diag = R.dev.diag; e.sigma = W->step_sigma;
-    e.g = g_dev ? g_dev : W->g_one.get(); e.g_stride = g_dev ? R.U : 0; e.u0 = u_dev;
+    e.g = g_dev ? g_dev : W->g_one.get(); e.g_stride = g_dev ? R.U : 0;
     e.x = R.x; e.r = R.r; e.p = R.p; e.stride = R.U;
     e.partB = R.dev.partB; e.s = W->s; e.summary = W->summary; e.norm0 = R.dev.norm0; e.done_count = W->done;
     e.book = W->book; e.step_it = counts ? W->step_it.get() : nullptr; e.nsteps = nsteps;
-    e.k = OnchipStepCoef{c->gp.A, c->gp.x_k, c->gp.y_k, theta, (1.0 - theta) / theta, theta < 1.0 ? 1 : 0};       // launch_step_rhs's
     e.rp = R.rp;
-    { void* args[] = {&e}; if (int rc = R.start((const void*)&k_onchip_steps_init, args)) return rc; }
+    if (int rc = prepare(e)) return rc;
+    { void* args[] = {&e}; if (int rc = R.start(k_init, args)) return rc; }
     if (int rc = R.begin_loop(msg)) return rc;                     // the start states were tested, as mi355cg_solve polls a warm MSG start
 
-    const void* k_chunk = onchip_dispatch(R.pl.elems, msg, [](auto el, auto m) { return (const void*)&k_onchip_steps<decltype(el)::value, decltype(m)::value>; });
+    const void* k_chunk = chunk_kernel(R.pl.elems, msg);
     if (int rc = R.allow_lds(k_chunk)) return rc;
     e.m = default_sync_every(prm, msg);                            // units per member and launch: an iteration or a transition each
     const long long max_launches = onchip_steps_launch_cap(nsteps, prm->max_iterations, e.m);
     void* args[] = {&R.a, &e};
     for (long long launches = 0; R.more(); ++launches) {
-        if (launches >= max_launches) return fail(MI355CG_ERR_HIP, "on-chip stepping: %d of %d members still step after %lld launches", R.unfinished(), nsys, launches);
+        if (launches >= max_launches) return fail(MI355CG_ERR_HIP, "on-chip %s: %d of %d members still step after %lld launches", label, R.unfinished(), nsys, launches);
         if (int rc = R.launch_and_poll(k_chunk, args)) return rc;
     }
     if (int rc = R.end_loop(true)) return rc;
     HIPCK(hipMemcpyAsync(W->book_h, W->book, sizeof(OcStepBook) * nsys, hipMemcpyDeviceToHost, c->stream));
     if (!msg) HIPCK(hipMemcpyAsync(R.host.partB, R.dev.partB, sizeof(double) * FB_COUNT * nsys, hipMemcpyDeviceToHost, c->stream));     // |r| of the last update
     if (R.interrupted) HIPCK(hipMemcpyAsync(W->s_h, W->s, sizeof(CgState) * nsys, hipMemcpyDeviceToHost, c->stream));
-    if (int rc = R.finish(u_dev)) return rc;
+    if (int rc = deliver(R, e)) return rc;
     if (counts) HIPCK(hipMemcpy(step_iterations, W->step_it, sizeof(int) * counts, hipMemcpyDeviceToHost));
     for (int s = 0; s < nsys; ++s) {                               // onchip_plan.h: what a member reports
         const OcStepReport rep = onchip_step_report(prm, msg, R.polled, R.interrupted, W->book_h[s], W->summary_h[s], W->s_h[s], R.host.norm0[s],
@@ -3328,12 +3364,30 @@ static int steps_many(mi355cg_ctx* c, const mi355cg_params* prm, int nsys, int n
     }
     return R.stamp_times(out);
 }
+}  // extern "C++"
+
+// g_dev (or NULL), u_dev: nsys packed vectors each in device memory; tau: host memory, checked; nsteps >= 1.
+static int steps_many(mi355cg_ctx* c, const mi355cg_params* prm, int nsys, int nsteps, double theta, const double* tau, const double* g_dev,
+                      double* u_dev, const volatile int* stop_flag, mi355cg_results* out, int* steps_done, int* step_iterations) {
+    return implicit_steps<OnchipStepsArgs>(
+        c, prm, nsys, nsteps, g_dev, stop_flag, out, steps_done, step_iterations, "stepping",
+        [&](int s) { return 1.0 / (theta * tau[s]); },            // mi355cg_time_steps's shift, in that form
+        [] { return MI355CG_OK; },
+        [&](OnchipStepsArgs& e) {
+            e.u0 = u_dev;
+            e.k = OnchipStepCoef{c->gp.A, c->gp.x_k, c->gp.y_k, theta, (1.0 - theta) / theta, theta < 1.0 ? 1 : 0};       // launch_step_rhs's
+            return g_dev ? MI355CG_OK : g_one_pack(c);             // the handle's right-hand side for every member
+        },
+        (const void*)&k_onchip_steps_init,
+        [](int elems, bool msg) { return onchip_dispatch(elems, msg, [](auto el, auto m) { return (const void*)&k_onchip_steps<decltype(el)::value, decltype(m)::value>; }); },
+        [&](OnchipManyRun& R, OnchipStepsArgs&) { return R.finish(u_dev); });
+}
 
 int mi355cg_time_steps_many_device(mi355cg_handle c, const mi355cg_params* prm, int nsys, int nsteps, double theta, const double* tau,
                                    const double* g_dev, double* u_dev, const volatile int* stop_flag, mi355cg_results* out, int* steps_done,
                                    int* step_iterations) {
     if (int rc = steps_many_check(c, prm, nsys, nsteps, theta, tau, g_dev, u_dev, out, steps_done, step_iterations)) return rc;
-    if (nsteps == 0) { for (int s = 0; s < nsys; ++s) steps_done[s] = 0; return MI355CG_OK; }
+    if (StepChecks::none(nsys, nsteps, steps_done)) return MI355CG_OK;
     HIPCK(hipSetDevice(c->device));
     if (int rc = onchip_steps_ensure(c, nsys, step_iterations ? (long long)nsys * nsteps : 0, 0)) return rc;
     return steps_many(c, prm, nsys, nsteps, theta, tau, g_dev, u_dev, stop_flag, out, steps_done, step_iterations);
@@ -3341,7 +3395,7 @@ int mi355cg_time_steps_many_device(mi355cg_handle c, const mi355cg_params* prm, 
 int mi355cg_time_steps_many(mi355cg_handle c, const mi355cg_params* prm, int nsys, int nsteps, double theta, const double* tau, const double* g,
                             double* u, const volatile int* stop_flag, mi355cg_results* out, int* steps_done, int* step_iterations) {
     if (int rc = steps_many_check(c, prm, nsys, nsteps, theta, tau, g, u, out, steps_done, step_iterations)) return rc;
-    if (nsteps == 0) { for (int s = 0; s < nsys; ++s) steps_done[s] = 0; return MI355CG_OK; }
+    if (StepChecks::none(nsys, nsteps, steps_done)) return MI355CG_OK;
     HIPCK(hipSetDevice(c->device));
     if (int rc = onchip_steps_ensure(c, nsys, step_iterations ? (long long)nsys * nsteps : 0, 2)) return rc;
     const size_t count = (size_t)c->pk_len * (size_t)nsys;         // g in the first half, the states in the second
@@ -3369,22 +3423,21 @@ static int wave_check(mi355cg_ctx* c, const mi355cg_params* prm, int nsys, int n
     const bool newmark = scheme == MI355CG_WAVE_NEWMARK;
     if (newmark && !prm) return fail(MI355CG_ERR_INVALID, "null argument: the Newmark scheme reads params");
     if (int rc = kWaveEnsemble.count(nsys)) return rc;
-    if (nsteps < 0 || nsteps > MI355CG_STEPS_MANY_MAX_STEPS) return fail(MI355CG_ERR_INVALID, "nsteps %d rejected: it must be 0 .. %d", nsteps, MI355CG_STEPS_MANY_MAX_STEPS);
+    if (int rc = StepChecks::nsteps(nsteps)) return rc;
     if (steps_per_launch < 0) return fail(MI355CG_ERR_INVALID, "steps_per_launch %d rejected: 0 (the default) or a positive number of steps", steps_per_launch);
-    if (newmark && step_iterations && (long long)nsys * nsteps > kOnchipStepsMaxCounts)
-        return fail(MI355CG_ERR_INVALID, "step_iterations for %d members x %d steps rejected: at most %lld counts", nsys, nsteps, kOnchipStepsMaxCounts);
+    if (newmark) if (int rc = StepChecks::counts(step_iterations, nsys, nsteps)) return rc;
     if (newmark) if (int rc = kWaveEnsemble.params(prm)) return rc;
     if (int rc = kWaveEnsemble.onchip(c)) return rc;
     const double bound = onchip_wave_cfl(c->gp.A);
     for (int s = 0; s < nsys; ++s) {
-        if (!std::isfinite(tau[s]) || !(tau[s] > 0.0)) return fail(MI355CG_ERR_INVALID, "time step %g of member %d rejected: tau must be finite and > 0", tau[s], s);
+        if (int rc = StepChecks::tau(tau[s], s)) return rc;
         if (newmark && !std::isfinite(4.0 / (tau[s] * tau[s]))) return fail(MI355CG_ERR_INVALID, "time step %g of member %d rejected: 4 / tau^2 is not finite", tau[s], s);
         if (!newmark && tau[s] > bound)
             return fail(MI355CG_ERR_INVALID, "time step %.17g of member %d rejected: velocity Verlet needs tau <= %.17g on this grid (mi355cg_wave_cfl); MI355CG_WAVE_NEWMARK has no bound",
                         tau[s], s, bound);
     }
     if (int rc = BatchKind::apart(c, nsys, u, v, "u overlaps v")) return rc;
-    if (g) if (int rc = BatchKind::apart(c, nsys, u, g, "u overlaps g")) return rc;
+    if (int rc = StepChecks::forcing_apart(c, nsys, u, g)) return rc;
     return g ? BatchKind::apart(c, nsys, v, g, "v overlaps g") : MI355CG_OK;
 }
 
@@ -3401,7 +3454,7 @@ static int onchip_wave_ensure(mi355cg_ctx* c, int nsys, int scheme, long long co
         W->wave_tau = std::move(tau); W->wave_tau_h = std::move(tau_h);
         W->wave_cap = nsys;
     }
-    if (!W->g_one && Buf<double>::device(W->g_one, c->pk_len)) return failed("vector");
+    if (g_one_alloc_failed(c)) return failed("vector");
     return MI355CG_OK;
 }
 
@@ -3409,11 +3462,7 @@ static int onchip_wave_ensure(mi355cg_ctx* c, int nsys, int scheme, long long co
 static int wave_upload(mi355cg_ctx* c, OnchipManyWs* W, int nsys, const double* tau, const double* g_dev) {
     for (int s = 0; s < nsys; ++s) { W->wave_tau_h[s] = tau[s]; W->wave_tau_h[nsys + s] = 2.0 / tau[s]; }
     HIPCK(hipMemcpyAsync(W->wave_tau, W->wave_tau_h, sizeof(double) * 2 * nsys, hipMemcpyHostToDevice, c->stream));
-    if (!g_dev) {
-        hipLaunchKernelGGL((k_pack<double>), dim3(flat_grid(c->pk_len)), dim3(kBlock), 0, c->stream, c->pg, (const double*)c->b, W->g_one.get());
-        HIPCK(hipGetLastError());
-    }
-    return MI355CG_OK;
+    return g_dev ? MI355CG_OK : g_one_pack(c);
 }
 
 // Explicit: ceil(nsteps / m) launches of m steps; before each the host waits for the one before it and tests the caller's flag.
@@ -3450,65 +3499,30 @@ static int wave_verlet(mi355cg_ctx* c, int nsys, int nsteps, const double* tau, 
     return R.stamp_times(out);
 }
 
-// Implicit: the loop, cap and poll of steps_many on k_onchip_wave_newmark.  The state moves in u_dev, v_dev themselves.
+// Implicit: implicit_steps on k_onchip_wave_newmark.  The state moves in u_dev, v_dev themselves.
 static int wave_newmark(mi355cg_ctx* c, const mi355cg_params* prm, int nsys, int nsteps, const double* tau, const double* g_dev, double* u_dev,
                         double* v_dev, const volatile int* stop_flag, mi355cg_results* out, int* steps_done, int* step_iterations) {
-    OnchipManyRun R;
-    if (int rc = R.open(c, prm, nsys, stop_flag, "wave stepping")) return rc;
-    OnchipManyWs* W = R.W;
-    const bool msg = R.msg;
-    const long long counts = step_iterations ? (long long)nsys * nsteps : 0;
-    for (int s = 0; s < nsys; ++s) {
-        W->step_sigma_h[s] = 4.0 / (tau[s] * tau[s]);
-        R.host.diag[s] = c->gp.A - W->step_sigma_h[s];               // mi355cg_set_shift's rounding
-    }
-    if (int rc = R.upload_diag()) return rc;
-    HIPCK(hipMemcpyAsync(W->step_sigma, W->step_sigma_h, sizeof(double) * nsys, hipMemcpyHostToDevice, c->stream));
-    if (int rc = wave_upload(c, W, nsys, tau, g_dev)) return rc;
-    if (int rc = R.reset_done()) return rc;
-    HIPCK(hipMemsetAsync(W->book, 0, sizeof(OcStepBook) * nsys, c->stream));
-    if (counts) HIPCK(hipMemsetAsync(W->step_it, 0xff, sizeof(int) * counts, c->stream));              // -1: not taken
-
-    OnchipNewmarkArgs e{};
-    e.pl = R.pl; e.xk = c->g.xk; e.yk = c->g.yk; e.diag = R.dev.diag; e.sigma = W->step_sigma; e.tau = W->wave_tau;
-    e.g = g_dev ? g_dev : W->g_one.get(); e.g_stride = g_dev ? R.U : 0; e.u = u_dev; e.v = v_dev;
-    e.x = R.x; e.r = R.r; e.p = R.p; e.stride = R.U;
-    e.partB = R.dev.partB; e.s = W->s; e.summary = W->summary; e.norm0 = R.dev.norm0; e.done_count = W->done;
-    e.book = W->book; e.step_it = counts ? W->step_it.get() : nullptr; e.nsteps = nsteps; e.nsys = nsys;
-    e.k = OnchipWaveCoef{c->gp.A, c->gp.x_k, c->gp.y_k};
-    e.rp = R.rp;
-    { void* args[] = {&e}; if (int rc = R.start((const void*)&k_onchip_wave_newmark_init, args)) return rc; }
-    if (int rc = R.begin_loop(msg)) return rc;
-
-    const void* k_chunk = onchip_dispatch(R.pl.elems, msg, [](auto el, auto m) { return (const void*)&k_onchip_wave_newmark<decltype(el)::value, decltype(m)::value>; });
-    if (int rc = R.allow_lds(k_chunk)) return rc;
-    e.m = default_sync_every(prm, msg);
-    const long long max_launches = onchip_steps_launch_cap(nsteps, prm->max_iterations, e.m);
-    void* args[] = {&R.a, &e};
-    for (long long launches = 0; R.more(); ++launches) {
-        if (launches >= max_launches) return fail(MI355CG_ERR_HIP, "on-chip wave stepping: %d of %d members still step after %lld launches", R.unfinished(), nsys, launches);
-        if (int rc = R.launch_and_poll(k_chunk, args)) return rc;
-    }
-    if (int rc = R.end_loop(true)) return rc;
-    HIPCK(hipMemcpyAsync(W->book_h, W->book, sizeof(OcStepBook) * nsys, hipMemcpyDeviceToHost, c->stream));
-    if (!msg) HIPCK(hipMemcpyAsync(R.host.partB, R.dev.partB, sizeof(double) * FB_COUNT * nsys, hipMemcpyDeviceToHost, c->stream));
-    if (R.interrupted) {
-        // A member stopped between two steps has a converged step whose transition waited for a launch that never came.  The report
-        // counts that step (onchip_step_report), so its state moves on now: the transition's velocity and state update alone.
-        HIPCK(hipMemcpyAsync(W->s_h, W->s, sizeof(CgState) * nsys, hipMemcpyDeviceToHost, c->stream));
-        void* fargs[] = {&e};
-        if (int rc = R.start((const void*)&k_onchip_wave_newmark_finish, fargs)) return rc;
-    }
-    HIPCK(hipStreamSynchronize(c->stream));
-    if (counts) HIPCK(hipMemcpy(step_iterations, W->step_it, sizeof(int) * counts, hipMemcpyDeviceToHost));
-    for (int s = 0; s < nsys; ++s) {                               // onchip_plan.h: what a member reports
-        const OcStepReport rep = onchip_step_report(prm, msg, R.polled, R.interrupted, W->book_h[s], W->summary_h[s], W->s_h[s], R.host.norm0[s],
-                                                    R.host.partB[(long long)s * FB_COUNT + FB_RMAX], e.m, stop_flag != nullptr);
-        steps_done[s] = rep.steps_done;
-        out[s] = rep.res;
-        if (counts && rep.patch_step >= 0) step_iterations[(long long)s * nsteps + rep.patch_step] = rep.patch_iterations;
-    }
-    return R.stamp_times(out);
+    return implicit_steps<OnchipNewmarkArgs>(
+        c, prm, nsys, nsteps, g_dev, stop_flag, out, steps_done, step_iterations, "wave stepping",
+        [&](int s) { return 4.0 / (tau[s] * tau[s]); },
+        [&] { return wave_upload(c, c->many.get(), nsys, tau, g_dev); },
+        [&](OnchipNewmarkArgs& e) {
+            e.tau = c->many->wave_tau; e.u = u_dev; e.v = v_dev; e.nsys = nsys;
+            e.k = OnchipWaveCoef{c->gp.A, c->gp.x_k, c->gp.y_k};
+            return MI355CG_OK;
+        },
+        (const void*)&k_onchip_wave_newmark_init,
+        [](int elems, bool msg) { return onchip_dispatch(elems, msg, [](auto el, auto m) { return (const void*)&k_onchip_wave_newmark<decltype(el)::value, decltype(m)::value>; }); },
+        [&](OnchipManyRun& R, OnchipNewmarkArgs& e) {
+            if (R.interrupted) {
+                // A member stopped between two steps has a converged step whose transition waited for a launch that never came.  The report
+                // counts that step (onchip_step_report), so its state moves on now: the transition's velocity and state update alone.
+                void* fargs[] = {&e};
+                if (int rc = R.start((const void*)&k_onchip_wave_newmark_finish, fargs)) return rc;
+            }
+            HIPCK(hipStreamSynchronize(c->stream));
+            return MI355CG_OK;
+        });
 }
 
 static int wave_steps_many(mi355cg_ctx* c, const mi355cg_params* prm, int nsys, int nsteps, int scheme, const double* tau, const double* g_dev,
@@ -3522,7 +3536,7 @@ int mi355cg_wave_steps_many_device(mi355cg_handle c, const mi355cg_params* prm, 
                                    const double* g_dev, double* u_dev, double* v_dev, int steps_per_launch, const volatile int* stop_flag,
                                    mi355cg_results* out, int* steps_done, int* step_iterations) {
     if (int rc = wave_check(c, prm, nsys, nsteps, scheme, tau, g_dev, u_dev, v_dev, steps_per_launch, out, steps_done, step_iterations)) return rc;
-    if (nsteps == 0) { for (int s = 0; s < nsys; ++s) steps_done[s] = 0; return MI355CG_OK; }
+    if (StepChecks::none(nsys, nsteps, steps_done)) return MI355CG_OK;
     HIPCK(hipSetDevice(c->device));
     if (int rc = onchip_wave_ensure(c, nsys, scheme, step_iterations ? (long long)nsys * nsteps : 0, 0)) return rc;
     return wave_steps_many(c, prm, nsys, nsteps, scheme, tau, g_dev, u_dev, v_dev, steps_per_launch, stop_flag, out, steps_done, step_iterations);
@@ -3531,7 +3545,7 @@ int mi355cg_wave_steps_many(mi355cg_handle c, const mi355cg_params* prm, int nsy
                             double* u, double* v, int steps_per_launch, const volatile int* stop_flag, mi355cg_results* out, int* steps_done,
                             int* step_iterations) {
     if (int rc = wave_check(c, prm, nsys, nsteps, scheme, tau, g, u, v, steps_per_launch, out, steps_done, step_iterations)) return rc;
-    if (nsteps == 0) { for (int s = 0; s < nsys; ++s) steps_done[s] = 0; return MI355CG_OK; }
+    if (StepChecks::none(nsys, nsteps, steps_done)) return MI355CG_OK;
     HIPCK(hipSetDevice(c->device));
     if (int rc = onchip_wave_ensure(c, nsys, scheme, step_iterations ? (long long)nsys * nsteps : 0, 3)) return rc;
     const size_t count = (size_t)c->pk_len * (size_t)nsys;         // g, then u, then v; the state comes down

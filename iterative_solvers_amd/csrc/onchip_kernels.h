@@ -541,17 +541,35 @@ struct OcSteps : OcMany {
     // cells and offsets of its slots) would otherwise be computed once in front of the loop and kept in registers across all of it.
     __device__ static int tid() { int t = threadIdx.x; asm volatile("" : "+v"(t)); return t; }
 };
-__device__ __forceinline__ void oc_step_start(const OnchipStepsArgs& e, const OcLds& l, const double* x0, int t) {
+// A scheme of implicit steps is what the step loop below does not know: Args, the kernel's second argument -- its fields pl, xk,
+// yk, diag, sigma, g, g_stride, x, r, p, stride, partB, s, summary, norm0, done_count, book, step_it, nsteps, rp and m have one
+// meaning in every scheme, and the loop reads none but these --; start(e, lds, t), the warm start of the member's next step from
+// its state; kAdvances and advance(e, t), what a CONVERGED step does to a state the member keeps outside the workspace, before the
+// book moves on.  OcTheta: the state is the workspace's x itself, nothing to advance.
+template <class Args>
+__device__ __forceinline__ OcStartOut oc_member_out(const Args& e) {     // member blockIdx.x's share of the workspace; it is not counted when a start says done
     const long long sys = blockIdx.x, base = sys * e.stride;
-    const OcStartOut o{e.x + base, e.r + base, e.p + base, e.partB + sys * FB_COUNT, e.s + sys, e.summary + sys, e.norm0 + sys, nullptr};
-    oc_start<true, false>(e.pl, l, e.rp, e.diag[sys], e.xk, e.yk, x0, o, OcBStep{e.g + sys * e.g_stride, e.k, e.sigma[sys]}, t);
+    return OcStartOut{e.x + base, e.r + base, e.p + base, e.partB + sys * FB_COUNT, e.s + sys, e.summary + sys, e.norm0 + sys, nullptr};
 }
+struct OcTheta {
+    typedef OnchipStepsArgs Args;
+    static constexpr bool kAdvances = false;
+    __device__ static __forceinline__ void start_from(const Args& e, const OcLds& l, const double* x0, int t) {
+        const long long sys = blockIdx.x;
+        oc_start<true, false>(e.pl, l, e.rp, e.diag[sys], e.xk, e.yk, x0, oc_member_out(e), OcBStep{e.g + sys * e.g_stride, e.k, e.sigma[sys]}, t);
+    }
+    __device__ static __forceinline__ void start(const Args& e, const OcLds& l, int t) {
+        start_from(e, l, e.x + blockIdx.x * e.stride, t);          // u: the x the chunk (or the start before it) left
+    }
+    __device__ static __forceinline__ void advance(const Args&, int) {}
+};
 // the first step's start, from the caller's states (the book is zeroed by the host)
 __global__ __launch_bounds__(kOnchipMaxThreads) void k_onchip_steps_init(const OnchipStepsArgs e) {
-    oc_step_start(e, OcMany::lds(e.pl.cells), e.u0 + blockIdx.x * e.stride, threadIdx.x);
+    OcTheta::start_from(e, OcMany::lds(e.pl.cells), e.u0 + blockIdx.x * e.stride, threadIdx.x);
 }
-template <int E, bool MSG>
-__global__ __launch_bounds__(kOnchipMaxThreads) void k_onchip_steps(const OnchipManyArgs a, const OnchipStepsArgs e) {
+// The step loop, written once for every scheme.  (Both arguments by value and as a whole, as oc_chunk takes its own.)
+template <int E, bool MSG, class Scheme>
+__device__ __forceinline__ void oc_step_loop(const OnchipManyArgs a, const typename Scheme::Args e) {
     extern __shared__ __attribute__((aligned(16))) char oc_dyn_lds[];
     int* const budget_w = reinterpret_cast<int*>(oc_dyn_lds + kOnchipBudgetOffset);
     const int t = threadIdx.x;
@@ -582,11 +600,16 @@ __global__ __launch_bounds__(kOnchipMaxThreads) void k_onchip_steps(const Onchip
             bk->step = step + (conv ? 1 : 0);
             if (last) { bk->ended = 1; atomicAdd(e.done_count, 1); }
         }
+        if constexpr (Scheme::kAdvances) if (conv) { Scheme::advance(e, OcSteps::tid()); __syncthreads(); }
         if (last) break;
         budget -= 1; ++step;
-        oc_step_start(e, OcMany::lds(e.pl.cells), e.x + sys * e.stride, OcSteps::tid());      // u: the x the chunk (or the start before it) left
+        Scheme::start(e, OcMany::lds(e.pl.cells), OcSteps::tid());
         __syncthreads();                                           // thread 0's state, partials and norm
     }
+}
+template <int E, bool MSG>
+__global__ __launch_bounds__(kOnchipMaxThreads) void k_onchip_steps(const OnchipManyArgs a, const OnchipStepsArgs e) {
+    oc_step_loop<E, MSG, OcTheta>(a, e);
 }
 
 // ---- ensemble wave-equation steps: u_tt = A u - g ---------------------------------------------------------
@@ -663,11 +686,11 @@ __global__ __launch_bounds__(kOnchipMaxThreads) void k_onchip_wave_verlet(const 
     }
 }
 
-// Implicit: average-acceleration Newmark.  k_onchip_steps with another right-hand side and a velocity: a step is the warm-started
+// Implicit: average-acceleration Newmark.  oc_step_loop with another right-hand side and a velocity: a step is the warm-started
 // solve of (A - sigma_s I) x = b_wave(u, v), sigma_s = 4 / tau_s^2, and the transition after a CONVERGED step updates the member's
 // state in the caller's vectors -- v = hv (x - u) - v, u = x, with u the state the step started from -- before the next step
 // starts from it.  After a step that did not converge (u, v) stay: the state after the last converged step.  Budget of units,
-// system type, book and report are k_onchip_steps's.
+// system type, book and report are the loop's.
 struct OcBWave {
     const double* g; const double* v; OnchipWaveCoef k; double sigma, tau;
     __device__ double at(int i, int c, const double* img, int pitch) const {
@@ -690,71 +713,39 @@ struct OnchipNewmarkArgs {
     RuleParams rp;
     int m;
 };
-__device__ __forceinline__ void oc_newmark_start(const OnchipNewmarkArgs& e, const OcLds& l, int t) {
-    const long long sys = blockIdx.x, base = sys * e.stride;
-    const OcStartOut o{e.x + base, e.r + base, e.p + base, e.partB + sys * FB_COUNT, e.s + sys, e.summary + sys, e.norm0 + sys, nullptr};
-    oc_start<true, false>(e.pl, l, e.rp, e.diag[sys], e.xk, e.yk, e.u + base, o,
-                          OcBWave{e.g + sys * e.g_stride, e.v + base, e.k, e.sigma[sys], e.tau[sys]}, t);
-}
-// the member's state moves on after a converged step: v first, it reads the u the step started from
-__device__ __forceinline__ void oc_newmark_advance(const OnchipNewmarkArgs& e, int t) {
-    const long long base = (long long)blockIdx.x * e.stride;
-    const double hv = e.tau[e.nsys + blockIdx.x];
-    for (int i = t; i < e.pl.unknowns; i += (int)blockDim.x) {
-        const double xv = e.x[base + i], uo = e.u[base + i];
-        e.v[base + i] = onchip_newmark_velocity(hv, xv, uo, e.v[base + i]);
-        e.u[base + i] = xv;
+// OcNewmark: the scheme of oc_step_loop.  The state moves on after a converged step: v first, it reads the u the step started from.
+struct OcNewmark {
+    typedef OnchipNewmarkArgs Args;
+    static constexpr bool kAdvances = true;
+    __device__ static __forceinline__ void start(const Args& e, const OcLds& l, int t) {
+        const long long sys = blockIdx.x, base = sys * e.stride;
+        oc_start<true, false>(e.pl, l, e.rp, e.diag[sys], e.xk, e.yk, e.u + base, oc_member_out(e),
+                              OcBWave{e.g + sys * e.g_stride, e.v + base, e.k, e.sigma[sys], e.tau[sys]}, t);
     }
-}
+    __device__ static __forceinline__ void advance(const Args& e, int t) {
+        const long long base = (long long)blockIdx.x * e.stride;
+        const double hv = e.tau[e.nsys + blockIdx.x];
+        for (int i = t; i < e.pl.unknowns; i += (int)blockDim.x) {
+            const double xv = e.x[base + i], uo = e.u[base + i];
+            e.v[base + i] = onchip_newmark_velocity(hv, xv, uo, e.v[base + i]);
+            e.u[base + i] = xv;
+        }
+    }
+};
 // After a call the host's stop flag ended: a member that has not ended but whose state says done has converged a step (one that
 // did not converge ends the member at once, without budget) and its transition waited for the next launch.  The host counts
 // that step, so this launch does the state's part of the transition; the book stays.
 __global__ __launch_bounds__(kOnchipMaxThreads) void k_onchip_wave_newmark_finish(const OnchipNewmarkArgs e) {
     const CgState* const sp = e.s + blockIdx.x;
     if (oc_wg_load(&e.book[blockIdx.x].ended) || !oc_wg_load(&sp->done) || !oc_wg_load(&sp->converged)) return;
-    oc_newmark_advance(e, threadIdx.x);
+    OcNewmark::advance(e, threadIdx.x);
 }
 __global__ __launch_bounds__(kOnchipMaxThreads) void k_onchip_wave_newmark_init(const OnchipNewmarkArgs e) {
-    oc_newmark_start(e, OcMany::lds(e.pl.cells), threadIdx.x);
+    OcNewmark::start(e, OcMany::lds(e.pl.cells), threadIdx.x);
 }
 template <int E, bool MSG>
 __global__ __launch_bounds__(kOnchipMaxThreads) void k_onchip_wave_newmark(const OnchipManyArgs a, const OnchipNewmarkArgs e) {
-    extern __shared__ __attribute__((aligned(16))) char oc_dyn_lds[];
-    int* const budget_w = reinterpret_cast<int*>(oc_dyn_lds + kOnchipBudgetOffset);
-    const int t = threadIdx.x;
-    const long long sys = blockIdx.x;
-    OcStepBook* const bk = e.book + sys;
-    const CgState* const sp = e.s + sys;
-    if (oc_wg_load(&bk->ended)) return;
-    int step = oc_wg_load(&bk->step), budget = e.m;
-    for (;;) {                                                     // every pass but the last costs a unit or more
-        int done = oc_wg_load(&sp->done);
-        if (!done) {
-            if (budget < 1) break;
-            const int it0 = oc_wg_load(&sp->it);
-            if (t == 0) *budget_w = budget;
-            __syncthreads();
-            oc_chunk<E, MSG, OcSteps>(a);
-            __syncthreads();                                       // the state the chunk left, for every thread
-            budget -= oc_wg_load(&sp->it) - it0;
-            done = oc_wg_load(&sp->done);
-            if (!done) break;                                      // the budget ran out inside the step
-        }
-        // the step is over: the member's end, or the transition to its next step
-        const int conv = oc_wg_load(&sp->converged);
-        const bool last = !conv || step + 1 >= e.nsteps;
-        if (!last && budget < 1) break;                            // the transition waits for the next launch
-        if (t == 0) {
-            if (e.step_it) e.step_it[sys * e.nsteps + step] = oc_wg_load(&sp->it);
-            bk->step = step + (conv ? 1 : 0);
-            if (last) { bk->ended = 1; atomicAdd(e.done_count, 1); }
-        }
-        if (conv) { oc_newmark_advance(e, OcSteps::tid()); __syncthreads(); }
-        if (last) break;
-        budget -= 1; ++step;
-        oc_newmark_start(e, OcMany::lds(e.pl.cells), OcSteps::tid());
-        __syncthreads();                                           // thread 0's state, partials and norm
-    }
+    oc_step_loop<E, MSG, OcNewmark>(a, e);
 }
 
 }  // namespace mi355cg

@@ -350,6 +350,23 @@ class _Handle:
         self._check_rc(rc)
         return x, list(res)
 
+    @staticmethod
+    def _ensemble_steps(nsys, tau, nsteps, step_iterations):
+        """What time_steps_many and wave_steps_many make of their step arguments: (tau as contiguous float64 [nsys], nsteps as an
+        int in range, the Results array, steps_done, step_it or None without step_iterations)."""
+        if hasattr(tau, "data_ptr"):
+            tau = tau.detach().cpu().numpy()
+        tau = np.ascontiguousarray(np.broadcast_to(np.asarray(tau, dtype=np.float64), (nsys,)) if np.ndim(tau) == 0 else tau, dtype=np.float64)
+        if tau.shape != (nsys,):
+            raise ValueError(f"tau has shape {tau.shape}, expected a scalar or ({nsys},)")
+        nsteps = int(nsteps)
+        if not 0 <= nsteps <= _capi.STEPS_MANY_MAX_STEPS:
+            raise ValueError(f"nsteps {nsteps} rejected: it must be 0 .. {_capi.STEPS_MANY_MAX_STEPS}")
+        if step_iterations and nsys * nsteps > 1 << 26:
+            raise ValueError(f"{nsys} members x {nsteps} steps: more than 2^26 iteration counts")
+        step_it = np.full((nsys, nsteps), -1, dtype=np.int32) if step_iterations else None
+        return tau, nsteps, (_capi.Results * nsys)(), np.zeros(nsys, dtype=np.int32), step_it
+
     def time_steps_many(self, params: _capi.Params, u0, tau, theta: float, nsteps: int, g=None, stop_flag: Optional[C.c_int] = None):
         """Extension (no reference twin): an ensemble of time steppers on this grid, one workgroup per member with the step loop
         inside the launch (mi355cg_time_steps_many; the handles solve_many takes).  Member s is integrated over nsteps steps of the
@@ -361,19 +378,7 @@ class _Handle:
         shape, None = the handle's right-hand side for every member.  tau: a scalar or [nsys] (host values).
         params.use_true_solution and params.diagnostics must be 0."""
         nsys, on_device, sp = self._batched(u0, g, ("u0", "g", "forcings", "ensemble"), _capi.MANY_MAX, stop_flag)
-        if hasattr(tau, "data_ptr"):
-            tau = tau.detach().cpu().numpy()
-        tau = np.ascontiguousarray(np.broadcast_to(np.asarray(tau, dtype=np.float64), (nsys,)) if np.ndim(tau) == 0 else tau, dtype=np.float64)
-        if tau.shape != (nsys,):
-            raise ValueError(f"tau has shape {tau.shape}, expected a scalar or ({nsys},)")
-        nsteps = int(nsteps)
-        if not 0 <= nsteps <= _capi.STEPS_MANY_MAX_STEPS:
-            raise ValueError(f"nsteps {nsteps} rejected: it must be 0 .. {_capi.STEPS_MANY_MAX_STEPS}")
-        if nsys * nsteps > 1 << 26:
-            raise ValueError(f"{nsys} members x {nsteps} steps: more than 2^26 iteration counts")
-        res = (_capi.Results * nsys)()
-        steps_done = np.zeros(nsys, dtype=np.int32)
-        step_it = np.full((nsys, nsteps), -1, dtype=np.int32)
+        tau, nsteps, res, steps_done, step_it = self._ensemble_steps(nsys, tau, nsteps, True)
         if on_device:
             import torch
             u = u0.clone()
@@ -409,19 +414,7 @@ class _Handle:
             raise ValueError(f"unknown wave scheme {scheme}")
         if scheme == _capi.WAVE_NEWMARK and params is None:
             raise ValueError("the Newmark scheme reads params")
-        if hasattr(tau, "data_ptr"):
-            tau = tau.detach().cpu().numpy()
-        tau = np.ascontiguousarray(np.broadcast_to(np.asarray(tau, dtype=np.float64), (nsys,)) if np.ndim(tau) == 0 else tau, dtype=np.float64)
-        if tau.shape != (nsys,):
-            raise ValueError(f"tau has shape {tau.shape}, expected a scalar or ({nsys},)")
-        nsteps = int(nsteps)
-        if not 0 <= nsteps <= _capi.STEPS_MANY_MAX_STEPS:
-            raise ValueError(f"nsteps {nsteps} rejected: it must be 0 .. {_capi.STEPS_MANY_MAX_STEPS}")
-        if step_iterations and nsys * nsteps > 1 << 26:
-            raise ValueError(f"{nsys} members x {nsteps} steps: more than 2^26 iteration counts")
-        res = (_capi.Results * nsys)()
-        steps_done = np.zeros(nsys, dtype=np.int32)
-        step_it = np.full((nsys, nsteps), -1, dtype=np.int32) if step_iterations else None
+        tau, nsteps, res, steps_done, step_it = self._ensemble_steps(nsys, tau, nsteps, step_iterations)
         pp = C.byref(params) if params is not None else None
         ip = step_it.ctypes.data if step_it is not None and scheme == _capi.WAVE_NEWMARK else None
         if on_device:

@@ -204,6 +204,26 @@ def test_zero_iteration_steps_cost_a_unit_each():
         assert np.array_equal(got[0], u0)
 
 
+def test_one_or_two_units_per_launch():
+    """sync_every = 1: every step converges exactly when its launch's budget is used up, so every transition waits for the next
+    launch; sync_every = 2: some do, some do not.  Against the reference at the file's sync_every = 7: the bits of u, steps_done,
+    the count of every step, iterations and converged (final_residual_norm follows the poll schedule, by contract)."""
+    many, ref = pair(10)
+    nsteps = 3
+    for rule, kw in rules():
+        for theta in (0.5, 1.0):
+            u0, tau, g = ensemble(many, seed=13, factors=(1e3, 10.0, 0.03), theta=theta)
+            want = sequential(ref, params(rule, **kw), u0, tau, theta, nsteps, g=g)
+            assert all(w[1] == nsteps for w in want) and len({tuple(w[2]) for w in want}) == 3, [w[2] for w in want]
+            for units in (1, 2):
+                u, res, done, its = many._handle.time_steps_many(params(rule, **dict(kw, sync_every=units)), u0, tau, theta, nsteps, g=g)
+                for s, (us, ds, is_, fs) in enumerate(want):
+                    mine = (int(done[s]), [int(v) for v in its[s]], res[s].iterations, res[s].converged)
+                    print("units", units, rule, theta, "member", s, "ensemble", mine, "| sequential", (ds, is_, fs[0], fs[2]))
+                    assert mine == (ds, is_, fs[0], fs[2]), (units, rule, theta, s)
+                    assert np.array_equal(u[s], us), (units, rule, theta, s)
+
+
 def test_the_iteration_cap_ends_a_member():
     from iterative_solvers_amd import _capi
     many, ref = pair(30)
