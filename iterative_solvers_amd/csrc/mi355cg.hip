@@ -2199,9 +2199,10 @@ int mi355cg_create_csr(long long nrows, const int* row_map, const int* entries, 
                        int device, mi355cg_handle* out) {
     if (!out) return fail(MI355CG_ERR_INVALID, "out is null");
     *out = nullptr;
-    if (nrows <= 0 || !row_map || !entries || !values) return fail(MI355CG_ERR_INVALID, "bad CSR arguments");
+    if (nrows <= 0 || !row_map) return fail(MI355CG_ERR_INVALID, "bad CSR arguments");
     if (row_map[0] != 0) return fail(MI355CG_ERR_INVALID, "row_map[0] must be 0");
     const long long nnz = row_map[nrows];
+    if (nnz > 0 && (!entries || !values)) return fail(MI355CG_ERR_INVALID, "bad CSR arguments");      // a matrix without entries may come with null arrays
     for (long long i = 0; i < nrows; ++i) if (row_map[i + 1] < row_map[i]) return fail(MI355CG_ERR_INVALID, "row_map is not monotone at row %lld", i);
     for (long long j = 0; j < nnz; ++j) if (entries[j] < 0 || entries[j] >= nrows) return fail(MI355CG_ERR_INVALID, "column index %d out of range at entry %lld", entries[j], j);
     int ndev = 0;
@@ -2225,8 +2226,8 @@ int mi355cg_create_csr(long long nrows, const int* row_map, const int* entries, 
     if ((rc = Buf<int>::device(c->csr_row_map, nrows + 1, "allocation failed")) || (rc = Buf<int>::device(c->csr_entries, std::max<long long>(nnz, 1), "allocation failed")) ||
         (rc = Buf<double>::device(c->csr_values, std::max<long long>(nnz, 1), "allocation failed"))) return cleanup();
     if (hipMemcpy(c->csr_row_map, row_map, sizeof(int) * (nrows + 1), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(c->csr_entries, entries, sizeof(int) * nnz, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(c->csr_values, values, sizeof(double) * nnz, hipMemcpyHostToDevice) != hipSuccess) {
+        (nnz > 0 && hipMemcpy(c->csr_entries, entries, sizeof(int) * nnz, hipMemcpyHostToDevice) != hipSuccess) ||
+        (nnz > 0 && hipMemcpy(c->csr_values, values, sizeof(double) * nnz, hipMemcpyHostToDevice) != hipSuccess)) {
         rc = fail(MI355CG_ERR_HIP, "CSR upload failed"); return cleanup();
     }
     if (hipDeviceSynchronize() != hipSuccess) { rc = fail(MI355CG_ERR_HIP, "hipDeviceSynchronize failed"); return cleanup(); }      // the zero-fills: see create_state

@@ -56,18 +56,45 @@ class _Handle:
 
     @classmethod
     def from_csr(cls, row_map, entries, values, device=0):
-        """Handle for a caller-supplied CSR matrix (mi355cg_create_csr)."""
+        """Handle for a caller-supplied CSR matrix (mi355cg_create_csr).  The library reads row_map[-1] entries and values
+        through bare pointers, so the arrays' lengths and integer ranges are checked here first: ValueError, and the library has
+        not been called when it is raised."""
+        row_map, entries, values = cls._check_csr(row_map, entries, values)
         self = cls.__new__(cls)
         self._lib = _capi.load()
         self._h = C.c_void_p()
-        row_map = np.ascontiguousarray(row_map, dtype=np.int32)
-        entries = np.ascontiguousarray(entries, dtype=np.int32)
-        values = np.ascontiguousarray(values, dtype=np.float64)
         rc = self._lib.mi355cg_create_csr(len(row_map) - 1, row_map, entries, values, int(device), C.byref(self._h))
         self._check_rc(rc)
         self.size = int(self._lib.mi355cg_size(self._h))
         self._device = int(device)
         return self
+
+    @staticmethod
+    def _check_csr(row_map, entries, values):
+        """(row_map int32, entries int32, values float64), contiguous, or ValueError: row_map is one-dimensional and not empty,
+        row_map and entries hold integers that fit in int32 (compared before the cast, which would wrap), and entries and values
+        have exactly row_map[-1] elements.  Monotone offsets and the column range are the library's to check."""
+        row_map, entries, values = np.asarray(row_map), np.asarray(entries), np.asarray(values)
+        if row_map.ndim != 1 or row_map.size == 0:
+            raise ValueError(f"row_map has shape {row_map.shape}, expected (rows + 1,) with at least one offset")
+        if entries.ndim != 1 or values.ndim != 1:
+            raise ValueError(f"entries and values have shapes {entries.shape} and {values.shape}, expected one dimension each")
+        i32 = np.iinfo(np.int32)
+        for name, a in (("row_map", row_map), ("entries", entries)):
+            if a.size == 0:                                       # an empty list arrives as float64 and holds nothing to misread
+                continue
+            if a.dtype.kind not in "iu":
+                raise ValueError(f"{name} has dtype {a.dtype}, expected an integer type")
+            if int(a.min()) < i32.min or int(a.max()) > i32.max:
+                raise ValueError(f"{name} holds values in [{int(a.min())}, {int(a.max())}], which do not fit in int32")
+        nnz = int(row_map[-1])
+        if len(entries) != nnz or len(values) != nnz:
+            raise ValueError(f"row_map[-1] = {nnz}, but entries has {len(entries)} and values has {len(values)} elements")
+        try:
+            values = np.ascontiguousarray(values, dtype=np.float64)
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"values has dtype {values.dtype}, expected real numbers") from e
+        return np.ascontiguousarray(row_map, dtype=np.int32), np.ascontiguousarray(entries, dtype=np.int32), values
 
     def set_true_solution(self, u):
         u = np.ascontiguousarray(u, dtype=np.float64)
