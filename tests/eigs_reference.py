@@ -1,5 +1,5 @@
 """A NumPy restatement of the block eigensolver (include/mi355cg.h, mi355cg_eigs) on top of the multigrid
-restatements of tests/test_mg_cpu.py and tests/test_mg_any_cpu.py: K = -A, T = -M (one V-cycle), a locally optimal block
+restatement of tests/mg_model.py: K = -A, T = -M (one V-cycle), a locally optimal block
 preconditioned iteration with soft locking, and the Rayleigh-Ritz step exactly as the header states it.  tests/test_eigs_cpu.py
 checks it against the dense operator; tests/test_gpu_eigs.py bounds the device's iteration counts by its own."""
 import os
@@ -8,8 +8,7 @@ import sys
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import test_mg_any_cpu as any_ref  # noqa: E402
-import test_mg_cpu as ref  # noqa: E402
+import mg_model as ref  # noqa: E402
 
 CONVERGED, ITERATIONS, INTERRUPTED, BREAKDOWN = range(4)
 
@@ -17,7 +16,7 @@ CONVERGED, ITERATIONS, INTERRUPTED, BREAKDOWN = range(4)
 def levels_for(N, dom=(1.0, 2.0, 1.0, 2.0)):
     """The hierarchy MI355CG_PRECOND_MG_ANY builds (where MI355CG_PRECOND_MG has one it is the same)."""
     a, b, c, d = dom
-    return any_ref.hierarchy_any(N, (b - a) / N, (d - c) / N)
+    return ref.hierarchy_any(N, (b - a) / N, (d - c) / N)
 
 
 def apply_K(levels, v):
@@ -26,7 +25,7 @@ def apply_K(levels, v):
 
 
 def apply_T(levels, r):
-    return -any_ref.apply_M(levels, r)
+    return -ref.apply_M(levels, r)
 
 
 def dense_K(levels):

@@ -1,11 +1,10 @@
 """The restatement of the line smoother of the fp64 V-cycle (mi355cg_set_smoother) on top of
-tests/test_mg_cpu.py, tests/test_mg_any_cpu.py and tests/mg_reference.py, imported, not copied: the line solve (Thomas with the
-reciprocal pivots the device keeps in its tables, vectorised across the lines of one length), the sweep
-t = u + omega T^-1 (r - A u), the V-cycle of both hierarchy kinds with a smoother argument, and the same in long double for the
-rounding floor.  A plain module: no test in here, nothing that needs a GPU.
+tests/mg_model.py and tests/mg_reference.py, imported, not copied: the line solve (Thomas with the reciprocal pivots the device
+keeps in its tables, vectorised across the lines of one length), the sweep t = u + omega T^-1 (r - A u) as the smoother of
+their V-cycles, in fp64 and in long double for the rounding floor.  A plain module: no test in here, nothing that needs a GPU.
 
 Directions carry the values mi355cg_get_smoother reports: 0 = damped point Jacobi, 1 = lines along x (rows), 2 = lines along y
-(columns).  Grids are [y, x] arrays as in test_mg_cpu; the L-shaped interior is symmetric under x <-> y, so a solve along
+(columns).  Grids are [y, x] arrays as in mg_model; the L-shaped interior is symmetric under x <-> y, so a solve along
 columns is the solve along rows of the transposed grid with y_k in the place of x_k."""
 import functools
 import os
@@ -15,9 +14,8 @@ from types import SimpleNamespace
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import mg_model as ref  # noqa: E402
 import mg_reference as R  # noqa: E402
-import test_mg_any_cpu as ref_any  # noqa: E402
-import test_mg_cpu as ref  # noqa: E402
 
 JACOBI, LINE_X, LINE_Y = 0, 1, 2
 LD = np.longdouble
@@ -81,30 +79,14 @@ def smooth_line(L, u, r, direction):
     return t
 
 
-def smooth(L, u, r, direction):
-    return smooth_line(L, u, r, direction) if direction else ref.smooth(L, u, r)
-
-
-def vcycle(levels, l, r, direction):
-    """test_mg_any_cpu.vcycle (which is test_mg_cpu's on nested levels) with the smoother of `direction`"""
-    L = levels[l]
-    if l == len(levels) - 1:
-        return ref.grid(L, L.inv @ ref.packed(L, r))
-    Cl = levels[l + 1]
-    nested = L.N == 2 * Cl.N
-    u = smooth(L, np.zeros_like(r), r, direction)
-    u = smooth(L, u, r, direction)
-    s = r - ref.apply_A(L, u)
-    s[~L.mask] = 0.0
-    e = vcycle(levels, l + 1, ref.restrict(L, Cl, s) if nested else ref_any.restrict_nn(L, Cl, s), direction)
-    u = u + (ref.prolong(L, e) if nested else ref_any.prolong_nn(L, e))
-    u = smooth(L, u, r, direction)
-    return smooth(L, u, r, direction)
+def smoother_of(direction):
+    """the smoother of `direction` as mg_model.vcycle takes it"""
+    return functools.partial(smooth_line, direction=direction) if direction else ref.smooth
 
 
 def apply_M_line(levels, r_packed, direction):
     """z = M r with the smoother of `direction` (0: the point cycle, bit for bit mg_reference.apply_M)"""
-    return ref.packed(levels[0], vcycle(levels, 0, ref.grid(levels[0], r_packed), direction))
+    return ref.apply_M(levels, r_packed, smoother_of(direction))
 
 
 def M_of(levels, direction):
@@ -122,34 +104,9 @@ def _smooth_ld(L, u, r, direction):
     return t
 
 
-def _vcycle_ld(levels, l, r, direction):
-    """mg_reference._vcycle_ld with the smoother of `direction`"""
-    L = levels[l]
-    if l == len(levels) - 1:
-        g = np.zeros_like(r)
-        g[L.mask] = L.inv.astype(LD) @ r[L.mask]
-        return g
-    Cl = levels[l + 1]
-    u = _smooth_ld(L, np.zeros_like(r), r, direction)
-    u = _smooth_ld(L, u, r, direction)
-    s = R._sweep_ld(L, u, r, False)
-    idx, w = R._taps(L.N, Cl.N)
-    rc = LD(Cl.N * Cl.N / (L.N * L.N)) * R._restrict_rows_ld(R._restrict_rows_ld(s, idx, w).T, idx, w).T
-    rc[~Cl.mask] = 0
-    e = _vcycle_ld(levels, l + 1, rc, direction)
-    pe = R._prolong_rows_ld(R._prolong_rows_ld(e, L.N, idx, w).T, L.N, idx, w).T
-    pe[~L.mask] = 0
-    u = u + pe
-    u = _smooth_ld(L, u, r, direction)
-    return _smooth_ld(L, u, r, direction)
-
-
 def apply_M_line_longdouble(levels, r, direction):
     """z = M r with every array and coefficient of the fp64 restatement, the Thomas factors included, in long double"""
-    L = levels[0]
-    g = np.zeros((L.N + 1, L.N + 1), dtype=LD)
-    g[L.mask] = r.astype(LD)
-    return _vcycle_ld(levels, 0, g, direction)[L.mask]
+    return R.apply_M_longdouble(levels, r, functools.partial(_smooth_ld, direction=direction))
 
 
 def cycle_floor_line(levels, r, direction, z=None):

@@ -1,9 +1,9 @@
 """The high-precision restatement the preconditioned-CG GPU tests compare against: the hierarchies and the
-V-cycle of tests/test_mg_cpu.py and tests/test_mg_any_cpu.py on any domain, the PCG loop of solve_mg with exactly rounded inner
-products and every quantity the library reports recorded per iteration, the loop's own sensitivity to the order of its sums, and
-the V-cycle in long double.  A plain module: no test in here, nothing that needs a GPU or the oracle binaries.
+V-cycle of tests/mg_model.py on any domain, the PCG loop of solve_mg with exactly rounded inner products and every quantity the
+library reports recorded per iteration, the loop's own sensitivity to the order of its sums, and the V-cycle in long double, its
+smoother an argument.  A plain module: no test in here, nothing that needs a GPU or the oracle binaries.
 
-Packed vectors are in the library's order (row-major over the interior nodes), as in test_mg_cpu."""
+Packed vectors are in the library's order (row-major over the interior nodes), as in mg_model."""
 import math
 import os
 import sys
@@ -14,8 +14,7 @@ from types import SimpleNamespace
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import test_mg_any_cpu as ref_any  # noqa: E402
-import test_mg_cpu as ref  # noqa: E402
+import mg_model as model  # noqa: E402
 
 ISO = (1.0, 2.0, 1.0, 2.0)
 WIDE_Y = (0.0, 1.0, 0.0, 2.0)          # hy = 2 hx: xk = 4 yk
@@ -27,25 +26,25 @@ ITERATIONS, PRECISION, RESIDUAL, EXACT_ERROR = 0, 1, 2, 3
 LD = np.longdouble
 
 
-def levels_for(N, dom, kind, exchanged=False):
-    """the restatement hierarchy of an N x N grid on the domain (a, b, c, d); exchanged=True builds the wrong one, with hx and
-    hy exchanged (what the tests must be able to tell from the right one)"""
+def levels_for(N, dom, kind, exchanged=False, sigma=0.0):
+    """the restatement hierarchy of an N x N grid on the domain (a, b, c, d), of A - sigma I; exchanged=True builds the wrong one,
+    with hx and hy exchanged (what the tests must be able to tell from the right one)"""
     a, b, c, d = dom
     hx, hy = (b - a) / N, (d - c) / N
     if exchanged:
         hx, hy = hy, hx
-    return ref.hierarchy(N, hx, hy) if kind == MG else ref_any.hierarchy_any(N, hx, hy)
+    return model.hierarchy(N, hx, hy, sigma) if kind == MG else model.hierarchy_any(N, hx, hy, sigma)
 
 
 def apply_M(levels, r):
-    """z = M r; test_mg_any_cpu's cycle, which is test_mg_cpu's on nested levels"""
-    return ref_any.apply_M(levels, r)
+    """z = M r, one V-cycle"""
+    return model.apply_M(levels, r)
 
 
 def apply_A(levels, v):
     """A v for a packed v on level 0"""
     L = levels[0]
-    return ref.packed(L, ref.apply_A(L, ref.grid(L, v)))
+    return model.packed(L, model.apply_A(L, model.grid(L, v)))
 
 
 # ---- sums -----------------------------------------------------------------------------------------------------------------------
@@ -176,7 +175,7 @@ def stop_margin(t, rule, eps, eps_exact_error=None):
     return min(m)
 
 
-# The plain formulas of test_mg_cpu in long double would do; the row blocks, the threads and the tap-based transfers below are
+# The plain formulas of mg_model in long double would do; the row blocks, the threads and the tap-based transfers below are
 # there only for the time a cycle takes at N = 4100 (long double has no SIMD and no BLAS).  test_mg_reference_cpu pins the
 # result to apply_M at 1e-14.
 # ---- the V-cycle in long double ----------------------------------------------------------------------------------------------------
@@ -191,7 +190,7 @@ def _sweep_ld(L, u, r, smooth):
     so that no operation allocates."""
     N = L.N
     out = np.zeros_like(u)
-    d, xk, yk, om = LD(L.diag), LD(L.xk), LD(L.yk), LD(ref.OMEGA)
+    d, xk, yk, om = LD(L.diag), LD(L.xk), LD(L.yk), LD(model.OMEGA)
 
     def rows(lo):
         hi = min(lo + _BLOCK, N)
@@ -227,7 +226,7 @@ def _smooth_ld(L, u, r):
 
 
 def _taps(Nf, Nc):
-    """the 1-D transfer of ref_any.weights(Nf, Nc) without the dense matrix: per coarse node X the <= 5 fine nodes of its support
+    """the 1-D transfer of mg_model.weights(Nf, Nc) without the dense matrix: per coarse node X the <= 5 fine nodes of its support
     (clipped to the grid; a node off the support has weight 0) and their long double weights"""
     X = np.arange(Nc + 1, dtype=np.int64)
     lo = (X - 1) * Nf // Nc + 1
@@ -272,34 +271,34 @@ def _prolong_rows_ld(e, Nf, idx, w):
     return out
 
 
-def _vcycle_ld(levels, l, r):
+def _vcycle_ld(levels, l, r, smooth=_smooth_ld):
     L = levels[l]
     if l == len(levels) - 1:
         g = np.zeros_like(r)
         g[L.mask] = L.inv.astype(LD) @ r[L.mask]
         return g
     Cl = levels[l + 1]
-    u = _smooth_ld(L, np.zeros_like(r), r)
-    u = _smooth_ld(L, u, r)
+    u = smooth(L, np.zeros_like(r), r)
+    u = smooth(L, u, r)
     s = _sweep_ld(L, u, r, False)
     idx, w = _taps(L.N, Cl.N)                                       # nested or not: R = (N_c / N_f)^2 W s W^T, P = W^T e W
     rc = LD(Cl.N * Cl.N / (L.N * L.N)) * _restrict_rows_ld(_restrict_rows_ld(s, idx, w).T, idx, w).T
     rc[~Cl.mask] = 0
-    e = _vcycle_ld(levels, l + 1, rc)
+    e = _vcycle_ld(levels, l + 1, rc, smooth)
     pe = _prolong_rows_ld(_prolong_rows_ld(e, L.N, idx, w).T, L.N, idx, w).T
     pe[~L.mask] = 0
     u = u + pe
-    u = _smooth_ld(L, u, r)
-    return _smooth_ld(L, u, r)
+    u = smooth(L, u, r)
+    return smooth(L, u, r)
 
 
-def apply_M_longdouble(levels, r):
+def apply_M_longdouble(levels, r, smooth=_smooth_ld):
     """z = M r with every array and every coefficient of the fp64 restatement (diagonal, x_k, y_k, omega, the transfer weights,
     the coarse inverse) promoted to long double: the same operator, its rounding errors some 2^-11 of the fp64 cycle's."""
     L = levels[0]
     g = np.zeros((L.N + 1, L.N + 1), dtype=LD)
     g[L.mask] = r.astype(LD)
-    return _vcycle_ld(levels, 0, g)[L.mask]
+    return _vcycle_ld(levels, 0, g, smooth)[L.mask]
 
 
 def cycle_floor(levels, r, z=None):

@@ -13,7 +13,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import mg_reference as R  # noqa: E402
-import test_mg_cpu as ref  # noqa: E402
+import mg_model as ref  # noqa: E402
 
 EPS = 1e-8
 MARGIN = 0.01                          # iteration counts are compared only where the reference's deciding ratio stays this far from 1
@@ -28,20 +28,8 @@ STEPS = 4
 
 def shifted_levels(N, dom, kind, sigma):
     """mg_reference.levels_for with every level's diagonal shifted by sigma (the same sigma on every level, no scaling) and the
-    coarsest level's dense inverse recomputed from the shifted matrix by the recipe of test_mg_cpu.hierarchy"""
-    levels = R.levels_for(N, dom, kind)
-    for L in levels:
-        L.diag = L.diag - sigma
-    C = levels[-1]
-    n = int(C.mask.sum())
-    S = np.empty((n, n))
-    for j in range(n):
-        e = np.zeros(n)
-        e[j] = 1.0
-        S[:, j] = -ref.packed(C, ref.apply_A(C, ref.grid(C, e)))
-    T = np.linalg.inv(np.linalg.cholesky(S))
-    C.inv = -(T.T @ T)
-    return levels
+    coarsest level's dense inverse that of the shifted matrix"""
+    return R.levels_for(N, dom, kind, sigma=sigma)
 
 
 def theta_rhs(base_levels, u, g, sigma, theta):

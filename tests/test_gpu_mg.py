@@ -1,5 +1,5 @@
 """The multigrid preconditioner on the GPU (mi355cg_set_preconditioner): the device V-cycle against the NumPy restatement in
-tests/test_mg_cpu.py, preconditioned CG under both stop rules, determinism, the way back to the plain path, the refusals, and
+tests/mg_model.py, preconditioned CG under both stop rules, determinism, the way back to the plain path, the refusals, and
 time to solution against the plain solve."""
 import ctypes as C
 import os
@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import test_mg_cpu as ref  # noqa: E402
+import mg_model as ref  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 

@@ -1,4 +1,4 @@
-"""MI355CG_PRECOND_MG_ANY on the GPU: the device V-cycle against the NumPy restatement in tests/test_mg_any_cpu.py, the same bits
+"""MI355CG_PRECOND_MG_ANY on the GPU: the device V-cycle against the NumPy restatement in tests/mg_model.py, the same bits
 as MI355CG_PRECOND_MG where both have a hierarchy, preconditioned CG under both stop rules on grids MG refuses, determinism, the
 way back to the plain path, the refusals, time to solution against the plain solve, and the C++ layer."""
 import ctypes as C
@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import test_mg_any_cpu as ref  # noqa: E402
+import mg_model as ref  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 

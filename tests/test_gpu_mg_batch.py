@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from test_mg_batch_cpu import batch_rhs  # noqa: E402
+from mg_cases import batch_rhs  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 

@@ -1,4 +1,4 @@
-"""MI355CG_CYCLE_F32 on the GPU: the device's fp32 V-cycle against the fp64 NumPy restatement tests/test_mg_any_cpu.apply_M (which
+"""MI355CG_CYCLE_F32 on the GPU: the device's fp32 V-cycle against the fp64 NumPy restatement tests/mg_model.apply_M (which
 is independent of the code under test and pinned to the fp64 device cycle at 1e-13), its symmetry, preconditioned CG under both
 stop rules with the iteration counts of the fp64 cycle, one-level grids, exact scaling by powers of two, determinism, the way
 back to the fp64 cycle and to the plain path, preconditioner_info, the refusals, the C++ layer, and a speed guard at N = 4096."""
@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import test_mg_any_cpu as ref  # noqa: E402
+import mg_model as ref  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 

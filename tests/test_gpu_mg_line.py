@@ -106,7 +106,7 @@ def test_solves_under_line_auto_against_the_trace(c):
         assert solver.getStopReason() == isa.StopCriterion(t.reason)
         ok = show("max|dx|", rel(solver.getFinalPrecision(), t.dx_max[last]), ref.tol["dx_max"][last])
         ok &= show("max|r|", rel(solver.getFinalResidualNorm(), t.r_max[last]), ref.tol["r_max"][last])
-        # a difference of nearly equal vectors: bounded as x is (test_mg_reference_cpu, the error norms)
+        # a difference of nearly equal vectors: bounded as x is (mg_cases, the error norms)
         ok &= show("max|x - u| over max|x_ref|", abs(solver.getFinalErrorNorm() - t.e_max[last]) / np.abs(t.x[last]).max(), ref.tol["x"][last])
     ok &= show("x, max|x - x_ref| / max|x_ref|", np.abs(x - t.x[last]).max() / np.abs(t.x[last]).max(), ref.tol["x"][last])
     tr = np.linalg.norm(OracleGrid(N, N, *dom).apply(x) - ref.b) / np.linalg.norm(ref.b)
@@ -172,7 +172,7 @@ def test_time_steps_have_the_bits_of_set_rhs_and_a_warm_solve():
     N, dom, tau, steps = 64, LR.STRETCH_X, 1e-4, 3
     sigma = 1.0 / tau
     rng = np.random.default_rng(N)
-    n = int(R.ref.interior_mask(N).sum())
+    n = int(R.model.interior_mask(N).sum())
     u0, g = 1e-4 * rng.standard_normal(n), rng.standard_normal(n)
     s = system(N, dom, R.MG, isa.SMOOTHER_LINE_AUTO)
     s._handle.set_rhs(g)
@@ -288,7 +288,7 @@ def test_jacobi_after_line_has_the_bits_of_a_fresh_handle(N, kind):
 def test_one_level_grids_give_the_same_bits_under_every_smoother(n):
     import iterative_solvers_amd as isa
     dom = LR.STRETCH_X
-    r = np.random.default_rng(n).standard_normal(int(R.ref.interior_mask(n).sum()))
+    r = np.random.default_rng(n).standard_normal(int(R.model.interior_mask(n).sum()))
     outs = []
     for smoother in (isa.SMOOTHER_JACOBI, isa.SMOOTHER_LINE_X, isa.SMOOTHER_LINE_Y, isa.SMOOTHER_LINE_AUTO):
         s = system(n, dom, R.MG_ANY, smoother)

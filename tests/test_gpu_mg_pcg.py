@@ -1,6 +1,6 @@
 """Multigrid-preconditioned CG on the GPU against the high-precision restatement of tests/mg_reference.py, on
-the cases of tests/test_mg_reference_cpu.py, which shows that each of them can tell exchanged steps from the right ones, measures
-the reference's own uncertainty and keeps every stop away from its threshold.
+the cases of tests/mg_cases.py; tests/test_mg_reference_cpu.py shows that each of them can tell exchanged steps from the right
+ones, measures the reference's own uncertainty and keeps every stop away from its threshold.
   a  the V-cycle on stretched domains (hx != hy in both directions), fp64 and fp32, and its symmetry
   b  the V-cycle where a block marches over more than one row (N = 2050; N = 4100: levels 0 and 1)
   c  the PCG iterates x_k, ||r_k|| and ||b|| after k fixed iterations
@@ -16,8 +16,8 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import test_mg_reference_cpu as T  # noqa: E402
-import test_mg_f32_cpu as ref32  # noqa: E402
+import mg_cases as T  # noqa: E402
+import mg_model  # noqa: E402
 
 R = T.R
 LD = np.longdouble
@@ -124,8 +124,7 @@ def test_rel_2norm_diagnostics_under_a_preconditioner(c):
     print(f"{T.case_id(c)}: {res.iterations} iterations (reference {t.iterations}, margin {100 * ref.margin:.1f} %)")
     assert [q[0] for q in calls] == list(range(res.iterations))
     if c.f32:
-        lv32 = ref32.hierarchy32(ref.levels)
-        assert res.iterations == ref32.pcg(lambda r: ref32.apply_M32(lv32, r), ref.levels[0], ref.b, eps=c.eps)[1]
+        assert res.iterations == mg_model.pcg(ref.levels, ref.b, eps=c.eps, M=lambda r: mg_model.apply_M32(ref.levels, r))[1]
         assert res.converged
     else:
         assert res.iterations == t.iterations and bool(res.converged) == t.converged
@@ -134,7 +133,7 @@ def test_rel_2norm_diagnostics_under_a_preconditioner(c):
             print(f" callback {i}")
             ok &= show("||dx||_2", rel(dx, t.dx2[i]), ref.tol["dx2"][i])
             ok &= show("||b - A x||_2 over ||b||_2", abs(tr - t.true2[i]) / t.b_norm2, ref.tol["true2"][i])
-            # a difference of nearly equal vectors: bounded as x is (test_mg_reference_cpu, the error norms)
+            # a difference of nearly equal vectors: bounded as x is (mg_cases, the error norms)
             ok &= show("||x - u||_2 over ||x_ref||_2", abs(e - t.e2[i]) / np.linalg.norm(t.x[i]), ref.tol["x"][i])
         assert ok
     # apart from the trace: the last callback's norms are those of the returned x
@@ -172,7 +171,7 @@ def test_msg_rule_against_the_trace(c):
     for call, i in ((calls[1], 0), (calls[2], it - 1)):
         for name, v, q in (("max|dx|", call[1], "dx_max"), ("max|r|", call[2], "r_max")):
             ok &= show(f"callback {call[0]}, {name}", rel(v, getattr(t, q)[i]), ref.tol[q][i])
-        # a difference of nearly equal vectors: bounded as x is, |e - e_ref| <= tol max|x_ref| (test_mg_reference_cpu, the error norms)
+        # a difference of nearly equal vectors: bounded as x is, |e - e_ref| <= tol max|x_ref| (mg_cases, the error norms)
         ok &= show(f"callback {call[0]}, max|x - u| over max|x_ref|", abs(call[3] - t.e_max[i]) / np.abs(t.x[i]).max(), ref.tol["x"][i])
     assert ok
     assert calls[-1][1:] == (solver.getFinalPrecision(), solver.getFinalResidualNorm(), solver.getFinalErrorNorm())

@@ -7,39 +7,17 @@ import ctypes as C
 import json
 import os
 import subprocess
+import sys
 
 import numpy as np
 import pytest
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from onchip_support import DOMAIN, cap as _cap, system as _system  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DOMAIN = (1.0, 2.0, 1.0, 2.0)
-
-
-def _cap():
-    import iterative_solvers_amd as isa
-    cap = 64
-    while True:                                   # the largest n mi355cg_onchip_plan accepts
-        try:
-            isa.onchip_plan(cap + 2)
-        except ValueError:
-            return cap
-        cap += 2
-
-
-def _system(n, onchip, domain=DOMAIN):
-    import iterative_solvers_amd as isa
-    old = os.environ.pop("MI355CG_ONCHIP", None)
-    try:
-        s = isa.MatrixFreeSystem(n, n, *domain)
-    finally:
-        if old is not None:
-            os.environ["MI355CG_ONCHIP"] = old
-    if onchip:
-        s.set_solve_mode(isa.SOLVE_ONCHIP)
-    assert s.solve_mode_info()["mode"] == (isa.SOLVE_ONCHIP if onchip else isa.SOLVE_LAUNCHES)
-    return s
 
 
 _pairs = {}
@@ -54,6 +32,7 @@ def pair(n, domain=DOMAIN):
 
 
 def params(rule, **kw):
+    """onchip_support.params with the true solution kept: these solves report final_error_norm"""
     import iterative_solvers_amd as isa
     p = isa.default_params(rule)
     for k, v in kw.items():

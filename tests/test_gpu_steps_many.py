@@ -14,39 +14,17 @@ import sys
 import numpy as np
 import pytest
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from onchip_support import DOMAIN, fields, params  # noqa: E402
+from onchip_support import cap as _cap, system as _system  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DOMAIN = (1.0, 2.0, 1.0, 2.0)
-FIELDS = ("iterations", "stop_reason", "converged", "r_norm2", "initial_r_norm2", "final_precision", "final_residual_norm")
 SIZES = [10, 12, 20, 30, 64, 100, "cap"]            # every workgroup size and unroll class of the plan (asserted below)
 FACTORS = (1e6, 1e3, 10.0, 0.03)                    # sigma = |A_diag| * factor: 2 / 3 / 6 / 9 - 77 iterations per step in a NumPy model
 REL = dict(eps_rel=1e-8, sync_every=7)
 MSG = dict(eps_precision=1e-8, eps_residual=1e-8, eps_exact_error=0.0, sync_every=7)
-
-
-def _cap():
-    import iterative_solvers_amd as isa
-    cap = 64
-    while True:                                   # the largest n mi355cg_onchip_plan accepts
-        try:
-            isa.onchip_plan(cap + 2)
-        except ValueError:
-            return cap
-        cap += 2
-
-
-def _system(n, onchip=False):
-    import iterative_solvers_amd as isa
-    old = os.environ.pop("MI355CG_ONCHIP", None)
-    try:
-        s = isa.MatrixFreeSystem(n, n, *DOMAIN)
-    finally:
-        if old is not None:
-            os.environ["MI355CG_ONCHIP"] = old
-    if onchip:
-        s.set_solve_mode(isa.SOLVE_ONCHIP)
-    return s
 
 
 _pairs = {}
@@ -60,22 +38,9 @@ def pair(n):
     return _pairs[n]
 
 
-def params(rule, **kw):
-    import iterative_solvers_amd as isa
-    p = isa.default_params(rule)
-    p.use_true_solution = 0
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
-
-
 def rules():
     from iterative_solvers_amd import _capi
     return ((_capi.RULE_REL_2NORM, REL), (_capi.RULE_MSG_MAXNORM, MSG))
-
-
-def fields(res):
-    return tuple(getattr(res, f) for f in FIELDS)
 
 
 def diag_abs(sys_):

@@ -1,11 +1,5 @@
-"""MI355CG_PRECOND_MG_ANY without a GPU: the ladder of mi355cg_mg_hierarchy, and a NumPy restatement of the non-nested levels
-(include/mi355cg.h) on top of the one in tests/test_mg_cpu.py, which tests/test_gpu_mg_any.py compares the
-device against.
-
-Ladder: N_{l+1} = 2 floor(N_l / 4) while N_l > 32.  A level with N_f = 2 N_c is nested and uses test_mg_cpu's full weighting and
-bilinear prolongation; any other (N_f % 4 == 2) keeps the domain (h_c = h_f N_f / N_c) and transfers by the 1-D bilinear weights
-w(x, X) = max(0, 1 - |x N_c - X N_f| / N_f): P e = W^T e W masked to the fine interior, R s = (N_c / N_f)^2 W s W^T masked to
-the coarse interior, so R = (N_c / N_f)^2 P^T."""
+"""MI355CG_PRECOND_MG_ANY without a GPU: the ladder of mi355cg_mg_hierarchy, and the non-nested levels of the NumPy restatement
+(tests/mg_model.py; include/mi355cg.h), which tests/test_gpu_mg_any.py compares the device against."""
 import ctypes as C
 import os
 import sys
@@ -14,93 +8,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import test_mg_cpu as ref  # noqa: E402
-
-DOM = (1.0, 2.0, 1.0, 2.0)
-
-
-def ladder(N):
-    ns = [N]
-    while ns[-1] > 32:
-        ns.append(2 * (ns[-1] // 4))
-    return ns
-
-
-def weights(Nf, Nc):
-    """W[X, x] = w(x, X); the numerator |x N_c - X N_f| is an exact integer"""
-    d = np.abs(np.arange(Nf + 1, dtype=np.int64)[None, :] * Nc - np.arange(Nc + 1, dtype=np.int64)[:, None] * Nf)
-    return np.where(d < Nf, (Nf - d) / Nf, 0.0)
-
-
-def hierarchy_any(N, hx, hy):
-    levels = [ref.Level(N, hx, hy)]
-    for Nc in ladder(N)[1:]:
-        F = levels[-1]
-        if F.N == 2 * Nc:
-            levels.append(ref.Level(Nc, 2 * F.hx, 2 * F.hy))
-        else:
-            levels.append(ref.Level(Nc, F.hx * F.N / Nc, F.hy * F.N / Nc))
-            F.W = weights(F.N, Nc)
-    Lc = levels[-1]
-    Lc.inv = ref.hierarchy(Lc.N, Lc.hx, Lc.hy)[0].inv          # N_L <= 32: one level, its dense inverse
-    return levels
-
-
-def restrict_nn(F, Cl, s):
-    out = (Cl.N * Cl.N / (F.N * F.N)) * (F.W @ s @ F.W.T)
-    out[~Cl.mask] = 0.0
-    return out
-
-
-def prolong_nn(F, e):
-    out = F.W.T @ e @ F.W
-    out[~F.mask] = 0.0
-    return out
-
-
-def vcycle(levels, l, r):
-    L = levels[l]
-    if l == len(levels) - 1:
-        return ref.grid(L, L.inv @ ref.packed(L, r))
-    Cl = levels[l + 1]
-    nested = L.N == 2 * Cl.N
-    u = ref.smooth(L, np.zeros_like(r), r)
-    u = ref.smooth(L, u, r)
-    s = r - ref.apply_A(L, u)
-    s[~L.mask] = 0.0
-    e = vcycle(levels, l + 1, ref.restrict(L, Cl, s) if nested else restrict_nn(L, Cl, s))
-    u = u + (ref.prolong(L, e) if nested else prolong_nn(L, e))
-    u = ref.smooth(L, u, r)
-    return ref.smooth(L, u, r)
-
-
-def apply_M(levels, r_packed):
-    return ref.packed(levels[0], vcycle(levels, 0, ref.grid(levels[0], r_packed)))
-
-
-def pcg(levels, b, eps=1e-8, max_iterations=100):
-    """Hestenes-Stiefel PCG from x = 0, REL_2NORM stop on the recursive residual; returns (x, iterations)."""
-    L = levels[0]
-    x = np.zeros_like(b)
-    r = b.copy()
-    r0 = np.linalg.norm(r)
-    it, rho, p = 0, 0.0, None
-    while it < max_iterations and np.linalg.norm(r) > eps * r0:
-        z = apply_M(levels, r)
-        rz = r @ z
-        p = z if it == 0 else z + (rz / rho) * p
-        rho = rz
-        q = ref.packed(L, ref.apply_A(L, ref.grid(L, p)))
-        alpha = rho / (p @ q)
-        x = x + alpha * p
-        r = r - alpha * q
-        it += 1
-    return x, it
-
-
-def steps(N):
-    a, b, c, d = DOM
-    return (b - a) / N, (d - c) / N
+import mg_model as ref  # noqa: E402
 
 
 # ---- the library's ladder (host arithmetic: no GPU) --------------------------------------------------------------------
@@ -114,7 +22,7 @@ def test_mg_hierarchy_in_python(n, expected):
     import iterative_solvers_amd as isa
     assert isa.mg_hierarchy(n) == expected
     assert isa.mg_hierarchy(n, kind=isa.PRECOND_MG_ANY) == expected
-    assert tuple(ladder(n)) == expected
+    assert tuple(ref.ladder(n)) == expected
 
 
 @pytest.mark.parametrize("n,expected", LADDERS)
@@ -178,7 +86,7 @@ def test_every_even_grid_up_to_10000_has_a_ladder_and_agrees_with_mg():
     with_mg = 0
     for n in range(6, 10001, 2):
         ns = isa.mg_hierarchy(n)
-        assert list(ns) == ladder(n)
+        assert list(ns) == ref.ladder(n)
         assert (16 <= ns[-1] <= 32) if n > 32 else ns == (n,)
         try:
             mg = isa.mg_hierarchy(n, kind=isa.PRECOND_MG)
@@ -193,7 +101,7 @@ def test_every_even_grid_up_to_10000_has_a_ladder_and_agrees_with_mg():
 @pytest.mark.parametrize("Nc", [16, 32, 64])
 def test_weights_of_a_nested_pair_are_full_weighting_and_bilinear(Nc):
     Nf = 2 * Nc
-    W = weights(Nf, Nc)
+    W = ref.weights(Nf, Nc)
     expect = np.zeros((Nc + 1, Nf + 1))
     for X in range(Nc + 1):
         expect[X, 2 * X] = 1.0
@@ -208,29 +116,29 @@ def test_weights_of_a_nested_pair_are_full_weighting_and_bilinear(Nc):
     # small integers: every sum is exact in fp64, so equal operators give equal bits whatever the order of the sums
     s = ref.grid(F, rng.integers(-8, 9, int(F.mask.sum())).astype(np.float64))
     e = ref.grid(Cl, rng.integers(-8, 9, int(Cl.mask.sum())).astype(np.float64))
-    assert np.array_equal(restrict_nn(F, Cl, s), ref.restrict(F, Cl, s))
-    assert np.array_equal(prolong_nn(F, e), ref.prolong(F, e))
+    assert np.array_equal(ref.restrict(F, Cl, s, nested=False), ref.restrict(F, Cl, s))
+    assert np.array_equal(ref.prolong(F, Cl, e, nested=False), ref.prolong(F, Cl, e))
 
 
 @pytest.mark.parametrize("Nf", [34, 50, 258])
 def test_restriction_is_a_multiple_of_the_transposed_prolongation(Nf):
-    Nc = ladder(Nf)[1]
+    Nc = ref.ladder(Nf)[1]
     assert Nf != 2 * Nc
     F, Cl = ref.Level(Nf, 1 / Nf, 1 / Nf), ref.Level(Nc, 1 / Nc, 1 / Nc)
-    F.W = weights(Nf, Nc)
+    F.W = ref.weights(Nf, Nc)
     rng = np.random.default_rng(Nf)
     for _ in range(3):
         s = ref.grid(F, rng.standard_normal(int(F.mask.sum())))
         e = ref.grid(Cl, rng.standard_normal(int(Cl.mask.sum())))
-        lhs = ref.packed(Cl, restrict_nn(F, Cl, s)) @ ref.packed(Cl, e)          # (R s, e)
-        rhs = (Nc * Nc / (Nf * Nf)) * (ref.packed(F, s) @ ref.packed(F, prolong_nn(F, e)))   # (N_c/N_f)^2 (s, P e)
+        lhs = ref.packed(Cl, ref.restrict(F, Cl, s)) @ ref.packed(Cl, e)          # (R s, e)
+        rhs = (Nc * Nc / (Nf * Nf)) * (ref.packed(F, s) @ ref.packed(F, ref.prolong(F, Cl, e)))   # (N_c/N_f)^2 (s, P e)
         assert abs(lhs - rhs) <= 1e-13 * abs(lhs)
     # each fine node is covered by weights summing to 1 in each direction: P reproduces constants away from the boundary
     assert np.allclose(F.W.sum(axis=0), 1.0, rtol=0, atol=1e-15)
 
 
 def test_restatement_ladder_and_steps():
-    levels = hierarchy_any(1000, *steps(1000))
+    levels = ref.hierarchy_any(1000, *ref.steps(1000))
     assert [L.N for L in levels] == [1000, 500, 250, 124, 62, 30]
     for L in levels:                                    # every level spans the same domain (to rounding on non-nested levels)
         assert L.hx * L.N == pytest.approx(1.0, rel=1e-15) and L.hy * L.N == pytest.approx(1.0, rel=1e-15)
@@ -239,29 +147,36 @@ def test_restatement_ladder_and_steps():
 
 @pytest.mark.parametrize("N", [34, 50, 258])
 def test_restatement_is_symmetric_and_negative_definite(N):
-    levels = hierarchy_any(N, *steps(N))
+    levels = ref.hierarchy_any(N, *ref.steps(N))
     rng = np.random.default_rng(N)
     n = int(levels[0].mask.sum())
     for _ in range(3):
         u, v = rng.standard_normal(n), rng.standard_normal(n)
-        Mu, Mv = apply_M(levels, u), apply_M(levels, v)
+        Mu, Mv = ref.apply_M(levels, u), ref.apply_M(levels, v)
         assert abs(Mu @ v - u @ Mv) <= 1e-12 * abs(Mu @ v)
         assert Mu @ u < 0 and Mv @ v < 0
 
 
 def test_restatement_equals_test_mg_cpu_on_a_nested_grid():
-    levels, nested = hierarchy_any(256, *steps(256)), ref.hierarchy(256, *steps(256))
+    levels, nested = ref.hierarchy_any(256, *ref.steps(256)), ref.hierarchy(256, *ref.steps(256))
     assert [(L.N, L.hx, L.hy) for L in levels] == [(L.N, L.hx, L.hy) for L in nested]
     r = np.random.default_rng(5).standard_normal(int(levels[0].mask.sum()))
-    assert np.array_equal(apply_M(levels, r), ref.apply_M(nested, r))
+    assert np.array_equal(ref.apply_M(levels, r), ref.apply_M(nested, r))
+
+
+@pytest.mark.parametrize("N", [34, 64])
+def test_the_default_smoother_is_the_point_smoother(N):
+    levels = ref.hierarchy_any(N, *ref.steps(N))
+    r = np.random.default_rng(N).standard_normal(int(levels[0].mask.sum()))
+    assert np.array_equal(ref.apply_M(levels, r, smoother=ref.smooth), ref.apply_M(levels, r))
 
 
 @pytest.mark.parametrize("N", [258, 1000])
 def test_restatement_pcg_converges_in_at_most_10_iterations(N):
-    levels = hierarchy_any(N, *steps(N))
+    levels = ref.hierarchy_any(N, *ref.steps(N))
     L = levels[0]
     b = np.random.default_rng(N).standard_normal(int(L.mask.sum()))
-    x, it = pcg(levels, b)
+    x, it = ref.pcg(levels, b)
     assert it <= 10, it
     true_r = b - ref.packed(L, ref.apply_A(L, ref.grid(L, x)))
     assert np.linalg.norm(true_r) <= 2e-8 * np.linalg.norm(b)

@@ -11,8 +11,8 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import test_mg_any_cpu as any_ref  # noqa: E402
-import test_mg_cpu as ref  # noqa: E402
+import mg_model as ref  # noqa: E402
+from mg_cases import batch_rhs  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DOM = (1.0, 2.0, 1.0, 2.0)
@@ -20,22 +20,6 @@ BATCH_SYMBOLS = ("mi355cg_solve_batch", "mi355cg_solve_batch_device", "mi355cg_b
 BATCH_KERNELS = ("k_mgb_smooth", "k_mgb_restrict", "k_mgb_prolong", "k_mgb_residual", "k_mgb_restrict_nn", "k_mgb_prolong_nn",
                  "k_mgb_coarse", "k_mgb_dir_apply", "k_mgb_update", "k_mgb_init", "k_mgb_dot", "k_mgb_reduce", "k_mgb_unpack",
                  "k_mgb_pack")
-
-
-def checkerboard(N):
-    """+-1 on the interior of the L-shaped grid by the parity of x + y, packed order"""
-    y, x = np.mgrid[0:N + 1, 0:N + 1]
-    return np.where((x + y) % 2 == 0, 1.0, -1.0)[ref.interior_mask(N)]
-
-
-def batch_rhs(N, b, scaled=True):
-    """The right-hand sides of the bit-identity tests, in this order: the grid's b, zeros, ones, the interior checkerboard,
-    seeded standard-normal [, b * 2^200, b * 2^-200]."""
-    n = b.size
-    out = [b.copy(), np.zeros(n), np.ones(n), checkerboard(N), np.random.default_rng(N).standard_normal(n)]
-    if scaled:
-        out += [np.ldexp(b, 200), np.ldexp(b, -200)]
-    return np.ascontiguousarray(np.stack(out))
 
 
 def test_library_exports_the_batch_entry_points():
@@ -122,14 +106,14 @@ def test_batched_kernels_are_compiled_without_scratch_and_without_store_hazards(
 @pytest.mark.parametrize("N", [130, 258])
 def test_the_right_hand_sides_of_the_gpu_tests_stop_at_different_iterations(N):
     """The freeze rule only runs if the systems of a batch stop at different iterations.  This is the NumPy restatement of the
-    REL_2NORM PCG (test_mg_any_cpu.pcg, eps 1e-8) on the unscaled right-hand sides; it guards the inputs, not the device code."""
+    REL_2NORM PCG (mg_model.pcg, eps 1e-8) on the unscaled right-hand sides; it guards the inputs, not the device code."""
     from oracle.oracle import OracleGrid
-    levels = any_ref.hierarchy_any(N, *any_ref.steps(N))
+    levels = ref.hierarchy_any(N, *ref.steps(N))
     b = OracleGrid(N, N, *DOM).rhs()
     rhs = batch_rhs(N, b, scaled=False)
     assert rhs.shape == (5, int(levels[0].mask.sum()))
     assert set(np.unique(rhs[3])) == {-1.0, 1.0} and abs(rhs[3].sum()) <= N
-    its = [any_ref.pcg(levels, v)[1] for v in rhs]
+    its = [ref.pcg(levels, v)[1] for v in rhs]
     print("iterations (b, zeros, ones, checkerboard, normal):", its)
     assert len(set(its)) >= 2, its
     assert its[1] == 0 and all(1 <= k <= 12 for k in its[:1] + its[2:]), its

@@ -15,7 +15,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import line_reference as LR  # noqa: E402
 
 R = LR.R
-CAP = 1e-11                                                        # test_mg_reference_cpu's: no cycle tolerance may need more
+CAP = 1e-11                                                        # mg_cases's: no cycle tolerance may need more
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -35,7 +35,7 @@ def test_the_line_solve_inverts_the_line_operator(direction):
     """T e = s back through the three-point formula along the lines, the short lines and the long ones"""
     lv = R.levels_for(50, LR.STRETCH_Y, R.MG_ANY)
     L = lv[0]
-    s = R.ref.grid(L, normal(lv, 2))
+    s = R.model.grid(L, normal(lv, 2))
     e = LR.line_solve(L, s, direction)
     k = L.xk if direction == LR.LINE_X else L.yk
     g = e if direction == LR.LINE_X else e.T

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import mg_model  # noqa: E402
 import shift_reference as S  # noqa: E402
 
 R = S.R
@@ -31,6 +32,17 @@ def test_shifted_restatement_is_symmetric_and_negative_definite(N, sigma):
     base = R.levels_for(N, R.ISO, R.MG_ANY)
     v = np.random.default_rng(N).standard_normal(n)
     assert np.abs(A @ v - (R.apply_A(base, v) - sigma * v)).max() <= 1e-12 * np.abs(A @ v).max()
+
+
+@pytest.mark.parametrize("N", [34, 64])
+def test_the_sigma_of_the_hierarchy_is_the_shifted_levels(N):
+    sigma = S.SIGMAS[3]
+    assert sigma != 0
+    hx, hy = mg_model.steps(N)
+    levels, shifted, base = mg_model.hierarchy_any(N, hx, hy, sigma), S.shifted_levels(N, R.ISO, R.MG_ANY, sigma), R.levels_for(N, R.ISO, R.MG_ANY)
+    assert [L.diag for L in levels] == [L.diag for L in shifted] == [L.diag - sigma for L in base]
+    assert np.array_equal(levels[-1].inv, shifted[-1].inv) and not np.array_equal(levels[-1].inv, base[-1].inv)
+    assert np.array_equal(levels[-1].inv, mg_model.coarse_inverse(levels[-1]))          # the inverse of the diagonal the level has now
 
 
 @pytest.mark.parametrize("N,kind,dom", S.GRIDS, ids=lambda v: str(v) if isinstance(v, int) else None)

@@ -1,7 +1,7 @@
 """Warm starts (mi355cg_set_initial_guess*, mi355cg_use_solution_as_initial_guess, mi355cg_solve_batch*_from)
 without a GPU: the declared and exported symbols, the refusals that need no device, the Python wrappers' argument checks, the
-compiled kernels, and a NumPy restatement of warm multigrid-PCG (on tests/test_mg_cpu.py's apply_A and tests/test_mg_any_cpu.py's
-apply_M) that establishes the identities tests/test_gpu_warm_start.py leans on."""
+compiled kernels, and a NumPy restatement of warm multigrid-PCG (on the apply_A and apply_M of
+tests/mg_model.py) that establishes the identities tests/test_gpu_warm_start.py leans on."""
 import ctypes as C
 import os
 import re
@@ -12,11 +12,10 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import test_mg_any_cpu as any_ref  # noqa: E402
-import test_mg_cpu as ref  # noqa: E402
+import mg_model as ref  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DOM = any_ref.DOM
+DOM = ref.DOM
 GUESS_SYMBOLS = ("mi355cg_set_initial_guess", "mi355cg_set_initial_guess_device", "mi355cg_use_solution_as_initial_guess")
 BATCH_SYMBOLS = ("mi355cg_solve_batch_from", "mi355cg_solve_batch_device_from")
 
@@ -136,7 +135,7 @@ def apply_A_packed(L, v):
 
 
 def warm_pcg(levels, b, x0=None, eps=1e-8, max_iterations=100, fixed_iterations=False):
-    """test_mg_any_cpu.pcg with a start: x = x0, r0 = b - A x0, REL_2NORM relative to ||b||.  x0 = None is that function's cold
+    """mg_model.pcg with a start: x = x0, r0 = b - A x0, REL_2NORM relative to ||b||.  x0 = None is that function's cold
     start (r0 = b, relative to ||r0|| = ||b||).  Returns (x, r, iterations, [||r_k||_2 for k = 0 .. iterations])."""
     L = levels[0]
     if x0 is None:
@@ -148,7 +147,7 @@ def warm_pcg(levels, b, x0=None, eps=1e-8, max_iterations=100, fixed_iterations=
     norms = [np.linalg.norm(r)]
     it, rho, p = 0, 0.0, None
     while it < max_iterations and (fixed_iterations or norms[-1] > eps * target):
-        z = any_ref.apply_M(levels, r)
+        z = ref.apply_M(levels, r)
         rz = r @ z
         p = z if it == 0 else z + (rz / rho) * p
         rho = rz
@@ -163,7 +162,7 @@ def warm_pcg(levels, b, x0=None, eps=1e-8, max_iterations=100, fixed_iterations=
 
 def problem(N):
     from oracle.oracle import OracleGrid
-    levels = any_ref.hierarchy_any(N, *any_ref.steps(N))
+    levels = ref.hierarchy_any(N, *ref.steps(N))
     return levels, OracleGrid(N, N, *DOM).rhs()
 
 
@@ -174,7 +173,7 @@ def test_a_zero_guess_reproduces_the_cold_solve_exactly(N):
     xw, rw, itw, nw = warm_pcg(levels, b, x0=np.zeros_like(b))
     assert itc == itw >= 1 and nc == nw
     assert np.array_equal(xc, xw) and np.array_equal(rc, rw)
-    assert np.array_equal(xc, any_ref.pcg(levels, b)[0])                     # and the cold start is the existing restatement's
+    assert np.array_equal(xc, ref.pcg(levels, b)[0])                     # and the cold start is the existing restatement's
 
 
 @pytest.mark.parametrize("N", [34, 64])

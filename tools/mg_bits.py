@@ -8,7 +8,7 @@ asserts that the tree under test reproduces it.  It is recorded from a build of 
 --baseline-tree; --commit HASH: noted in the file).
 
 Cases (CASES): the smallest grids at which each element-wise body of csrc/mg_kernels.h can still go wrong, fp64 cycle, right-hand
-sides from tests/test_mg_batch_cpu.batch_rhs.  Per case: the sha256 of the right-hand sides' bytes (a changed input is then
+sides from batch_rhs below (tests/mg_cases.py hands the same function to the batch tests).  Per case: the sha256 of the right-hand sides' bytes (a changed input is then
 reported as such); per system iterations, stop_reason, the hex of r_norm2 and initial_r_norm2 and the sha256 of x, from single
 solves and from one batch; and the sha256 of apply_preconditioner(last right-hand side).
 Usage: python tools/mg_bits.py --commit HASH [--tree DIR] [--out FILE]"""
@@ -36,6 +36,25 @@ CASES = [
 ]
 
 
+def checkerboard(N):
+    """+-1 on the interior of the L-shaped grid (tests/mg_model.interior_mask) by the parity of x + y, packed order"""
+    y, x = np.mgrid[0:N + 1, 0:N + 1]
+    h = N // 2
+    interior = (y >= 1) & (y <= N - 1) & (x <= N - 1) & (x >= np.where(y <= h, h + 1, 1))
+    return np.where((x + y) % 2 == 0, 1.0, -1.0)[interior]
+
+
+def batch_rhs(N, b, scaled=True):
+    """The right-hand sides of the bit-identity tests, in this order: the grid's b, zeros, ones, the interior checkerboard,
+    seeded standard-normal [, b * 2^200, b * 2^-200].  They are part of what the recorded file pins, so they are stated here,
+    where nothing under tests/ is needed to record or replay it."""
+    n = b.size
+    out = [b.copy(), np.zeros(n), np.ones(n), checkerboard(N), np.random.default_rng(N).standard_normal(n)]
+    if scaled:
+        out += [np.ldexp(b, 200), np.ldexp(b, -200)]
+    return np.ascontiguousarray(np.stack(out))
+
+
 def sha(a):
     return hashlib.sha256(np.ascontiguousarray(a, dtype=np.float64).tobytes()).hexdigest()
 
@@ -56,8 +75,6 @@ def case_params(isa, rule):
 def compute(case):
     """One case's record by the package that is importable now."""
     import iterative_solvers_amd as isa
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    from test_mg_batch_cpu import batch_rhs
     name, N, kind, rule, rows = case
     s = isa.MatrixFreeSystem(N, N, *DOM)
     s.set_preconditioner(isa.PRECOND_MG if kind == "mg" else isa.PRECOND_MG_ANY)
