@@ -47,6 +47,7 @@
  *   mi355cg_time_steps_many_workspace   the device workspace bytes of such an ensemble (pure host arithmetic, no GPU needed)
  *   mi355cg_wave_steps_many / _device   an ensemble of small wave-equation steppers u_tt = A u - g: velocity Verlet or Newmark
  *   mi355cg_wave_steps_many_workspace / mi355cg_wave_cfl   its workspace bytes; the explicit scheme's bound on tau (host arithmetic)
+ *   mi355cg_wave_record_many / _device / _workspace   the explicit scheme with a source time function and receiver traces
  *
  * Plain pointers and sizes only; no C++/torch types.  All host vectors are in the reference's
  * PACKED unknown order (bottom-right block row-major, then the upper block row-major;
@@ -576,6 +577,38 @@ int  mi355cg_wave_steps_many_device(mi355cg_handle h, const mi355cg_params *para
                                     const volatile int *stop_flag, mi355cg_results *out, int *steps_done, int *step_iterations);
 int  mi355cg_wave_steps_many_workspace(int n, int nsys, int nsteps, int scheme, int with_step_iterations, long long *bytes);
 int  mi355cg_wave_cfl(mi355cg_handle h, double *tau_max);
+
+/* The explicit scheme with a source time function and receiver traces: mi355cg_wave_steps_many with
+ * MI355CG_WAVE_VERLET, its forcing scaled in time and u sampled at a few nodes inside the launch.  tau, g, u, v, steps_per_launch,
+ * stop_flag, out and steps_done are that call's; params, scheme and step_iterations have no part in it.
+ * w: the amplitudes of the source, nsteps + 1 doubles per member, member s at w + s * w_stride; w_stride = 0: one row for all,
+ * otherwise at least nsteps + 1.  w_s[n] is the amplitude at local time n tau_s.  With h = 0.5 tau the step from n to n + 1 is
+ *    f = w[n] g;  a = au(u) - f;  vh = v + h a;  u = u + tau vh;  f = w[n + 1] g;  a = au(u) - f;  v = vh + h a,
+ * one rounding per operation; the second a of step n is the first of step n + 1.  w = 1 gives the bits of mi355cg_wave_steps_many.
+ * rec_nodes: nrec packed unknown indices in [0, mi355cg_size(h)), HOST memory in both entry points, shared by all members; nrec = 0:
+ * none, rec_nodes and traces are not read.  After local step n = 1 .. nsteps with n % record_every == 0, sample j = n /
+ * record_every - 1 is traces[(s * (nsteps / record_every) + j) * nrec + r] = u_s at receiver r after that step.
+ * A call of k * record_every steps with the amplitudes w + k0, ..., then a call from the returned state with the amplitudes from
+ * w + k0 + nsteps on give the bits of one long call, the traces one after the other; the cut into launches is as invisible.
+ * When stop_flag ends the call, steps_done is what ran, (u, v) the state at that step, and the samples of steps that did not run
+ * are left unwritten.
+ * MI355CG_ERR_INVALID, before anything is allocated or written: everything mi355cg_wave_steps_many refuses of a Verlet call, a null
+ * w, a w_stride that is neither 0 nor >= nsteps + 1, nrec outside 0 .. MI355CG_WAVE_MAX_RECEIVERS, record_every < 1, nrec > 0 with
+ * a null rec_nodes or traces, a receiver outside [0, size), w or traces overlapping u, v, g or each other, and (host entry
+ * point: the table can be read) an amplitude that is not finite.
+ * _device: g_dev, u_dev, v_dev, w_dev and traces_dev are in device memory of the handle's GPU, everything else in host memory.
+ * Workspace: that of the Verlet call and the image cells of MI355CG_WAVE_MAX_RECEIVERS receivers (ints); the host entry point
+ * stages the tables and the traces on top of g, u and v.  It is the handle's batch workspace, freed by mi355cg_batch_release and
+ * mi355cg_destroy.  mi355cg_wave_record_many_workspace: that many bytes, pure host arithmetic.                               */
+#define MI355CG_WAVE_MAX_RECEIVERS 64
+int  mi355cg_wave_record_many(mi355cg_handle h, int nsys, int nsteps, const double *tau, const double *g, double *u, double *v,
+                              const double *w, long long w_stride, int nrec, const int *rec_nodes, int record_every, double *traces,
+                              int steps_per_launch, const volatile int *stop_flag, mi355cg_results *out, int *steps_done);
+int  mi355cg_wave_record_many_device(mi355cg_handle h, int nsys, int nsteps, const double *tau, const double *g_dev, double *u_dev,
+                                     double *v_dev, const double *w_dev, long long w_stride, int nrec, const int *rec_nodes,
+                                     int record_every, double *traces_dev, int steps_per_launch, const volatile int *stop_flag,
+                                     mi355cg_results *out, int *steps_done);
+int  mi355cg_wave_record_many_workspace(int n, int nsys, int nsteps, int nrec, int record_every, long long *bytes);
 
 /* ---- multi-GPU: one context per rank, one contiguous slab of grid rows per context --------------
  * The reference is single-process (no collectives exist in it); this is the scaling

@@ -41,6 +41,7 @@ EXPORTS = [
     "mi355cg_solve_many", "mi355cg_solve_many_from", "mi355cg_solve_many_device", "mi355cg_solve_many_device_from", "mi355cg_solve_many_info",
     "mi355cg_time_steps_many", "mi355cg_time_steps_many_device", "mi355cg_time_steps_many_workspace",
     "mi355cg_wave_steps_many", "mi355cg_wave_steps_many_device", "mi355cg_wave_steps_many_workspace", "mi355cg_wave_cfl",
+    "mi355cg_wave_record_many", "mi355cg_wave_record_many_device", "mi355cg_wave_record_many_workspace",
 ]
 WAVE_VERLET, WAVE_NEWMARK = 0, 1    # MI355CG_WAVE_VERLET, MI355CG_WAVE_NEWMARK
 DECOMP_ROWS, DECOMP_2D = 0, 1
@@ -51,6 +52,7 @@ SMOOTHER_JACOBI, SMOOTHER_LINE_X, SMOOTHER_LINE_Y, SMOOTHER_LINE_AUTO = 0, 1, 2,
 BATCH_MAX = 64          # MI355CG_BATCH_MAX
 MANY_MAX = 65536        # MI355CG_MANY_MAX
 STEPS_MANY_MAX_STEPS = 65536   # MI355CG_STEPS_MANY_MAX_STEPS
+WAVE_MAX_RECEIVERS = 64        # MI355CG_WAVE_MAX_RECEIVERS
 EIG_BLOCK_MAX = 16      # MI355CG_EIG_BLOCK_MAX
 EIG_BASIS_MAX = 48      # vectors of a Rayleigh-Ritz basis, and of a group of block_gram
 EIG_CONVERGED, EIG_ITERATIONS, EIG_INTERRUPTED, EIG_BREAKDOWN = range(4)
@@ -239,6 +241,12 @@ def load():
                            C.c_void_p, C.POINTER(Results), C.c_void_p, C.c_void_p]
         L.mi355cg_wave_steps_many_workspace.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, LLP]
         L.mi355cg_wave_cfl.argtypes = [H, DBP]
+    if hasattr(L, "mi355cg_wave_record_many"):  # absent from an older build loaded through MI355CG_LIB
+        # tau and rec_nodes (host), g, u, v, w and traces (host arrays / device memory for _device), the stop flag and steps_done as plain addresses
+        for fn in (L.mi355cg_wave_record_many, L.mi355cg_wave_record_many_device):
+            fn.argtypes = [H, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_int,
+                           C.c_void_p, C.c_int, C.c_void_p, C.POINTER(Results), C.c_void_p]
+        L.mi355cg_wave_record_many_workspace.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, LLP]
     if hasattr(L, "mi355cg_get_xfold"):         # absent from an older build loaded through MI355CG_LIB
         L.mi355cg_get_xfold.argtypes = [H, IP, IP]
     _lib = L

@@ -570,6 +570,57 @@ public:
         if (results) *results = std::move(res);
         if (steps_done) *steps_done = std::move(done);
     }
+    // Extension: waveStepsMany with MI355CG_WAVE_VERLET, a source time function and receiver traces (mi355cg_wave_record_many).
+    // source: one row of nsteps + 1 amplitudes for all members, or one row per member; member s feels source[s][n] * g[s] at its
+    // local time n tau[s].  receivers: at most MI355CG_WAVE_MAX_RECEIVERS packed indices; traces[s][j][r] is u of member s at
+    // receiver r after step (j + 1) * record_every, nsteps / record_every samples (empty without receivers).  (u, v) are updated
+    // in place; an empty g means this system's right-hand side for every member.  std::invalid_argument for vectors of the
+    // wrong count or size and what the library refuses as invalid; std::runtime_error on a system with a preconditioner.
+    void waveRecordMany(std::vector<std::vector<double>>& u, std::vector<std::vector<double>>& v, const std::vector<double>& tau, int nsteps,
+                        const std::vector<std::vector<double>>& source, const std::vector<int>& receivers, int record_every,
+                        std::vector<std::vector<std::vector<double>>>* traces, std::vector<mi355cg_results>* results = nullptr,
+                        std::vector<int>* steps_done = nullptr, const std::vector<std::vector<double>>& g = {}, int steps_per_launch = 0) {
+        if (u.empty() || u.size() > (size_t)MI355CG_MANY_MAX) throw std::invalid_argument("waveRecordMany: an ensemble has 1 .. MI355CG_MANY_MAX members");
+        const size_t n = rhs.size(), k = u.size();
+        if (v.size() != k) throw std::invalid_argument("waveRecordMany: v does not have one vector per member");
+        if (tau.size() != k) throw std::invalid_argument("waveRecordMany: tau does not have one entry per member");
+        if (!g.empty() && g.size() != k) throw std::invalid_argument("waveRecordMany: g does not have one vector per member");
+        if (nsteps < 0 || nsteps > MI355CG_STEPS_MANY_MAX_STEPS) throw std::invalid_argument("waveRecordMany: nsteps is 0 .. MI355CG_STEPS_MANY_MAX_STEPS");
+        if (source.size() != 1 && source.size() != k) throw std::invalid_argument("waveRecordMany: source has one row, or one row per member");
+        if (record_every < 1) throw std::invalid_argument("waveRecordMany: record_every is at least 1");
+        if (receivers.size() > (size_t)MI355CG_WAVE_MAX_RECEIVERS) throw std::invalid_argument("waveRecordMany: at most MI355CG_WAVE_MAX_RECEIVERS receivers");
+        const size_t row = (size_t)nsteps + 1, nrec = receivers.size(), samples = (size_t)(nsteps / record_every);
+        std::vector<double> gp(g.empty() ? 0 : n * k), up(n * k), vp(n * k), wp(source.size() * row), tp(k * samples * nrec);
+        for (size_t s = 0; s < k; ++s) {
+            if (u[s].size() != n || v[s].size() != n || (!g.empty() && g[s].size() != n)) throw std::invalid_argument("waveRecordMany: vector size does not match the system");
+            std::copy(u[s].begin(), u[s].end(), up.begin() + (std::ptrdiff_t)(s * n));
+            std::copy(v[s].begin(), v[s].end(), vp.begin() + (std::ptrdiff_t)(s * n));
+            if (!g.empty()) std::copy(g[s].begin(), g[s].end(), gp.begin() + (std::ptrdiff_t)(s * n));
+        }
+        for (size_t s = 0; s < source.size(); ++s) {
+            if (source[s].size() != row) throw std::invalid_argument("waveRecordMany: a row of the source has nsteps + 1 amplitudes");
+            std::copy(source[s].begin(), source[s].end(), wp.begin() + (std::ptrdiff_t)(s * row));
+        }
+        std::vector<mi355cg_results> res(k);
+        std::vector<int> done(k, 0);
+        mi355cg_compat::check(mi355cg_wave_record_many(ctx_->h, (int)k, nsteps, tau.data(), g.empty() ? nullptr : gp.data(), up.data(), vp.data(), wp.data(),
+                                                       source.size() == 1 ? 0 : (long long)row, (int)nrec, nrec ? receivers.data() : nullptr, record_every,
+                                                       nrec ? tp.data() : nullptr, steps_per_launch, nullptr, res.data(), done.data()));
+        for (size_t s = 0; s < k; ++s) {
+            u[s].assign(up.begin() + (std::ptrdiff_t)(s * n), up.begin() + (std::ptrdiff_t)((s + 1) * n));
+            v[s].assign(vp.begin() + (std::ptrdiff_t)(s * n), vp.begin() + (std::ptrdiff_t)((s + 1) * n));
+        }
+        if (traces) {
+            traces->assign(nrec ? k : 0, std::vector<std::vector<double>>(samples));
+            for (size_t s = 0; s < traces->size(); ++s)
+                for (size_t j = 0; j < samples; ++j) {
+                    const std::ptrdiff_t at = (std::ptrdiff_t)((s * samples + j) * nrec);
+                    (*traces)[s][j].assign(tp.begin() + at, tp.begin() + at + (std::ptrdiff_t)nrec);
+                }
+        }
+        if (results) *results = std::move(res);
+        if (steps_done) *steps_done = std::move(done);
+    }
     // the largest time step MI355CG_WAVE_VERLET takes on this grid (mi355cg_wave_cfl)
     double waveCfl() const { double t = 0.0; mi355cg_compat::check(mi355cg_wave_cfl(ctx_->h, &t)); return t; }
     void batchRelease() { mi355cg_compat::check(mi355cg_batch_release(ctx_->h)); }

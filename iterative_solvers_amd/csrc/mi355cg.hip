@@ -185,6 +185,11 @@ struct OnchipManyWs {
     int wave_cap = 0;                   // members the next two hold
     Buf<double> wave_tau;               // tau_s of every member, then 2 / tau_s
     Buf<double> wave_tau_h;             // pinned copy
+    // mi355cg_wave_record_many* on top (onchip_wave_record_workspace_bytes), allocated by the first such call
+    Buf<int> rec_cell;                  // the image cells of kOnchipWaveMaxRec receivers
+    Buf<int> rec_cell_h;                // pinned copy
+    Buf<double> rec_stage;              // the host entry point: the amplitude tables, then the traces
+    long long rec_stage_cap = 0;        // doubles it holds
 };
 
 // `small` and its pinned mirror in a call of nsys <= cap systems: nsys x FB_COUNT update partials, then nsys diagonals, then nsys ||r0||_2
@@ -3415,7 +3420,7 @@ int mi355cg_time_steps_many_workspace(int n, int nsys, int nsteps, int with_step
 }
 
 // ---- ensemble wave-equation steps on chip: velocity Verlet and Newmark ---------------------------------------
-static_assert(MI355CG_WAVE_VERLET == kWaveVerlet && MI355CG_WAVE_NEWMARK == kWaveNewmark, "onchip_plan.h: the schemes");
+static_assert(MI355CG_WAVE_VERLET == kWaveVerlet && MI355CG_WAVE_NEWMARK == kWaveNewmark && MI355CG_WAVE_MAX_RECEIVERS == kOnchipWaveMaxRec, "onchip_plan.h: the schemes, the receivers");
 // what both entry points refuse before anything is allocated or written (tau is in host memory for both)
 static int wave_check(mi355cg_ctx* c, const mi355cg_params* prm, int nsys, int nsteps, int scheme, const double* tau, const void* g, const void* u,
                       const void* v, int steps_per_launch, const mi355cg_results* out, const int* steps_done, const int* step_iterations) {
@@ -3466,9 +3471,14 @@ static int wave_upload(mi355cg_ctx* c, OnchipManyWs* W, int nsys, const double* 
     return g_dev ? MI355CG_OK : g_one_pack(c);
 }
 
+// What mi355cg_wave_record_many* adds to an explicit call: w and traces in device memory, nodes (the packed
+// indices of the receivers) in host memory; w_stride 0: one row of amplitudes for all members.
+struct WaveRecord { const double* w; long long w_stride; int nrec; const int* nodes; int every; double* traces; };
+
 // Explicit: ceil(nsteps / m) launches of m steps; before each the host waits for the one before it and tests the caller's flag.
+// rec: with a source and receivers; every launch is told where in the call it starts.
 static int wave_verlet(mi355cg_ctx* c, int nsys, int nsteps, const double* tau, const double* g_dev, double* u_dev, double* v_dev,
-                       int steps_per_launch, const volatile int* stop_flag, mi355cg_results* out, int* steps_done) {
+                       int steps_per_launch, const volatile int* stop_flag, mi355cg_results* out, int* steps_done, const WaveRecord* rec = nullptr) {
     mi355cg_params none;                                           // the driver reads a rule; the scheme decides nothing
     mi355cg_default_params(&none, MI355CG_RULE_REL_2NORM);
     OnchipManyRun R;
@@ -3479,16 +3489,25 @@ static int wave_verlet(mi355cg_ctx* c, int nsys, int nsteps, const double* tau, 
     a.pl = R.pl; a.k = OnchipWaveCoef{c->gp.A, c->gp.x_k, c->gp.y_k};
     a.tau = W->wave_tau; a.g = g_dev ? g_dev : W->g_one.get(); a.g_stride = g_dev ? R.U : 0;
     a.u = u_dev; a.v = v_dev; a.stride = R.U;
-    const void* k_steps = onchip_dispatch(R.pl.elems, false, [](auto el, auto) { return (const void*)&k_onchip_wave_verlet<decltype(el)::value>; });
+    OnchipWaveRecArgs x{};
+    if (rec) {
+        for (int r = 0; r < rec->nrec; ++r) { int xx, yy; onchip_node(R.pl, rec->nodes[r], &xx, &yy); W->rec_cell_h[r] = onchip_cell(R.pl, xx, yy); }
+        if (rec->nrec) HIPCK(hipMemcpyAsync(W->rec_cell, W->rec_cell_h, sizeof(int) * rec->nrec, hipMemcpyHostToDevice, c->stream));
+        x.w = rec->w; x.w_stride = rec->w_stride; x.rec_cell = W->rec_cell; x.nrec = rec->nrec; x.every = rec->every;
+        x.traces = rec->traces; x.tr_stride = (long long)(nsteps / rec->every) * rec->nrec;
+    }
+    const void* k_steps = rec ? onchip_dispatch(R.pl.elems, false, [](auto el, auto) { return (const void*)&k_oc_wave_record<decltype(el)::value>; })
+                              : onchip_dispatch(R.pl.elems, false, [](auto el, auto) { return (const void*)&k_onchip_wave_verlet<decltype(el)::value>; });
     if (int rc = R.allow_lds(k_steps)) return rc;
     if (int rc = loop_timer_begin(c, c->stream)) return rc;
     const int m = steps_per_launch > 0 ? steps_per_launch : kOnchipWaveDefaultSteps;
-    void* args[] = {&a};
+    void* args[] = {&a, &x};                                       // (the plain kernel takes the first alone)
     int done = 0;
     while (done < nsteps) {
         if (done > 0) HIPCK(hipStreamSynchronize(c->stream));
         if (stop_flag && *stop_flag) { R.interrupted = true; break; }
         a.m = std::min(m, nsteps - done);
+        if (rec) { x.step0 = done; x.phase = done % rec->every; x.slot = done / rec->every; }
         if (int rc = R.launch(k_steps, args)) return rc;
         done += a.m;
     }
@@ -3562,6 +3581,109 @@ int mi355cg_wave_steps_many_workspace(int n, int nsys, int nsteps, int scheme, i
     if (v == 0)
         return fail(MI355CG_ERR_INVALID, "wave ensemble rejected: even n from 6 to %d, 1 .. %d members, 0 .. %d steps, scheme 0 or 1, at most %lld iteration counts",
                     kOnchipMaxN, kOnchipStepsMaxSys, kOnchipStepsMaxSteps, kOnchipStepsMaxCounts);
+    *bytes = v;
+    return MI355CG_OK;
+}
+// ---- the explicit scheme with a source time function and receiver traces -----------------------------------
+static bool ranges_meet(const void* a, size_t abytes, const void* b, size_t bbytes) {
+    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+    return a && b && abytes && bbytes && pb < pa + abytes && pa < pb + bbytes;
+}
+// What both entry points refuse before anything is allocated or written: what mi355cg_wave_steps_many refuses of a Verlet call
+// (wave_check itself), then what the table, the receivers and the traces add.  host_tables: w can be read here.
+static int wave_record_check(mi355cg_ctx* c, int nsys, int nsteps, const double* tau, const void* g, const void* u, const void* v, const double* w,
+                             long long w_stride, int nrec, const int* rec_nodes, int record_every, const void* traces, int steps_per_launch,
+                             const mi355cg_results* out, const int* steps_done, bool host_tables) {
+    if (int rc = wave_check(c, nullptr, nsys, nsteps, MI355CG_WAVE_VERLET, tau, g, u, v, steps_per_launch, out, steps_done, nullptr)) return rc;
+    if (!w) return fail(MI355CG_ERR_INVALID, "null argument: w, the amplitudes of the source");
+    if (w_stride != 0 && w_stride < (long long)nsteps + 1)
+        return fail(MI355CG_ERR_INVALID, "w_stride %lld rejected: 0 (one row for all members) or at least nsteps + 1 = %d", w_stride, nsteps + 1);
+    if (nrec < 0 || nrec > MI355CG_WAVE_MAX_RECEIVERS) return fail(MI355CG_ERR_INVALID, "nrec %d rejected: a call records 0 .. %d receivers", nrec, MI355CG_WAVE_MAX_RECEIVERS);
+    if (record_every < 1) return fail(MI355CG_ERR_INVALID, "record_every %d rejected: it must be >= 1", record_every);
+    if (nrec > 0 && (!rec_nodes || !traces)) return fail(MI355CG_ERR_INVALID, "null argument: %d receivers need rec_nodes and traces", nrec);
+    for (int r = 0; r < nrec; ++r)
+        if (rec_nodes[r] < 0 || rec_nodes[r] >= c->pk_len)
+            return fail(MI355CG_ERR_INVALID, "receiver %d is unknown %d: outside [0, %lld)", r, rec_nodes[r], c->pk_len);
+    const size_t state = sizeof(double) * (size_t)c->gp.size * (size_t)nsys;
+    const size_t wbytes = sizeof(double) * ((size_t)(nsys - 1) * (size_t)w_stride + (size_t)nsteps + 1);
+    const size_t tbytes = nrec > 0 ? sizeof(double) * (size_t)nsys * (size_t)(nsteps / record_every) * (size_t)nrec : 0;
+    const struct { const void* p; const char* name; } vecs[3] = {{u, "u"}, {v, "v"}, {g, "g"}};
+    for (const auto& q : vecs) {
+        if (ranges_meet(w, wbytes, q.p, state)) return fail(MI355CG_ERR_INVALID, "w overlaps %s", q.name);
+        if (ranges_meet(traces, tbytes, q.p, state)) return fail(MI355CG_ERR_INVALID, "traces overlaps %s", q.name);
+    }
+    if (ranges_meet(traces, tbytes, w, wbytes)) return fail(MI355CG_ERR_INVALID, "traces overlaps w");
+    if (host_tables)
+        for (int s = 0; s < (w_stride ? nsys : 1); ++s)
+            for (int n = 0; n <= nsteps; ++n)
+                if (!std::isfinite(w[(long long)s * w_stride + n]))
+                    return fail(MI355CG_ERR_INVALID, "amplitude %g of member %d at step %d rejected: the source must be finite", w[(long long)s * w_stride + n], s, n);
+    return MI355CG_OK;
+}
+
+// The Verlet workspace, then the receiver cells and (stage_doubles > 0: the host entry point) the staging of the tables and the
+// traces on top: built complete before they replace what is there.
+static int onchip_wave_record_ensure(mi355cg_ctx* c, int nsys, int stage_vecs, long long stage_doubles) {
+    if (int rc = onchip_wave_ensure(c, nsys, MI355CG_WAVE_VERLET, 0, stage_vecs)) return rc;
+    OnchipManyWs* W = c->many.get();
+    auto failed = [&](const char* what) { return fail(MI355CG_ERR_HIP, "on-chip wave recording workspace for %d members: %s allocation failed", nsys, what); };
+    if (!W->rec_cell) {
+        Buf<int> cell, cell_h;
+        if (Buf<int>::device(cell, kOnchipWaveMaxRec)) return failed("receiver");
+        if (Buf<int>::pinned(cell_h, kOnchipWaveMaxRec)) return failed("pinned copy");
+        W->rec_cell = std::move(cell); W->rec_cell_h = std::move(cell_h);
+    }
+    if (stage_doubles > W->rec_stage_cap) {
+        Buf<double> stage;
+        if (Buf<double>::device(stage, stage_doubles)) return failed("staging");
+        HIPCK(hipStreamSynchronize(c->stream));                    // nothing in flight reads the buffer that is replaced
+        W->rec_stage = std::move(stage);
+        W->rec_stage_cap = stage_doubles;
+    }
+    return MI355CG_OK;
+}
+
+int mi355cg_wave_record_many_device(mi355cg_handle c, int nsys, int nsteps, const double* tau, const double* g_dev, double* u_dev, double* v_dev,
+                                    const double* w_dev, long long w_stride, int nrec, const int* rec_nodes, int record_every, double* traces_dev,
+                                    int steps_per_launch, const volatile int* stop_flag, mi355cg_results* out, int* steps_done) {
+    if (int rc = wave_record_check(c, nsys, nsteps, tau, g_dev, u_dev, v_dev, w_dev, w_stride, nrec, rec_nodes, record_every, traces_dev, steps_per_launch,
+                                   out, steps_done, false)) return rc;
+    if (StepChecks::none(nsys, nsteps, steps_done)) return MI355CG_OK;
+    HIPCK(hipSetDevice(c->device));
+    if (int rc = onchip_wave_record_ensure(c, nsys, 0, 0)) return rc;
+    const WaveRecord rec{w_dev, w_stride, nrec, rec_nodes, record_every, traces_dev};
+    return wave_verlet(c, nsys, nsteps, tau, g_dev, u_dev, v_dev, steps_per_launch, stop_flag, out, steps_done, &rec);
+}
+int mi355cg_wave_record_many(mi355cg_handle c, int nsys, int nsteps, const double* tau, const double* g, double* u, double* v, const double* w,
+                             long long w_stride, int nrec, const int* rec_nodes, int record_every, double* traces, int steps_per_launch,
+                             const volatile int* stop_flag, mi355cg_results* out, int* steps_done) {
+    if (int rc = wave_record_check(c, nsys, nsteps, tau, g, u, v, w, w_stride, nrec, rec_nodes, record_every, traces, steps_per_launch, out, steps_done, true)) return rc;
+    if (StepChecks::none(nsys, nsteps, steps_done)) return MI355CG_OK;
+    HIPCK(hipSetDevice(c->device));
+    const size_t row = (size_t)nsteps + 1, rows = w_stride ? (size_t)nsys : 1;             // the tables go up packed: row doubles per row
+    const size_t sample = (size_t)nrec, samples = (size_t)(nsteps / record_every);          // a member's traces: samples x sample doubles
+    if (int rc = onchip_wave_record_ensure(c, nsys, 3, (long long)(rows * row + (size_t)nsys * samples * sample))) return rc;
+    const size_t count = (size_t)c->pk_len * (size_t)nsys;         // g, then u, then v; the state comes down
+    double* const g_dev = c->many->stage; double* const u_dev = g_dev + count; double* const v_dev = u_dev + count;
+    double* const w_dev = c->many->rec_stage; double* const traces_dev = w_dev + rows * row;
+    const StagedGroup groups[3] = {{0, g, nullptr}, {count, u, u}, {2 * count, v, v}};
+    return run_staged_groups(c, g_dev, count, groups, [&]() {
+        HIPCK(hipMemcpy2DAsync(w_dev, sizeof(double) * row, w, sizeof(double) * (w_stride ? (size_t)w_stride : row), sizeof(double) * row, rows, hipMemcpyHostToDevice, c->stream));
+        const WaveRecord rec{w_dev, w_stride ? (long long)row : 0, nrec, rec_nodes, record_every, nrec ? traces_dev : nullptr};
+        if (int rc = wave_verlet(c, nsys, nsteps, tau, g ? g_dev : nullptr, u_dev, v_dev, steps_per_launch, stop_flag, out, steps_done, &rec)) return rc;
+        // the samples of the steps that ran come down; the others stay as the caller left them
+        const size_t ran = (size_t)(steps_done[0] / record_every) * sample;
+        if (ran) HIPCK(hipMemcpy2DAsync(traces, sizeof(double) * samples * sample, traces_dev, sizeof(double) * samples * sample, sizeof(double) * ran, (size_t)nsys,
+                                        hipMemcpyDeviceToHost, c->stream));
+        return (int)MI355CG_OK;
+    });
+}
+int mi355cg_wave_record_many_workspace(int n, int nsys, int nsteps, int nrec, int record_every, long long* bytes) {
+    if (!bytes) return fail(MI355CG_ERR_INVALID, "null argument");
+    const long long v = onchip_wave_record_workspace_bytes(n, nsys, nsteps, nrec, record_every);
+    if (v == 0)
+        return fail(MI355CG_ERR_INVALID, "recorded wave ensemble rejected: even n from 6 to %d, 1 .. %d members, 0 .. %d steps, 0 .. %d receivers, record_every >= 1",
+                    kOnchipMaxN, kOnchipStepsMaxSys, kOnchipStepsMaxSteps, kOnchipWaveMaxRec);
     *bytes = v;
     return MI355CG_OK;
 }

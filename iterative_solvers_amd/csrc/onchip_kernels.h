@@ -686,6 +686,106 @@ __global__ __launch_bounds__(kOnchipMaxThreads) void k_onchip_wave_verlet(const 
     }
 }
 
+// With a source time function and receivers (mi355cg_wave_record_many*): the forcing of the call's step n is
+// w[n] g with the member's amplitude table w, and after every `every`-th step u at nrec nodes goes to the traces.  The step is
+// k_onchip_wave_verlet's, still between two barriers, in a kernel of its own: that one stays the code it is (its body moved
+// into a function both kernels share is optimized before it meets its launch bounds, and E = 16 comes out another kernel).
+//   * The amplitudes reach a step through LDS.  Two blocks of 64 doubles at the head of the side data (the kernel uses the image
+//     alone): lane t of wave 0 holds w at the end of the launch's step 64 b + t in block b % 2.  Block 0 is written before the
+//     loop; the load of block b + 1 is issued in step 64 b into a register and stored in step 64 b + 32, both behind barrier 2.
+//     So the global latency has 32 steps to pass, the block that is overwritten was last read in step 64 b - 1, and the first
+//     step that reads the new one lies 32 steps and their barriers ahead.
+//   * Thread r < nrec keeps the image cell of receiver r.  Behind barrier 2 the new image is complete and no owner writes before
+//     the next barrier 1: in that window it reads its cell and stores it, an ordinary vector store nobody waits for.
+// step0, the steps of the call before this launch, places the launch in the table; phase and slot are step0 % every and
+// step0 / every, so that the cadence and the sample a step writes do not depend on how the host cuts the call into launches.
+// The acceleration at the entry of a launch is formed from (u, g, w[step0]): the expression that left it at the end of step0.
+struct OnchipWaveRecArgs {
+    const double* w; long long w_stride;             // amplitudes: member s reads w + s * w_stride (0: one row for all), nsteps + 1 each
+    int step0;
+    const int* rec_cell; int nrec;                   // image cells of the receivers, nrec <= kOnchipWaveMaxRec
+    int every, phase, slot;
+    double* traces; long long tr_stride;             // member s writes traces + s * tr_stride: its samples, nrec doubles each
+};
+constexpr int kOcAmpBlock = 64;                      // amplitudes per block: one per lane of wave 0
+static_assert(2 * kOcAmpBlock * 8 <= kOnchipSideBytes && kOcAmpBlock <= kWave && kOnchipWaveMaxRec <= kWave, "the amplitude blocks fit in the side data; wave 0 fills them and holds the receivers");
+template <int E>
+__global__ __launch_bounds__(kOnchipMaxThreads) void k_oc_wave_record(const OnchipWaveArgs a, const OnchipWaveRecArgs x) {
+    const OnchipPlan& pl = a.pl;
+    extern __shared__ __attribute__((aligned(16))) char oc_dyn_lds[];
+    double* const wbuf = reinterpret_cast<double*>(oc_dyn_lds);
+    double* const img = OcMany::lds(pl.cells).img;
+    const int t = threadIdx.x, T = blockDim.x, pitch = pl.pitch;
+    const long long sys = blockIdx.x;
+    const double tau = a.tau[sys], h = 0.5 * tau;
+    const double* const gin = a.g + sys * a.g_stride;
+    double* const uio = a.u + sys * a.stride; double* const vio = a.v + sys * a.stride;
+    const double* const wrow = x.w + sys * x.w_stride + x.step0;   // wrow[s]: at the start of the launch's step s, wrow[s + 1]: at its end
+    double* trow = x.traces + sys * x.tr_stride + (long long)x.slot * x.nrec;
+
+    for (int i = t; i < pl.cells; i += T) img[i] = 0.0;
+    __syncthreads();                                               // the image is zero everywhere before the owners fill their cells
+    unsigned cell2[(E + 1) / 2] = {};
+    double v[E], acc[E], g[E];
+    int cnt = 0;
+#pragma unroll
+    for (int k = 0; k < E; ++k) {
+        const int i = onchip_owned(pl, t, k);
+        if (i >= 0) {                                              // (slots beyond cnt are never read: nothing to initialise)
+            int xx, yy;
+            onchip_node(pl, i, &xx, &yy);
+            const int c = onchip_cell(pl, xx, yy);
+            cell2[k / 2] |= (unsigned)c << (16 * (k & 1));
+            img[c] = uio[i]; v[k] = vio[i]; g[k] = gin[i];
+            cnt = k + 1;
+        }
+    }
+    if (t < kOcAmpBlock && t < a.m) wbuf[t] = wrow[t + 1];
+    int rcell = 0, phase = x.phase;
+    if (t < x.nrec) rcell = x.rec_cell[t];
+    double w_now = wrow[0], w_next = 0.0;
+    __syncthreads();
+    auto own_cell = [&](int k) { unsigned c2 = cell2[k / 2]; asm volatile("" : "+v"(c2)); return (int)((c2 >> (16 * (k & 1))) & 0xffffu); };
+    auto accel_at = [&](int c, double f) { return onchip_wave_accel(a.k, f, img[c], img[c - 1], img[c + 1], img[c - pitch], img[c + pitch]); };
+#pragma unroll
+    for (int k = 0; k < E; ++k) if (k < cnt) { acc[k] = accel_at(own_cell(k), onchip_wave_forcing(w_now, g[k])); __builtin_amdgcn_sched_barrier(0); }
+
+    for (int s = 0; s < a.m; ++s) {
+        __syncthreads();                                           // barrier 1: every neighbour has read the old cells
+        w_now = wbuf[((s / kOcAmpBlock) & 1) * kOcAmpBlock + s % kOcAmpBlock];        // the amplitude at the END of this step
+#pragma unroll
+        for (int k = 0; k < E; ++k) if (k < cnt) {
+            const int c = own_cell(k);
+            v[k] = onchip_wave_kick(v[k], h, acc[k]);              // vh
+            img[c] = onchip_wave_drift(img[c], tau, v[k]);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        __syncthreads();                                           // barrier 2: the new image is complete
+#pragma unroll
+        for (int k = 0; k < E; ++k) if (k < cnt) {
+            acc[k] = accel_at(own_cell(k), onchip_wave_forcing(w_now, g[k]));
+            v[k] = onchip_wave_kick(v[k], h, acc[k]);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        if (++phase == x.every) {                                  // uniform: this step is sampled
+            phase = 0;
+            if (t < x.nrec) trow[t] = img[rcell];
+            trow += x.nrec;
+        }
+        const int q = s % kOcAmpBlock, nb = s - q + kOcAmpBlock + t;                  // this lane's step in the next block
+        if (t < kOcAmpBlock && nb < a.m) {
+            if (q == 0) w_next = wrow[nb + 1];
+            if (q == kOcAmpBlock / 2) wbuf[((nb / kOcAmpBlock) & 1) * kOcAmpBlock + t] = w_next;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < E; ++k) if (k < cnt) {
+        int i = k * T + t;
+        asm volatile("" : "+v"(i));                                // recomputed here, not carried through the loop
+        uio[i] = img[own_cell(k)]; vio[i] = v[k];
+    }
+}
+
 // Implicit: average-acceleration Newmark.  oc_step_loop with another right-hand side and a velocity: a step is the warm-started
 // solve of (A - sigma_s I) x = b_wave(u, v), sigma_s = 4 / tau_s^2, and the transition after a CONVERGED step updates the member's
 // state in the caller's vectors -- v = hv (x - u) - v, u = x, with u the state the step started from -- before the next step

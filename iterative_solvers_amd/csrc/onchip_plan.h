@@ -182,6 +182,9 @@ MI355CG_HD inline double onchip_wave_au(const OnchipWaveCoef& k, double uc, doub
 MI355CG_HD inline double onchip_wave_accel(const OnchipWaveCoef& k, double g, double uc, double left, double right, double down, double up) {
     return onchip_wave_au(k, uc, left, right, down, up) - g;
 }
+// A source time function (mi355cg_wave_record_many): the forcing at the time of amplitude w is w g, rounded
+// once, and takes g's place in onchip_wave_accel.  1.0 * g == g: an amplitude of one is the constant forcing, bit for bit.
+MI355CG_HD inline double onchip_wave_forcing(double w, double g) { return w * g; }
 MI355CG_HD inline double onchip_wave_kick(double v, double h, double a) { return v + h * a; }            // both half kicks
 MI355CG_HD inline double onchip_wave_drift(double u, double tau, double vh) { return u + tau * vh; }
 MI355CG_HD inline double onchip_newmark_rhs(const OnchipWaveCoef& k, double sigma, double tau, double g, double v, double uc, double left,
@@ -206,6 +209,16 @@ MI355CG_HD inline long long onchip_wave_workspace_bytes(int n, int nsys, int nst
     if (steps == 0) return 0;
     if (scheme == kWaveNewmark) return steps + (long long)nsys * kOnchipWaveSysBytes;
     return onchip_many_workspace_bytes(n, nsys) + (long long)nsys * kOnchipWaveSysBytes + 8LL * onchip_plan(n).unknowns;
+}
+// With a source and receivers (mi355cg_wave_record_many*): the Verlet workspace and the image cells of kOnchipWaveMaxRec receivers
+// (ints).  The amplitude tables and the traces live in the caller's memory.  (The host entry point stages them on top of g, u and
+// v: the tables, nsteps + 1 doubles per row, and nsys x (nsteps / record_every) x nrec doubles of traces.)  0: refused -- what the
+// Verlet workspace refuses, nrec outside 0 .. kOnchipWaveMaxRec, record_every < 1.
+constexpr int kOnchipWaveMaxRec = 64;
+MI355CG_HD inline long long onchip_wave_record_workspace_bytes(int n, int nsys, int nsteps, int nrec, int record_every) {
+    if (nrec < 0 || nrec > kOnchipWaveMaxRec || record_every < 1) return 0;
+    const long long verlet = onchip_wave_workspace_bytes(n, nsys, nsteps, kWaveVerlet, 0);
+    return verlet == 0 ? 0 : verlet + 4LL * kOnchipWaveMaxRec;
 }
 // Steps of one explicit launch when the caller does not say: the host tests the stop flag between two launches, so the longest
 // launch is the latency of a stop request, to stay under 10 ms.  Measured on one MI355X at N = 128, a launch of 1024 steps: 3.7 ms

@@ -462,6 +462,63 @@ class _Handle:
         self._check_rc(rc)
         return (u, v, list(res), steps_done) + ((step_it,) if step_iterations else ())
 
+    def wave_record_many(self, u0, v0, tau, nsteps: int, source, g=None, receivers=None, record_every: int = 1, steps_per_launch: int = 0,
+                         stop_flag: Optional[C.c_int] = None, traces=None):
+        """Extension (no reference twin): wave_steps_many with WAVE_VERLET, a source time function and receiver traces
+        (mi355cg_wave_record_many).  source: the amplitudes, [nsteps + 1] (one row for all members) or [nsys, nsteps + 1], of u0's
+        kind; the forcing of member s at its local time n tau[s] is source[s][n] * g[s].  receivers: a sequence of at most
+        WAVE_MAX_RECEIVERS packed indices, or None; record_every: the cadence.  Returns (u, v, traces, [Results per member],
+        steps_done): traces [nsys, nsteps // record_every, len(receivers)] of u0's kind, u at the receivers after every
+        record_every-th step, None without receivers.  traces: an array of that shape to write into (a stop flag leaves the samples
+        of steps that did not run as they are).  u0, v0, g, tau, steps_per_launch and stop_flag as in wave_steps_many."""
+        nsys, on_device, sp = self._batched(u0, g, ("u0", "g", "forcings", "ensemble"), _capi.MANY_MAX, stop_flag)
+        if self._check_batch(v0, self.size, _capi.MANY_MAX) != (nsys, on_device) or (on_device and v0.device != u0.device):
+            raise ValueError(f"v0 has shape {tuple(v0.shape)}: the velocities are of the kind (NumPy / CUDA tensor), shape and device of u0, {tuple(u0.shape)}")
+        tau, nsteps, res, steps_done, _ = self._ensemble_steps(nsys, tau, nsteps, False)
+        record_every = int(record_every)
+        if record_every < 1:
+            raise ValueError(f"record_every {record_every} rejected: it must be >= 1")
+        nodes = np.ascontiguousarray(receivers if receivers is not None else [], dtype=np.int32)
+        if nodes.ndim != 1 or len(nodes) > _capi.WAVE_MAX_RECEIVERS:
+            raise ValueError(f"receivers has shape {nodes.shape}: a sequence of at most {_capi.WAVE_MAX_RECEIVERS} packed indices")
+        nrec = len(nodes)
+        if not on_device and hasattr(source, "data_ptr"):
+            raise ValueError("source is of the kind (NumPy / CUDA tensor) of u0")
+        shapes = ((nsteps + 1,), (nsys, nsteps + 1))
+        tshape = (nsys, nsteps // record_every, nrec)
+        if on_device:
+            import torch
+            for name, a, want in (("source", source, shapes), ("traces", traces, (tshape,))):
+                if a is not None and not (hasattr(a, "data_ptr") and a.is_cuda and a.device == u0.device and a.dtype == torch.float64
+                                          and tuple(a.shape) in want and a.is_contiguous()):
+                    raise ValueError(f"{name} beside CUDA states is a contiguous float64 tensor of shape {' or '.join(map(str, want))} on {u0.device}")
+            u, v = u0.clone(), v0.clone()
+            if nrec and traces is None:
+                traces = torch.zeros(tshape, dtype=torch.float64, device=u0.device)
+            torch.cuda.current_stream(u0.device).synchronize()
+            rc = self._lib.mi355cg_wave_record_many_device(
+                self._h, nsys, nsteps, tau.ctypes.data, g.data_ptr() if g is not None else None, u.data_ptr(), v.data_ptr(), source.data_ptr(),
+                nsteps + 1 if source.dim() == 2 else 0, nrec, nodes.ctypes.data if nrec else None, record_every, traces.data_ptr() if nrec else None,
+                int(steps_per_launch), sp, res, steps_done.ctypes.data)
+        else:
+            source = np.ascontiguousarray(source, dtype=np.float64)
+            if source.shape not in shapes:
+                raise ValueError(f"source has shape {source.shape}, expected {shapes[0]} or {shapes[1]}")
+            if traces is not None and not (isinstance(traces, np.ndarray) and traces.dtype == np.float64 and traces.shape == tshape and traces.flags.c_contiguous):
+                raise ValueError(f"traces is a contiguous float64 array of shape {tshape}")
+            u = np.array(u0, dtype=np.float64, order="C", copy=True)
+            v = np.array(v0, dtype=np.float64, order="C", copy=True)
+            if g is not None:
+                g = np.ascontiguousarray(g)
+            if nrec and traces is None:
+                traces = np.zeros(tshape)
+            rc = self._lib.mi355cg_wave_record_many(
+                self._h, nsys, nsteps, tau.ctypes.data, g.ctypes.data if g is not None else None, u.ctypes.data, v.ctypes.data, source.ctypes.data,
+                nsteps + 1 if source.ndim == 2 else 0, nrec, nodes.ctypes.data if nrec else None, record_every, traces.ctypes.data if nrec else None,
+                int(steps_per_launch), sp, res, steps_done.ctypes.data)
+        self._check_rc(rc)
+        return u, v, (traces if nrec else None), list(res), steps_done
+
     def wave_cfl(self) -> float:
         """The largest time step velocity Verlet takes on this grid, 2 / sqrt(2 |A_diag|) of the unshifted operator (mi355cg_wave_cfl)."""
         out = C.c_double()
@@ -640,6 +697,18 @@ def wave_steps_many_workspace(n: int, nsys: int, nsteps: int, scheme: int = _cap
     out = C.c_longlong()
     lib = _capi.load()
     rc = lib.mi355cg_wave_steps_many_workspace(int(n), int(nsys), int(nsteps), int(scheme), 1 if with_step_iterations else 0, C.byref(out))
+    if rc == _capi.ERR_INVALID:
+        raise ValueError(lib.mi355cg_last_error().decode())
+    _capi.check(rc)
+    return out.value
+
+
+def wave_record_many_workspace(n: int, nsys: int, nsteps: int, nrec: int = 0, record_every: int = 1) -> int:
+    """The device workspace bytes of MatrixFreeSystem.wave_record_many for nsys members, nsteps steps and nrec receivers on an n x n
+    grid (host arithmetic, no GPU; mi355cg_wave_record_many_workspace).  ValueError for what the call refuses."""
+    out = C.c_longlong()
+    lib = _capi.load()
+    rc = lib.mi355cg_wave_record_many_workspace(int(n), int(nsys), int(nsteps), int(nrec), int(record_every), C.byref(out))
     if rc == _capi.ERR_INVALID:
         raise ValueError(lib.mi355cg_last_error().decode())
     _capi.check(rc)
@@ -834,6 +903,36 @@ class MatrixFreeSystem:
             params.use_true_solution = 0
         return self._handle.wave_steps_many(params, u0, v0, tau, nsteps, scheme=scheme, g=g, steps_per_launch=steps_per_launch,
                                             stop_flag=stop_flag, step_iterations=step_iterations)
+
+    def wave_record_many(self, u0, v0, tau, nsteps: int, source, g=None, receivers=None, record_every: int = 1, steps_per_launch: int = 0,
+                         stop_flag: Optional[C.c_int] = None, traces=None):
+        """Extension (no reference twin): wave_steps_many with WAVE_VERLET, a source time function and receiver traces, all inside
+        the launch.  source: [nsteps + 1] (one row for all members) or [nsys, nsteps + 1] amplitudes of u0's kind; member s feels
+        the forcing source[s][n] * g[s] at its local time n tau[s], so a step from n to n + 1 uses source[n] in its first half
+        kick and source[n + 1] in its second (second order in tau for a smooth source); source = 1 gives the bits of
+        wave_steps_many.  receivers: at most WAVE_MAX_RECEIVERS packed indices (packed_index) shared by all members, None = no
+        traces.  Returns (u, v, traces, results, steps_done) with traces [nsys, nsteps // record_every, len(receivers)] of u0's
+        kind -- sample j is u at the receivers after step (j + 1) * record_every -- or None without receivers.  A call of k *
+        record_every steps followed by a call from its state with the next slice of the source gives the bits of one long call.
+        traces: an array of that shape to write into; a stop flag leaves the samples of steps that did not run untouched.  u0,
+        v0, tau, g, steps_per_launch and stop_flag as in wave_steps_many; this system is left as it was."""
+        return self._handle.wave_record_many(u0, v0, tau, nsteps, source, g=g, receivers=receivers, record_every=record_every,
+                                             steps_per_launch=steps_per_launch, stop_flag=stop_flag, traces=traces)
+
+    def packed_index(self, ix: int, iy: int) -> int:
+        """The packed index of grid node (ix, iy), 0 <= ix, iy <= n, in the order of the batch and ensemble calls (solve_many,
+        wave_record_many's receivers): row by row, x fastest, first the rows 1 .. n/2 of the bottom-right block (columns n/2 + 1
+        .. n - 1), then the rows n/2 + 1 .. n - 1 of the upper block (columns 1 .. n - 1).  -1: the node is not an unknown (a
+        boundary node, or in the cut-out quadrant).  ValueError on a grid that is not square with an even n."""
+        n = self.n
+        if self.m != n or n % 2 or n < 4:
+            raise ValueError(f"packed_index is defined on square grids with an even n, not {self.m} x {n}")
+        half, ix, iy = n // 2, int(ix), int(iy)
+        if 1 <= iy <= half and half + 1 <= ix <= n - 1:
+            return (iy - 1) * (half - 1) + (ix - half - 1)
+        if half + 1 <= iy <= n - 1 and 1 <= ix <= n - 1:
+            return half * (half - 1) + (iy - half - 1) * (n - 1) + (ix - 1)
+        return -1
 
     def wave_cfl(self) -> float:
         """The largest time step wave_steps_many takes with WAVE_VERLET on this grid: 2 / sqrt(2 |A_diag|), Gershgorin's bound."""
