@@ -48,6 +48,7 @@
  *   mi355cg_wave_steps_many / _device   an ensemble of small wave-equation steppers u_tt = A u - g: velocity Verlet or Newmark
  *   mi355cg_wave_steps_many_workspace / mi355cg_wave_cfl   its workspace bytes; the explicit scheme's bound on tau (host arithmetic)
  *   mi355cg_wave_record_many / _device / _workspace   the explicit scheme with a source time function and receiver traces
+ *   mi355cg_wave_medium_many / _device / _workspace / mi355cg_wave_medium_cfl   that scheme in a medium: a squared wave speed per unknown and member
  *
  * Plain pointers and sizes only; no C++/torch types.  All host vectors are in the reference's
  * PACKED unknown order (bottom-right block row-major, then the upper block row-major;
@@ -609,6 +610,37 @@ int  mi355cg_wave_record_many_device(mi355cg_handle h, int nsys, int nsteps, con
                                      int record_every, double *traces_dev, int steps_per_launch, const volatile int *stop_flag,
                                      mi355cg_results *out, int *steps_done);
 int  mi355cg_wave_record_many_workspace(int n, int nsys, int nsteps, int nrec, int record_every, long long *bytes);
+
+/* The recorded explicit scheme in a medium (no reference twin): member s integrates
+ *    u_tt = c2_s o (A u) - w_s(t) g_s,
+ * c2_s > 0 the squared wave speed at every unknown; the source is not scaled by it.  Everything but c2 and c2_stride is
+ * mi355cg_wave_record_many's, the semantics of launches, chained calls, steps_done and the traces under a stop flag included.
+ * c2: size doubles per member in the packed order, member s at c2 + s * c2_stride; c2_stride = 0: one medium for all members,
+ * otherwise at least mi355cg_size(h).  With t = au(u) the acceleration is a = c2 * t - f, f = w g: two roundings after t, and the step is
+ *    f = w[n] g;  a = c2 au(u) - f;  vh = v + h a;  u = u + tau vh;  f = w[n + 1] g;  a = c2 au(u) - f;  v = vh + h a.
+ * c2 = 1 gives the bits of mi355cg_wave_record_many; every scaling by a power of two is exact, so c2 = 4 with (tau, v, g) gives
+ * the u of that call with (2 tau, v / 2, g / 4) and twice its v.
+ * The bound of member s is its own: mi355cg_wave_medium_cfl(h, max c2_s) = 2 / sqrt(2 |A_diag| max c2_s), sufficient, not sharp;
+ * c2max = 1 gives the bits of mi355cg_wave_cfl.
+ * MI355CG_ERR_INVALID, the handle's state, right-hand side, shift and solve mode untouched: everything mi355cg_wave_record_many
+ * refuses, with its bound on tau replaced by the member's own; a null c2; a c2_stride that is neither 0 nor >= size; c2
+ * overlapping u, v, g, w or the traces; an entry of c2 that is not finite or not > 0 (the message names the member); tau_s above
+ * the member's bound (the message names the member and the bound).
+ * _device: c2_dev is in device memory like g_dev, u_dev, v_dev, w_dev and traces_dev; one small launch reduces every medium to
+ * its least and largest entry, which the host reads back once before the first step launch.  The host entry point finds them on
+ * the host.  Workspace: that of mi355cg_wave_record_many and 16 bytes per member for those two numbers; the host entry point
+ * stages the media beside g, u and v.  It is the handle's batch workspace, freed by mi355cg_batch_release and mi355cg_destroy.
+ * mi355cg_wave_medium_many_workspace: that many bytes, pure host arithmetic.                                                   */
+int  mi355cg_wave_medium_many(mi355cg_handle h, int nsys, int nsteps, const double *tau, const double *g, double *u, double *v,
+                              const double *c2, long long c2_stride, const double *w, long long w_stride, int nrec, const int *rec_nodes,
+                              int record_every, double *traces, int steps_per_launch, const volatile int *stop_flag, mi355cg_results *out,
+                              int *steps_done);
+int  mi355cg_wave_medium_many_device(mi355cg_handle h, int nsys, int nsteps, const double *tau, const double *g_dev, double *u_dev,
+                                     double *v_dev, const double *c2_dev, long long c2_stride, const double *w_dev, long long w_stride,
+                                     int nrec, const int *rec_nodes, int record_every, double *traces_dev, int steps_per_launch,
+                                     const volatile int *stop_flag, mi355cg_results *out, int *steps_done);
+int  mi355cg_wave_medium_many_workspace(int n, int nsys, int nsteps, int nrec, int record_every, long long *bytes);
+int  mi355cg_wave_medium_cfl(mi355cg_handle h, double c2max, double *tau_max);
 
 /* ---- multi-GPU: one context per rank, one contiguous slab of grid rows per context --------------
  * The reference is single-process (no collectives exist in it); this is the scaling

@@ -580,32 +580,66 @@ public:
                         const std::vector<std::vector<double>>& source, const std::vector<int>& receivers, int record_every,
                         std::vector<std::vector<std::vector<double>>>* traces, std::vector<mi355cg_results>* results = nullptr,
                         std::vector<int>* steps_done = nullptr, const std::vector<std::vector<double>>& g = {}, int steps_per_launch = 0) {
-        if (u.empty() || u.size() > (size_t)MI355CG_MANY_MAX) throw std::invalid_argument("waveRecordMany: an ensemble has 1 .. MI355CG_MANY_MAX members");
+        waveRecorded("waveRecordMany", u, v, tau, nsteps, nullptr, source, receivers, record_every, traces, results, steps_done, g, steps_per_launch);
+    }
+    // Extension: waveRecordMany in a medium (mi355cg_wave_medium_many): member s integrates u_tt = c2_s o (A u) - source_s(t) g_s.
+    // media: one vector of size() positive squared wave speeds for all members, or one per member; everything else is
+    // waveRecordMany's.  A member's tau must not exceed waveCfl(its largest c2).  std::invalid_argument as there, and for media of
+    // the wrong count or size, an entry that is not finite or not > 0, and a tau above the member's bound.
+    void waveMediumMany(std::vector<std::vector<double>>& u, std::vector<std::vector<double>>& v, const std::vector<double>& tau, int nsteps,
+                        const std::vector<std::vector<double>>& media, const std::vector<std::vector<double>>& source, const std::vector<int>& receivers,
+                        int record_every, std::vector<std::vector<std::vector<double>>>* traces, std::vector<mi355cg_results>* results = nullptr,
+                        std::vector<int>* steps_done = nullptr, const std::vector<std::vector<double>>& g = {}, int steps_per_launch = 0) {
+        waveRecorded("waveMediumMany", u, v, tau, nsteps, &media, source, receivers, record_every, traces, results, steps_done, g, steps_per_launch);
+    }
+private:
+    // both of the above; media: null for the homogeneous medium
+    void waveRecorded(const char* who, std::vector<std::vector<double>>& u, std::vector<std::vector<double>>& v, const std::vector<double>& tau, int nsteps,
+                      const std::vector<std::vector<double>>* media, const std::vector<std::vector<double>>& source, const std::vector<int>& receivers,
+                      int record_every, std::vector<std::vector<std::vector<double>>>* traces, std::vector<mi355cg_results>* results,
+                      std::vector<int>* steps_done, const std::vector<std::vector<double>>& g, int steps_per_launch) {
+        const std::string me = std::string(who) + ": ";
+        if (u.empty() || u.size() > (size_t)MI355CG_MANY_MAX) throw std::invalid_argument(me + "an ensemble has 1 .. MI355CG_MANY_MAX members");
         const size_t n = rhs.size(), k = u.size();
-        if (v.size() != k) throw std::invalid_argument("waveRecordMany: v does not have one vector per member");
-        if (tau.size() != k) throw std::invalid_argument("waveRecordMany: tau does not have one entry per member");
-        if (!g.empty() && g.size() != k) throw std::invalid_argument("waveRecordMany: g does not have one vector per member");
-        if (nsteps < 0 || nsteps > MI355CG_STEPS_MANY_MAX_STEPS) throw std::invalid_argument("waveRecordMany: nsteps is 0 .. MI355CG_STEPS_MANY_MAX_STEPS");
-        if (source.size() != 1 && source.size() != k) throw std::invalid_argument("waveRecordMany: source has one row, or one row per member");
-        if (record_every < 1) throw std::invalid_argument("waveRecordMany: record_every is at least 1");
-        if (receivers.size() > (size_t)MI355CG_WAVE_MAX_RECEIVERS) throw std::invalid_argument("waveRecordMany: at most MI355CG_WAVE_MAX_RECEIVERS receivers");
+        if (v.size() != k) throw std::invalid_argument(me + "v does not have one vector per member");
+        if (tau.size() != k) throw std::invalid_argument(me + "tau does not have one entry per member");
+        if (!g.empty() && g.size() != k) throw std::invalid_argument(me + "g does not have one vector per member");
+        if (nsteps < 0 || nsteps > MI355CG_STEPS_MANY_MAX_STEPS) throw std::invalid_argument(me + "nsteps is 0 .. MI355CG_STEPS_MANY_MAX_STEPS");
+        if (source.size() != 1 && source.size() != k) throw std::invalid_argument(me + "source has one row, or one row per member");
+        if (record_every < 1) throw std::invalid_argument(me + "record_every is at least 1");
+        if (receivers.size() > (size_t)MI355CG_WAVE_MAX_RECEIVERS) throw std::invalid_argument(me + "at most MI355CG_WAVE_MAX_RECEIVERS receivers");
         const size_t row = (size_t)nsteps + 1, nrec = receivers.size(), samples = (size_t)(nsteps / record_every);
         std::vector<double> gp(g.empty() ? 0 : n * k), up(n * k), vp(n * k), wp(source.size() * row), tp(k * samples * nrec);
         for (size_t s = 0; s < k; ++s) {
-            if (u[s].size() != n || v[s].size() != n || (!g.empty() && g[s].size() != n)) throw std::invalid_argument("waveRecordMany: vector size does not match the system");
+            if (u[s].size() != n || v[s].size() != n || (!g.empty() && g[s].size() != n)) throw std::invalid_argument(me + "vector size does not match the system");
             std::copy(u[s].begin(), u[s].end(), up.begin() + (std::ptrdiff_t)(s * n));
             std::copy(v[s].begin(), v[s].end(), vp.begin() + (std::ptrdiff_t)(s * n));
             if (!g.empty()) std::copy(g[s].begin(), g[s].end(), gp.begin() + (std::ptrdiff_t)(s * n));
         }
         for (size_t s = 0; s < source.size(); ++s) {
-            if (source[s].size() != row) throw std::invalid_argument("waveRecordMany: a row of the source has nsteps + 1 amplitudes");
+            if (source[s].size() != row) throw std::invalid_argument(me + "a row of the source has nsteps + 1 amplitudes");
             std::copy(source[s].begin(), source[s].end(), wp.begin() + (std::ptrdiff_t)(s * row));
+        }
+        std::vector<double> cp;
+        if (media) {
+            if (media->size() != 1 && media->size() != k) throw std::invalid_argument(me + "media has one vector, or one per member");
+            cp.resize(media->size() * n);
+            for (size_t s = 0; s < media->size(); ++s) {
+                if ((*media)[s].size() != n) throw std::invalid_argument(me + "a medium does not have the size of the system");
+                std::copy((*media)[s].begin(), (*media)[s].end(), cp.begin() + (std::ptrdiff_t)(s * n));
+            }
         }
         std::vector<mi355cg_results> res(k);
         std::vector<int> done(k, 0);
-        mi355cg_compat::check(mi355cg_wave_record_many(ctx_->h, (int)k, nsteps, tau.data(), g.empty() ? nullptr : gp.data(), up.data(), vp.data(), wp.data(),
-                                                       source.size() == 1 ? 0 : (long long)row, (int)nrec, nrec ? receivers.data() : nullptr, record_every,
-                                                       nrec ? tp.data() : nullptr, steps_per_launch, nullptr, res.data(), done.data()));
+        const long long w_stride = source.size() == 1 ? 0 : (long long)row;
+        if (media)
+            mi355cg_compat::check(mi355cg_wave_medium_many(ctx_->h, (int)k, nsteps, tau.data(), g.empty() ? nullptr : gp.data(), up.data(), vp.data(), cp.data(),
+                                                           media->size() == 1 ? 0 : (long long)n, wp.data(), w_stride, (int)nrec, nrec ? receivers.data() : nullptr,
+                                                           record_every, nrec ? tp.data() : nullptr, steps_per_launch, nullptr, res.data(), done.data()));
+        else
+            mi355cg_compat::check(mi355cg_wave_record_many(ctx_->h, (int)k, nsteps, tau.data(), g.empty() ? nullptr : gp.data(), up.data(), vp.data(), wp.data(),
+                                                           w_stride, (int)nrec, nrec ? receivers.data() : nullptr, record_every,
+                                                           nrec ? tp.data() : nullptr, steps_per_launch, nullptr, res.data(), done.data()));
         for (size_t s = 0; s < k; ++s) {
             u[s].assign(up.begin() + (std::ptrdiff_t)(s * n), up.begin() + (std::ptrdiff_t)((s + 1) * n));
             v[s].assign(vp.begin() + (std::ptrdiff_t)(s * n), vp.begin() + (std::ptrdiff_t)((s + 1) * n));
@@ -621,8 +655,11 @@ public:
         if (results) *results = std::move(res);
         if (steps_done) *steps_done = std::move(done);
     }
+public:
     // the largest time step MI355CG_WAVE_VERLET takes on this grid (mi355cg_wave_cfl)
     double waveCfl() const { double t = 0.0; mi355cg_compat::check(mi355cg_wave_cfl(ctx_->h, &t)); return t; }
+    // ... in a medium whose largest squared wave speed is c2max (mi355cg_wave_medium_cfl); waveCfl(1.0) == waveCfl()
+    double waveCfl(double c2max) const { double t = 0.0; mi355cg_compat::check(mi355cg_wave_medium_cfl(ctx_->h, c2max, &t)); return t; }
     void batchRelease() { mi355cg_compat::check(mi355cg_batch_release(ctx_->h)); }
     // Extension: the nev lowest eigenpairs of this system's operator by a block preconditioned iteration with one multigrid V-cycle
     // per vector and iteration (mi355cg_eigs; needs setPreconditioner with the fp64 cycle first).  lambda > 0 ascending with

@@ -190,6 +190,10 @@ struct OnchipManyWs {
     Buf<int> rec_cell_h;                // pinned copy
     Buf<double> rec_stage;              // the host entry point: the amplitude tables, then the traces
     long long rec_stage_cap = 0;        // doubles it holds
+    // mi355cg_wave_medium_many* on top (onchip_wave_medium_workspace_bytes), allocated by the first such call
+    int med_cap = 0;                    // members the next two hold
+    Buf<double> med_range;              // the least and the largest entry of every member's medium (k_oc_medium_range)
+    Buf<double> med_range_h;            // pinned copy
 };
 
 // `small` and its pinned mirror in a call of nsys <= cap systems: nsys x FB_COUNT update partials, then nsys diagonals, then nsys ||r0||_2
@@ -3423,7 +3427,8 @@ int mi355cg_time_steps_many_workspace(int n, int nsys, int nsteps, int with_step
 static_assert(MI355CG_WAVE_VERLET == kWaveVerlet && MI355CG_WAVE_NEWMARK == kWaveNewmark && MI355CG_WAVE_MAX_RECEIVERS == kOnchipWaveMaxRec, "onchip_plan.h: the schemes, the receivers");
 // what both entry points refuse before anything is allocated or written (tau is in host memory for both)
 static int wave_check(mi355cg_ctx* c, const mi355cg_params* prm, int nsys, int nsteps, int scheme, const double* tau, const void* g, const void* u,
-                      const void* v, int steps_per_launch, const mi355cg_results* out, const int* steps_done, const int* step_iterations) {
+                      const void* v, int steps_per_launch, const mi355cg_results* out, const int* steps_done, const int* step_iterations,
+                      bool own_bound = false) {                    // a call in a medium tests every member against its own bound (wave_medium_bounds)
     if (!c || !tau || !u || !v || !out || !steps_done) return fail(MI355CG_ERR_INVALID, "null argument");
     if (scheme != MI355CG_WAVE_VERLET && scheme != MI355CG_WAVE_NEWMARK) return fail(MI355CG_ERR_INVALID, "unknown wave scheme %d", scheme);
     const bool newmark = scheme == MI355CG_WAVE_NEWMARK;
@@ -3438,7 +3443,7 @@ static int wave_check(mi355cg_ctx* c, const mi355cg_params* prm, int nsys, int n
     for (int s = 0; s < nsys; ++s) {
         if (int rc = StepChecks::tau(tau[s], s)) return rc;
         if (newmark && !std::isfinite(4.0 / (tau[s] * tau[s]))) return fail(MI355CG_ERR_INVALID, "time step %g of member %d rejected: 4 / tau^2 is not finite", tau[s], s);
-        if (!newmark && tau[s] > bound)
+        if (!newmark && !own_bound && tau[s] > bound)
             return fail(MI355CG_ERR_INVALID, "time step %.17g of member %d rejected: velocity Verlet needs tau <= %.17g on this grid (mi355cg_wave_cfl); MI355CG_WAVE_NEWMARK has no bound",
                         tau[s], s, bound);
     }
@@ -3473,7 +3478,8 @@ static int wave_upload(mi355cg_ctx* c, OnchipManyWs* W, int nsys, const double* 
 
 // What mi355cg_wave_record_many* adds to an explicit call: w and traces in device memory, nodes (the packed
 // indices of the receivers) in host memory; w_stride 0: one row of amplitudes for all members.
-struct WaveRecord { const double* w; long long w_stride; int nrec; const int* nodes; int every; double* traces; };
+// c2 (or NULL: none): the media of mi355cg_wave_medium_many* (section 12.5) in device memory; c2_stride 0: one for all members.
+struct WaveRecord { const double* w; long long w_stride; int nrec; const int* nodes; int every; double* traces; const double* c2 = nullptr; long long c2_stride = 0; };
 
 // Explicit: ceil(nsteps / m) launches of m steps; before each the host waits for the one before it and tests the caller's flag.
 // rec: with a source and receivers; every launch is told where in the call it starts.
@@ -3496,12 +3502,14 @@ static int wave_verlet(mi355cg_ctx* c, int nsys, int nsteps, const double* tau, 
         x.w = rec->w; x.w_stride = rec->w_stride; x.rec_cell = W->rec_cell; x.nrec = rec->nrec; x.every = rec->every;
         x.traces = rec->traces; x.tr_stride = (long long)(nsteps / rec->every) * rec->nrec;
     }
-    const void* k_steps = rec ? onchip_dispatch(R.pl.elems, false, [](auto el, auto) { return (const void*)&k_oc_wave_record<decltype(el)::value>; })
+    const OnchipWaveMediumArgs md{rec ? rec->c2 : nullptr, rec ? rec->c2_stride : 0};
+    const void* k_steps = md.c2 ? onchip_dispatch(R.pl.elems, false, [](auto el, auto) { return (const void*)&k_oc_wave_medium<decltype(el)::value>; })
+                          : rec ? onchip_dispatch(R.pl.elems, false, [](auto el, auto) { return (const void*)&k_oc_wave_record<decltype(el)::value>; })
                               : onchip_dispatch(R.pl.elems, false, [](auto el, auto) { return (const void*)&k_onchip_wave_verlet<decltype(el)::value>; });
     if (int rc = R.allow_lds(k_steps)) return rc;
     if (int rc = loop_timer_begin(c, c->stream)) return rc;
     const int m = steps_per_launch > 0 ? steps_per_launch : kOnchipWaveDefaultSteps;
-    void* args[] = {&a, &x};                                       // (the plain kernel takes the first alone)
+    void* args[] = {&a, &x, (void*)&md};                           // (the plain kernel takes the first alone, the recording one two)
     int done = 0;
     while (done < nsteps) {
         if (done > 0) HIPCK(hipStreamSynchronize(c->stream));
@@ -3593,8 +3601,8 @@ static bool ranges_meet(const void* a, size_t abytes, const void* b, size_t bbyt
 // (wave_check itself), then what the table, the receivers and the traces add.  host_tables: w can be read here.
 static int wave_record_check(mi355cg_ctx* c, int nsys, int nsteps, const double* tau, const void* g, const void* u, const void* v, const double* w,
                              long long w_stride, int nrec, const int* rec_nodes, int record_every, const void* traces, int steps_per_launch,
-                             const mi355cg_results* out, const int* steps_done, bool host_tables) {
-    if (int rc = wave_check(c, nullptr, nsys, nsteps, MI355CG_WAVE_VERLET, tau, g, u, v, steps_per_launch, out, steps_done, nullptr)) return rc;
+                             const mi355cg_results* out, const int* steps_done, bool host_tables, bool own_bound = false) {
+    if (int rc = wave_check(c, nullptr, nsys, nsteps, MI355CG_WAVE_VERLET, tau, g, u, v, steps_per_launch, out, steps_done, nullptr, own_bound)) return rc;
     if (!w) return fail(MI355CG_ERR_INVALID, "null argument: w, the amplitudes of the source");
     if (w_stride != 0 && w_stride < (long long)nsteps + 1)
         return fail(MI355CG_ERR_INVALID, "w_stride %lld rejected: 0 (one row for all members) or at least nsteps + 1 = %d", w_stride, nsteps + 1);
@@ -3685,6 +3693,131 @@ int mi355cg_wave_record_many_workspace(int n, int nsys, int nsteps, int nrec, in
         return fail(MI355CG_ERR_INVALID, "recorded wave ensemble rejected: even n from 6 to %d, 1 .. %d members, 0 .. %d steps, 0 .. %d receivers, record_every >= 1",
                     kOnchipMaxN, kOnchipStepsMaxSys, kOnchipStepsMaxSteps, kOnchipWaveMaxRec);
     *bytes = v;
+    return MI355CG_OK;
+}
+// ---- the recorded explicit scheme in a medium: u_tt = c2 o (A u) - w(t) g -----------------------------------
+static_assert(kOnchipWaveMediumSysBytes == 2 * sizeof(double), "onchip_plan.h: a member's share of the medium workspace");
+// What both entry points refuse on top of wave_record_check (whose homogeneous bound is off: every member has its own).
+static int wave_medium_check(mi355cg_ctx* c, int nsys, int nsteps, const double* tau, const void* g, const void* u, const void* v, const double* c2,
+                             long long c2_stride, const double* w, long long w_stride, int nrec, const int* rec_nodes, int record_every, const void* traces,
+                             int steps_per_launch, const mi355cg_results* out, const int* steps_done, bool host_tables) {
+    if (int rc = wave_record_check(c, nsys, nsteps, tau, g, u, v, w, w_stride, nrec, rec_nodes, record_every, traces, steps_per_launch, out, steps_done,
+                                   host_tables, true)) return rc;
+    if (!c2) return fail(MI355CG_ERR_INVALID, "null argument: c2, the squared wave speed of every unknown");
+    if (c2_stride != 0 && c2_stride < c->pk_len)
+        return fail(MI355CG_ERR_INVALID, "c2_stride %lld rejected: 0 (one medium for all members) or at least the %lld unknowns of a member", c2_stride, c->pk_len);
+    const size_t state = sizeof(double) * (size_t)c->gp.size * (size_t)nsys;
+    const size_t cbytes = sizeof(double) * ((c2_stride ? (size_t)(nsys - 1) * (size_t)c2_stride : 0) + (size_t)c->pk_len);
+    const size_t wbytes = sizeof(double) * ((size_t)(nsys - 1) * (size_t)w_stride + (size_t)nsteps + 1);
+    const size_t tbytes = nrec > 0 ? sizeof(double) * (size_t)nsys * (size_t)(nsteps / record_every) * (size_t)nrec : 0;
+    const struct { const void* p; size_t bytes; const char* name; } vecs[5] = {{u, state, "u"}, {v, state, "v"}, {g, state, "g"}, {w, wbytes, "w"}, {traces, tbytes, "traces"}};
+    for (const auto& q : vecs)
+        if (ranges_meet(c2, cbytes, q.p, q.bytes)) return fail(MI355CG_ERR_INVALID, "c2 overlaps %s", q.name);
+    return MI355CG_OK;
+}
+// range: the least and the largest entry of every row of the media (one row when c2_stride is 0), NaN for a row with an entry
+// that is not finite -- what k_oc_medium_range leaves, or the host's own pass.  Every member against its medium and its own bound.
+static int wave_medium_bounds(mi355cg_ctx* c, int nsys, const double* tau, const double* range, long long c2_stride) {
+    for (int s = 0; s < nsys; ++s) {
+        const double lo = range[c2_stride ? 2 * s : 0], hi = range[c2_stride ? 2 * s + 1 : 1];
+        if (!std::isfinite(lo) || !std::isfinite(hi))
+            return fail(MI355CG_ERR_INVALID, "medium of member %d rejected%s: an entry of c2 is not finite", s, c2_stride ? "" : " (the one medium of all members)");
+        if (!(lo > 0.0))
+            return fail(MI355CG_ERR_INVALID, "medium of member %d rejected%s: its least entry is %g, and c2, a squared wave speed, must be > 0", s,
+                        c2_stride ? "" : " (the one medium of all members)", lo);
+        const double bound = onchip_wave_medium_cfl(c->gp.A, hi);
+        if (tau[s] > bound)
+            return fail(MI355CG_ERR_INVALID, "time step %.17g of member %d rejected: velocity Verlet in its medium (largest c2 %.17g) needs tau <= %.17g (mi355cg_wave_medium_cfl)",
+                        tau[s], s, hi, bound);
+    }
+    return MI355CG_OK;
+}
+// The recording workspace, then the ranges on top: built complete before they replace what is there.
+static int onchip_wave_medium_ensure(mi355cg_ctx* c, int nsys, int stage_vecs, long long stage_doubles) {
+    if (int rc = onchip_wave_record_ensure(c, nsys, stage_vecs, stage_doubles)) return rc;
+    OnchipManyWs* W = c->many.get();
+    if (W->med_cap < nsys) {
+        auto failed = [&](const char* what) { return fail(MI355CG_ERR_HIP, "on-chip wave medium workspace for %d members: %s allocation failed", nsys, what); };
+        Buf<double> range, range_h;
+        if (Buf<double>::device(range, 2LL * nsys)) return failed("range");
+        if (Buf<double>::pinned(range_h, 2LL * nsys)) return failed("pinned copy");
+        HIPCK(hipStreamSynchronize(c->stream));
+        W->med_range = std::move(range); W->med_range_h = std::move(range_h);
+        W->med_cap = nsys;
+    }
+    return MI355CG_OK;
+}
+
+int mi355cg_wave_medium_many_device(mi355cg_handle c, int nsys, int nsteps, const double* tau, const double* g_dev, double* u_dev, double* v_dev,
+                                    const double* c2_dev, long long c2_stride, const double* w_dev, long long w_stride, int nrec, const int* rec_nodes,
+                                    int record_every, double* traces_dev, int steps_per_launch, const volatile int* stop_flag, mi355cg_results* out,
+                                    int* steps_done) {
+    if (int rc = wave_medium_check(c, nsys, nsteps, tau, g_dev, u_dev, v_dev, c2_dev, c2_stride, w_dev, w_stride, nrec, rec_nodes, record_every, traces_dev,
+                                   steps_per_launch, out, steps_done, false)) return rc;
+    if (StepChecks::none(nsys, nsteps, steps_done)) return MI355CG_OK;
+    HIPCK(hipSetDevice(c->device));
+    if (int rc = onchip_wave_medium_ensure(c, nsys, 0, 0)) return rc;
+    OnchipManyWs* W = c->many.get();
+    const int rows = c2_stride ? nsys : 1;                         // the media are in device memory: one launch reduces them, one read-back
+    hipLaunchKernelGGL(k_oc_medium_range, dim3(rows), dim3(kOcRangeThreads), 0, c->stream, c2_dev, c2_stride, (int)c->pk_len, W->med_range.get());
+    HIPCK(hipGetLastError());
+    HIPCK(hipMemcpyAsync(W->med_range_h, W->med_range, sizeof(double) * 2 * rows, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(hipStreamSynchronize(c->stream));
+    if (int rc = wave_medium_bounds(c, nsys, tau, W->med_range_h, c2_stride)) return rc;
+    const WaveRecord rec{w_dev, w_stride, nrec, rec_nodes, record_every, traces_dev, c2_dev, c2_stride};
+    return wave_verlet(c, nsys, nsteps, tau, g_dev, u_dev, v_dev, steps_per_launch, stop_flag, out, steps_done, &rec);
+}
+int mi355cg_wave_medium_many(mi355cg_handle c, int nsys, int nsteps, const double* tau, const double* g, double* u, double* v, const double* c2,
+                             long long c2_stride, const double* w, long long w_stride, int nrec, const int* rec_nodes, int record_every, double* traces,
+                             int steps_per_launch, const volatile int* stop_flag, mi355cg_results* out, int* steps_done) {
+    if (int rc = wave_medium_check(c, nsys, nsteps, tau, g, u, v, c2, c2_stride, w, w_stride, nrec, rec_nodes, record_every, traces, steps_per_launch, out,
+                                   steps_done, true)) return rc;
+    const size_t len = (size_t)c->pk_len, mrows = c2_stride ? (size_t)nsys : 1;
+    {                                                              // the media can be read here: the two numbers of a row without a launch
+        std::vector<double> range(2 * mrows);
+        for (size_t s = 0; s < mrows; ++s) {
+            const double* const row = c2 + s * (size_t)c2_stride;
+            double lo = row[0], hi = row[0];
+            bool bad = false;
+            for (size_t i = 0; i < len; ++i) { bad = bad || !std::isfinite(row[i]); lo = std::fmin(lo, row[i]); hi = std::fmax(hi, row[i]); }
+            range[2 * s] = bad ? NAN : lo; range[2 * s + 1] = bad ? NAN : hi;
+        }
+        if (int rc = wave_medium_bounds(c, nsys, tau, range.data(), c2_stride)) return rc;
+    }
+    if (StepChecks::none(nsys, nsteps, steps_done)) return MI355CG_OK;
+    HIPCK(hipSetDevice(c->device));
+    const size_t row = (size_t)nsteps + 1, rows = w_stride ? (size_t)nsys : 1;             // the tables go up packed: row doubles per row
+    const size_t sample = (size_t)nrec, samples = (size_t)(nsteps / record_every);          // a member's traces: samples x sample doubles
+    if (int rc = onchip_wave_medium_ensure(c, nsys, 4, (long long)(rows * row + (size_t)nsys * samples * sample))) return rc;
+    const size_t count = len * (size_t)nsys;                       // g, then u, then v, then the media (packed: nsys vectors, or one); the state comes down
+    double* const g_dev = c->many->stage; double* const u_dev = g_dev + count; double* const v_dev = u_dev + count; double* const c2_dev = v_dev + count;
+    double* const w_dev = c->many->rec_stage; double* const traces_dev = w_dev + rows * row;
+    const StagedGroup groups[3] = {{0, g, nullptr}, {count, u, u}, {2 * count, v, v}};
+    return run_staged_groups(c, g_dev, count, groups, [&]() {
+        HIPCK(hipMemcpy2DAsync(c2_dev, sizeof(double) * len, c2, sizeof(double) * (c2_stride ? (size_t)c2_stride : len), sizeof(double) * len, mrows, hipMemcpyHostToDevice, c->stream));
+        HIPCK(hipMemcpy2DAsync(w_dev, sizeof(double) * row, w, sizeof(double) * (w_stride ? (size_t)w_stride : row), sizeof(double) * row, rows, hipMemcpyHostToDevice, c->stream));
+        const WaveRecord rec{w_dev, w_stride ? (long long)row : 0, nrec, rec_nodes, record_every, nrec ? traces_dev : nullptr, c2_dev, c2_stride ? (long long)len : 0};
+        if (int rc = wave_verlet(c, nsys, nsteps, tau, g ? g_dev : nullptr, u_dev, v_dev, steps_per_launch, stop_flag, out, steps_done, &rec)) return rc;
+        const size_t ran = (size_t)(steps_done[0] / record_every) * sample;                 // the samples of the steps that ran come down
+        if (ran) HIPCK(hipMemcpy2DAsync(traces, sizeof(double) * samples * sample, traces_dev, sizeof(double) * samples * sample, sizeof(double) * ran, (size_t)nsys,
+                                        hipMemcpyDeviceToHost, c->stream));
+        return (int)MI355CG_OK;
+    });
+}
+int mi355cg_wave_medium_many_workspace(int n, int nsys, int nsteps, int nrec, int record_every, long long* bytes) {
+    if (!bytes) return fail(MI355CG_ERR_INVALID, "null argument");
+    const long long v = onchip_wave_medium_workspace_bytes(n, nsys, nsteps, nrec, record_every);
+    if (v == 0)
+        return fail(MI355CG_ERR_INVALID, "recorded wave ensemble in a medium rejected: even n from 6 to %d, 1 .. %d members, 0 .. %d steps, 0 .. %d receivers, record_every >= 1",
+                    kOnchipMaxN, kOnchipStepsMaxSys, kOnchipStepsMaxSteps, kOnchipWaveMaxRec);
+    *bytes = v;
+    return MI355CG_OK;
+}
+int mi355cg_wave_medium_cfl(mi355cg_handle c, double c2max, double* tau_max) {
+    if (!c || !tau_max) return fail(MI355CG_ERR_INVALID, "null argument");
+    if (c->is_csr) return fail(MI355CG_ERR_INVALID, "a CSR handle has no grid: the bound is the grid operator's");
+    if (!std::isfinite(c2max) || !(c2max > 0.0)) return fail(MI355CG_ERR_INVALID, "c2max %g rejected: the largest squared wave speed is finite and > 0", c2max);
+    *tau_max = onchip_wave_medium_cfl(c->gp.A, c2max);
     return MI355CG_OK;
 }
 int mi355cg_wave_cfl(mi355cg_handle c, double* tau_max) {

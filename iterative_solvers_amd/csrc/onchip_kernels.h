@@ -786,6 +786,117 @@ __global__ __launch_bounds__(kOnchipMaxThreads) void k_oc_wave_record(const Onch
     }
 }
 
+// In a medium (mi355cg_wave_medium_many*): u_tt = c2 o (A u) - w(t) g, the squared wave speed c2 of every
+// unknown given per member or once for all.  k_oc_wave_record's step with onchip_wave_medium_accel in both places, c2 of the
+// thread's slots in registers beside g (the LDS cannot hold a medium beside the image at the cap), loaded once.  The barriers, the
+// amplitude blocks, the receiver window and step0 / phase / slot are that kernel's; it is a kernel of its own for that kernel's
+// reason, so the other two stay the code they are.
+struct OnchipWaveMediumArgs { const double* c2; long long c2_stride; };      // member s reads c2 + s * c2_stride (0: one vector for all)
+template <int E>
+__global__ __launch_bounds__(kOnchipMaxThreads) void k_oc_wave_medium(const OnchipWaveArgs a, const OnchipWaveRecArgs x, const OnchipWaveMediumArgs md) {
+    const OnchipPlan& pl = a.pl;
+    extern __shared__ __attribute__((aligned(16))) char oc_dyn_lds[];
+    double* const wbuf = reinterpret_cast<double*>(oc_dyn_lds);
+    double* const img = OcMany::lds(pl.cells).img;
+    const int t = threadIdx.x, T = blockDim.x, pitch = pl.pitch;
+    const long long sys = blockIdx.x;
+    const double tau = a.tau[sys], h = 0.5 * tau;
+    const double* const gin = a.g + sys * a.g_stride;
+    const double* const cin = md.c2 + sys * md.c2_stride;
+    double* const uio = a.u + sys * a.stride; double* const vio = a.v + sys * a.stride;
+    const double* const wrow = x.w + sys * x.w_stride + x.step0;   // wrow[s]: at the start of the launch's step s, wrow[s + 1]: at its end
+    double* trow = x.traces + sys * x.tr_stride + (long long)x.slot * x.nrec;
+
+    for (int i = t; i < pl.cells; i += T) img[i] = 0.0;
+    __syncthreads();                                               // the image is zero everywhere before the owners fill their cells
+    unsigned cell2[(E + 1) / 2] = {};
+    double v[E], acc[E], g[E], c2[E];
+    int cnt = 0;
+#pragma unroll
+    for (int k = 0; k < E; ++k) {
+        const int i = onchip_owned(pl, t, k);
+        if (i >= 0) {                                              // (slots beyond cnt are never read: nothing to initialise)
+            int xx, yy;
+            onchip_node(pl, i, &xx, &yy);
+            const int c = onchip_cell(pl, xx, yy);
+            cell2[k / 2] |= (unsigned)c << (16 * (k & 1));
+            img[c] = uio[i]; v[k] = vio[i]; g[k] = gin[i]; c2[k] = cin[i];
+            cnt = k + 1;
+        }
+    }
+    if (t < kOcAmpBlock && t < a.m) wbuf[t] = wrow[t + 1];
+    int rcell = 0, phase = x.phase;
+    if (t < x.nrec) rcell = x.rec_cell[t];
+    double w_now = wrow[0], w_next = 0.0;
+    __syncthreads();
+    auto own_cell = [&](int k) { unsigned cc = cell2[k / 2]; asm volatile("" : "+v"(cc)); return (int)((cc >> (16 * (k & 1))) & 0xffffu); };
+    auto accel_at = [&](int c, double ck, double f) { return onchip_wave_medium_accel(a.k, ck, f, img[c], img[c - 1], img[c + 1], img[c - pitch], img[c + pitch]); };
+#pragma unroll
+    for (int k = 0; k < E; ++k) if (k < cnt) { acc[k] = accel_at(own_cell(k), c2[k], onchip_wave_forcing(w_now, g[k])); __builtin_amdgcn_sched_barrier(0); }
+
+    for (int s = 0; s < a.m; ++s) {
+        __syncthreads();                                           // barrier 1: every neighbour has read the old cells
+        w_now = wbuf[((s / kOcAmpBlock) & 1) * kOcAmpBlock + s % kOcAmpBlock];        // the amplitude at the END of this step
+#pragma unroll
+        for (int k = 0; k < E; ++k) if (k < cnt) {
+            const int c = own_cell(k);
+            v[k] = onchip_wave_kick(v[k], h, acc[k]);              // vh
+            img[c] = onchip_wave_drift(img[c], tau, v[k]);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        __syncthreads();                                           // barrier 2: the new image is complete
+#pragma unroll
+        for (int k = 0; k < E; ++k) if (k < cnt) {
+            acc[k] = accel_at(own_cell(k), c2[k], onchip_wave_forcing(w_now, g[k]));
+            v[k] = onchip_wave_kick(v[k], h, acc[k]);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        if (++phase == x.every) {                                  // uniform: this step is sampled
+            phase = 0;
+            if (t < x.nrec) trow[t] = img[rcell];
+            trow += x.nrec;
+        }
+        const int q = s % kOcAmpBlock, nb = s - q + kOcAmpBlock + t;                  // this lane's step in the next block
+        if (t < kOcAmpBlock && nb < a.m) {
+            if (q == 0) w_next = wrow[nb + 1];
+            if (q == kOcAmpBlock / 2) wbuf[((nb / kOcAmpBlock) & 1) * kOcAmpBlock + t] = w_next;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < E; ++k) if (k < cnt) {
+        int i = k * T + t;
+        asm volatile("" : "+v"(i));                                // recomputed here, not carried through the loop
+        uio[i] = img[own_cell(k)]; vio[i] = v[k];
+    }
+}
+
+// The check launch for media in device memory: workgroup b reduces row b of the media (`rows` of them, `len` doubles each, row b
+// at c2 + b * stride) to its least and its largest entry and writes them to out[2 b], out[2 b + 1]; a row with an entry that is
+// not finite gets NaN in both.  The host reads them back once and refuses there, so that the message can name the member.
+constexpr int kOcRangeThreads = 256;
+__global__ __launch_bounds__(kOcRangeThreads) void k_oc_medium_range(const double* c2, long long stride, int len, double* out) {
+    __shared__ double part[3][kOcRangeThreads / kWave];
+    const double* const row = c2 + (long long)blockIdx.x * stride;
+    const int t = threadIdx.x;
+    double lo = INFINITY, hi = -INFINITY, bad = 0.0;
+    for (int i = t; i < len; i += kOcRangeThreads) {
+        const double x = row[i];
+        if (!(fabs(x) <= 1.7976931348623157e308)) bad = 1.0;       // NaN or an infinity
+        lo = fmin(lo, x); hi = fmax(hi, x);
+    }
+    for (int d = kWave / 2; d > 0; d >>= 1) {
+        lo = fmin(lo, __shfl_xor(lo, d)); hi = fmax(hi, __shfl_xor(hi, d)); bad = fmax(bad, __shfl_xor(bad, d));
+    }
+    if (t % kWave == 0) { part[0][t / kWave] = lo; part[1][t / kWave] = hi; part[2][t / kWave] = bad; }
+    __syncthreads();
+    if (t == 0) {
+        for (int w = 1; w < kOcRangeThreads / kWave; ++w) { lo = fmin(lo, part[0][w]); hi = fmax(hi, part[1][w]); bad = fmax(bad, part[2][w]); }
+        const double nan = __builtin_nan("");
+        out[2 * (long long)blockIdx.x] = bad != 0.0 ? nan : lo;
+        out[2 * (long long)blockIdx.x + 1] = bad != 0.0 ? nan : hi;
+    }
+}
+
 // Implicit: average-acceleration Newmark.  oc_step_loop with another right-hand side and a velocity: a step is the warm-started
 // solve of (A - sigma_s I) x = b_wave(u, v), sigma_s = 4 / tau_s^2, and the transition after a CONVERGED step updates the member's
 // state in the caller's vectors -- v = hv (x - u) - v, u = x, with u the state the step started from -- before the next step

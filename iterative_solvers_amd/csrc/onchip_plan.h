@@ -220,6 +220,24 @@ MI355CG_HD inline long long onchip_wave_record_workspace_bytes(int n, int nsys, 
     const long long verlet = onchip_wave_workspace_bytes(n, nsys, nsteps, kWaveVerlet, 0);
     return verlet == 0 ? 0 : verlet + 4LL * kOnchipWaveMaxRec;
 }
+// A medium (mi355cg_wave_medium_many): u_tt = c2 o (A u) - w(t) g with the squared wave speed c2 > 0 of every
+// unknown.  The acceleration is the stencil scaled, then the forcing taken off, two roundings after au; the source is not scaled.
+// 1.0 * t == t: a unit medium is onchip_wave_accel with the forcing w g, bit for bit.
+MI355CG_HD inline double onchip_wave_medium_accel(const OnchipWaveCoef& k, double c2, double f, double uc, double left, double right, double down, double up) {
+    const double t = onchip_wave_au(k, uc, left, right, down, up);
+    return c2 * t - f;
+}
+// Its bound: -C A with C = diag(c2) is similar to the symmetric C^(1/2) (-A) C^(1/2), whose eigenvalues lie in [0, 2 |A0| max c2].
+// Sufficient, not sharp.  (2 |A0|) * 1.0 is exact: c2max == 1.0 gives the bits of onchip_wave_cfl.
+inline double onchip_wave_medium_cfl(double A0, double c2max) { return 2.0 / std::sqrt(2.0 * std::fabs(A0) * c2max); }
+// Its workspace: that of the recorded call and two doubles per member, the least and the largest entry of its medium as
+// k_oc_medium_range leaves them for the host.  (The host entry point stages the media on top of g, u and v: nsys packed vectors,
+// or one.)  0: refused, as onchip_wave_record_workspace_bytes refuses.
+constexpr int kOnchipWaveMediumSysBytes = 2 * 8;
+MI355CG_HD inline long long onchip_wave_medium_workspace_bytes(int n, int nsys, int nsteps, int nrec, int record_every) {
+    const long long record = onchip_wave_record_workspace_bytes(n, nsys, nsteps, nrec, record_every);
+    return record == 0 ? 0 : record + (long long)nsys * kOnchipWaveMediumSysBytes;
+}
 // Steps of one explicit launch when the caller does not say: the host tests the stop flag between two launches, so the longest
 // launch is the latency of a stop request, to stay under 10 ms.  Measured on one MI355X at N = 128, a launch of 1024 steps: 3.7 ms
 // for one member, 4.0 ms for 256, 15.3 ms for 1024 members (one workgroup per CU at that size, so four in turn) -- hence half of

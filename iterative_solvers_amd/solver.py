@@ -463,9 +463,10 @@ class _Handle:
         return (u, v, list(res), steps_done) + ((step_it,) if step_iterations else ())
 
     def wave_record_many(self, u0, v0, tau, nsteps: int, source, g=None, receivers=None, record_every: int = 1, steps_per_launch: int = 0,
-                         stop_flag: Optional[C.c_int] = None, traces=None):
+                         stop_flag: Optional[C.c_int] = None, traces=None, c2=None):
         """Extension (no reference twin): wave_steps_many with WAVE_VERLET, a source time function and receiver traces
-        (mi355cg_wave_record_many).  source: the amplitudes, [nsteps + 1] (one row for all members) or [nsys, nsteps + 1], of u0's
+        (mi355cg_wave_record_many).  c2 (or None): a medium, [size] (one for all members) or [nsys, size] of u0's kind, the squared
+        wave speed of every unknown; the call is then mi355cg_wave_medium_many, u_tt = c2 o (A u) - w(t) g.  source: the amplitudes, [nsteps + 1] (one row for all members) or [nsys, nsteps + 1], of u0's
         kind; the forcing of member s at its local time n tau[s] is source[s][n] * g[s].  receivers: a sequence of at most
         WAVE_MAX_RECEIVERS packed indices, or None; record_every: the cadence.  Returns (u, v, traces, [Results per member],
         steps_done): traces [nsys, nsteps // record_every, len(receivers)] of u0's kind, u at the receivers after every
@@ -486,9 +487,16 @@ class _Handle:
             raise ValueError("source is of the kind (NumPy / CUDA tensor) of u0")
         shapes = ((nsteps + 1,), (nsys, nsteps + 1))
         tshape = (nsys, nsteps // record_every, nrec)
+        cshapes = ((self.size,), (nsys, self.size))
+        if c2 is not None and not on_device:
+            if hasattr(c2, "data_ptr"):
+                raise ValueError("c2 is of the kind (NumPy / CUDA tensor) of u0")
+            c2 = np.ascontiguousarray(c2, dtype=np.float64)
+            if c2.shape not in cshapes:
+                raise ValueError(f"c2 has shape {c2.shape}, expected {cshapes[0]} or {cshapes[1]}")
         if on_device:
             import torch
-            for name, a, want in (("source", source, shapes), ("traces", traces, (tshape,))):
+            for name, a, want in (("source", source, shapes), ("traces", traces, (tshape,)), ("c2", c2, cshapes)):
                 if a is not None and not (hasattr(a, "data_ptr") and a.is_cuda and a.device == u0.device and a.dtype == torch.float64
                                           and tuple(a.shape) in want and a.is_contiguous()):
                     raise ValueError(f"{name} beside CUDA states is a contiguous float64 tensor of shape {' or '.join(map(str, want))} on {u0.device}")
@@ -496,10 +504,11 @@ class _Handle:
             if nrec and traces is None:
                 traces = torch.zeros(tshape, dtype=torch.float64, device=u0.device)
             torch.cuda.current_stream(u0.device).synchronize()
-            rc = self._lib.mi355cg_wave_record_many_device(
-                self._h, nsys, nsteps, tau.ctypes.data, g.data_ptr() if g is not None else None, u.data_ptr(), v.data_ptr(), source.data_ptr(),
-                nsteps + 1 if source.dim() == 2 else 0, nrec, nodes.ctypes.data if nrec else None, record_every, traces.data_ptr() if nrec else None,
-                int(steps_per_launch), sp, res, steps_done.ctypes.data)
+            fn = self._lib.mi355cg_wave_record_many_device if c2 is None else self._lib.mi355cg_wave_medium_many_device
+            medium = () if c2 is None else (c2.data_ptr(), self.size if c2.dim() == 2 else 0)
+            rc = fn(self._h, nsys, nsteps, tau.ctypes.data, g.data_ptr() if g is not None else None, u.data_ptr(), v.data_ptr(), *medium, source.data_ptr(),
+                    nsteps + 1 if source.dim() == 2 else 0, nrec, nodes.ctypes.data if nrec else None, record_every, traces.data_ptr() if nrec else None,
+                    int(steps_per_launch), sp, res, steps_done.ctypes.data)
         else:
             source = np.ascontiguousarray(source, dtype=np.float64)
             if source.shape not in shapes:
@@ -512,16 +521,29 @@ class _Handle:
                 g = np.ascontiguousarray(g)
             if nrec and traces is None:
                 traces = np.zeros(tshape)
-            rc = self._lib.mi355cg_wave_record_many(
-                self._h, nsys, nsteps, tau.ctypes.data, g.ctypes.data if g is not None else None, u.ctypes.data, v.ctypes.data, source.ctypes.data,
-                nsteps + 1 if source.ndim == 2 else 0, nrec, nodes.ctypes.data if nrec else None, record_every, traces.ctypes.data if nrec else None,
-                int(steps_per_launch), sp, res, steps_done.ctypes.data)
+            fn = self._lib.mi355cg_wave_record_many if c2 is None else self._lib.mi355cg_wave_medium_many
+            medium = () if c2 is None else (c2.ctypes.data, self.size if c2.ndim == 2 else 0)
+            rc = fn(self._h, nsys, nsteps, tau.ctypes.data, g.ctypes.data if g is not None else None, u.ctypes.data, v.ctypes.data, *medium, source.ctypes.data,
+                    nsteps + 1 if source.ndim == 2 else 0, nrec, nodes.ctypes.data if nrec else None, record_every, traces.ctypes.data if nrec else None,
+                    int(steps_per_launch), sp, res, steps_done.ctypes.data)
         self._check_rc(rc)
         return u, v, (traces if nrec else None), list(res), steps_done
 
-    def wave_cfl(self) -> float:
-        """The largest time step velocity Verlet takes on this grid, 2 / sqrt(2 |A_diag|) of the unshifted operator (mi355cg_wave_cfl)."""
+    def wave_cfl(self, c2=None):
+        """The largest time step velocity Verlet takes on this grid, 2 / sqrt(2 |A_diag|) of the unshifted operator (mi355cg_wave_cfl).
+        c2: a medium, [size] or [nsys, size] (NumPy or tensor): the bound 2 / sqrt(2 |A_diag| max c2) of that medium, or an array
+        [nsys] of them (mi355cg_wave_medium_cfl); the max is NumPy's or torch's."""
         out = C.c_double()
+        if c2 is not None:
+            top = c2.amax(dim=-1).cpu().numpy() if hasattr(c2, "data_ptr") else np.max(np.asarray(c2, dtype=np.float64), axis=-1)
+            if top.ndim > 1:
+                raise ValueError(f"c2 has shape {tuple(c2.shape)}: a medium is [size] or [nsys, size]")
+            bounds = []
+            for c2max in np.atleast_1d(top):
+                rc = self._lib.mi355cg_wave_medium_cfl(self._h, float(c2max), C.byref(out))
+                self._check_rc(rc)
+                bounds.append(out.value)
+            return bounds[0] if top.ndim == 0 else np.array(bounds)
         self._check_rc(self._lib.mi355cg_wave_cfl(self._h, C.byref(out)))
         return out.value
 
@@ -709,6 +731,18 @@ def wave_record_many_workspace(n: int, nsys: int, nsteps: int, nrec: int = 0, re
     out = C.c_longlong()
     lib = _capi.load()
     rc = lib.mi355cg_wave_record_many_workspace(int(n), int(nsys), int(nsteps), int(nrec), int(record_every), C.byref(out))
+    if rc == _capi.ERR_INVALID:
+        raise ValueError(lib.mi355cg_last_error().decode())
+    _capi.check(rc)
+    return out.value
+
+
+def wave_medium_many_workspace(n: int, nsys: int, nsteps: int, nrec: int = 0, record_every: int = 1) -> int:
+    """The device workspace bytes of MatrixFreeSystem.wave_record_many with a medium c2 (host arithmetic, no GPU;
+    mi355cg_wave_medium_many_workspace): those of the call without it and 16 bytes per member.  ValueError for what the call refuses."""
+    out = C.c_longlong()
+    lib = _capi.load()
+    rc = lib.mi355cg_wave_medium_many_workspace(int(n), int(nsys), int(nsteps), int(nrec), int(record_every), C.byref(out))
     if rc == _capi.ERR_INVALID:
         raise ValueError(lib.mi355cg_last_error().decode())
     _capi.check(rc)
@@ -905,9 +939,12 @@ class MatrixFreeSystem:
                                             stop_flag=stop_flag, step_iterations=step_iterations)
 
     def wave_record_many(self, u0, v0, tau, nsteps: int, source, g=None, receivers=None, record_every: int = 1, steps_per_launch: int = 0,
-                         stop_flag: Optional[C.c_int] = None, traces=None):
+                         stop_flag: Optional[C.c_int] = None, traces=None, c2=None):
         """Extension (no reference twin): wave_steps_many with WAVE_VERLET, a source time function and receiver traces, all inside
-        the launch.  source: [nsteps + 1] (one row for all members) or [nsys, nsteps + 1] amplitudes of u0's kind; member s feels
+        the launch.  c2 (None: the homogeneous medium, exactly the call without it): the squared wave speed of every unknown,
+        [size] (one medium for all members) or [nsys, size], positive, of u0's kind; member s then integrates
+        u_tt = c2_s o (A u) - source_s(t) g_s (the source is not scaled), and its tau must not exceed wave_cfl(c2)[s].  c2 = 1
+        gives the bits of the call without it.  source: [nsteps + 1] (one row for all members) or [nsys, nsteps + 1] amplitudes of u0's kind; member s feels
         the forcing source[s][n] * g[s] at its local time n tau[s], so a step from n to n + 1 uses source[n] in its first half
         kick and source[n + 1] in its second (second order in tau for a smooth source); source = 1 gives the bits of
         wave_steps_many.  receivers: at most WAVE_MAX_RECEIVERS packed indices (packed_index) shared by all members, None = no
@@ -917,7 +954,7 @@ class MatrixFreeSystem:
         traces: an array of that shape to write into; a stop flag leaves the samples of steps that did not run untouched.  u0,
         v0, tau, g, steps_per_launch and stop_flag as in wave_steps_many; this system is left as it was."""
         return self._handle.wave_record_many(u0, v0, tau, nsteps, source, g=g, receivers=receivers, record_every=record_every,
-                                             steps_per_launch=steps_per_launch, stop_flag=stop_flag, traces=traces)
+                                             steps_per_launch=steps_per_launch, stop_flag=stop_flag, traces=traces, c2=c2)
 
     def packed_index(self, ix: int, iy: int) -> int:
         """The packed index of grid node (ix, iy), 0 <= ix, iy <= n, in the order of the batch and ensemble calls (solve_many,
@@ -934,9 +971,11 @@ class MatrixFreeSystem:
             return half * (half - 1) + (iy - half - 1) * (n - 1) + (ix - 1)
         return -1
 
-    def wave_cfl(self) -> float:
-        """The largest time step wave_steps_many takes with WAVE_VERLET on this grid: 2 / sqrt(2 |A_diag|), Gershgorin's bound."""
-        return self._handle.wave_cfl()
+    def wave_cfl(self, c2=None):
+        """The largest time step wave_steps_many takes with WAVE_VERLET on this grid: 2 / sqrt(2 |A_diag|), Gershgorin's bound.
+        c2: a medium of wave_record_many, [size] or [nsys, size]: its bound 2 / sqrt(2 |A_diag| max c2), one float or an array
+        [nsys]; sufficient, not sharp."""
+        return self._handle.wave_cfl(c2)
 
     def solve_many_info(self, nsys: int):
         """What a solve_many batch of nsys systems costs on this grid: the LDS bytes of one workgroup, how many workgroups the
