@@ -49,6 +49,7 @@
  *   mi355cg_wave_steps_many_workspace / mi355cg_wave_cfl   its workspace bytes; the explicit scheme's bound on tau (host arithmetic)
  *   mi355cg_wave_record_many / _device / _workspace   the explicit scheme with a source time function and receiver traces
  *   mi355cg_wave_medium_many / _device / _workspace / mi355cg_wave_medium_cfl   that scheme in a medium: a squared wave speed per unknown and member
+ *   mi355cg_wave_sponge_many / _device / _workspace   ... with a damping rate per unknown and member: absorbing (sponge) layers
  *
  * Plain pointers and sizes only; no C++/torch types.  All host vectors are in the reference's
  * PACKED unknown order (bottom-right block row-major, then the upper block row-major;
@@ -641,6 +642,37 @@ int  mi355cg_wave_medium_many_device(mi355cg_handle h, int nsys, int nsteps, con
                                      const volatile int *stop_flag, mi355cg_results *out, int *steps_done);
 int  mi355cg_wave_medium_many_workspace(int n, int nsys, int nsteps, int nrec, int record_every, long long *bytes);
 int  mi355cg_wave_medium_cfl(mi355cg_handle h, double c2max, double *tau_max);
+
+/* ... with a damping field, for absorbing (sponge) layers at the reflecting boundary (no reference twin):
+ * member s integrates
+ *    u_tt + d_s o u_t = c2_s o (A u) - w_s(t) g_s,
+ * d_s >= 0 the damping rate (1 / time) at every unknown.  Everything but d and d_stride is mi355cg_wave_medium_many's, the
+ * semantics of launches, chained calls, steps_done and the traces under a stop flag included.
+ * d: size doubles per member in the packed order, member s at d + s * d_stride; d_stride = 0: one field for all members,
+ * otherwise at least mi355cg_size(h).  The damping enters by a symmetric splitting, v times one factor per unknown at both ends
+ * of a step, the factor the Cayley transform of the damping flow over tau / 2 (second order, time-symmetric):
+ *    e = (0.25 tau) d;  s = (1 - e) / (1 + e)                      (every operation rounded once, the division IEEE's)
+ *    v = s v;  f = w[n] g;  a = c2 au(u) - f;  vh = v + h a;  u = u + tau vh;  f = w[n + 1] g;  a = c2 au(u) - f;  v = vh + h a;  v = s v
+ * and the v returned is the one after the closing multiply.  d = 0 gives s = 1 and the bits of mi355cg_wave_medium_many.  Without
+ * a forcing the scheme's modified energy never grows.  The bound on tau is the medium's, mi355cg_wave_medium_cfl, unchanged.
+ * MI355CG_ERR_INVALID, the handle's state, right-hand side, shift and solve mode untouched: everything
+ * mi355cg_wave_medium_many refuses; a null d; a d_stride that is neither 0 nor >= size; d overlapping u, v, g, c2, w or the
+ * traces; an entry of d that is negative or not finite (the message names the member); (0.25 tau_s) max d_s > 1, where the factor
+ * turns negative and stronger damping would damp less (the message names the member and the bound 4 / tau_s).
+ * _device: d_dev is in device memory like c2_dev; a second small launch reduces every damping row to its least and largest
+ * entry, read back with the media's.  Workspace: that of mi355cg_wave_medium_many and 16 bytes per member for those two
+ * numbers; the host entry point stages the damping rows beside the media.  It is the handle's batch workspace, freed by
+ * mi355cg_batch_release and mi355cg_destroy.  mi355cg_wave_sponge_many_workspace: that many bytes, pure host arithmetic.        */
+int  mi355cg_wave_sponge_many(mi355cg_handle h, int nsys, int nsteps, const double *tau, const double *g, double *u, double *v,
+                              const double *c2, long long c2_stride, const double *d, long long d_stride, const double *w, long long w_stride,
+                              int nrec, const int *rec_nodes, int record_every, double *traces, int steps_per_launch,
+                              const volatile int *stop_flag, mi355cg_results *out, int *steps_done);
+int  mi355cg_wave_sponge_many_device(mi355cg_handle h, int nsys, int nsteps, const double *tau, const double *g_dev, double *u_dev,
+                                     double *v_dev, const double *c2_dev, long long c2_stride, const double *d_dev, long long d_stride,
+                                     const double *w_dev, long long w_stride, int nrec, const int *rec_nodes, int record_every,
+                                     double *traces_dev, int steps_per_launch, const volatile int *stop_flag, mi355cg_results *out,
+                                     int *steps_done);
+int  mi355cg_wave_sponge_many_workspace(int n, int nsys, int nsteps, int nrec, int record_every, long long *bytes);
 
 /* ---- multi-GPU: one context per rank, one contiguous slab of grid rows per context --------------
  * The reference is single-process (no collectives exist in it); this is the scaling

@@ -43,6 +43,7 @@ EXPORTS = [
     "mi355cg_wave_steps_many", "mi355cg_wave_steps_many_device", "mi355cg_wave_steps_many_workspace", "mi355cg_wave_cfl",
     "mi355cg_wave_record_many", "mi355cg_wave_record_many_device", "mi355cg_wave_record_many_workspace",
     "mi355cg_wave_medium_many", "mi355cg_wave_medium_many_device", "mi355cg_wave_medium_many_workspace", "mi355cg_wave_medium_cfl",
+    "mi355cg_wave_sponge_many", "mi355cg_wave_sponge_many_device", "mi355cg_wave_sponge_many_workspace",
 ]
 WAVE_VERLET, WAVE_NEWMARK = 0, 1    # MI355CG_WAVE_VERLET, MI355CG_WAVE_NEWMARK
 DECOMP_ROWS, DECOMP_2D = 0, 1
@@ -255,6 +256,12 @@ def load():
                            C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(Results), C.c_void_p]
         L.mi355cg_wave_medium_many_workspace.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, LLP]
         L.mi355cg_wave_medium_cfl.argtypes = [H, C.c_double, DBP]
+    if hasattr(L, "mi355cg_wave_sponge_many"):  # absent from an older build loaded through MI355CG_LIB
+        # mi355cg_wave_medium_many's arguments with d (a host array / device memory for _device) and its stride behind c2's
+        for fn in (L.mi355cg_wave_sponge_many, L.mi355cg_wave_sponge_many_device):
+            fn.argtypes = [H, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p,
+                           C.c_longlong, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(Results), C.c_void_p]
+        L.mi355cg_wave_sponge_many_workspace.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, LLP]
     if hasattr(L, "mi355cg_get_xfold"):         # absent from an older build loaded through MI355CG_LIB
         L.mi355cg_get_xfold.argtypes = [H, IP, IP]
     _lib = L

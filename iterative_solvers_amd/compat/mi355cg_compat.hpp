@@ -580,7 +580,7 @@ public:
                         const std::vector<std::vector<double>>& source, const std::vector<int>& receivers, int record_every,
                         std::vector<std::vector<std::vector<double>>>* traces, std::vector<mi355cg_results>* results = nullptr,
                         std::vector<int>* steps_done = nullptr, const std::vector<std::vector<double>>& g = {}, int steps_per_launch = 0) {
-        waveRecorded("waveRecordMany", u, v, tau, nsteps, nullptr, source, receivers, record_every, traces, results, steps_done, g, steps_per_launch);
+        waveRecorded("waveRecordMany", u, v, tau, nsteps, nullptr, nullptr, source, receivers, record_every, traces, results, steps_done, g, steps_per_launch);
     }
     // Extension: waveRecordMany in a medium (mi355cg_wave_medium_many): member s integrates u_tt = c2_s o (A u) - source_s(t) g_s.
     // media: one vector of size() positive squared wave speeds for all members, or one per member; everything else is
@@ -590,14 +590,26 @@ public:
                         const std::vector<std::vector<double>>& media, const std::vector<std::vector<double>>& source, const std::vector<int>& receivers,
                         int record_every, std::vector<std::vector<std::vector<double>>>* traces, std::vector<mi355cg_results>* results = nullptr,
                         std::vector<int>* steps_done = nullptr, const std::vector<std::vector<double>>& g = {}, int steps_per_launch = 0) {
-        waveRecorded("waveMediumMany", u, v, tau, nsteps, &media, source, receivers, record_every, traces, results, steps_done, g, steps_per_launch);
+        waveRecorded("waveMediumMany", u, v, tau, nsteps, &media, nullptr, source, receivers, record_every, traces, results, steps_done, g, steps_per_launch);
+    }
+    // Extension: waveMediumMany with a damping field, for absorbing (sponge) layers (mi355cg_wave_sponge_many): member s integrates
+    // u_tt + d_s o u_t = c2_s o (A u) - source_s(t) g_s.  damping: one vector of size() damping rates >= 0 for all members, or one
+    // per member; everything else is waveMediumMany's (a unit medium: media = {std::vector<double>(size(), 1.0)}).  tau[s] times
+    // the largest entry of the member's damping must not exceed 4.  std::invalid_argument as there, and for damping of the wrong
+    // count or size, an entry that is negative or not finite, and a damping above that bound.
+    void waveSpongeMany(std::vector<std::vector<double>>& u, std::vector<std::vector<double>>& v, const std::vector<double>& tau, int nsteps,
+                        const std::vector<std::vector<double>>& media, const std::vector<std::vector<double>>& damping,
+                        const std::vector<std::vector<double>>& source, const std::vector<int>& receivers, int record_every,
+                        std::vector<std::vector<std::vector<double>>>* traces, std::vector<mi355cg_results>* results = nullptr,
+                        std::vector<int>* steps_done = nullptr, const std::vector<std::vector<double>>& g = {}, int steps_per_launch = 0) {
+        waveRecorded("waveSpongeMany", u, v, tau, nsteps, &media, &damping, source, receivers, record_every, traces, results, steps_done, g, steps_per_launch);
     }
 private:
-    // both of the above; media: null for the homogeneous medium
+    // all of the above; media: null for the homogeneous medium; damping: null for none (with media only)
     void waveRecorded(const char* who, std::vector<std::vector<double>>& u, std::vector<std::vector<double>>& v, const std::vector<double>& tau, int nsteps,
-                      const std::vector<std::vector<double>>* media, const std::vector<std::vector<double>>& source, const std::vector<int>& receivers,
-                      int record_every, std::vector<std::vector<std::vector<double>>>* traces, std::vector<mi355cg_results>* results,
-                      std::vector<int>* steps_done, const std::vector<std::vector<double>>& g, int steps_per_launch) {
+                      const std::vector<std::vector<double>>* media, const std::vector<std::vector<double>>* damping,
+                      const std::vector<std::vector<double>>& source, const std::vector<int>& receivers, int record_every,
+                      std::vector<std::vector<std::vector<double>>>* traces, std::vector<mi355cg_results>* results, std::vector<int>* steps_done, const std::vector<std::vector<double>>& g, int steps_per_launch) {
         const std::string me = std::string(who) + ": ";
         if (u.empty() || u.size() > (size_t)MI355CG_MANY_MAX) throw std::invalid_argument(me + "an ensemble has 1 .. MI355CG_MANY_MAX members");
         const size_t n = rhs.size(), k = u.size();
@@ -620,19 +632,29 @@ private:
             if (source[s].size() != row) throw std::invalid_argument(me + "a row of the source has nsteps + 1 amplitudes");
             std::copy(source[s].begin(), source[s].end(), wp.begin() + (std::ptrdiff_t)(s * row));
         }
-        std::vector<double> cp;
-        if (media) {
-            if (media->size() != 1 && media->size() != k) throw std::invalid_argument(me + "media has one vector, or one per member");
-            cp.resize(media->size() * n);
-            for (size_t s = 0; s < media->size(); ++s) {
-                if ((*media)[s].size() != n) throw std::invalid_argument(me + "a medium does not have the size of the system");
-                std::copy((*media)[s].begin(), (*media)[s].end(), cp.begin() + (std::ptrdiff_t)(s * n));
+        // a field per unknown, one for all members or one each: packed
+        auto packed = [&](const std::vector<std::vector<double>>* field, const char* count, const char* size) {
+            std::vector<double> p;
+            if (!field) return p;
+            if (field->size() != 1 && field->size() != k) throw std::invalid_argument(me + count);
+            p.resize(field->size() * n);
+            for (size_t s = 0; s < field->size(); ++s) {
+                if ((*field)[s].size() != n) throw std::invalid_argument(me + size);
+                std::copy((*field)[s].begin(), (*field)[s].end(), p.begin() + (std::ptrdiff_t)(s * n));
             }
-        }
+            return p;
+        };
+        const std::vector<double> cp = packed(media, "media has one vector, or one per member", "a medium does not have the size of the system");
+        const std::vector<double> dp = packed(damping, "damping has one vector, or one per member", "a damping field does not have the size of the system");
         std::vector<mi355cg_results> res(k);
         std::vector<int> done(k, 0);
         const long long w_stride = source.size() == 1 ? 0 : (long long)row;
-        if (media)
+        if (damping)
+            mi355cg_compat::check(mi355cg_wave_sponge_many(ctx_->h, (int)k, nsteps, tau.data(), g.empty() ? nullptr : gp.data(), up.data(), vp.data(), cp.data(),
+                                                           media->size() == 1 ? 0 : (long long)n, dp.data(), damping->size() == 1 ? 0 : (long long)n, wp.data(),
+                                                           w_stride, (int)nrec, nrec ? receivers.data() : nullptr, record_every, nrec ? tp.data() : nullptr,
+                                                           steps_per_launch, nullptr, res.data(), done.data()));
+        else if (media)
             mi355cg_compat::check(mi355cg_wave_medium_many(ctx_->h, (int)k, nsteps, tau.data(), g.empty() ? nullptr : gp.data(), up.data(), vp.data(), cp.data(),
                                                            media->size() == 1 ? 0 : (long long)n, wp.data(), w_stride, (int)nrec, nrec ? receivers.data() : nullptr,
                                                            record_every, nrec ? tp.data() : nullptr, steps_per_launch, nullptr, res.data(), done.data()));

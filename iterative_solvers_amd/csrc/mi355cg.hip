@@ -194,6 +194,10 @@ struct OnchipManyWs {
     int med_cap = 0;                    // members the next two hold
     Buf<double> med_range;              // the least and the largest entry of every member's medium (k_oc_medium_range)
     Buf<double> med_range_h;            // pinned copy
+    // mi355cg_wave_sponge_many* on top (onchip_wave_sponge_workspace_bytes), allocated by the first such call
+    int damp_cap = 0;                   // members the next two hold
+    Buf<double> damp_range;             // the least and the largest entry of every member's damping row (k_oc_medium_range)
+    Buf<double> damp_range_h;           // pinned copy
 };
 
 // `small` and its pinned mirror in a call of nsys <= cap systems: nsys x FB_COUNT update partials, then nsys diagonals, then nsys ||r0||_2
@@ -3479,7 +3483,9 @@ static int wave_upload(mi355cg_ctx* c, OnchipManyWs* W, int nsys, const double* 
 // What mi355cg_wave_record_many* adds to an explicit call: w and traces in device memory, nodes (the packed
 // indices of the receivers) in host memory; w_stride 0: one row of amplitudes for all members.
 // c2 (or NULL: none): the media of mi355cg_wave_medium_many* (section 12.5) in device memory; c2_stride 0: one for all members.
-struct WaveRecord { const double* w; long long w_stride; int nrec; const int* nodes; int every; double* traces; const double* c2 = nullptr; long long c2_stride = 0; };
+// d (or NULL: none; with c2 only): the damping rows of mi355cg_wave_sponge_many* (section 12.6), likewise.
+struct WaveRecord { const double* w; long long w_stride; int nrec; const int* nodes; int every; double* traces; const double* c2 = nullptr; long long c2_stride = 0;
+                    const double* d = nullptr; long long d_stride = 0; };
 
 // Explicit: ceil(nsteps / m) launches of m steps; before each the host waits for the one before it and tests the caller's flag.
 // rec: with a source and receivers; every launch is told where in the call it starts.
@@ -3503,13 +3509,15 @@ static int wave_verlet(mi355cg_ctx* c, int nsys, int nsteps, const double* tau, 
         x.traces = rec->traces; x.tr_stride = (long long)(nsteps / rec->every) * rec->nrec;
     }
     const OnchipWaveMediumArgs md{rec ? rec->c2 : nullptr, rec ? rec->c2_stride : 0};
-    const void* k_steps = md.c2 ? onchip_dispatch(R.pl.elems, false, [](auto el, auto) { return (const void*)&k_oc_wave_medium<decltype(el)::value>; })
+    const OnchipWaveSpongeArgs sp{rec ? rec->d : nullptr, rec ? rec->d_stride : 0};
+    const void* k_steps = sp.d  ? onchip_dispatch(R.pl.elems, false, [](auto el, auto) { return (const void*)&k_oc_wave_sponge<decltype(el)::value>; })
+                          : md.c2 ? onchip_dispatch(R.pl.elems, false, [](auto el, auto) { return (const void*)&k_oc_wave_medium<decltype(el)::value>; })
                           : rec ? onchip_dispatch(R.pl.elems, false, [](auto el, auto) { return (const void*)&k_oc_wave_record<decltype(el)::value>; })
                               : onchip_dispatch(R.pl.elems, false, [](auto el, auto) { return (const void*)&k_onchip_wave_verlet<decltype(el)::value>; });
     if (int rc = R.allow_lds(k_steps)) return rc;
     if (int rc = loop_timer_begin(c, c->stream)) return rc;
     const int m = steps_per_launch > 0 ? steps_per_launch : kOnchipWaveDefaultSteps;
-    void* args[] = {&a, &x, (void*)&md};                           // (the plain kernel takes the first alone, the recording one two)
+    void* args[] = {&a, &x, (void*)&md, (void*)&sp};               // (the plain kernel takes the first alone, the recording one two, the medium's three)
     int done = 0;
     while (done < nsteps) {
         if (done > 0) HIPCK(hipStreamSynchronize(c->stream));
@@ -3732,6 +3740,18 @@ static int wave_medium_bounds(mi355cg_ctx* c, int nsys, const double* tau, const
     }
     return MI355CG_OK;
 }
+// k_oc_medium_range's result for rows in host memory: `rows` rows of `len` doubles, row s at p + s * stride.
+static std::vector<double> host_row_ranges(const double* p, long long stride, size_t rows, size_t len) {
+    std::vector<double> range(2 * rows);
+    for (size_t s = 0; s < rows; ++s) {
+        const double* const row = p + s * (size_t)stride;
+        double lo = row[0], hi = row[0];
+        bool bad = false;
+        for (size_t i = 0; i < len; ++i) { bad = bad || !std::isfinite(row[i]); lo = std::fmin(lo, row[i]); hi = std::fmax(hi, row[i]); }
+        range[2 * s] = bad ? NAN : lo; range[2 * s + 1] = bad ? NAN : hi;
+    }
+    return range;
+}
 // The recording workspace, then the ranges on top: built complete before they replace what is there.
 static int onchip_wave_medium_ensure(mi355cg_ctx* c, int nsys, int stage_vecs, long long stage_doubles) {
     if (int rc = onchip_wave_record_ensure(c, nsys, stage_vecs, stage_doubles)) return rc;
@@ -3773,17 +3793,8 @@ int mi355cg_wave_medium_many(mi355cg_handle c, int nsys, int nsteps, const doubl
     if (int rc = wave_medium_check(c, nsys, nsteps, tau, g, u, v, c2, c2_stride, w, w_stride, nrec, rec_nodes, record_every, traces, steps_per_launch, out,
                                    steps_done, true)) return rc;
     const size_t len = (size_t)c->pk_len, mrows = c2_stride ? (size_t)nsys : 1;
-    {                                                              // the media can be read here: the two numbers of a row without a launch
-        std::vector<double> range(2 * mrows);
-        for (size_t s = 0; s < mrows; ++s) {
-            const double* const row = c2 + s * (size_t)c2_stride;
-            double lo = row[0], hi = row[0];
-            bool bad = false;
-            for (size_t i = 0; i < len; ++i) { bad = bad || !std::isfinite(row[i]); lo = std::fmin(lo, row[i]); hi = std::fmax(hi, row[i]); }
-            range[2 * s] = bad ? NAN : lo; range[2 * s + 1] = bad ? NAN : hi;
-        }
-        if (int rc = wave_medium_bounds(c, nsys, tau, range.data(), c2_stride)) return rc;
-    }
+    // the media can be read here: the two numbers of a row without a launch
+    if (int rc = wave_medium_bounds(c, nsys, tau, host_row_ranges(c2, c2_stride, mrows, len).data(), c2_stride)) return rc;
     if (StepChecks::none(nsys, nsteps, steps_done)) return MI355CG_OK;
     HIPCK(hipSetDevice(c->device));
     const size_t row = (size_t)nsteps + 1, rows = w_stride ? (size_t)nsys : 1;             // the tables go up packed: row doubles per row
@@ -3818,6 +3829,124 @@ int mi355cg_wave_medium_cfl(mi355cg_handle c, double c2max, double* tau_max) {
     if (c->is_csr) return fail(MI355CG_ERR_INVALID, "a CSR handle has no grid: the bound is the grid operator's");
     if (!std::isfinite(c2max) || !(c2max > 0.0)) return fail(MI355CG_ERR_INVALID, "c2max %g rejected: the largest squared wave speed is finite and > 0", c2max);
     *tau_max = onchip_wave_medium_cfl(c->gp.A, c2max);
+    return MI355CG_OK;
+}
+// ---- ... with a damping field: u_tt + d o u_t = c2 o (A u) - w(t) g ------------------------------------------
+static_assert(kOnchipWaveSpongeSysBytes == 2 * sizeof(double), "onchip_plan.h: a member's share of the sponge workspace");
+// What both entry points refuse on top of wave_medium_check.
+static int wave_sponge_check(mi355cg_ctx* c, int nsys, int nsteps, const double* tau, const void* g, const void* u, const void* v, const double* c2,
+                             long long c2_stride, const double* d, long long d_stride, const double* w, long long w_stride, int nrec, const int* rec_nodes,
+                             int record_every, const void* traces, int steps_per_launch, const mi355cg_results* out, const int* steps_done, bool host_tables) {
+    if (int rc = wave_medium_check(c, nsys, nsteps, tau, g, u, v, c2, c2_stride, w, w_stride, nrec, rec_nodes, record_every, traces, steps_per_launch, out,
+                                   steps_done, host_tables)) return rc;
+    if (!d) return fail(MI355CG_ERR_INVALID, "null argument: d, the damping rate of every unknown");
+    if (d_stride != 0 && d_stride < c->pk_len)
+        return fail(MI355CG_ERR_INVALID, "d_stride %lld rejected: 0 (one damping field for all members) or at least the %lld unknowns of a member", d_stride, c->pk_len);
+    const size_t state = sizeof(double) * (size_t)c->gp.size * (size_t)nsys;
+    const size_t dbytes = sizeof(double) * ((d_stride ? (size_t)(nsys - 1) * (size_t)d_stride : 0) + (size_t)c->pk_len);
+    const size_t cbytes = sizeof(double) * ((c2_stride ? (size_t)(nsys - 1) * (size_t)c2_stride : 0) + (size_t)c->pk_len);
+    const size_t wbytes = sizeof(double) * ((size_t)(nsys - 1) * (size_t)w_stride + (size_t)nsteps + 1);
+    const size_t tbytes = nrec > 0 ? sizeof(double) * (size_t)nsys * (size_t)(nsteps / record_every) * (size_t)nrec : 0;
+    const struct { const void* p; size_t bytes; const char* name; } vecs[6] = {{u, state, "u"}, {v, state, "v"}, {g, state, "g"}, {c2, cbytes, "c2"},
+                                                                               {w, wbytes, "w"}, {traces, tbytes, "traces"}};
+    for (const auto& q : vecs)
+        if (ranges_meet(d, dbytes, q.p, q.bytes)) return fail(MI355CG_ERR_INVALID, "d overlaps %s", q.name);
+    return MI355CG_OK;
+}
+// range: the least and the largest entry of every damping row, as for the media.  Every member against its row: no entry below
+// zero, and (0.25 tau_s) max d_s, the e of onchip_wave_sponge_factor, at most kOnchipWaveSpongeMaxE -- beyond it the factor is
+// negative and tends to -1, so that stronger damping would damp less.
+static int wave_sponge_bounds(int nsys, const double* tau, const double* range, long long d_stride) {
+    for (int s = 0; s < nsys; ++s) {
+        const double lo = range[d_stride ? 2 * s : 0], hi = range[d_stride ? 2 * s + 1 : 1];
+        const char* const shared = d_stride ? "" : " (the one damping field of all members)";
+        if (!std::isfinite(lo) || !std::isfinite(hi))
+            return fail(MI355CG_ERR_INVALID, "damping of member %d rejected%s: an entry of d is not finite", s, shared);
+        if (lo < 0.0)
+            return fail(MI355CG_ERR_INVALID, "damping of member %d rejected%s: its least entry is %g, and d, a damping rate, must be >= 0", s, shared, lo);
+        if ((0.25 * tau[s]) * hi > kOnchipWaveSpongeMaxE)
+            return fail(MI355CG_ERR_INVALID, "damping of member %d rejected%s: its largest entry %.17g with the time step %.17g needs d <= 4 / tau = %.17g; beyond it the "
+                        "factor (1 - tau d / 4) / (1 + tau d / 4) turns negative and damps less", s, shared, hi, tau[s], 4.0 / tau[s]);
+    }
+    return MI355CG_OK;
+}
+// The medium workspace, then the second pair of ranges on top: built complete before they replace what is there.
+static int onchip_wave_sponge_ensure(mi355cg_ctx* c, int nsys, int stage_vecs, long long stage_doubles) {
+    if (int rc = onchip_wave_medium_ensure(c, nsys, stage_vecs, stage_doubles)) return rc;
+    OnchipManyWs* W = c->many.get();
+    if (W->damp_cap < nsys) {
+        auto failed = [&](const char* what) { return fail(MI355CG_ERR_HIP, "on-chip wave sponge workspace for %d members: %s allocation failed", nsys, what); };
+        Buf<double> range, range_h;
+        if (Buf<double>::device(range, 2LL * nsys)) return failed("range");
+        if (Buf<double>::pinned(range_h, 2LL * nsys)) return failed("pinned copy");
+        HIPCK(hipStreamSynchronize(c->stream));
+        W->damp_range = std::move(range); W->damp_range_h = std::move(range_h);
+        W->damp_cap = nsys;
+    }
+    return MI355CG_OK;
+}
+
+int mi355cg_wave_sponge_many_device(mi355cg_handle c, int nsys, int nsteps, const double* tau, const double* g_dev, double* u_dev, double* v_dev,
+                                    const double* c2_dev, long long c2_stride, const double* d_dev, long long d_stride, const double* w_dev,
+                                    long long w_stride, int nrec, const int* rec_nodes, int record_every, double* traces_dev, int steps_per_launch,
+                                    const volatile int* stop_flag, mi355cg_results* out, int* steps_done) {
+    if (int rc = wave_sponge_check(c, nsys, nsteps, tau, g_dev, u_dev, v_dev, c2_dev, c2_stride, d_dev, d_stride, w_dev, w_stride, nrec, rec_nodes, record_every,
+                                   traces_dev, steps_per_launch, out, steps_done, false)) return rc;
+    if (StepChecks::none(nsys, nsteps, steps_done)) return MI355CG_OK;
+    HIPCK(hipSetDevice(c->device));
+    if (int rc = onchip_wave_sponge_ensure(c, nsys, 0, 0)) return rc;
+    OnchipManyWs* W = c->many.get();
+    const int crows = c2_stride ? nsys : 1, drows = d_stride ? nsys : 1;                   // two launches of the one range kernel, one wait
+    hipLaunchKernelGGL(k_oc_medium_range, dim3(crows), dim3(kOcRangeThreads), 0, c->stream, c2_dev, c2_stride, (int)c->pk_len, W->med_range.get());
+    HIPCK(hipGetLastError());
+    hipLaunchKernelGGL(k_oc_medium_range, dim3(drows), dim3(kOcRangeThreads), 0, c->stream, d_dev, d_stride, (int)c->pk_len, W->damp_range.get());
+    HIPCK(hipGetLastError());
+    HIPCK(hipMemcpyAsync(W->med_range_h, W->med_range, sizeof(double) * 2 * crows, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(hipMemcpyAsync(W->damp_range_h, W->damp_range, sizeof(double) * 2 * drows, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(hipStreamSynchronize(c->stream));
+    if (int rc = wave_medium_bounds(c, nsys, tau, W->med_range_h, c2_stride)) return rc;
+    if (int rc = wave_sponge_bounds(nsys, tau, W->damp_range_h, d_stride)) return rc;
+    const WaveRecord rec{w_dev, w_stride, nrec, rec_nodes, record_every, traces_dev, c2_dev, c2_stride, d_dev, d_stride};
+    return wave_verlet(c, nsys, nsteps, tau, g_dev, u_dev, v_dev, steps_per_launch, stop_flag, out, steps_done, &rec);
+}
+int mi355cg_wave_sponge_many(mi355cg_handle c, int nsys, int nsteps, const double* tau, const double* g, double* u, double* v, const double* c2,
+                             long long c2_stride, const double* d, long long d_stride, const double* w, long long w_stride, int nrec, const int* rec_nodes,
+                             int record_every, double* traces, int steps_per_launch, const volatile int* stop_flag, mi355cg_results* out, int* steps_done) {
+    if (int rc = wave_sponge_check(c, nsys, nsteps, tau, g, u, v, c2, c2_stride, d, d_stride, w, w_stride, nrec, rec_nodes, record_every, traces,
+                                   steps_per_launch, out, steps_done, true)) return rc;
+    const size_t len = (size_t)c->pk_len, mrows = c2_stride ? (size_t)nsys : 1, drows = d_stride ? (size_t)nsys : 1;
+    if (int rc = wave_medium_bounds(c, nsys, tau, host_row_ranges(c2, c2_stride, mrows, len).data(), c2_stride)) return rc;
+    if (int rc = wave_sponge_bounds(nsys, tau, host_row_ranges(d, d_stride, drows, len).data(), d_stride)) return rc;
+    if (StepChecks::none(nsys, nsteps, steps_done)) return MI355CG_OK;
+    HIPCK(hipSetDevice(c->device));
+    const size_t row = (size_t)nsteps + 1, rows = w_stride ? (size_t)nsys : 1;             // the tables go up packed: row doubles per row
+    const size_t sample = (size_t)nrec, samples = (size_t)(nsteps / record_every);          // a member's traces: samples x sample doubles
+    if (int rc = onchip_wave_sponge_ensure(c, nsys, 5, (long long)(rows * row + (size_t)nsys * samples * sample))) return rc;
+    const size_t count = len * (size_t)nsys;                       // g, u, v, the media, then the damping rows (packed: nsys vectors, or one)
+    double* const g_dev = c->many->stage; double* const u_dev = g_dev + count; double* const v_dev = u_dev + count; double* const c2_dev = v_dev + count;
+    double* const d_dev = c2_dev + count;
+    double* const w_dev = c->many->rec_stage; double* const traces_dev = w_dev + rows * row;
+    const StagedGroup groups[3] = {{0, g, nullptr}, {count, u, u}, {2 * count, v, v}};
+    return run_staged_groups(c, g_dev, count, groups, [&]() {
+        HIPCK(hipMemcpy2DAsync(c2_dev, sizeof(double) * len, c2, sizeof(double) * (c2_stride ? (size_t)c2_stride : len), sizeof(double) * len, mrows, hipMemcpyHostToDevice, c->stream));
+        HIPCK(hipMemcpy2DAsync(d_dev, sizeof(double) * len, d, sizeof(double) * (d_stride ? (size_t)d_stride : len), sizeof(double) * len, drows, hipMemcpyHostToDevice, c->stream));
+        HIPCK(hipMemcpy2DAsync(w_dev, sizeof(double) * row, w, sizeof(double) * (w_stride ? (size_t)w_stride : row), sizeof(double) * row, rows, hipMemcpyHostToDevice, c->stream));
+        const WaveRecord rec{w_dev, w_stride ? (long long)row : 0, nrec, rec_nodes, record_every, nrec ? traces_dev : nullptr, c2_dev, c2_stride ? (long long)len : 0,
+                             d_dev, d_stride ? (long long)len : 0};
+        if (int rc = wave_verlet(c, nsys, nsteps, tau, g ? g_dev : nullptr, u_dev, v_dev, steps_per_launch, stop_flag, out, steps_done, &rec)) return rc;
+        const size_t ran = (size_t)(steps_done[0] / record_every) * sample;                 // the samples of the steps that ran come down
+        if (ran) HIPCK(hipMemcpy2DAsync(traces, sizeof(double) * samples * sample, traces_dev, sizeof(double) * samples * sample, sizeof(double) * ran, (size_t)nsys,
+                                        hipMemcpyDeviceToHost, c->stream));
+        return (int)MI355CG_OK;
+    });
+}
+int mi355cg_wave_sponge_many_workspace(int n, int nsys, int nsteps, int nrec, int record_every, long long* bytes) {
+    if (!bytes) return fail(MI355CG_ERR_INVALID, "null argument");
+    const long long v = onchip_wave_sponge_workspace_bytes(n, nsys, nsteps, nrec, record_every);
+    if (v == 0)
+        return fail(MI355CG_ERR_INVALID, "recorded wave ensemble with a damping field rejected: even n from 6 to %d, 1 .. %d members, 0 .. %d steps, 0 .. %d receivers, record_every >= 1",
+                    kOnchipMaxN, kOnchipStepsMaxSys, kOnchipStepsMaxSteps, kOnchipWaveMaxRec);
+    *bytes = v;
     return MI355CG_OK;
 }
 int mi355cg_wave_cfl(mi355cg_handle c, double* tau_max) {

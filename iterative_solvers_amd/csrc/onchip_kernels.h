@@ -870,6 +870,101 @@ __global__ __launch_bounds__(kOnchipMaxThreads) void k_oc_wave_medium(const Onch
     }
 }
 
+// With a damping field (mi355cg_wave_sponge_many*): u_tt + d o u_t = c2 o (A u) - w(t) g, v scaled by
+// onchip_wave_sponge_factor at both ends of every step.  A fifth per-slot array does not fit beside v, acc, g and c2 at E = 24,
+// so this is k_oc_wave_medium with the loop rotated: acc lives only from the second half kick of a step to the first of the
+// next, with nothing but barrier 1 and the back edge between, so both kicks are made in one pass behind barrier 2, the
+// acceleration is a temporary, and its registers hold the factors.  At entry: the opening damp and the first half kick.  In the
+// loop: barrier 1, the drift, barrier 2, then a, the second kick, the closing damp and -- unless this is the launch's last step
+// -- the next step's opening damp and first kick with the same a (damping does not touch u).  The last step of a launch ends
+// behind its closing damp, so launches and chained calls stay invisible: the next launch forms the same a from (u, g, c2,
+// w[step0]).  The host never launches m = 0 steps.  Everything else is k_oc_wave_medium's; a kernel of its own for its reason.
+struct OnchipWaveSpongeArgs { const double* d; long long d_stride; };        // member s reads d + s * d_stride (0: one vector for all)
+template <int E>
+__global__ __launch_bounds__(kOnchipMaxThreads) void k_oc_wave_sponge(const OnchipWaveArgs a, const OnchipWaveRecArgs x, const OnchipWaveMediumArgs md,
+                                                                      const OnchipWaveSpongeArgs sp) {
+    const OnchipPlan& pl = a.pl;
+    extern __shared__ __attribute__((aligned(16))) char oc_dyn_lds[];
+    double* const wbuf = reinterpret_cast<double*>(oc_dyn_lds);
+    double* const img = OcMany::lds(pl.cells).img;
+    const int t = threadIdx.x, T = blockDim.x, pitch = pl.pitch;
+    const long long sys = blockIdx.x;
+    const double tau = a.tau[sys], h = 0.5 * tau;
+    const double* const gin = a.g + sys * a.g_stride;
+    const double* const cin = md.c2 + sys * md.c2_stride;
+    const double* const din = sp.d + sys * sp.d_stride;
+    double* const uio = a.u + sys * a.stride; double* const vio = a.v + sys * a.stride;
+    const double* const wrow = x.w + sys * x.w_stride + x.step0;   // wrow[s]: at the start of the launch's step s, wrow[s + 1]: at its end
+    double* trow = x.traces + sys * x.tr_stride + (long long)x.slot * x.nrec;
+
+    for (int i = t; i < pl.cells; i += T) img[i] = 0.0;
+    __syncthreads();                                               // the image is zero everywhere before the owners fill their cells
+    unsigned cell2[(E + 1) / 2] = {};
+    double v[E], g[E], c2[E], sf[E];
+    int cnt = 0;
+#pragma unroll
+    for (int k = 0; k < E; ++k) {
+        const int i = onchip_owned(pl, t, k);
+        if (i >= 0) {                                              // (slots beyond cnt are never read: nothing to initialise)
+            int xx, yy;
+            onchip_node(pl, i, &xx, &yy);
+            const int c = onchip_cell(pl, xx, yy);
+            cell2[k / 2] |= (unsigned)c << (16 * (k & 1));
+            img[c] = uio[i]; v[k] = vio[i]; g[k] = gin[i]; c2[k] = cin[i]; sf[k] = onchip_wave_sponge_factor(tau, din[i]);
+            cnt = k + 1;
+        }
+    }
+    if (t < kOcAmpBlock && t < a.m) wbuf[t] = wrow[t + 1];
+    int rcell = 0, phase = x.phase;
+    if (t < x.nrec) rcell = x.rec_cell[t];
+    double w_now = wrow[0], w_next = 0.0;
+    __syncthreads();
+    auto own_cell = [&](int k) { unsigned cc = cell2[k / 2]; asm volatile("" : "+v"(cc)); return (int)((cc >> (16 * (k & 1))) & 0xffffu); };
+    auto accel_at = [&](int c, double ck, double f) { return onchip_wave_medium_accel(a.k, ck, f, img[c], img[c - 1], img[c + 1], img[c - pitch], img[c + pitch]); };
+#pragma unroll
+    for (int k = 0; k < E; ++k) if (k < cnt) {
+        const double acc = accel_at(own_cell(k), c2[k], onchip_wave_forcing(w_now, g[k]));
+        v[k] = onchip_wave_kick(onchip_wave_damp(sf[k], v[k]), h, acc);        // the opening damp, then vh
+        __builtin_amdgcn_sched_barrier(0);
+    }
+
+    for (int s = 0; s < a.m; ++s) {
+        __syncthreads();                                           // barrier 1: every neighbour has read the old cells
+        w_now = wbuf[((s / kOcAmpBlock) & 1) * kOcAmpBlock + s % kOcAmpBlock];        // the amplitude at the END of this step
+#pragma unroll
+        for (int k = 0; k < E; ++k) if (k < cnt) {
+            const int c = own_cell(k);
+            img[c] = onchip_wave_drift(img[c], tau, v[k]);         // v holds vh
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        __syncthreads();                                           // barrier 2: the new image is complete
+        const bool more = s + 1 < a.m;                             // uniform: the next step is this launch's too
+#pragma unroll
+        for (int k = 0; k < E; ++k) if (k < cnt) {
+            const double acc = accel_at(own_cell(k), c2[k], onchip_wave_forcing(w_now, g[k]));
+            v[k] = onchip_wave_damp(sf[k], onchip_wave_kick(v[k], h, acc));    // the second kick, the closing damp
+            if (more) v[k] = onchip_wave_kick(onchip_wave_damp(sf[k], v[k]), h, acc);  // the next step's opening damp and vh
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        if (++phase == x.every) {                                  // uniform: this step is sampled
+            phase = 0;
+            if (t < x.nrec) trow[t] = img[rcell];
+            trow += x.nrec;
+        }
+        const int q = s % kOcAmpBlock, nb = s - q + kOcAmpBlock + t;                  // this lane's step in the next block
+        if (t < kOcAmpBlock && nb < a.m) {
+            if (q == 0) w_next = wrow[nb + 1];
+            if (q == kOcAmpBlock / 2) wbuf[((nb / kOcAmpBlock) & 1) * kOcAmpBlock + t] = w_next;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < E; ++k) if (k < cnt) {
+        int i = k * T + t;
+        asm volatile("" : "+v"(i));                                // recomputed here, not carried through the loop
+        uio[i] = img[own_cell(k)]; vio[i] = v[k];
+    }
+}
+
 // The check launch for media in device memory: workgroup b reduces row b of the media (`rows` of them, `len` doubles each, row b
 // at c2 + b * stride) to its least and its largest entry and writes them to out[2 b], out[2 b + 1]; a row with an entry that is
 // not finite gets NaN in both.  The host reads them back once and refuses there, so that the message can name the member.

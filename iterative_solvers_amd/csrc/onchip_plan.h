@@ -238,6 +238,27 @@ MI355CG_HD inline long long onchip_wave_medium_workspace_bytes(int n, int nsys, 
     const long long record = onchip_wave_record_workspace_bytes(n, nsys, nsteps, nrec, record_every);
     return record == 0 ? 0 : record + (long long)nsys * kOnchipWaveMediumSysBytes;
 }
+// A damping field (mi355cg_wave_sponge_many): u_tt + d o u_t = c2 o (A u) - w(t) g with the damping rate
+// d >= 0 (1 / time) of every unknown, for absorbing (sponge) layers.  The damping flow v' = -d v over tau / 2 enters at both ends
+// of the step as its Cayley transform, one factor per unknown formed once per launch; one rounding per operation, the division
+// IEEE's.  d = 0 gives s = 1.0 and 1.0 * v == v: the bits of the medium call.
+//   e = (0.25 tau) d;  s = (1 - e) / (1 + e);
+//   v = s v;  f = w[n] g;  a = c2 au(u) - f;  vh = v + h a;  u = u + tau vh;  f = w[n + 1] g;  a = c2 au(u) - f;  v = vh + h a;  v = s v
+// |s| <= 1 for e >= 0, but s < 0 for e > 1 and s -> -1 (no damping at all) as e grows: kOnchipWaveSpongeMaxE is the largest
+// (0.25 tau) max d a call takes.  No new restriction on tau: onchip_wave_medium_cfl stays the bound.
+constexpr double kOnchipWaveSpongeMaxE = 1.0;
+MI355CG_HD inline double onchip_wave_sponge_factor(double tau, double d) {
+    const double e = (0.25 * tau) * d;
+    return (1.0 - e) / (1.0 + e);
+}
+MI355CG_HD inline double onchip_wave_damp(double s, double v) { return s * v; }
+// Its workspace: that of the medium call and two more doubles per member, the least and the largest entry of its damping row.
+// (The host entry point stages the damping rows beside the media: nsys packed vectors, or one.)  0: refused as there.
+constexpr int kOnchipWaveSpongeSysBytes = 2 * 8;
+MI355CG_HD inline long long onchip_wave_sponge_workspace_bytes(int n, int nsys, int nsteps, int nrec, int record_every) {
+    const long long medium = onchip_wave_medium_workspace_bytes(n, nsys, nsteps, nrec, record_every);
+    return medium == 0 ? 0 : medium + (long long)nsys * kOnchipWaveSpongeSysBytes;
+}
 // Steps of one explicit launch when the caller does not say: the host tests the stop flag between two launches, so the longest
 // launch is the latency of a stop request, to stay under 10 ms.  Measured on one MI355X at N = 128, a launch of 1024 steps: 3.7 ms
 // for one member, 4.0 ms for 256, 15.3 ms for 1024 members (one workgroup per CU at that size, so four in turn) -- hence half of

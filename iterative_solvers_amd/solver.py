@@ -463,9 +463,10 @@ class _Handle:
         return (u, v, list(res), steps_done) + ((step_it,) if step_iterations else ())
 
     def wave_record_many(self, u0, v0, tau, nsteps: int, source, g=None, receivers=None, record_every: int = 1, steps_per_launch: int = 0,
-                         stop_flag: Optional[C.c_int] = None, traces=None, c2=None):
+                         stop_flag: Optional[C.c_int] = None, traces=None, c2=None, damping=None):
         """Extension (no reference twin): wave_steps_many with WAVE_VERLET, a source time function and receiver traces
-        (mi355cg_wave_record_many).  c2 (or None): a medium, [size] (one for all members) or [nsys, size] of u0's kind, the squared
+        (mi355cg_wave_record_many).  damping (or None): a damping rate per unknown, [size] or [nsys, size] of u0's kind; the call is
+        then mi355cg_wave_sponge_many, u_tt + d o u_t = c2 o (A u) - w(t) g, in a unit medium when c2 is None.  c2 (or None): a medium, [size] (one for all members) or [nsys, size] of u0's kind, the squared
         wave speed of every unknown; the call is then mi355cg_wave_medium_many, u_tt = c2 o (A u) - w(t) g.  source: the amplitudes, [nsteps + 1] (one row for all members) or [nsys, nsteps + 1], of u0's
         kind; the forcing of member s at its local time n tau[s] is source[s][n] * g[s].  receivers: a sequence of at most
         WAVE_MAX_RECEIVERS packed indices, or None; record_every: the cadence.  Returns (u, v, traces, [Results per member],
@@ -488,15 +489,26 @@ class _Handle:
         shapes = ((nsteps + 1,), (nsys, nsteps + 1))
         tshape = (nsys, nsteps // record_every, nrec)
         cshapes = ((self.size,), (nsys, self.size))
-        if c2 is not None and not on_device:
-            if hasattr(c2, "data_ptr"):
-                raise ValueError("c2 is of the kind (NumPy / CUDA tensor) of u0")
-            c2 = np.ascontiguousarray(c2, dtype=np.float64)
-            if c2.shape not in cshapes:
-                raise ValueError(f"c2 has shape {c2.shape}, expected {cshapes[0]} or {cshapes[1]}")
+        if damping is not None and c2 is None:                       # a unit medium: 1.0 * t == t
+            if on_device:
+                import torch
+                c2 = torch.ones(self.size, dtype=torch.float64, device=u0.device)
+            else:
+                c2 = np.ones(self.size)
+        if not on_device:
+            fields = {"c2": c2, "damping": damping}
+            for name, a in fields.items():
+                if a is None:
+                    continue
+                if hasattr(a, "data_ptr"):
+                    raise ValueError(f"{name} is of the kind (NumPy / CUDA tensor) of u0")
+                a = fields[name] = np.ascontiguousarray(a, dtype=np.float64)
+                if a.shape not in cshapes:
+                    raise ValueError(f"{name} has shape {a.shape}, expected {cshapes[0]} or {cshapes[1]}")
+            c2, damping = fields["c2"], fields["damping"]
         if on_device:
             import torch
-            for name, a, want in (("source", source, shapes), ("traces", traces, (tshape,)), ("c2", c2, cshapes)):
+            for name, a, want in (("source", source, shapes), ("traces", traces, (tshape,)), ("c2", c2, cshapes), ("damping", damping, cshapes)):
                 if a is not None and not (hasattr(a, "data_ptr") and a.is_cuda and a.device == u0.device and a.dtype == torch.float64
                                           and tuple(a.shape) in want and a.is_contiguous()):
                     raise ValueError(f"{name} beside CUDA states is a contiguous float64 tensor of shape {' or '.join(map(str, want))} on {u0.device}")
@@ -504,8 +516,9 @@ class _Handle:
             if nrec and traces is None:
                 traces = torch.zeros(tshape, dtype=torch.float64, device=u0.device)
             torch.cuda.current_stream(u0.device).synchronize()
-            fn = self._lib.mi355cg_wave_record_many_device if c2 is None else self._lib.mi355cg_wave_medium_many_device
-            medium = () if c2 is None else (c2.data_ptr(), self.size if c2.dim() == 2 else 0)
+            fn = (self._lib.mi355cg_wave_record_many_device if c2 is None else self._lib.mi355cg_wave_medium_many_device if damping is None
+                  else self._lib.mi355cg_wave_sponge_many_device)
+            medium = tuple(x for a in (c2, damping) if a is not None for x in (a.data_ptr(), self.size if a.dim() == 2 else 0))
             rc = fn(self._h, nsys, nsteps, tau.ctypes.data, g.data_ptr() if g is not None else None, u.data_ptr(), v.data_ptr(), *medium, source.data_ptr(),
                     nsteps + 1 if source.dim() == 2 else 0, nrec, nodes.ctypes.data if nrec else None, record_every, traces.data_ptr() if nrec else None,
                     int(steps_per_launch), sp, res, steps_done.ctypes.data)
@@ -521,8 +534,9 @@ class _Handle:
                 g = np.ascontiguousarray(g)
             if nrec and traces is None:
                 traces = np.zeros(tshape)
-            fn = self._lib.mi355cg_wave_record_many if c2 is None else self._lib.mi355cg_wave_medium_many
-            medium = () if c2 is None else (c2.ctypes.data, self.size if c2.ndim == 2 else 0)
+            fn = (self._lib.mi355cg_wave_record_many if c2 is None else self._lib.mi355cg_wave_medium_many if damping is None
+                  else self._lib.mi355cg_wave_sponge_many)
+            medium = tuple(x for a in (c2, damping) if a is not None for x in (a.ctypes.data, self.size if a.ndim == 2 else 0))
             rc = fn(self._h, nsys, nsteps, tau.ctypes.data, g.ctypes.data if g is not None else None, u.ctypes.data, v.ctypes.data, *medium, source.ctypes.data,
                     nsteps + 1 if source.ndim == 2 else 0, nrec, nodes.ctypes.data if nrec else None, record_every, traces.ctypes.data if nrec else None,
                     int(steps_per_launch), sp, res, steps_done.ctypes.data)
@@ -749,6 +763,44 @@ def wave_medium_many_workspace(n: int, nsys: int, nsteps: int, nrec: int = 0, re
     return out.value
 
 
+def wave_sponge_many_workspace(n: int, nsys: int, nsteps: int, nrec: int = 0, record_every: int = 1) -> int:
+    """The device workspace bytes of MatrixFreeSystem.wave_record_many with a damping field (host arithmetic, no GPU;
+    mi355cg_wave_sponge_many_workspace): those of the call with c2 alone and 16 bytes per member.  ValueError for what the call refuses."""
+    out = C.c_longlong()
+    lib = _capi.load()
+    rc = lib.mi355cg_wave_sponge_many_workspace(int(n), int(nsys), int(nsteps), int(nrec), int(record_every), C.byref(out))
+    if rc == _capi.ERR_INVALID:
+        raise ValueError(lib.mi355cg_last_error().decode())
+    _capi.check(rc)
+    return out.value
+
+
+def sponge_damping(n: int, width: int, dmax: float, sides: str = "lrbt"):
+    """A sponge layer for wave_record_many(damping=) on the L-shaped grid of n intervals a side, pure NumPy: the [size] field
+    dmax * ((width - k) / width)^2 in the packed order, k the node distance of an unknown to the nearest chosen outer side of the
+    bounding square, counted from the first interior line (k = 0 there: the field is dmax; the side itself holds no unknown), 0
+    where k >= width: `width` lines of unknowns are damped.  sides: letters of "lrbt" -- left (ix = 0), right (ix = n), bottom
+    (iy = 0), top (iy = n).  The two sides of the cut-out quadrant are not outer sides: they stay reflecting."""
+    n, width = int(n), int(width)
+    if n < 2 or n % 2:
+        raise ValueError(f"n = {n} rejected: the grid has an even number of intervals a side")
+    if width < 1:
+        raise ValueError(f"width {width} rejected: a layer is at least one node wide")
+    if not np.isfinite(dmax) or dmax < 0:
+        raise ValueError(f"dmax {dmax} rejected: a damping rate is finite and >= 0")
+    if not sides or set(sides) - set("lrbt"):
+        raise ValueError(f"sides {sides!r} rejected: letters of 'lrbt'")
+    half = n // 2
+    # the packed order (packed_index): the bottom-right block row-major, then the upper block row-major
+    ix = np.concatenate([np.tile(np.arange(half + 1, n), half), np.tile(np.arange(1, n), half - 1)])
+    iy = np.concatenate([np.repeat(np.arange(1, half + 1), half - 1), np.repeat(np.arange(half + 1, n), n - 1)])
+    k = np.full(ix.shape, width)
+    for side, dist in (("l", ix), ("r", n - ix), ("b", iy), ("t", n - iy)):
+        if side in sides:
+            k = np.minimum(k, dist - 1)
+    return float(dmax) * ((width - k) / width) ** 2
+
+
 def rayleigh_ritz(g, h):
     """The Rayleigh-Ritz step of eigs on the host (mi355cg_rayleigh_ritz, no GPU): for the k x k pair G = S^T S, H = S^T K S
     (k <= 48) returns (theta[k] ascending, coef[k, k]) with coef.T @ G @ coef = I and coef.T @ H @ coef = diag(theta).
@@ -939,9 +991,13 @@ class MatrixFreeSystem:
                                             stop_flag=stop_flag, step_iterations=step_iterations)
 
     def wave_record_many(self, u0, v0, tau, nsteps: int, source, g=None, receivers=None, record_every: int = 1, steps_per_launch: int = 0,
-                         stop_flag: Optional[C.c_int] = None, traces=None, c2=None):
+                         stop_flag: Optional[C.c_int] = None, traces=None, c2=None, damping=None):
         """Extension (no reference twin): wave_steps_many with WAVE_VERLET, a source time function and receiver traces, all inside
-        the launch.  c2 (None: the homogeneous medium, exactly the call without it): the squared wave speed of every unknown,
+        the launch.  damping (None: none, exactly the call without it): a damping rate d >= 0 (1 / time) of every unknown, [size] or
+        [nsys, size] of u0's kind, for absorbing layers (sponge_damping builds one); member s then integrates
+        u_tt + d_s o u_t = c2_s o (A u) - source_s(t) g_s, in a unit medium when c2 is None, with v scaled by
+        (1 - tau d / 4) / (1 + tau d / 4) at both ends of every step; tau_s * max d_s must not exceed 4, the bound on tau is
+        unchanged, and d = 0 gives the bits of the call with c2 alone.  c2 (None: the homogeneous medium, exactly the call without it): the squared wave speed of every unknown,
         [size] (one medium for all members) or [nsys, size], positive, of u0's kind; member s then integrates
         u_tt = c2_s o (A u) - source_s(t) g_s (the source is not scaled), and its tau must not exceed wave_cfl(c2)[s].  c2 = 1
         gives the bits of the call without it.  source: [nsteps + 1] (one row for all members) or [nsys, nsteps + 1] amplitudes of u0's kind; member s feels
@@ -954,7 +1010,14 @@ class MatrixFreeSystem:
         traces: an array of that shape to write into; a stop flag leaves the samples of steps that did not run untouched.  u0,
         v0, tau, g, steps_per_launch and stop_flag as in wave_steps_many; this system is left as it was."""
         return self._handle.wave_record_many(u0, v0, tau, nsteps, source, g=g, receivers=receivers, record_every=record_every,
-                                             steps_per_launch=steps_per_launch, stop_flag=stop_flag, traces=traces, c2=c2)
+                                             steps_per_launch=steps_per_launch, stop_flag=stop_flag, traces=traces, c2=c2, damping=damping)
+
+    def sponge_damping(self, width: int, dmax: float, sides: str = "lrbt"):
+        """The damping field of a sponge layer on this system's grid, for wave_record_many(damping=): the module's
+        sponge_damping(n, width, dmax, sides).  ValueError on a grid that is not square (the packed order is packed_index's)."""
+        if self.m != self.n:
+            raise ValueError(f"sponge_damping is defined on square grids, not {self.m} x {self.n}")
+        return sponge_damping(self.n, width, dmax, sides)
 
     def packed_index(self, ix: int, iy: int) -> int:
         """The packed index of grid node (ix, iy), 0 <= ix, iy <= n, in the order of the batch and ensemble calls (solve_many,
