@@ -50,6 +50,8 @@
  *   mi355cg_wave_record_many / _device / _workspace   the explicit scheme with a source time function and receiver traces
  *   mi355cg_wave_medium_many / _device / _workspace / mi355cg_wave_medium_cfl   that scheme in a medium: a squared wave speed per unknown and member
  *   mi355cg_wave_sponge_many / _device / _workspace   ... with a damping rate per unknown and member: absorbing (sponge) layers
+ *   mi355cg_wave_history_many / _device / mi355cg_wave_history_bytes   the scheme in a medium, keeping the history au(u_n) of every step
+ *   mi355cg_wave_adjoint_many / _device / _workspace   its exact transpose: adjoint steps and the sensitivity to c2
  *
  * Plain pointers and sizes only; no C++/torch types.  All host vectors are in the reference's
  * PACKED unknown order (bottom-right block row-major, then the upper block row-major;
@@ -673,6 +675,57 @@ int  mi355cg_wave_sponge_many_device(mi355cg_handle h, int nsys, int nsteps, con
                                      double *traces_dev, int steps_per_launch, const volatile int *stop_flag, mi355cg_results *out,
                                      int *steps_done);
 int  mi355cg_wave_sponge_many_workspace(int n, int nsys, int nsteps, int nrec, int record_every, long long *bytes);
+
+/* The adjoint of the scheme in a medium, for the derivative of a trace misfit with respect to c2 (DESIGN section 12.7;
+ * no reference twin): one forward run that keeps its history, one backward run.
+ * mi355cg_wave_history_many: mi355cg_wave_medium_many's arguments and, behind c2, hist and hist_stride -- the same u, v and
+ * traces, bit for bit, and row n of member s's history, size doubles at hist + s * hist_stride + n * size, is
+ *    H[n] = au(u_n),  n = 0 .. nsteps,
+ * the stencil value of the state after n steps before it is scaled by c2.  hist_stride is at least (nsteps + 1) * size;
+ * mi355cg_wave_history_bytes(n, nsys, nsteps) is 8 * nsys * (nsteps + 1) * size, pure host arithmetic.  A call of no steps
+ * writes nothing.  Under a stop flag rows 0 .. steps_done are written.  Refused on top of what mi355cg_wave_medium_many refuses:
+ * a null hist, a hist_stride below (nsteps + 1) * size, hist overlapping u, v, g, c2, w or the traces.
+ * mi355cg_wave_adjoint_many: the exact transpose of the scheme, from state index s = nsteps down to 1, with h = 0.5 tau, lam the
+ * adjoint of u, q = c2 o (the adjoint of v) and S the sensitivity accumulator, every operation rounded once:
+ *    if s % record_every == 0:  lam[rec_nodes[j]] = lam[rec_nodes[j]] + adj[s / record_every - 1][j],  j = 0 .. nrec - 1 ascending
+ *    S = S + q H[s];  lam = lam + h au(q);  q = q + tau (c2 lam);  S = S + q H[s - 1];  lam = lam + h au(q)
+ * adj: the adjoint sources, the derivative of the misfit with respect to the traces -- traces - observed for least squares --
+ * [nsteps / record_every][nrec] per member at adj + s * adj_stride; adj_stride = 0: one table for all members, otherwise at
+ * least (nsteps / record_every) * nrec.  lam, q, S: nsys packed vectors each, in and out.  From lam = q = S = 0:
+ *    dJ/dc2 = h S / c2,   dJ/du0 = lam,   dJ/dv0 = q / c2,
+ * divisions the caller makes once at the end: no division happens inside a call, so a backward run cut into calls at multiples
+ * of record_every -- each with its slice of the history and of adj, from the (lam, q, S) the call before it left -- gives the
+ * bits of one call, and a history can be rebuilt segment by segment from checkpoints of (u, v).  steps_per_launch, stop_flag,
+ * out and steps_done (steps taken, counted from nsteps down) as in mi355cg_wave_medium_many.
+ * MI355CG_ERR_INVALID, the handle's state, right-hand side, shift and solve mode untouched and nothing written: what
+ * mi355cg_wave_medium_many refuses of nsys, nsteps, tau, c2, c2_stride, the receivers and steps_per_launch; a member's tau above
+ * its own bound mi355cg_wave_medium_cfl(h, max c2_s) (the transpose has the forward scheme's stability); a null hist, lam, q or
+ * S; a hist_stride below (nsteps + 1) * size; with receivers a null adj, an adj_stride that is neither 0 nor large enough; any
+ * two of c2, hist, adj, lam, q, S overlapping; on the host entry point an adjoint source that is not finite.
+ * _device: c2, hist, adj, lam, q, S in device memory, tau and rec_nodes in host memory.  Workspace: that of
+ * mi355cg_wave_medium_many (mi355cg_wave_adjoint_many_workspace, pure host arithmetic); the host entry point stages the history,
+ * the sources, the media and the three vectors on top.
+ * Not built: the transpose of the damped step (mi355cg_wave_sponge_many), derivatives with respect to g or the amplitudes,
+ * Newmark, anything but fp64.                                                                                                    */
+int  mi355cg_wave_history_many(mi355cg_handle h, int nsys, int nsteps, const double *tau, const double *g, double *u, double *v,
+                               const double *c2, long long c2_stride, double *hist, long long hist_stride, const double *w, long long w_stride,
+                               int nrec, const int *rec_nodes, int record_every, double *traces, int steps_per_launch,
+                               const volatile int *stop_flag, mi355cg_results *out, int *steps_done);
+int  mi355cg_wave_history_many_device(mi355cg_handle h, int nsys, int nsteps, const double *tau, const double *g_dev, double *u_dev,
+                                      double *v_dev, const double *c2_dev, long long c2_stride, double *hist_dev, long long hist_stride,
+                                      const double *w_dev, long long w_stride, int nrec, const int *rec_nodes, int record_every,
+                                      double *traces_dev, int steps_per_launch, const volatile int *stop_flag, mi355cg_results *out,
+                                      int *steps_done);
+int  mi355cg_wave_history_bytes(int n, int nsys, int nsteps, long long *bytes);
+int  mi355cg_wave_adjoint_many(mi355cg_handle h, int nsys, int nsteps, const double *tau, const double *c2, long long c2_stride,
+                               const double *hist, long long hist_stride, int nrec, const int *rec_nodes, int record_every,
+                               const double *adj, long long adj_stride, double *lam, double *q, double *S, int steps_per_launch,
+                               const volatile int *stop_flag, mi355cg_results *out, int *steps_done);
+int  mi355cg_wave_adjoint_many_device(mi355cg_handle h, int nsys, int nsteps, const double *tau, const double *c2_dev, long long c2_stride,
+                                      const double *hist_dev, long long hist_stride, int nrec, const int *rec_nodes, int record_every,
+                                      const double *adj_dev, long long adj_stride, double *lam_dev, double *q_dev, double *S_dev,
+                                      int steps_per_launch, const volatile int *stop_flag, mi355cg_results *out, int *steps_done);
+int  mi355cg_wave_adjoint_many_workspace(int n, int nsys, int nsteps, int nrec, int record_every, long long *bytes);
 
 /* ---- multi-GPU: one context per rank, one contiguous slab of grid rows per context --------------
  * The reference is single-process (no collectives exist in it); this is the scaling

@@ -5,7 +5,7 @@ from ._capi import (BATCH_MAX, MANY_MAX, STEPS_MANY_MAX_STEPS, WAVE_MAX_RECEIVER
                     SMOOTHER_JACOBI, SMOOTHER_LINE_AUTO, SMOOTHER_LINE_X, SMOOTHER_LINE_Y, SOLVE_LAUNCHES, SOLVE_ONCHIP, WAVE_NEWMARK, WAVE_VERLET, Mi355cgError, lib_path, load)
 from .solver import (CrsMatrix, DirichletSolver, GridSystem, MatrixFreeSolver, MatrixFreeSystem, MSGSolver,
                      SolverResults, StopCriterion, default_params, mg_hierarchy, mg_levels, onchip_plan, rayleigh_ritz, sponge_damping, time_steps_many_workspace, wave_medium_many_workspace, wave_record_many_workspace, wave_sponge_many_workspace,
-                     wave_steps_many_workspace)
+                     wave_steps_many_workspace, wave_adjoint_many_workspace, wave_history_bytes)
 
 __all__ = ["CrsMatrix", "DirichletSolver", "GridSystem", "MatrixFreeSolver", "MatrixFreeSystem", "MSGSolver",
            "SolverResults", "StopCriterion", "default_params", "Mi355cgError", "lib_path", "load",
@@ -14,4 +14,4 @@ __all__ = ["CrsMatrix", "DirichletSolver", "GridSystem", "MatrixFreeSolver", "Ma
            "SMOOTHER_JACOBI", "SMOOTHER_LINE_X", "SMOOTHER_LINE_Y", "SMOOTHER_LINE_AUTO",
            "SOLVE_LAUNCHES", "SOLVE_ONCHIP", "onchip_plan", "time_steps_many_workspace", "STEPS_MANY_MAX_STEPS",
            "WAVE_VERLET", "WAVE_NEWMARK", "wave_steps_many_workspace", "wave_record_many_workspace", "WAVE_MAX_RECEIVERS", "wave_medium_many_workspace",
-           "wave_sponge_many_workspace", "sponge_damping"]
+           "wave_sponge_many_workspace", "sponge_damping", "wave_history_bytes", "wave_adjoint_many_workspace"]

@@ -44,6 +44,8 @@ EXPORTS = [
     "mi355cg_wave_record_many", "mi355cg_wave_record_many_device", "mi355cg_wave_record_many_workspace",
     "mi355cg_wave_medium_many", "mi355cg_wave_medium_many_device", "mi355cg_wave_medium_many_workspace", "mi355cg_wave_medium_cfl",
     "mi355cg_wave_sponge_many", "mi355cg_wave_sponge_many_device", "mi355cg_wave_sponge_many_workspace",
+    "mi355cg_wave_history_many", "mi355cg_wave_history_many_device", "mi355cg_wave_history_bytes",
+    "mi355cg_wave_adjoint_many", "mi355cg_wave_adjoint_many_device", "mi355cg_wave_adjoint_many_workspace",
 ]
 WAVE_VERLET, WAVE_NEWMARK = 0, 1    # MI355CG_WAVE_VERLET, MI355CG_WAVE_NEWMARK
 DECOMP_ROWS, DECOMP_2D = 0, 1
@@ -262,6 +264,17 @@ def load():
             fn.argtypes = [H, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p,
                            C.c_longlong, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(Results), C.c_void_p]
         L.mi355cg_wave_sponge_many_workspace.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, LLP]
+    if hasattr(L, "mi355cg_wave_adjoint_many"):  # absent from an older build loaded through MI355CG_LIB
+        # mi355cg_wave_medium_many's arguments with hist (written) and its stride behind c2's
+        for fn in (L.mi355cg_wave_history_many, L.mi355cg_wave_history_many_device):
+            fn.argtypes = [H, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p,
+                           C.c_longlong, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(Results), C.c_void_p]
+        L.mi355cg_wave_history_bytes.argtypes = [C.c_int, C.c_int, C.c_int, LLP]
+        # (h, nsys, nsteps, tau, c2, c2_stride, hist, hist_stride, nrec, rec_nodes, record_every, adj, adj_stride, lam, q, S, steps_per_launch, stop, out, done)
+        for fn in (L.mi355cg_wave_adjoint_many, L.mi355cg_wave_adjoint_many_device):
+            fn.argtypes = [H, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                           C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(Results), C.c_void_p]
+        L.mi355cg_wave_adjoint_many_workspace.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, LLP]
     if hasattr(L, "mi355cg_get_xfold"):         # absent from an older build loaded through MI355CG_LIB
         L.mi355cg_get_xfold.argtypes = [H, IP, IP]
     _lib = L

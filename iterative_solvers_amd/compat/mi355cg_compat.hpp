@@ -604,12 +604,92 @@ public:
                         std::vector<int>* steps_done = nullptr, const std::vector<std::vector<double>>& g = {}, int steps_per_launch = 0) {
         waveRecorded("waveSpongeMany", u, v, tau, nsteps, &media, &damping, source, receivers, record_every, traces, results, steps_done, g, steps_per_launch);
     }
+    // Extension: waveMediumMany that keeps its history (mi355cg_wave_history_many), the forward half of an adjoint-state gradient:
+    // the same u, v and traces, and history[s][n] = A u_n of member s, n = 0 .. nsteps, size() values each -- the stencil value of
+    // the state after n steps before c2 scales it.  Everything else is waveMediumMany's.
+    void waveHistoryMany(std::vector<std::vector<double>>& u, std::vector<std::vector<double>>& v, const std::vector<double>& tau, int nsteps,
+                         const std::vector<std::vector<double>>& media, const std::vector<std::vector<double>>& source, const std::vector<int>& receivers,
+                         int record_every, std::vector<std::vector<std::vector<double>>>* traces, std::vector<std::vector<std::vector<double>>>& history,
+                         std::vector<mi355cg_results>* results = nullptr, std::vector<int>* steps_done = nullptr, const std::vector<std::vector<double>>& g = {},
+                         int steps_per_launch = 0) {
+        waveRecorded("waveHistoryMany", u, v, tau, nsteps, &media, nullptr, source, receivers, record_every, traces, results, steps_done, g, steps_per_launch, &history);
+    }
+    // Extension: the exact transpose of the steps waveHistoryMany took (mi355cg_wave_adjoint_many).  history: as it returned it,
+    // nsteps + 1 rows per member; tau, media, receivers and record_every those of the forward run; adjoint_source: the derivative
+    // of the misfit with respect to the traces, [member][sample][receiver] (or one member's table for all) -- traces - observed
+    // for least squares.  lam, q and sens (one vector of size() per member; empty: zeros) are updated in place: from state index
+    // s = nsteps down to 1, h = tau / 2,
+    //     if s % record_every == 0:  lam[receivers[j]] += adjoint_source[s / record_every - 1][j]   (j ascending)
+    //     sens += q * history[s];  lam += h * A q;  q += tau * (c2 * lam);  sens += q * history[s - 1];  lam += h * A q.
+    // From zeros dJ/dc2 = (tau / 2) sens / c2, dJ/du0 = lam, dJ/dv0 = q / c2.  std::invalid_argument for vectors of the wrong count
+    // or size and what the library refuses as invalid (a tau above waveCfl(the member's largest c2) among it).
+    void waveAdjointMany(const std::vector<std::vector<std::vector<double>>>& history, const std::vector<double>& tau,
+                         const std::vector<std::vector<double>>& media, const std::vector<std::vector<std::vector<double>>>& adjoint_source,
+                         const std::vector<int>& receivers, int record_every, std::vector<std::vector<double>>& lam, std::vector<std::vector<double>>& q,
+                         std::vector<std::vector<double>>& sens, std::vector<mi355cg_results>* results = nullptr, std::vector<int>* steps_done = nullptr,
+                         int steps_per_launch = 0) {
+        const std::string me = "waveAdjointMany: ";
+        if (history.empty() || history.size() > (size_t)MI355CG_MANY_MAX) throw std::invalid_argument(me + "an ensemble has 1 .. MI355CG_MANY_MAX members");
+        const size_t n = rhs.size(), k = history.size(), rows = history[0].size();
+        if (rows < 1 || rows - 1 > (size_t)MI355CG_STEPS_MANY_MAX_STEPS) throw std::invalid_argument(me + "a history has 1 .. MI355CG_STEPS_MANY_MAX_STEPS + 1 rows");
+        const int nsteps = (int)rows - 1;
+        if (tau.size() != k) throw std::invalid_argument(me + "tau does not have one entry per member");
+        if (media.size() != 1 && media.size() != k) throw std::invalid_argument(me + "media has one vector, or one per member");
+        if (record_every < 1) throw std::invalid_argument(me + "record_every is at least 1");
+        if (receivers.size() > (size_t)MI355CG_WAVE_MAX_RECEIVERS) throw std::invalid_argument(me + "at most MI355CG_WAVE_MAX_RECEIVERS receivers");
+        const size_t nrec = receivers.size(), samples = (size_t)(nsteps / record_every);
+        if (nrec && adjoint_source.size() != 1 && adjoint_source.size() != k) throw std::invalid_argument(me + "adjoint_source has one table, or one per member");
+        std::vector<double> hp(k * rows * n), cp(media.size() * n), ap(nrec ? adjoint_source.size() * samples * nrec : 0), lp(k * n, 0.0), qp(k * n, 0.0), sp(k * n, 0.0);
+        for (size_t s = 0; s < k; ++s) {
+            if (history[s].size() != rows) throw std::invalid_argument(me + "every member's history has the same number of rows");
+            for (size_t r = 0; r < rows; ++r) {
+                if (history[s][r].size() != n) throw std::invalid_argument(me + "a row of the history does not have the size of the system");
+                std::copy(history[s][r].begin(), history[s][r].end(), hp.begin() + (std::ptrdiff_t)((s * rows + r) * n));
+            }
+        }
+        for (size_t s = 0; s < media.size(); ++s) {
+            if (media[s].size() != n) throw std::invalid_argument(me + "a medium does not have the size of the system");
+            std::copy(media[s].begin(), media[s].end(), cp.begin() + (std::ptrdiff_t)(s * n));
+        }
+        for (size_t s = 0; nrec && s < adjoint_source.size(); ++s) {
+            if (adjoint_source[s].size() != samples) throw std::invalid_argument(me + "a table of adjoint sources has nsteps / record_every samples");
+            for (size_t j = 0; j < samples; ++j) {
+                if (adjoint_source[s][j].size() != nrec) throw std::invalid_argument(me + "a sample of adjoint sources has one entry per receiver");
+                std::copy(adjoint_source[s][j].begin(), adjoint_source[s][j].end(), ap.begin() + (std::ptrdiff_t)((s * samples + j) * nrec));
+            }
+        }
+        const struct { std::vector<std::vector<double>>* in; std::vector<double>* packed; const char* name; } state[3] = {{&lam, &lp, "lam"}, {&q, &qp, "q"}, {&sens, &sp, "sens"}};
+        for (const auto& x : state) {
+            if (x.in->empty()) continue;
+            if (x.in->size() != k) throw std::invalid_argument(me + x.name + " is empty, or has one vector per member");
+            for (size_t s = 0; s < k; ++s) {
+                if ((*x.in)[s].size() != n) throw std::invalid_argument(me + x.name + ": vector size does not match the system");
+                std::copy((*x.in)[s].begin(), (*x.in)[s].end(), x.packed->begin() + (std::ptrdiff_t)(s * n));
+            }
+        }
+        std::vector<mi355cg_results> res(k);
+        std::vector<int> done(k, 0);
+        const double none = 0.0;                                       // with receivers but no sample: a table of no entries
+        mi355cg_compat::check(mi355cg_wave_adjoint_many(ctx_->h, (int)k, nsteps, tau.data(), cp.data(), media.size() == 1 ? 0 : (long long)n, hp.data(),
+                                                        (long long)(rows * n), (int)nrec, nrec ? receivers.data() : nullptr, record_every,
+                                                        nrec ? (ap.empty() ? &none : ap.data()) : nullptr,
+                                                        nrec && adjoint_source.size() != 1 ? (long long)(samples * nrec) : 0, lp.data(), qp.data(), sp.data(),
+                                                        steps_per_launch, nullptr, res.data(), done.data()));
+        for (const auto& x : state) {
+            x.in->assign(k, std::vector<double>());
+            for (size_t s = 0; s < k; ++s) (*x.in)[s].assign(x.packed->begin() + (std::ptrdiff_t)(s * n), x.packed->begin() + (std::ptrdiff_t)((s + 1) * n));
+        }
+        if (results) *results = std::move(res);
+        if (steps_done) *steps_done = std::move(done);
+    }
 private:
-    // all of the above; media: null for the homogeneous medium; damping: null for none (with media only)
+    // all of the above; media: null for the homogeneous medium; damping: null for none (with media only); history: null for none
+    // (with media, without damping)
     void waveRecorded(const char* who, std::vector<std::vector<double>>& u, std::vector<std::vector<double>>& v, const std::vector<double>& tau, int nsteps,
                       const std::vector<std::vector<double>>* media, const std::vector<std::vector<double>>* damping,
                       const std::vector<std::vector<double>>& source, const std::vector<int>& receivers, int record_every,
-                      std::vector<std::vector<std::vector<double>>>* traces, std::vector<mi355cg_results>* results, std::vector<int>* steps_done, const std::vector<std::vector<double>>& g, int steps_per_launch) {
+                      std::vector<std::vector<std::vector<double>>>* traces, std::vector<mi355cg_results>* results, std::vector<int>* steps_done, const std::vector<std::vector<double>>& g, int steps_per_launch,
+                      std::vector<std::vector<std::vector<double>>>* history = nullptr) {
         const std::string me = std::string(who) + ": ";
         if (u.empty() || u.size() > (size_t)MI355CG_MANY_MAX) throw std::invalid_argument(me + "an ensemble has 1 .. MI355CG_MANY_MAX members");
         const size_t n = rhs.size(), k = u.size();
@@ -649,7 +729,13 @@ private:
         std::vector<mi355cg_results> res(k);
         std::vector<int> done(k, 0);
         const long long w_stride = source.size() == 1 ? 0 : (long long)row;
-        if (damping)
+        std::vector<double> hp(history ? k * row * n : 0);
+        if (history)
+            mi355cg_compat::check(mi355cg_wave_history_many(ctx_->h, (int)k, nsteps, tau.data(), g.empty() ? nullptr : gp.data(), up.data(), vp.data(), cp.data(),
+                                                            media->size() == 1 ? 0 : (long long)n, hp.data(), (long long)(row * n), wp.data(), w_stride, (int)nrec,
+                                                            nrec ? receivers.data() : nullptr, record_every, nrec ? tp.data() : nullptr, steps_per_launch, nullptr,
+                                                            res.data(), done.data()));
+        else if (damping)
             mi355cg_compat::check(mi355cg_wave_sponge_many(ctx_->h, (int)k, nsteps, tau.data(), g.empty() ? nullptr : gp.data(), up.data(), vp.data(), cp.data(),
                                                            media->size() == 1 ? 0 : (long long)n, dp.data(), damping->size() == 1 ? 0 : (long long)n, wp.data(),
                                                            w_stride, (int)nrec, nrec ? receivers.data() : nullptr, record_every, nrec ? tp.data() : nullptr,
@@ -672,6 +758,14 @@ private:
                 for (size_t j = 0; j < samples; ++j) {
                     const std::ptrdiff_t at = (std::ptrdiff_t)((s * samples + j) * nrec);
                     (*traces)[s][j].assign(tp.begin() + at, tp.begin() + at + (std::ptrdiff_t)nrec);
+                }
+        }
+        if (history) {
+            history->assign(k, std::vector<std::vector<double>>(row));
+            for (size_t s = 0; s < k; ++s)
+                for (size_t r = 0; r < row; ++r) {
+                    const std::ptrdiff_t at = (std::ptrdiff_t)((s * row + r) * n);
+                    (*history)[s][r].assign(hp.begin() + at, hp.begin() + at + (std::ptrdiff_t)n);
                 }
         }
         if (results) *results = std::move(res);

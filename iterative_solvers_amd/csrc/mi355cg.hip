@@ -3485,7 +3485,8 @@ static int wave_upload(mi355cg_ctx* c, OnchipManyWs* W, int nsys, const double* 
 // c2 (or NULL: none): the media of mi355cg_wave_medium_many* (section 12.5) in device memory; c2_stride 0: one for all members.
 // d (or NULL: none; with c2 only): the damping rows of mi355cg_wave_sponge_many* (section 12.6), likewise.
 struct WaveRecord { const double* w; long long w_stride; int nrec; const int* nodes; int every; double* traces; const double* c2 = nullptr; long long c2_stride = 0;
-                    const double* d = nullptr; long long d_stride = 0; };
+                    const double* d = nullptr; long long d_stride = 0;
+                    double* hist = nullptr; long long hist_stride = 0; };     // hist (with c2, without d): the history of mi355cg_wave_history_many* (section 12.7)
 
 // Explicit: ceil(nsteps / m) launches of m steps; before each the host waits for the one before it and tests the caller's flag.
 // rec: with a source and receivers; every launch is told where in the call it starts.
@@ -3510,14 +3511,16 @@ static int wave_verlet(mi355cg_ctx* c, int nsys, int nsteps, const double* tau, 
     }
     const OnchipWaveMediumArgs md{rec ? rec->c2 : nullptr, rec ? rec->c2_stride : 0};
     const OnchipWaveSpongeArgs sp{rec ? rec->d : nullptr, rec ? rec->d_stride : 0};
-    const void* k_steps = sp.d  ? onchip_dispatch(R.pl.elems, false, [](auto el, auto) { return (const void*)&k_oc_wave_sponge<decltype(el)::value>; })
+    const OnchipWaveHistArgs hs{rec ? rec->hist : nullptr, rec ? rec->hist_stride : 0};
+    const void* k_steps = hs.hist ? onchip_dispatch(R.pl.elems, false, [](auto el, auto) { return (const void*)&k_oc_wave_history<decltype(el)::value>; })
+                          : sp.d  ? onchip_dispatch(R.pl.elems, false, [](auto el, auto) { return (const void*)&k_oc_wave_sponge<decltype(el)::value>; })
                           : md.c2 ? onchip_dispatch(R.pl.elems, false, [](auto el, auto) { return (const void*)&k_oc_wave_medium<decltype(el)::value>; })
                           : rec ? onchip_dispatch(R.pl.elems, false, [](auto el, auto) { return (const void*)&k_oc_wave_record<decltype(el)::value>; })
                               : onchip_dispatch(R.pl.elems, false, [](auto el, auto) { return (const void*)&k_onchip_wave_verlet<decltype(el)::value>; });
     if (int rc = R.allow_lds(k_steps)) return rc;
     if (int rc = loop_timer_begin(c, c->stream)) return rc;
     const int m = steps_per_launch > 0 ? steps_per_launch : kOnchipWaveDefaultSteps;
-    void* args[] = {&a, &x, (void*)&md, (void*)&sp};               // (the plain kernel takes the first alone, the recording one two, the medium's three)
+    void* args[] = {&a, &x, (void*)&md, hs.hist ? (void*)&hs : (void*)&sp};   // (the plain kernel takes the first alone, the recording one two, the medium's three)
     int done = 0;
     while (done < nsteps) {
         if (done > 0) HIPCK(hipStreamSynchronize(c->stream));
@@ -3945,6 +3948,227 @@ int mi355cg_wave_sponge_many_workspace(int n, int nsys, int nsteps, int nrec, in
     const long long v = onchip_wave_sponge_workspace_bytes(n, nsys, nsteps, nrec, record_every);
     if (v == 0)
         return fail(MI355CG_ERR_INVALID, "recorded wave ensemble with a damping field rejected: even n from 6 to %d, 1 .. %d members, 0 .. %d steps, 0 .. %d receivers, record_every >= 1",
+                    kOnchipMaxN, kOnchipStepsMaxSys, kOnchipStepsMaxSteps, kOnchipWaveMaxRec);
+    *bytes = v;
+    return MI355CG_OK;
+}
+// ---- the adjoint of the scheme in a medium: the forward run with its history, the backward run --------------
+// What both history entry points refuse on top of wave_medium_check.
+static int wave_history_check(mi355cg_ctx* c, int nsys, int nsteps, const double* tau, const void* g, const void* u, const void* v, const double* c2,
+                              long long c2_stride, const double* hist, long long hist_stride, const double* w, long long w_stride, int nrec, const int* rec_nodes,
+                              int record_every, const void* traces, int steps_per_launch, const mi355cg_results* out, const int* steps_done, bool host_tables) {
+    if (int rc = wave_medium_check(c, nsys, nsteps, tau, g, u, v, c2, c2_stride, w, w_stride, nrec, rec_nodes, record_every, traces, steps_per_launch, out,
+                                   steps_done, host_tables)) return rc;
+    if (!hist) return fail(MI355CG_ERR_INVALID, "null argument: hist, the history the run writes");
+    const long long rows = ((long long)nsteps + 1) * c->pk_len;
+    if (hist_stride < rows)
+        return fail(MI355CG_ERR_INVALID, "hist_stride %lld rejected: a member's history is (nsteps + 1) x %lld = %lld doubles", hist_stride, c->pk_len, rows);
+    const size_t state = sizeof(double) * (size_t)c->gp.size * (size_t)nsys;
+    const size_t hbytes = sizeof(double) * ((size_t)(nsys - 1) * (size_t)hist_stride + (size_t)rows);
+    const size_t cbytes = sizeof(double) * ((c2_stride ? (size_t)(nsys - 1) * (size_t)c2_stride : 0) + (size_t)c->pk_len);
+    const size_t wbytes = sizeof(double) * ((size_t)(nsys - 1) * (size_t)w_stride + (size_t)nsteps + 1);
+    const size_t tbytes = nrec > 0 ? sizeof(double) * (size_t)nsys * (size_t)(nsteps / record_every) * (size_t)nrec : 0;
+    const struct { const void* p; size_t bytes; const char* name; } vecs[6] = {{u, state, "u"}, {v, state, "v"}, {g, state, "g"}, {c2, cbytes, "c2"},
+                                                                               {w, wbytes, "w"}, {traces, tbytes, "traces"}};
+    for (const auto& q : vecs)
+        if (ranges_meet(hist, hbytes, q.p, q.bytes)) return fail(MI355CG_ERR_INVALID, "hist overlaps %s", q.name);
+    return MI355CG_OK;
+}
+int mi355cg_wave_history_many_device(mi355cg_handle c, int nsys, int nsteps, const double* tau, const double* g_dev, double* u_dev, double* v_dev,
+                                     const double* c2_dev, long long c2_stride, double* hist_dev, long long hist_stride, const double* w_dev,
+                                     long long w_stride, int nrec, const int* rec_nodes, int record_every, double* traces_dev, int steps_per_launch,
+                                     const volatile int* stop_flag, mi355cg_results* out, int* steps_done) {
+    if (int rc = wave_history_check(c, nsys, nsteps, tau, g_dev, u_dev, v_dev, c2_dev, c2_stride, hist_dev, hist_stride, w_dev, w_stride, nrec, rec_nodes,
+                                    record_every, traces_dev, steps_per_launch, out, steps_done, false)) return rc;
+    if (StepChecks::none(nsys, nsteps, steps_done)) return MI355CG_OK;
+    HIPCK(hipSetDevice(c->device));
+    if (int rc = onchip_wave_medium_ensure(c, nsys, 0, 0)) return rc;
+    OnchipManyWs* W = c->many.get();
+    const int rows = c2_stride ? nsys : 1;
+    hipLaunchKernelGGL(k_oc_medium_range, dim3(rows), dim3(kOcRangeThreads), 0, c->stream, c2_dev, c2_stride, (int)c->pk_len, W->med_range.get());
+    HIPCK(hipGetLastError());
+    HIPCK(hipMemcpyAsync(W->med_range_h, W->med_range, sizeof(double) * 2 * rows, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(hipStreamSynchronize(c->stream));
+    if (int rc = wave_medium_bounds(c, nsys, tau, W->med_range_h, c2_stride)) return rc;
+    WaveRecord rec{w_dev, w_stride, nrec, rec_nodes, record_every, traces_dev, c2_dev, c2_stride};
+    rec.hist = hist_dev; rec.hist_stride = hist_stride;
+    return wave_verlet(c, nsys, nsteps, tau, g_dev, u_dev, v_dev, steps_per_launch, stop_flag, out, steps_done, &rec);
+}
+int mi355cg_wave_history_many(mi355cg_handle c, int nsys, int nsteps, const double* tau, const double* g, double* u, double* v, const double* c2,
+                              long long c2_stride, double* hist, long long hist_stride, const double* w, long long w_stride, int nrec, const int* rec_nodes,
+                              int record_every, double* traces, int steps_per_launch, const volatile int* stop_flag, mi355cg_results* out, int* steps_done) {
+    if (int rc = wave_history_check(c, nsys, nsteps, tau, g, u, v, c2, c2_stride, hist, hist_stride, w, w_stride, nrec, rec_nodes, record_every, traces,
+                                    steps_per_launch, out, steps_done, true)) return rc;
+    const size_t len = (size_t)c->pk_len, mrows = c2_stride ? (size_t)nsys : 1;
+    if (int rc = wave_medium_bounds(c, nsys, tau, host_row_ranges(c2, c2_stride, mrows, len).data(), c2_stride)) return rc;
+    if (StepChecks::none(nsys, nsteps, steps_done)) return MI355CG_OK;
+    HIPCK(hipSetDevice(c->device));
+    const size_t row = (size_t)nsteps + 1, rows = w_stride ? (size_t)nsys : 1;             // the tables go up packed: row doubles per row
+    const size_t sample = (size_t)nrec, samples = (size_t)(nsteps / record_every);          // a member's traces: samples x sample doubles
+    const size_t hrow = row * len;                                                          // a member's history, packed
+    if (int rc = onchip_wave_medium_ensure(c, nsys, 4, (long long)(rows * row + (size_t)nsys * samples * sample + (size_t)nsys * hrow))) return rc;
+    const size_t count = len * (size_t)nsys;                       // g, then u, then v, then the media; the state comes down
+    double* const g_dev = c->many->stage; double* const u_dev = g_dev + count; double* const v_dev = u_dev + count; double* const c2_dev = v_dev + count;
+    double* const w_dev = c->many->rec_stage; double* const traces_dev = w_dev + rows * row; double* const hist_dev = traces_dev + (size_t)nsys * samples * sample;
+    const StagedGroup groups[3] = {{0, g, nullptr}, {count, u, u}, {2 * count, v, v}};
+    return run_staged_groups(c, g_dev, count, groups, [&]() {
+        HIPCK(hipMemcpy2DAsync(c2_dev, sizeof(double) * len, c2, sizeof(double) * (c2_stride ? (size_t)c2_stride : len), sizeof(double) * len, mrows, hipMemcpyHostToDevice, c->stream));
+        HIPCK(hipMemcpy2DAsync(w_dev, sizeof(double) * row, w, sizeof(double) * (w_stride ? (size_t)w_stride : row), sizeof(double) * row, rows, hipMemcpyHostToDevice, c->stream));
+        WaveRecord rec{w_dev, w_stride ? (long long)row : 0, nrec, rec_nodes, record_every, nrec ? traces_dev : nullptr, c2_dev, c2_stride ? (long long)len : 0};
+        rec.hist = hist_dev; rec.hist_stride = (long long)hrow;
+        if (int rc = wave_verlet(c, nsys, nsteps, tau, g ? g_dev : nullptr, u_dev, v_dev, steps_per_launch, stop_flag, out, steps_done, &rec)) return rc;
+        const size_t ran = (size_t)(steps_done[0] / record_every) * sample;                 // the samples and the rows of the steps that ran come down
+        if (ran) HIPCK(hipMemcpy2DAsync(traces, sizeof(double) * samples * sample, traces_dev, sizeof(double) * samples * sample, sizeof(double) * ran, (size_t)nsys,
+                                        hipMemcpyDeviceToHost, c->stream));
+        if (steps_done[0] > 0) HIPCK(hipMemcpy2DAsync(hist, sizeof(double) * (size_t)hist_stride, hist_dev, sizeof(double) * hrow,
+                                                      sizeof(double) * ((size_t)steps_done[0] + 1) * len, (size_t)nsys, hipMemcpyDeviceToHost, c->stream));
+        return (int)MI355CG_OK;
+    });
+}
+int mi355cg_wave_history_bytes(int n, int nsys, int nsteps, long long* bytes) {
+    if (!bytes) return fail(MI355CG_ERR_INVALID, "null argument");
+    const long long v = onchip_wave_history_bytes(n, nsys, nsteps);
+    if (v == 0)
+        return fail(MI355CG_ERR_INVALID, "wave history rejected: even n from 6 to %d, 1 .. %d members, 0 .. %d steps", kOnchipMaxN, kOnchipStepsMaxSys, kOnchipStepsMaxSteps);
+    *bytes = v;
+    return MI355CG_OK;
+}
+
+// What both adjoint entry points refuse before anything is allocated or written.  host_tables: adj can be read here.
+static int wave_adjoint_check(mi355cg_ctx* c, int nsys, int nsteps, const double* tau, const double* c2, long long c2_stride, const double* hist,
+                              long long hist_stride, int nrec, const int* rec_nodes, int record_every, const double* adj, long long adj_stride,
+                              const void* lam, const void* q, const void* S, int steps_per_launch, const mi355cg_results* out, const int* steps_done,
+                              bool host_tables) {
+    if (!c || !tau || !lam || !q || !S || !out || !steps_done) return fail(MI355CG_ERR_INVALID, "null argument");
+    if (int rc = kWaveEnsemble.count(nsys)) return rc;
+    if (int rc = StepChecks::nsteps(nsteps)) return rc;
+    if (steps_per_launch < 0) return fail(MI355CG_ERR_INVALID, "steps_per_launch %d rejected: 0 (the default) or a positive number of steps", steps_per_launch);
+    if (int rc = kWaveEnsemble.onchip(c)) return rc;
+    for (int s = 0; s < nsys; ++s) if (int rc = StepChecks::tau(tau[s], s)) return rc;
+    if (!c2) return fail(MI355CG_ERR_INVALID, "null argument: c2, the squared wave speed of every unknown");
+    if (c2_stride != 0 && c2_stride < c->pk_len)
+        return fail(MI355CG_ERR_INVALID, "c2_stride %lld rejected: 0 (one medium for all members) or at least the %lld unknowns of a member", c2_stride, c->pk_len);
+    if (!hist) return fail(MI355CG_ERR_INVALID, "null argument: hist, the history of the forward run");
+    const long long rows = ((long long)nsteps + 1) * c->pk_len;
+    if (hist_stride < rows)
+        return fail(MI355CG_ERR_INVALID, "hist_stride %lld rejected: a member's history is (nsteps + 1) x %lld = %lld doubles", hist_stride, c->pk_len, rows);
+    if (nrec < 0 || nrec > MI355CG_WAVE_MAX_RECEIVERS) return fail(MI355CG_ERR_INVALID, "nrec %d rejected: a call takes 0 .. %d receivers", nrec, MI355CG_WAVE_MAX_RECEIVERS);
+    if (record_every < 1) return fail(MI355CG_ERR_INVALID, "record_every %d rejected: it must be >= 1", record_every);
+    const long long table = (long long)(nsteps / record_every) * nrec;                      // a member's adjoint sources
+    if (nrec > 0 && (!rec_nodes || !adj)) return fail(MI355CG_ERR_INVALID, "null argument: %d receivers need rec_nodes and adj, the adjoint sources", nrec);
+    for (int r = 0; r < nrec; ++r)
+        if (rec_nodes[r] < 0 || rec_nodes[r] >= c->pk_len)
+            return fail(MI355CG_ERR_INVALID, "receiver %d is unknown %d: outside [0, %lld)", r, rec_nodes[r], c->pk_len);
+    if (adj_stride != 0 && adj_stride < table)
+        return fail(MI355CG_ERR_INVALID, "adj_stride %lld rejected: 0 (one table for all members) or at least (nsteps / record_every) x nrec = %lld", adj_stride, table);
+    if (BatchKind::apart(c, nsys, lam, q, "lam overlaps q") || BatchKind::apart(c, nsys, lam, S, "lam overlaps S") || BatchKind::apart(c, nsys, q, S, "q overlaps S"))
+        return MI355CG_ERR_INVALID;
+    const size_t state = sizeof(double) * (size_t)c->gp.size * (size_t)nsys;
+    const size_t hbytes = sizeof(double) * ((size_t)(nsys - 1) * (size_t)hist_stride + (size_t)rows);
+    const size_t cbytes = sizeof(double) * ((c2_stride ? (size_t)(nsys - 1) * (size_t)c2_stride : 0) + (size_t)c->pk_len);
+    const size_t abytes = nrec > 0 ? sizeof(double) * ((size_t)(nsys - 1) * (size_t)adj_stride + (size_t)table) : 0;
+    const struct { const void* p; size_t bytes; const char* name; } vecs[6] = {{lam, state, "lam"}, {q, state, "q"}, {S, state, "S"}, {c2, cbytes, "c2"},
+                                                                               {hist, hbytes, "hist"}, {adj, abytes, "adj"}};
+    for (int i = 3; i < 6; ++i)
+        for (int j = 0; j < i; ++j)
+            if (ranges_meet(vecs[i].p, vecs[i].bytes, vecs[j].p, vecs[j].bytes)) return fail(MI355CG_ERR_INVALID, "%s overlaps %s", vecs[i].name, vecs[j].name);
+    if (host_tables && nrec > 0)
+        for (int s = 0; s < (adj_stride ? nsys : 1); ++s)
+            for (long long i = 0; i < table; ++i)
+                if (!std::isfinite(adj[(long long)s * adj_stride + i]))
+                    return fail(MI355CG_ERR_INVALID, "adjoint source %g of member %d at sample %lld, receiver %lld rejected: it must be finite", adj[(long long)s * adj_stride + i],
+                                s, i / nrec, i % nrec);
+    return MI355CG_OK;
+}
+// Backwards: ceil(nsteps / m) launches of m steps from the state index nsteps down; the host tests the flag between two.
+// Everything in device memory but tau and the receivers.
+static int wave_adjoint(mi355cg_ctx* c, int nsys, int nsteps, const double* tau, const double* c2_dev, long long c2_stride, const double* hist_dev,
+                        long long hist_stride, int nrec, const int* rec_nodes, int record_every, const double* adj_dev, long long adj_stride, double* lam_dev,
+                        double* q_dev, double* S_dev, int steps_per_launch, const volatile int* stop_flag, mi355cg_results* out, int* steps_done) {
+    mi355cg_params none;                                           // the driver reads a rule; the scheme decides nothing
+    mi355cg_default_params(&none, MI355CG_RULE_REL_2NORM);
+    OnchipManyRun R;
+    if (int rc = R.open(c, &none, nsys, stop_flag, "adjoint wave stepping")) return rc;
+    OnchipManyWs* W = R.W;
+    for (int s = 0; s < nsys; ++s) { W->wave_tau_h[s] = tau[s]; W->wave_tau_h[nsys + s] = 2.0 / tau[s]; }
+    HIPCK(hipMemcpyAsync(W->wave_tau, W->wave_tau_h, sizeof(double) * 2 * nsys, hipMemcpyHostToDevice, c->stream));
+    for (int r = 0; r < nrec; ++r) W->rec_cell_h[r] = rec_nodes[r];                         // the kernel wants the packed indices themselves
+    if (nrec) HIPCK(hipMemcpyAsync(W->rec_cell, W->rec_cell_h, sizeof(int) * nrec, hipMemcpyHostToDevice, c->stream));
+    OnchipWaveAdjArgs a{};
+    a.pl = R.pl; a.k = OnchipWaveCoef{c->gp.A, c->gp.x_k, c->gp.y_k};
+    a.tau = W->wave_tau; a.c2 = c2_dev; a.c2_stride = c2_stride; a.hist = hist_dev; a.hist_stride = hist_stride;
+    a.adj = adj_dev; a.adj_stride = adj_stride; a.rec_node = W->rec_cell; a.nrec = nrec; a.every = record_every;
+    a.lam = lam_dev; a.q = q_dev; a.S = S_dev; a.stride = R.U;
+    const void* k_steps = onchip_dispatch(R.pl.elems, false, [](auto el, auto) { return (const void*)&k_oc_wave_adjoint<decltype(el)::value>; });
+    if (int rc = R.allow_lds(k_steps)) return rc;
+    if (int rc = loop_timer_begin(c, c->stream)) return rc;
+    const int m = steps_per_launch > 0 ? steps_per_launch : kOnchipWaveDefaultSteps;
+    void* args[] = {&a};
+    int done = 0;
+    while (done < nsteps) {
+        if (done > 0) HIPCK(hipStreamSynchronize(c->stream));
+        if (stop_flag && *stop_flag) { R.interrupted = true; break; }
+        a.m = std::min(m, nsteps - done);
+        a.s_top = nsteps - done;
+        if (int rc = R.launch(k_steps, args)) return rc;
+        done += a.m;
+    }
+    if (int rc = R.end_loop(false)) return rc;
+    HIPCK(hipStreamSynchronize(c->stream));
+    CgState fin{};
+    fin.done = 1; fin.converged = 1;
+    for (int s = 0; s < nsys; ++s) { steps_done[s] = done; out[s] = make_results(fin, R.interrupted, false, 0.0); }
+    return R.stamp_times(out);
+}
+int mi355cg_wave_adjoint_many_device(mi355cg_handle c, int nsys, int nsteps, const double* tau, const double* c2_dev, long long c2_stride,
+                                     const double* hist_dev, long long hist_stride, int nrec, const int* rec_nodes, int record_every, const double* adj_dev,
+                                     long long adj_stride, double* lam_dev, double* q_dev, double* S_dev, int steps_per_launch, const volatile int* stop_flag,
+                                     mi355cg_results* out, int* steps_done) {
+    if (int rc = wave_adjoint_check(c, nsys, nsteps, tau, c2_dev, c2_stride, hist_dev, hist_stride, nrec, rec_nodes, record_every, adj_dev, adj_stride, lam_dev,
+                                    q_dev, S_dev, steps_per_launch, out, steps_done, false)) return rc;
+    if (StepChecks::none(nsys, nsteps, steps_done)) return MI355CG_OK;
+    HIPCK(hipSetDevice(c->device));
+    if (int rc = onchip_wave_medium_ensure(c, nsys, 0, 0)) return rc;
+    OnchipManyWs* W = c->many.get();
+    const int rows = c2_stride ? nsys : 1;                         // the transpose has the forward scheme's stability: every member against its own bound
+    hipLaunchKernelGGL(k_oc_medium_range, dim3(rows), dim3(kOcRangeThreads), 0, c->stream, c2_dev, c2_stride, (int)c->pk_len, W->med_range.get());
+    HIPCK(hipGetLastError());
+    HIPCK(hipMemcpyAsync(W->med_range_h, W->med_range, sizeof(double) * 2 * rows, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(hipStreamSynchronize(c->stream));
+    if (int rc = wave_medium_bounds(c, nsys, tau, W->med_range_h, c2_stride)) return rc;
+    return wave_adjoint(c, nsys, nsteps, tau, c2_dev, c2_stride, hist_dev, hist_stride, nrec, rec_nodes, record_every, adj_dev, adj_stride, lam_dev, q_dev, S_dev,
+                        steps_per_launch, stop_flag, out, steps_done);
+}
+int mi355cg_wave_adjoint_many(mi355cg_handle c, int nsys, int nsteps, const double* tau, const double* c2, long long c2_stride, const double* hist,
+                              long long hist_stride, int nrec, const int* rec_nodes, int record_every, const double* adj, long long adj_stride, double* lam,
+                              double* q, double* S, int steps_per_launch, const volatile int* stop_flag, mi355cg_results* out, int* steps_done) {
+    if (int rc = wave_adjoint_check(c, nsys, nsteps, tau, c2, c2_stride, hist, hist_stride, nrec, rec_nodes, record_every, adj, adj_stride, lam, q, S,
+                                    steps_per_launch, out, steps_done, true)) return rc;
+    const size_t len = (size_t)c->pk_len, mrows = c2_stride ? (size_t)nsys : 1;
+    if (int rc = wave_medium_bounds(c, nsys, tau, host_row_ranges(c2, c2_stride, mrows, len).data(), c2_stride)) return rc;
+    if (StepChecks::none(nsys, nsteps, steps_done)) return MI355CG_OK;
+    HIPCK(hipSetDevice(c->device));
+    const size_t hrow = ((size_t)nsteps + 1) * len;                                         // a member's history, packed
+    const size_t table = (size_t)(nsteps / record_every) * (size_t)nrec, arows = adj_stride ? (size_t)nsys : 1;
+    if (int rc = onchip_wave_medium_ensure(c, nsys, 4, (long long)((size_t)nsys * hrow + arows * table))) return rc;
+    const size_t count = len * (size_t)nsys;                       // lam, then q, then S (up and down), then the media
+    double* const lam_dev = c->many->stage; double* const q_dev = lam_dev + count; double* const S_dev = q_dev + count; double* const c2_dev = S_dev + count;
+    double* const hist_dev = c->many->rec_stage; double* const adj_dev = hist_dev + (size_t)nsys * hrow;
+    const StagedGroup groups[3] = {{0, lam, lam}, {count, q, q}, {2 * count, S, S}};
+    return run_staged_groups(c, lam_dev, count, groups, [&]() {
+        HIPCK(hipMemcpy2DAsync(c2_dev, sizeof(double) * len, c2, sizeof(double) * (c2_stride ? (size_t)c2_stride : len), sizeof(double) * len, mrows, hipMemcpyHostToDevice, c->stream));
+        HIPCK(hipMemcpy2DAsync(hist_dev, sizeof(double) * hrow, hist, sizeof(double) * (size_t)hist_stride, sizeof(double) * hrow, (size_t)nsys, hipMemcpyHostToDevice, c->stream));
+        if (table) HIPCK(hipMemcpy2DAsync(adj_dev, sizeof(double) * table, adj, sizeof(double) * (adj_stride ? (size_t)adj_stride : table), sizeof(double) * table, arows,
+                                          hipMemcpyHostToDevice, c->stream));
+        return wave_adjoint(c, nsys, nsteps, tau, c2_dev, c2_stride ? (long long)len : 0, hist_dev, (long long)hrow, nrec, rec_nodes, record_every,
+                            table ? adj_dev : nullptr, adj_stride ? (long long)table : 0, lam_dev, q_dev, S_dev, steps_per_launch, stop_flag, out, steps_done);
+    });
+}
+int mi355cg_wave_adjoint_many_workspace(int n, int nsys, int nsteps, int nrec, int record_every, long long* bytes) {
+    if (!bytes) return fail(MI355CG_ERR_INVALID, "null argument");
+    const long long v = onchip_wave_adjoint_workspace_bytes(n, nsys, nsteps, nrec, record_every);
+    if (v == 0)
+        return fail(MI355CG_ERR_INVALID, "adjoint wave ensemble rejected: even n from 6 to %d, 1 .. %d members, 0 .. %d steps, 0 .. %d receivers, record_every >= 1",
                     kOnchipMaxN, kOnchipStepsMaxSys, kOnchipStepsMaxSteps, kOnchipWaveMaxRec);
     *bytes = v;
     return MI355CG_OK;

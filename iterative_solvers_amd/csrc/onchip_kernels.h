@@ -965,6 +965,260 @@ __global__ __launch_bounds__(kOnchipMaxThreads) void k_oc_wave_sponge(const Onch
     }
 }
 
+// The forward run that keeps its history (mi355cg_wave_history_many*): k_oc_wave_medium's step and bits,
+// and the stencil value t = au(u) of every owned slot stored as it is formed, before it is scaled: row step0 + n of the member's
+// history is au(u) at the launch's state n, unknown i = k T + t of it at [(step0 + n) size + i], so neighbouring lanes write
+// neighbouring doubles -- ordinary vector stores nobody waits for.  Row step0 is written at entry (a later launch rewrites the
+// bits the launch before it left there).  The loop is the rotated one of k_oc_wave_sponge, both half kicks from one a behind
+// barrier 2 (the same bits: the carried acceleration IS that a), so v, g and c2 are the per-slot arrays and the store has
+// registers to spare.  The host never launches m = 0 steps.  A kernel of its own for k_oc_wave_record's reason.
+struct OnchipWaveHistArgs { double* hist; long long hist_stride; };          // member s writes hist + s * hist_stride, rows of a.stride doubles
+template <int E>
+__global__ __launch_bounds__(kOnchipMaxThreads) void k_oc_wave_history(const OnchipWaveArgs a, const OnchipWaveRecArgs x, const OnchipWaveMediumArgs md,
+                                                                       const OnchipWaveHistArgs hs) {
+    const OnchipPlan& pl = a.pl;
+    extern __shared__ __attribute__((aligned(16))) char oc_dyn_lds[];
+    double* const wbuf = reinterpret_cast<double*>(oc_dyn_lds);
+    double* const img = OcMany::lds(pl.cells).img;
+    const int t = threadIdx.x, T = blockDim.x, pitch = pl.pitch;
+    const long long sys = blockIdx.x;
+    const double tau = a.tau[sys], h = 0.5 * tau;
+    const double* const gin = a.g + sys * a.g_stride;
+    const double* const cin = md.c2 + sys * md.c2_stride;
+    double* const uio = a.u + sys * a.stride; double* const vio = a.v + sys * a.stride;
+    const double* const wrow = x.w + sys * x.w_stride + x.step0;   // wrow[s]: at the start of the launch's step s, wrow[s + 1]: at its end
+    double* trow = x.traces + sys * x.tr_stride + (long long)x.slot * x.nrec;
+    double* hrow = hs.hist + sys * hs.hist_stride + (long long)x.step0 * a.stride + t;     // this lane's column of the row being written
+
+    for (int i = t; i < pl.cells; i += T) img[i] = 0.0;
+    __syncthreads();                                               // the image is zero everywhere before the owners fill their cells
+    unsigned cell2[(E + 1) / 2] = {};
+    double v[E], g[E], c2[E];
+    int cnt = 0;
+#pragma unroll
+    for (int k = 0; k < E; ++k) {
+        const int i = onchip_owned(pl, t, k);
+        if (i >= 0) {                                              // (slots beyond cnt are never read: nothing to initialise)
+            int xx, yy;
+            onchip_node(pl, i, &xx, &yy);
+            const int c = onchip_cell(pl, xx, yy);
+            cell2[k / 2] |= (unsigned)c << (16 * (k & 1));
+            img[c] = uio[i]; v[k] = vio[i]; g[k] = gin[i]; c2[k] = cin[i];
+            cnt = k + 1;
+        }
+    }
+    if (t < kOcAmpBlock && t < a.m) wbuf[t] = wrow[t + 1];
+    int rcell = 0, phase = x.phase;
+    if (t < x.nrec) rcell = x.rec_cell[t];
+    double w_now = wrow[0], w_next = 0.0;
+    __syncthreads();
+    auto own_cell = [&](int k) { unsigned cc = cell2[k / 2]; asm volatile("" : "+v"(cc)); return (int)((cc >> (16 * (k & 1))) & 0xffffu); };
+    auto stencil_at = [&](int c) { return onchip_wave_au(a.k, img[c], img[c - 1], img[c + 1], img[c - pitch], img[c + pitch]); };
+#pragma unroll
+    for (int k = 0; k < E; ++k) if (k < cnt) {
+        const double au = stencil_at(own_cell(k));
+        hrow[k * T] = au;                                          // row step0
+        v[k] = onchip_wave_kick(v[k], h, onchip_wave_medium_accel_of(c2[k], au, onchip_wave_forcing(w_now, g[k])));       // vh
+        __builtin_amdgcn_sched_barrier(0);
+    }
+
+    for (int s = 0; s < a.m; ++s) {
+        __syncthreads();                                           // barrier 1: every neighbour has read the old cells
+        w_now = wbuf[((s / kOcAmpBlock) & 1) * kOcAmpBlock + s % kOcAmpBlock];        // the amplitude at the END of this step
+        hrow += a.stride;
+#pragma unroll
+        for (int k = 0; k < E; ++k) if (k < cnt) {
+            const int c = own_cell(k);
+            img[c] = onchip_wave_drift(img[c], tau, v[k]);         // v holds vh
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        __syncthreads();                                           // barrier 2: the new image is complete
+        const bool more = s + 1 < a.m;                             // uniform: the next step is this launch's too
+#pragma unroll
+        for (int k = 0; k < E; ++k) if (k < cnt) {
+            const double au = stencil_at(own_cell(k));
+            hrow[k * T] = au;                                      // row step0 + s + 1
+            const double acc = onchip_wave_medium_accel_of(c2[k], au, onchip_wave_forcing(w_now, g[k]));
+            v[k] = onchip_wave_kick(v[k], h, acc);                 // the second kick
+            if (more) v[k] = onchip_wave_kick(v[k], h, acc);       // the next step's vh
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        if (++phase == x.every) {                                  // uniform: this step is sampled
+            phase = 0;
+            if (t < x.nrec) trow[t] = img[rcell];
+            trow += x.nrec;
+        }
+        const int q = s % kOcAmpBlock, nb = s - q + kOcAmpBlock + t;                  // this lane's step in the next block
+        if (t < kOcAmpBlock && nb < a.m) {
+            if (q == 0) w_next = wrow[nb + 1];
+            if (q == kOcAmpBlock / 2) wbuf[((nb / kOcAmpBlock) & 1) * kOcAmpBlock + t] = w_next;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < E; ++k) if (k < cnt) {
+        int i = k * T + t;
+        asm volatile("" : "+v"(i));                                // recomputed here, not carried through the loop
+        uio[i] = img[own_cell(k)]; vio[i] = v[k];
+    }
+}
+
+// The adjoint of that run (mi355cg_wave_adjoint_many*): onchip_plan.h's recurrence from the launch's state
+// index s_top down through m steps.  The forward step with the roles swapped: q is the image, lam a register array where the
+// forward kernels keep v, and the loop is the rotated one -- au(q) behind the drift of step s is the au(q) the first kick of step
+// s - 1 needs, so one stencil pass behind barrier 2 makes both kicks, with only the injection of step s - 1 between them.  The
+// per-slot arrays are lam, c2, S and the history row of the NEXT state index, loaded one step before it is used; rows below the
+// launch's last state or above s_top are never read.  The last step of a launch ends behind its second kick: the next launch
+// forms the same au(q) from the same q, so launches and chained calls are invisible.
+//   * Adjoint sources: only a sampled step (s % every == 0, uniform) has a row.  Lane j < nrec of wave 0 loads its entry of the
+//     next sampled step's row into a register when the row before it is consumed (`every` steps ahead), stores it to the head of
+//     the side data between the barriers of the step above the sampled one, and the injection reads it behind barrier 2.
+//   * Injection: a thread finds at load time which of its slots are receivers (a bit per slot) from the table of the receivers'
+//     packed indices in the side data; on a sampled step only threads with a bit set walk the receivers, ascending, so
+//     duplicates add in that order.
+struct OnchipWaveAdjArgs {
+    OnchipPlan pl;
+    OnchipWaveCoef k;
+    const double* tau;                               // nsys
+    const double* c2; long long c2_stride;           // member s reads c2 + s * c2_stride (0: one medium for all)
+    const double* hist; long long hist_stride;       // member s reads hist + s * hist_stride: rows of `stride` doubles, row n = au(u_n)
+    const double* adj; long long adj_stride;         // member s reads adj + s * adj_stride (0: one table for all): row j for step (j + 1) every
+    const int* rec_node; int nrec;                   // packed indices of the receivers, nrec <= kOnchipWaveMaxRec
+    int every;
+    int s_top;                                       // the state index the launch starts from: the call's nsteps - steps done before
+    double* lam; double* q; double* S;               // nsys packed vectors of `stride` doubles each, in and out
+    long long stride;
+    int m;                                           // steps of this launch, 1 <= m <= s_top
+};
+static_assert(kOnchipWaveMaxRec * (8 + 4) <= kOnchipSideBytes, "a row of adjoint sources and the receiver table fit in the side data");
+template <int E>
+__global__ __launch_bounds__(kOnchipMaxThreads) void k_oc_wave_adjoint(const OnchipWaveAdjArgs a) {
+    const OnchipPlan& pl = a.pl;
+    extern __shared__ __attribute__((aligned(16))) char oc_dyn_lds[];
+    double* const rbuf = reinterpret_cast<double*>(oc_dyn_lds);                                    // the row of the sampled step
+    int* const rnode = reinterpret_cast<int*>(oc_dyn_lds + kOnchipWaveMaxRec * sizeof(double));    // the receivers
+    double* const img = OcMany::lds(pl.cells).img;
+    const int t = threadIdx.x, T = blockDim.x, pitch = pl.pitch, nrec = a.nrec, every = a.every;
+    const long long sys = blockIdx.x;
+    const double tau = a.tau[sys], h = 0.5 * tau;
+    const double* const cin = a.c2 + sys * a.c2_stride;
+    const double* const hcol = a.hist + sys * a.hist_stride + t;   // this lane's column of the history
+    double* const lio = a.lam + sys * a.stride; double* const qio = a.q + sys * a.stride; double* const sio = a.S + sys * a.stride;
+    int s = a.s_top, ph = s % every;                               // ph == 0: state index s is sampled
+    const int lo = s - a.m;                                        // the launch's last state: its steps are s_top .. lo + 1
+    // the row of the next sampled step at or below s (never dereferenced when that step is not this launch's)
+    const double* arow = a.adj + sys * a.adj_stride + ((long long)((s - ph) / every) - 1) * nrec;
+    const bool holder = t < nrec;
+
+    for (int i = t; i < pl.cells; i += T) img[i] = 0.0;
+    if (holder) rnode[t] = a.rec_node[t];
+    double r_next = 0.0;
+    if (ph == 0) {                                                 // uniform: the launch's first step is sampled (s >= 1 > lo)
+        if (holder) rbuf[t] = arow[t];
+        arow -= nrec;
+        if (holder && s - every > lo) r_next = arow[t];
+    } else if (holder && s - ph > lo) r_next = arow[t];
+    __syncthreads();                                               // the image is zero, the table and the first row are there
+    unsigned cell2[(E + 1) / 2] = {};
+    double lam[E], c2[E], S[E], hn[E];
+    int cnt = 0;
+    unsigned mask = 0;
+#pragma unroll
+    for (int k = 0; k < E; ++k) {
+        const int i = onchip_owned(pl, t, k);
+        if (i >= 0) {                                              // (slots beyond cnt are never read: nothing to initialise)
+            int xx, yy;
+            onchip_node(pl, i, &xx, &yy);
+            const int c = onchip_cell(pl, xx, yy);
+            cell2[k / 2] |= (unsigned)c << (16 * (k & 1));
+            img[c] = qio[i]; lam[k] = lio[i]; c2[k] = cin[i]; S[k] = sio[i];
+            cnt = k + 1;
+        }
+    }
+    const unsigned last = (unsigned)pl.unknowns - 1u;
+    const int ucnt = (pl.unknowns + T - 1) / T;                    // uniform: the slots that any thread owns
+    const int shift = __builtin_ctz((unsigned)T);                  // T is a power of two: unknown i sits in slot i / T of thread i % T
+    for (int j = 0; j < nrec; ++j) {
+        const int node = rnode[j];
+        if ((node & (T - 1)) == t) mask |= 1u << (node >> shift);
+    }
+    __syncthreads();
+    auto own_cell = [&](int k) { unsigned cc = cell2[k / 2]; asm volatile("" : "+v"(cc)); return (int)((cc >> (16 * (k & 1))) & 0xffffu); };
+    auto stencil_at = [&](int c) { return onchip_wave_au(a.k, img[c], img[c - 1], img[c + 1], img[c - pitch], img[c + pitch]); };
+    auto inject = [&](int k, double l) {                           // the sampled step's sources at unknown k T + t, ascending
+        const int i = k * T + t;
+        for (int j = 0; j < nrec; ++j) if (rnode[j] == i) l = onchip_wave_adjoint_inject(l, rbuf[j]);
+        return l;
+    };
+#pragma unroll
+    for (int k = 0; k < E; ++k) if (k < cnt) {                     // the first half of step s_top
+        const int c = own_cell(k);
+        const double qv = img[c], aq = stencil_at(c);
+        if (ph == 0 && ((mask >> k) & 1u)) lam[k] = inject(k, lam[k]);
+        S[k] = onchip_wave_adjoint_sens(S[k], qv, hcol[(long long)s * a.stride + k * T]);
+        lam[k] = onchip_wave_adjoint_kick(lam[k], h, aq);
+        hn[k] = hcol[(long long)(s - 1) * a.stride + k * T];       // s - 1 >= lo >= 0
+        __builtin_amdgcn_sched_barrier(0);
+    }
+
+    for (; s > lo; --s) {
+        __syncthreads();                                           // barrier 1: every neighbour has read the old cells, the row is consumed
+        const bool more = s - 1 > lo;                              // uniform: step s - 1 is this launch's too
+        ph = ph == 0 ? every - 1 : ph - 1;                         // of state index s - 1
+        const bool sampled = more && ph == 0;                      // uniform: step s - 1 injects
+        if (sampled) {
+            if (holder) rbuf[t] = r_next;
+            arow -= nrec;
+            if (holder && s - 1 - every > lo) r_next = arow[t];
+        }
+#pragma unroll
+        for (int k = 0; k < E; ++k) if (k < cnt) {
+            const int c = own_cell(k);
+            img[c] = onchip_wave_adjoint_drift(img[c], tau, c2[k], lam[k]);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        __syncthreads();                                           // barrier 2: the new image is complete
+        // the prefetched row has landed in EVERY slot before the pass, on every lane's path: the pass reads a slot only under the
+        // lane's own guard, and without this the compiler must assume a load still in flight when the row's registers are next
+        // written, and waits before each of them
+#pragma unroll
+        for (int k = 0; k < E; ++k) asm volatile("" :: "v"(hn[k]));
+#pragma unroll
+        for (int k = 0; k < E; ++k) if (k < cnt) {
+            const int c = own_cell(k);
+            const double qv = img[c], aq = stencil_at(c);
+            S[k] = onchip_wave_adjoint_sens(S[k], qv, hn[k]);      // H[s - 1]
+            lam[k] = onchip_wave_adjoint_kick(lam[k], h, aq);
+            if (more) {                                            // the first half of step s - 1, with the same au(q)
+                if (sampled && ((mask >> k) & 1u)) lam[k] = inject(k, lam[k]);
+                S[k] = onchip_wave_adjoint_sens(S[k], qv, hn[k]);
+                lam[k] = onchip_wave_adjoint_kick(lam[k], h, aq);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        // H[s - 2], for the next step: the loads of all slots go out back to back behind the pass.  No lane-dependent branch
+        // guards them, not even a uniform one -- a lane reads the row's last unknown for a slot it does not own (one cache line
+        // for all such lanes, a value that is never used) -- and the address is the uniform row plus a 32-bit lane index: inside the pass, or
+        // behind a per-lane guard, the compiler waits for every load before it issues the next (24 dependent round trips a
+        // step at the cap).
+        if (more) {
+            const double* const hrow = a.hist + sys * a.hist_stride + (long long)(s - 2) * a.stride;
+            unsigned idx = (unsigned)t;                            // one index register walks the slots
+#pragma unroll
+            for (int k = 0; k < E; ++k) if (k < ucnt) {
+                hn[k] = hrow[min(idx, last)];
+                idx += (unsigned)T;
+                __builtin_amdgcn_sched_barrier(0);                 // slot by slot: 24 indices formed ahead would spill
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < E; ++k) if (k < cnt) {
+        int i = k * T + t;
+        asm volatile("" : "+v"(i));                                // recomputed here, not carried through the loop
+        qio[i] = img[own_cell(k)]; lio[i] = lam[k]; sio[i] = S[k];
+    }
+}
+
 // The check launch for media in device memory: workgroup b reduces row b of the media (`rows` of them, `len` doubles each, row b
 // at c2 + b * stride) to its least and its largest entry and writes them to out[2 b], out[2 b + 1]; a row with an entry that is
 // not finite gets NaN in both.  The host reads them back once and refuses there, so that the message can name the member.

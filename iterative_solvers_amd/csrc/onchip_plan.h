@@ -259,6 +259,29 @@ MI355CG_HD inline long long onchip_wave_sponge_workspace_bytes(int n, int nsys, 
     const long long medium = onchip_wave_medium_workspace_bytes(n, nsys, nsteps, nrec, record_every);
     return medium == 0 ? 0 : medium + (long long)nsys * kOnchipWaveSpongeSysBytes;
 }
+// The adjoint of the scheme in a medium (mi355cg_wave_history_many, mi355cg_wave_adjoint_many).  The forward
+// run keeps H[n] = au(u_n), n = 0 .. nsteps: the stencil value t that onchip_wave_medium_accel forms before it scales it.  The
+// onchip_wave_au and the function below are that expression in its two halves, so a kernel can store t between them: the same bits.
+MI355CG_HD inline double onchip_wave_medium_accel_of(double c2, double t, double f) { return c2 * t - f; }
+// The exact transpose of the step, from state index s = nsteps down to 1, h = 0.5 tau; lam is the adjoint of u, q = c2 o (the
+// adjoint of v) the field the stencil acts on, S the sensitivity accumulator; one rounding per operation:
+//   if s % record_every == 0:  lam[rec[j]] = lam[rec[j]] + r[s / record_every - 1][j],  j ascending
+//   S = S + q H[s];  lam = lam + h au(q);  q = q + tau (c2 lam);  S = S + q H[s - 1];  lam = lam + h au(q)
+// From lam = q = S = 0:  dJ/dc2 = h S / c2,  dJ/du0 = lam,  dJ/dv0 = q / c2 -- divisions the caller makes, once, at the end.
+MI355CG_HD inline double onchip_wave_adjoint_inject(double lam, double r) { return lam + r; }
+MI355CG_HD inline double onchip_wave_adjoint_sens(double S, double q, double H) { return S + q * H; }
+MI355CG_HD inline double onchip_wave_adjoint_kick(double lam, double h, double aq) { return lam + h * aq; }
+MI355CG_HD inline double onchip_wave_adjoint_drift(double q, double tau, double c2, double lam) { return q + tau * (c2 * lam); }
+// The history of nsys members over nsteps steps: nsteps + 1 rows of one double per unknown each.  0: refused, as the workspaces.
+MI355CG_HD inline long long onchip_wave_history_bytes(int n, int nsys, int nsteps) {
+    if (!onchip_supported(n) || nsys < 1 || nsys > kOnchipStepsMaxSys || nsteps < 0 || nsteps > kOnchipStepsMaxSteps) return 0;
+    return 8LL * nsys * ((long long)nsteps + 1) * onchip_plan(n).unknowns;
+}
+// The adjoint call's workspace is the medium call's: the driver's, tau, the receivers (their packed indices here) and the ranges
+// of the media.  lam, q, S, the history and the adjoint sources live in the caller's memory.  0: refused as there.
+MI355CG_HD inline long long onchip_wave_adjoint_workspace_bytes(int n, int nsys, int nsteps, int nrec, int record_every) {
+    return onchip_wave_medium_workspace_bytes(n, nsys, nsteps, nrec, record_every);
+}
 // Steps of one explicit launch when the caller does not say: the host tests the stop flag between two launches, so the longest
 // launch is the latency of a stop request, to stay under 10 ms.  Measured on one MI355X at N = 128, a launch of 1024 steps: 3.7 ms
 // for one member, 4.0 ms for 256, 15.3 ms for 1024 members (one workgroup per CU at that size, so four in turn) -- hence half of

@@ -473,6 +473,10 @@ class _Handle:
         steps_done): traces [nsys, nsteps // record_every, len(receivers)] of u0's kind, u at the receivers after every
         record_every-th step, None without receivers.  traces: an array of that shape to write into (a stop flag leaves the samples
         of steps that did not run as they are).  u0, v0, g, tau, steps_per_launch and stop_flag as in wave_steps_many."""
+        return self._wave_recorded(u0, v0, tau, nsteps, source, g, receivers, record_every, steps_per_launch, stop_flag, traces, c2, damping, None)
+
+    def _wave_recorded(self, u0, v0, tau, nsteps, source, g, receivers, record_every, steps_per_launch, stop_flag, traces, c2, damping, _hist):
+        """wave_record_many, and with _hist ([nsys, nsteps + 1, size] of u0's kind, zeros; c2 given, no damping) wave_history_many."""
         nsys, on_device, sp = self._batched(u0, g, ("u0", "g", "forcings", "ensemble"), _capi.MANY_MAX, stop_flag)
         if self._check_batch(v0, self.size, _capi.MANY_MAX) != (nsys, on_device) or (on_device and v0.device != u0.device):
             raise ValueError(f"v0 has shape {tuple(v0.shape)}: the velocities are of the kind (NumPy / CUDA tensor), shape and device of u0, {tuple(u0.shape)}")
@@ -519,6 +523,8 @@ class _Handle:
             fn = (self._lib.mi355cg_wave_record_many_device if c2 is None else self._lib.mi355cg_wave_medium_many_device if damping is None
                   else self._lib.mi355cg_wave_sponge_many_device)
             medium = tuple(x for a in (c2, damping) if a is not None for x in (a.data_ptr(), self.size if a.dim() == 2 else 0))
+            if _hist is not None:                                    # wave_history_many: checked there
+                fn, medium = self._lib.mi355cg_wave_history_many_device, medium + (_hist.data_ptr(), (nsteps + 1) * self.size)
             rc = fn(self._h, nsys, nsteps, tau.ctypes.data, g.data_ptr() if g is not None else None, u.data_ptr(), v.data_ptr(), *medium, source.data_ptr(),
                     nsteps + 1 if source.dim() == 2 else 0, nrec, nodes.ctypes.data if nrec else None, record_every, traces.data_ptr() if nrec else None,
                     int(steps_per_launch), sp, res, steps_done.ctypes.data)
@@ -537,11 +543,177 @@ class _Handle:
             fn = (self._lib.mi355cg_wave_record_many if c2 is None else self._lib.mi355cg_wave_medium_many if damping is None
                   else self._lib.mi355cg_wave_sponge_many)
             medium = tuple(x for a in (c2, damping) if a is not None for x in (a.ctypes.data, self.size if a.ndim == 2 else 0))
+            if _hist is not None:
+                fn, medium = self._lib.mi355cg_wave_history_many, medium + (_hist.ctypes.data, (nsteps + 1) * self.size)
             rc = fn(self._h, nsys, nsteps, tau.ctypes.data, g.ctypes.data if g is not None else None, u.ctypes.data, v.ctypes.data, *medium, source.ctypes.data,
                     nsteps + 1 if source.ndim == 2 else 0, nrec, nodes.ctypes.data if nrec else None, record_every, traces.ctypes.data if nrec else None,
                     int(steps_per_launch), sp, res, steps_done.ctypes.data)
         self._check_rc(rc)
         return u, v, (traces if nrec else None), list(res), steps_done
+
+    def wave_history_many(self, u0, v0, tau, nsteps: int, source, g=None, receivers=None, record_every: int = 1, steps_per_launch: int = 0,
+                          stop_flag: Optional[C.c_int] = None, traces=None, c2=None):
+        """wave_record_many in the medium c2 (None: a unit medium) that also returns the history (mi355cg_wave_history_many):
+        (u, v, traces, hist, [Results per member], steps_done), hist [nsys, nsteps + 1, size] of u0's kind with hist[s, n] = au(u_n)
+        of member s, zeros in the rows of steps that did not run."""
+        nsys, on_device = self._check_batch(u0, self.size, _capi.MANY_MAX)
+        nsteps = int(nsteps)
+        if not 0 <= nsteps <= _capi.STEPS_MANY_MAX_STEPS:
+            raise ValueError(f"nsteps {nsteps} rejected: it must be 0 .. {_capi.STEPS_MANY_MAX_STEPS}")
+        if on_device:
+            import torch
+            if c2 is None:
+                c2 = torch.ones(self.size, dtype=torch.float64, device=u0.device)
+            hist = torch.zeros((nsys, nsteps + 1, self.size), dtype=torch.float64, device=u0.device)
+        else:
+            if c2 is None:
+                c2 = np.ones(self.size)
+            hist = np.zeros((nsys, nsteps + 1, self.size))
+        u, v, traces, res, done = self._wave_recorded(u0, v0, tau, nsteps, source, g, receivers, record_every, steps_per_launch, stop_flag, traces, c2, None, hist)
+        return u, v, traces, hist, res, done
+
+    def wave_adjoint_many(self, hist, tau, c2, adjoint_source, receivers=None, record_every: int = 1, lam=None, q=None, sens=None,
+                          steps_per_launch: int = 0, stop_flag: Optional[C.c_int] = None, return_info: bool = False):
+        """The transpose of the steps whose history is hist (mi355cg_wave_adjoint_many): (lam, q, sens) after nsteps =
+        hist.shape[1] - 1 backward steps from the incoming (lam, q, sens), None = zeros; with return_info also ([Results per
+        member], steps_done).  hist: [nsys, nsteps + 1, size] float64, NumPy or a contiguous CUDA tensor; c2 ([size] or [nsys,
+        size], None: a unit medium), adjoint_source ([nsteps // record_every, nrec] for all members or [nsys, nsteps //
+        record_every, nrec]; None without receivers) and lam, q, sens ([nsys, size]) of its kind.  Nothing passed in is modified."""
+        on_device = not isinstance(hist, np.ndarray)
+        if on_device:
+            if not (type(hist).__module__.split(".")[0] == "torch" and hasattr(hist, "data_ptr")):
+                raise ValueError(f"a history is a NumPy array or a CUDA torch tensor, not {type(hist).__name__}")
+            import torch
+            if not (hist.is_cuda and hist.dtype == torch.float64 and hist.is_contiguous()):
+                raise ValueError("a torch history is a contiguous float64 tensor in device memory")
+            if hist.device.index != self._device:
+                raise ValueError(f"hist is on {hist.device}, the handle on device {self._device}")
+        elif hist.dtype != np.float64:
+            raise ValueError(f"hist has dtype {hist.dtype}, expected float64")
+        shape = tuple(hist.shape)
+        if len(shape) != 3 or shape[2] != self.size or shape[1] < 1 or not 1 <= shape[0] <= _capi.MANY_MAX:
+            raise ValueError(f"hist has shape {shape}, expected (1 .. {_capi.MANY_MAX} members, nsteps + 1, {self.size})")
+        nsys, nsteps = shape[0], shape[1] - 1
+        tau, nsteps, res, steps_done, _ = self._ensemble_steps(nsys, tau, nsteps, False)
+        record_every = int(record_every)
+        if record_every < 1:
+            raise ValueError(f"record_every {record_every} rejected: it must be >= 1")
+        nodes = np.ascontiguousarray(receivers if receivers is not None else [], dtype=np.int32)
+        if nodes.ndim != 1 or len(nodes) > _capi.WAVE_MAX_RECEIVERS:
+            raise ValueError(f"receivers has shape {nodes.shape}: a sequence of at most {_capi.WAVE_MAX_RECEIVERS} packed indices")
+        nrec = len(nodes)
+        samples = nsteps // record_every
+        cshapes = ((self.size,), (nsys, self.size))
+        ashapes = ((samples, nrec), (nsys, samples, nrec))
+        state = ((nsys, self.size),)
+        sp = C.cast(C.pointer(stop_flag), C.c_void_p) if stop_flag is not None else None
+        if nrec and adjoint_source is None:
+            raise ValueError(f"{nrec} receivers need adjoint_source")
+        if on_device:
+            if c2 is None:
+                c2 = torch.ones(self.size, dtype=torch.float64, device=hist.device)
+            for name, a, want in (("c2", c2, cshapes), ("adjoint_source", adjoint_source if nrec else None, ashapes), ("lam", lam, state), ("q", q, state), ("sens", sens, state)):
+                if a is not None and not (hasattr(a, "data_ptr") and a.is_cuda and a.device == hist.device and a.dtype == torch.float64
+                                          and tuple(a.shape) in want and a.is_contiguous()):
+                    raise ValueError(f"{name} beside a CUDA history is a contiguous float64 tensor of shape {' or '.join(map(str, want))} on {hist.device}")
+            lam, q, sens = (torch.zeros(state[0], dtype=torch.float64, device=hist.device) if a is None else a.clone() for a in (lam, q, sens))
+            torch.cuda.current_stream(hist.device).synchronize()
+            rc = self._lib.mi355cg_wave_adjoint_many_device(
+                self._h, nsys, nsteps, tau.ctypes.data, c2.data_ptr(), self.size if c2.dim() == 2 else 0, hist.data_ptr(), (nsteps + 1) * self.size, nrec,
+                nodes.ctypes.data if nrec else None, record_every, adjoint_source.data_ptr() if nrec else None,
+                samples * nrec if nrec and adjoint_source.dim() == 3 else 0, lam.data_ptr(), q.data_ptr(), sens.data_ptr(), int(steps_per_launch), sp, res,
+                steps_done.ctypes.data)
+        else:
+            c2 = np.ones(self.size) if c2 is None else c2
+            arrays = {"c2": (c2, cshapes), "adjoint_source": (adjoint_source if nrec else None, ashapes), "lam": (lam, state), "q": (q, state), "sens": (sens, state)}
+            for name, (a, want) in arrays.items():
+                if a is None:
+                    continue
+                if hasattr(a, "data_ptr"):
+                    raise ValueError(f"{name} is of the kind (NumPy / CUDA tensor) of hist")
+                a = np.ascontiguousarray(a, dtype=np.float64)
+                if a.shape not in want:
+                    raise ValueError(f"{name} has shape {a.shape}, expected {' or '.join(map(str, want))}")
+                arrays[name] = (a, want)
+            c2, adjoint_source = arrays["c2"][0], arrays["adjoint_source"][0]
+            lam, q, sens = (np.zeros(state[0]) if arrays[k][0] is None else np.array(arrays[k][0], dtype=np.float64, order="C", copy=True) for k in ("lam", "q", "sens"))
+            hist = np.ascontiguousarray(hist)
+            rc = self._lib.mi355cg_wave_adjoint_many(
+                self._h, nsys, nsteps, tau.ctypes.data, c2.ctypes.data, self.size if c2.ndim == 2 else 0, hist.ctypes.data, (nsteps + 1) * self.size, nrec,
+                nodes.ctypes.data if nrec else None, record_every, adjoint_source.ctypes.data if nrec else None,
+                samples * nrec if nrec and adjoint_source.ndim == 3 else 0, lam.ctypes.data, q.ctypes.data, sens.ctypes.data, int(steps_per_launch), sp, res,
+                steps_done.ctypes.data)
+        self._check_rc(rc)
+        return (lam, q, sens, list(res), steps_done) if return_info else (lam, q, sens)
+
+    def wave_gradient_many(self, u0, v0, tau, nsteps: int, source, observed, g=None, receivers=None, record_every: int = 1, c2=None, segment=None):
+        """(misfit [nsys], grad_c2, grad_u0, grad_v0, traces) of J_s = 1/2 sum (traces_s - observed_s)^2 by one forward run with
+        its history and one backward run; with segment=K in segments of K steps from checkpoints of (u, v).  Everything runs on
+        the device; NumPy arguments go up once and the results come down once."""
+        nsys, on_device = self._check_batch(u0, self.size, _capi.MANY_MAX)
+        import torch
+        dev = torch.device("cuda", self._device)
+        nodes = [int(r) for r in (receivers if receivers is not None else [])]
+        if not nodes:
+            raise ValueError("wave_gradient_many needs receivers: the misfit is a sum over the traces")
+        tau, nsteps, _, _, _ = self._ensemble_steps(nsys, tau, nsteps, False)
+        record_every = int(record_every)
+        if record_every < 1:
+            raise ValueError(f"record_every {record_every} rejected: it must be >= 1")
+        K = nsteps if segment is None else int(segment)
+        if segment is not None and (K < 1 or K % record_every):
+            raise ValueError(f"segment {segment} rejected: a positive multiple of record_every = {record_every}")
+        samples = nsteps // record_every
+
+        def up(name, a, shapes):
+            if a is None:
+                return None
+            if on_device != (not isinstance(a, np.ndarray) and hasattr(a, "data_ptr")):
+                raise ValueError(f"{name} is of the kind (NumPy / CUDA tensor) of u0")
+            if not on_device:
+                a = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
+            if tuple(a.shape) not in shapes or a.dtype != torch.float64 or not a.is_cuda:
+                raise ValueError(f"{name} has shape {tuple(a.shape)}, expected float64 of shape {' or '.join(map(str, shapes))}")
+            return a.contiguous()
+
+        state = ((nsys, self.size),)
+        u0d, v0d, gd = up("u0", u0, state), up("v0", v0, state), up("g", g, state)
+        c2d = up("c2", c2, ((self.size,), (nsys, self.size)))
+        if c2d is None:
+            c2d = torch.ones(self.size, dtype=torch.float64, device=dev)
+        wd = up("source", source, ((nsteps + 1,), (nsys, nsteps + 1)))
+        od = up("observed", observed, ((nsys, samples, len(nodes)),))
+        if wd is None or od is None:
+            raise ValueError("source and observed are required")
+        cuts = [(a, min(K, nsteps - a)) for a in range(0, nsteps, max(K, 1))]
+        hist = None
+        if len(cuts) <= 1:                                           # the whole history at once
+            _, _, traces, hist, _, _ = self.wave_history_many(u0d, v0d, tau, nsteps, wd, g=gd, receivers=nodes, record_every=record_every, c2=c2d)
+            starts = [(u0d, v0d)]
+        else:                                                        # forward in segments: (u, v) at every segment start stays on the device
+            traces = torch.zeros((nsys, samples, len(nodes)), dtype=torch.float64, device=dev)
+            starts, u, v = [], u0d, v0d
+            for a, k in cuts:
+                starts.append((u, v))
+                u, v, tr, _, _ = self.wave_record_many(u, v, tau, k, wd[..., a:a + k + 1].contiguous(), g=gd, receivers=nodes, record_every=record_every, c2=c2d)
+                traces[:, a // record_every:(a + k) // record_every] = tr
+        r = traces - od                                              # the adjoint source: one rounding
+        rh = r.cpu().numpy()
+        misfit = 0.5 * np.sum((rh * rh).reshape(nsys, -1), axis=-1)
+        lam = q = sens = None
+        for (a, k), (u, v) in zip(reversed(cuts), reversed(starts)):
+            if hist is None:
+                hist = self.wave_history_many(u, v, tau, k, wd[..., a:a + k + 1].contiguous(), g=gd, receivers=nodes, record_every=record_every, c2=c2d)[3]
+            lam, q, sens = self.wave_adjoint_many(hist, tau, c2d, r[:, a // record_every:(a + k) // record_every].contiguous(), receivers=nodes,
+                                                  record_every=record_every, lam=lam, q=q, sens=sens)
+            hist = None
+        if lam is None:                                              # no steps: nothing depends on anything
+            lam = q = sens = torch.zeros((nsys, self.size), dtype=torch.float64, device=dev)
+        h = torch.from_numpy(0.5 * tau).to(dev)[:, None]
+        out = (h * sens / c2d, lam, q / c2d, traces)
+        if on_device:
+            return (torch.from_numpy(misfit).to(dev),) + out
+        return (misfit,) + tuple(t.cpu().numpy() for t in out)
 
     def wave_cfl(self, c2=None):
         """The largest time step velocity Verlet takes on this grid, 2 / sqrt(2 |A_diag|) of the unshifted operator (mi355cg_wave_cfl).
@@ -769,6 +941,30 @@ def wave_sponge_many_workspace(n: int, nsys: int, nsteps: int, nrec: int = 0, re
     out = C.c_longlong()
     lib = _capi.load()
     rc = lib.mi355cg_wave_sponge_many_workspace(int(n), int(nsys), int(nsteps), int(nrec), int(record_every), C.byref(out))
+    if rc == _capi.ERR_INVALID:
+        raise ValueError(lib.mi355cg_last_error().decode())
+    _capi.check(rc)
+    return out.value
+
+
+def wave_history_bytes(n: int, nsys: int, nsteps: int) -> int:
+    """The bytes of the history MatrixFreeSystem.wave_history_many writes for nsys members and nsteps steps on an n x n grid: 8 *
+    nsys * (nsteps + 1) * size (host arithmetic, no GPU; mi355cg_wave_history_bytes).  ValueError for what the call refuses."""
+    out = C.c_longlong()
+    lib = _capi.load()
+    rc = lib.mi355cg_wave_history_bytes(int(n), int(nsys), int(nsteps), C.byref(out))
+    if rc == _capi.ERR_INVALID:
+        raise ValueError(lib.mi355cg_last_error().decode())
+    _capi.check(rc)
+    return out.value
+
+
+def wave_adjoint_many_workspace(n: int, nsys: int, nsteps: int, nrec: int = 0, record_every: int = 1) -> int:
+    """The device workspace bytes of MatrixFreeSystem.wave_adjoint_many (host arithmetic, no GPU;
+    mi355cg_wave_adjoint_many_workspace): those of wave_record_many with a medium.  ValueError for what the call refuses."""
+    out = C.c_longlong()
+    lib = _capi.load()
+    rc = lib.mi355cg_wave_adjoint_many_workspace(int(n), int(nsys), int(nsteps), int(nrec), int(record_every), C.byref(out))
     if rc == _capi.ERR_INVALID:
         raise ValueError(lib.mi355cg_last_error().decode())
     _capi.check(rc)
@@ -1011,6 +1207,49 @@ class MatrixFreeSystem:
         v0, tau, g, steps_per_launch and stop_flag as in wave_steps_many; this system is left as it was."""
         return self._handle.wave_record_many(u0, v0, tau, nsteps, source, g=g, receivers=receivers, record_every=record_every,
                                              steps_per_launch=steps_per_launch, stop_flag=stop_flag, traces=traces, c2=c2, damping=damping)
+
+    def wave_history_many(self, u0, v0, tau, nsteps: int, source, g=None, receivers=None, record_every: int = 1, steps_per_launch: int = 0,
+                          stop_flag: Optional[C.c_int] = None, traces=None, c2=None):
+        """Extension (no reference twin): wave_record_many in the medium c2 (None: a unit medium) that keeps its history, the
+        forward half of an adjoint-state gradient.  Returns (u, v, traces, hist, results, steps_done): u, v and traces with the
+        bits of wave_record_many(c2=), and hist [nsys, nsteps + 1, size()] of u0's kind, hist[s, n] = A u_n of member s -- the
+        stencil value of its state after n steps, before c2 scales it.  wave_history_bytes(n, nsys, nsteps) is its size: 8 bytes
+        per unknown, member and state.  The arguments are wave_record_many's; damping= is not taken."""
+        return self._handle.wave_history_many(u0, v0, tau, nsteps, source, g=g, receivers=receivers, record_every=record_every,
+                                              steps_per_launch=steps_per_launch, stop_flag=stop_flag, traces=traces, c2=c2)
+
+    def wave_adjoint_many(self, hist, tau, c2, adjoint_source, receivers=None, record_every: int = 1, lam=None, q=None, sens=None,
+                          steps_per_launch: int = 0, stop_flag: Optional[C.c_int] = None, return_info: bool = False):
+        """Extension (no reference twin): the exact transpose of the steps wave_history_many took, ONE workgroup per member, the
+        step loop inside the launch.  hist: [nsys, nsteps + 1, size()] as wave_history_many returns it (NumPy or a CUDA tensor);
+        tau, c2, receivers and record_every those of the forward run; adjoint_source: the derivative of the misfit with respect
+        to the traces, [nsys, nsteps // record_every, nrec] (or one table for all members without the first axis) -- traces -
+        observed for a least-squares misfit.  From state index s = nsteps down to 1, with h = tau / 2:
+            if s % record_every == 0:  lam[receivers[j]] += adjoint_source[s / record_every - 1][j]   (j ascending)
+            sens += q * hist[s];  lam += h * A q;  q += tau * (c2 * lam);  sens += q * hist[s - 1];  lam += h * A q
+        Returns (lam, q, sens), [nsys, size()] each, from the incoming ones (None: zeros); with return_info also (results,
+        steps_done).  From zeros, dJ/dc2 = (tau / 2) * sens / c2, dJ/du0 = lam and dJ/dv0 = q / c2.  No division happens inside the
+        call, so a backward run cut at multiples of record_every into calls that pass (lam, q, sens) on, each with its slice of
+        the history and of the sources, gives the bits of one call.  A tau above wave_cfl(c2) is refused.  This system is left as
+        it was."""
+        return self._handle.wave_adjoint_many(hist, tau, c2, adjoint_source, receivers=receivers, record_every=record_every, lam=lam, q=q, sens=sens,
+                                              steps_per_launch=steps_per_launch, stop_flag=stop_flag, return_info=return_info)
+
+    def wave_gradient_many(self, u0, v0, tau, nsteps: int, source, observed, g=None, receivers=None, record_every: int = 1, c2=None, segment=None, damping=None):
+        """Extension (no reference twin): the least-squares misfit of a recorded run and its gradient by the adjoint-state method:
+        one forward run (wave_history_many) and one backward run (wave_adjoint_many) instead of one forward run per unknown.
+        observed: [nsys, nsteps // record_every, nrec] of u0's kind.  Returns (misfit [nsys], grad_c2, grad_u0, grad_v0, traces):
+        misfit_s = 1/2 sum (traces_s - observed_s)^2, the adjoint source is traces - observed (one rounding), grad_c2 = (tau / 2)
+        sens / c2, grad_u0 = lam, grad_v0 = q / c2.  segment=K (a multiple of record_every): the forward run goes in segments of K
+        steps and keeps (u, v) at every segment start on the device; the segments are then walked backwards, each with one
+        history call of K steps from its checkpoint and one adjoint call, so never more than K + 1 history rows per member exist
+        (wave_history_bytes(n, nsys, K)); the bits are those of segment=None.  c2=None is a unit medium.  NumPy arrays or CUDA
+        tensors, as wave_record_many takes them; unlike that call this one needs torch for either kind: NumPy arguments go to the
+        device once, everything runs there through the device entry points, and the results come down once.  The transpose of
+        the damped step is not built: a damping that is not None is a ValueError."""
+        if damping is not None:
+            raise ValueError("wave_gradient_many takes no damping: the transpose of the damped step is not built")
+        return self._handle.wave_gradient_many(u0, v0, tau, nsteps, source, observed, g=g, receivers=receivers, record_every=record_every, c2=c2, segment=segment)
 
     def sponge_damping(self, width: int, dmax: float, sides: str = "lrbt"):
         """The damping field of a sponge layer on this system's grid, for wave_record_many(damping=): the module's
